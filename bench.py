@@ -33,6 +33,11 @@ latency configuration.
 
 N > 1: one process per GPU, independent stories per rank (SURVEY §8e story-level replicas, no
 data-path collective), weak scaling; value = story-steps of all ranks / max-over-ranks time.
+
+A plain run sets up, warms up, times ``--steps`` rounds and prints the JSON line.  ``--full`` adds the legs the
+headline does not need, after the timed region: the batch-1 story, the roofline section, the tolerance-mode legs
+and the CPU baseline (each ``--no-*`` switch still drops its leg from a ``--full`` run).  ``--dump-outputs DIR``
+writes what the last timed round handed back (see ``dump_outputs``) so that two builds can be compared.
 """
 import argparse
 import json
@@ -592,6 +597,32 @@ class Runner:
         self.sts = None              # the timed region starts at a story boundary
 
 
+DUMP_MAX_ELEMS = {"img_gen_feat": 1 << 23, "images": 1 << 22}    # float32: at most 32 MiB + 16 MiB on disk
+
+
+def dump_outputs(sts, out_dir):
+    """--dump-outputs: what the last timed round handed back to its caller, one float32 .npy per array — ``img_gen_feat``
+    [S,256,4096] (the regressed image features of the round's S stories, the MLLM half's output) and ``images``
+    [S,1024,1024,3] (the rendered uint8 pictures; absent with --mllm-only).  An array with more elements than
+    DUMP_MAX_ELEMS allows is stored as a fixed sample: the elements of the flattened array at the sorted first k
+    positions of ``torch.randperm(numel, generator=torch.Generator().manual_seed(0))``, the same positions in every run."""
+    import numpy as np
+    arrays = {"img_gen_feat": torch.cat([st.image_embeds[-1:] for st in sts])}
+    if all(getattr(st, "last_image", None) is not None for st in sts):
+        arrays["images"] = torch.stack([st.last_image for st in sts])
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1).cpu()
+        k = DUMP_MAX_ELEMS[name]
+        if flat.numel() > k:
+            idx = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(0))[:k].sort().values
+            flat = flat[idx]
+        else:
+            flat = flat.reshape(t.shape)
+        np.save(os.path.join(out_dir, name + ".npy"), flat.float().numpy())
+    print("bench: wrote %s to %s" % (", ".join(sorted(arrays)), out_dir), file=sys.stderr)
+
+
 def measure_roofline(eng, adapter, SPG, RG, device, dtype, args):
     """The `roofline` section of the JSON line (rank 0, after the timed region; shared by the replica and the slot-ring
     partitions): the HBM-bound half (decode GEMV, stacked image-token block, stacked prompt prefill) measured with HIP
@@ -1062,7 +1093,7 @@ def main():
                          "use with --story-len 25")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--config0", action="store_true", help="BASELINE configs[0]: the CPU plumbing case (S=256, 1 image placeholder, full 7B dims) on the host, no GPU")
-    ap.add_argument("--no-roofline", action="store_true", help="flow tests only: skip the roofline section (the JSON line is then not a bench record)")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without the roofline section")
     ap.add_argument("--no-tolerance-modes", action="store_true",
                     help="skip the extra legs that price the reference-arithmetic modes (fp32 VAE decode, fp32 MLLM half)")
     ap.add_argument("--no-batch1", action="store_true", help="skip the additional 1-story-per-GPU (reference batch-1) measurement")
@@ -1099,7 +1130,14 @@ def main():
     ap.add_argument("--knob", action="append", default=[], metavar="NAME=INT",
                     help="A/B runs: set a library tuning knob before anything is built (e.g. --knob attn_ver=6); recorded in "
                          "config.knobs — a line with knobs is not the shipped configuration")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the legs the headline does not need: the batch-1 story, the roofline "
+                         "section, the tolerance-mode legs and the CPU baseline (a plain run skips all four)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed round computed (img_gen_feat, images) as float32 DIR/<name>.npy")
     args = ap.parse_args()
+    if not args.full:
+        args.no_batch1 = args.no_roofline = args.no_tolerance_modes = args.no_cpu_baseline = True
     if args.max_slots:
         global MAX_SLOTS
         MAX_SLOTS = max(1, min(8, args.max_slots))
@@ -1154,6 +1192,8 @@ def main():
         args.stories_per_gpu = 4 if slots_mode else 8
     SPG = args.stories_per_gpu
     if slots_mode:
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs is a replica-partition option")
         from seedstory import parallel
         return parallel.bench_slot_partition(args, rank, world, device, dtype, sys.modules[__name__])
 
@@ -1223,6 +1263,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt_s = float(t.item())
     overlap = runner.overlap
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(runner.sts, args.dump_outputs)
 
     # ---- the reference's batch-1 configuration (1 story per GPU), same model, same schedule, rank 0 at N = 1 --------
     batch1 = None

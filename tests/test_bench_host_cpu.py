@@ -54,3 +54,37 @@ def test_sink_mode_bookkeeping_matches_the_story_module():
     assert log[0] == (875, 87) and log[1] == (899, 90) and sink == 4 + 24 * 17
     assert all(d in (87, 90) for _, d in log)            # first eviction drops the BOS-side rows too, later ones 114 - 24
     assert peak <= cap == 1664
+
+
+def test_dump_outputs_float32_capped_and_repeatable(tmp_path):
+    """--dump-outputs: the last round's img_gen_feat whole, the uint8 images as the same seeded sample in every run, all float32,
+    within the 64 MB the comparison of two builds may read; no images with --mllm-only."""
+    import numpy as np
+    import torch
+    b = _bench()
+
+    class St:
+        pass
+    g = torch.Generator().manual_seed(3)
+    sts = []
+    for _ in range(2):
+        st = St()
+        st.image_embeds = torch.randn(3, 256, 4096, generator=g).to(torch.bfloat16)     # features of the images in context
+        st.last_image = torch.randint(0, 256, (1024, 1024, 3), generator=g, dtype=torch.uint8)
+        sts.append(st)
+    b.dump_outputs(sts, str(tmp_path / "a"))
+    b.dump_outputs(sts, str(tmp_path / "b"))
+    feat = np.load(tmp_path / "a" / "img_gen_feat.npy")
+    assert feat.dtype == np.float32 and feat.shape == (2, 256, 4096)
+    assert np.array_equal(feat, torch.cat([st.image_embeds[-1:] for st in sts]).float().numpy())
+    imgs = np.load(tmp_path / "a" / "images.npy")
+    assert imgs.dtype == np.float32 and imgs.shape == (b.DUMP_MAX_ELEMS["images"],)
+    assert np.array_equal(imgs, np.load(tmp_path / "b" / "images.npy"))
+    flat = torch.stack([st.last_image for st in sts]).reshape(-1)
+    idx = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(0))[:imgs.size].sort().values     # the documented sample
+    assert np.array_equal(imgs, flat[idx].float().numpy())
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 64 * 2 ** 20
+    for st in sts:
+        del st.last_image
+    b.dump_outputs(sts, str(tmp_path / "c"))
+    assert sorted(p.name for p in (tmp_path / "c").iterdir()) == ["img_gen_feat.npy"]

@@ -72,7 +72,7 @@ def _two_rank_bench(env_extra, extra_args, port, timeout=900):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0", **env_extra)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--stories-per-gpu", "2", "--diffusion-steps", "2", "--story-len", "3", "--no-cpu-baseline", "--no-batch1",
+           "--stories-per-gpu", "2", "--diffusion-steps", "2", "--story-len", "3", "--full", "--no-cpu-baseline", "--no-batch1",
            "--no-tolerance-modes"] + extra_args
     return subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=timeout)
 
