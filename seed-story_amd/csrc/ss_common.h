@@ -11,6 +11,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <atomic>
 
 #include "../../include/seedstory_hip.h"
 
@@ -180,22 +181,24 @@ int check_hip(hipError_t e, const char* what);
     } while (0)
 // Raise a kernel's dynamic-LDS limit: once per (kernel instantiation, device) — the attribute belongs to the DEVICE's copy of the
 // code object, so a process that drives several devices must set it on each — with the return code checked (a part with
-// less LDS fails here, by name, not later as a generic launch error).  `done` = the call site's static device mask.
-inline int ensure_dyn_lds(const void* kern, size_t bytes, uint64_t& done) {
+// less LDS fails here, by name, not later as a generic launch error).  `done` = the call site's static device mask (atomic: host
+// threads launch concurrently; two that race both set the attribute, which is harmless).  The attribute is set ONCE, with the first
+// caller's byte count: `bytes` must be the MAXIMUM the call site ever launches that kernel with (gemv_launch_nb, whose size varies, sets it per launch).
+inline int ensure_dyn_lds(const void* kern, size_t bytes, std::atomic<uint64_t>& done) {
     int dev = 0;
     int rc = check_hip(hipGetDevice(&dev), "hipGetDevice");
     if (rc) return rc;
     const uint64_t bit = 1ull << (dev & 63);
-    if (!(done & bit)) {
+    if (!(done.load(std::memory_order_acquire) & bit)) {
         rc = check_hip(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes), "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
         if (rc) return rc;
-        done |= bit;
+        done.fetch_or(bit, std::memory_order_release);
     }
     return 0;
 }
 #define SS_DYN_LDS(kern, bytes)                                        \
     do {                                                               \
-        static uint64_t _done = 0;                                     \
+        static std::atomic<uint64_t> _done{0};                         \
         int _rc = ::ss::ensure_dyn_lds((const void*)(kern), (bytes), _done); \
         if (_rc) return _rc;                                           \
     } while (0)

@@ -140,14 +140,12 @@ int ss_gemm_fp8(const void* A8, const float* scale_a, const void* W8, const floa
     SS_REQUIRE((epilogue & ~(SS_EPI_BIAS | SS_EPI_GELU | SS_EPI_RESIDUAL | SS_EPI_GEGLU_PAIR)) == 0, "ss_gemm_fp8: unsupported epilogue %d", epilogue);
     SS_REQUIRE(!(epilogue & SS_EPI_BIAS) || bias, "ss_gemm_fp8: bias epilogue without bias");
     SS_REQUIRE(!(epilogue & SS_EPI_RESIDUAL) || residual, "ss_gemm_fp8: residual epilogue without residual");
-    ss::GemmArgs g;
-    g.A = A8; g.W = W8; g.C = C; g.bias = bias; g.residual = residual;
-    g.M = (int)M; g.N = (int)N; g.K = (int)K; g.lda = K; g.ldw = K; g.ldc = ldc; g.ldr = ldr; g.epi = epilogue;
-    g.rowvec = nullptr; g.rows_per_batch = 1; g.rowvec_ld = 0;
-    g.conv_H = g.conv_W = g.conv_Cin = g.conv_stride = g.conv_up = g.conv_Ho = g.conv_Wo = 0;
+    ss::GemmArgs g = ss::gemm_args(A8, W8, C, M, N, K, K, K, ldc, epilogue, bias, residual, ldr);
     g.scale_a = scale_a; g.scale_w = scale_w;
     const int cfg = ss::pick_cfg_fp8(M, N, K);
-    const int mt = (cfg == 85 || cfg == 86) ? 64 : (cfg == 82 || cfg >= 90) ? 256 : 128;
+    // rows of the tile that will run: the id's own, or for an id the 4-wave dispatcher does not know its fallback below (82)
+    const ss::GemmTile tile = ss::fp8_tile(cfg);
+    const int mt = tile.id ? tile.BM : cfg >= 90 ? ss::fp8_tile(82).BM : 128;
     g.swz = ss::tuning_get("gemm_fp8_swz", (int)((M + mt - 1) / mt) >= 16 ? 8 : 0);
     if (ss::tuning_get("gemm_fp8_debug", 0)) fprintf(stderr, "ss_gemm_fp8 [%lld,%lld,%lld] epi %d cfg %d swz %d\n", (long long)M, (long long)N, (long long)K, epilogue, cfg, g.swz);
     int rc = 1;

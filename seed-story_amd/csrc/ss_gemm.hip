@@ -455,17 +455,11 @@ static int gemm_glds_launch_cfg(const GemmArgs& g, hipStream_t s) {
     }
 }
 
-template <typename T> int gemm_sp_dispatch_conv(int cfg, const GemmArgs& g, hipStream_t s);
+// the LDS-DMA families are 16-bit only: fp32 (CPU-parity mode) is "not eligible" everywhere
 template <> int gemm_sp_dispatch<float>(int, const GemmArgs&, hipStream_t) { return 1; }
 template <> int gemm_sp_dispatch_conv<float>(int, const GemmArgs&, hipStream_t) { return 1; }
-// ping-pong 8-phase 256x256 tiles (ss_gemm_pp.inc): cfg 50-59; same contract (1 = not eligible)
-template <typename T> int gemm_pp_dispatch(int cfg, const GemmArgs& g, hipStream_t s);
-template <typename T> int gemm_pp_dispatch_conv(int cfg, const GemmArgs& g, hipStream_t s);
 template <> int gemm_pp_dispatch<float>(int, const GemmArgs&, hipStream_t) { return 1; }
 template <> int gemm_pp_dispatch_conv<float>(int, const GemmArgs&, hipStream_t) { return 1; }
-// one-stream-per-SIMD kernels (ss_gemm_w4.inc): cfg 90-99; same contract (1 = not eligible)
-template <typename T> int gemm_w4_dispatch(int cfg, const GemmArgs& g, hipStream_t s);
-template <typename T> int gemm_w4_dispatch_conv(int cfg, const GemmArgs& g, hipStream_t s);
 template <> int gemm_w4_dispatch<float>(int, const GemmArgs&, hipStream_t) { return 1; }
 template <> int gemm_w4_dispatch_conv<float>(int, const GemmArgs&, hipStream_t) { return 1; }
 
@@ -475,19 +469,20 @@ template <> int gemm_w4_dispatch_conv<float>(int, const GemmArgs&, hipStream_t) 
 template <typename T>
 static int gemm_dispatch_cfg(int cfg, const GemmArgs& g, hipStream_t s) {
     if (cfg >= 90 && cfg < 100 && Tr<T>::kVec == 8) {   // 4-wave / AGPR-accumulator tiles; ineligible shapes take the 8-wave 256x256 tile
-        const int rc = g.conv_Cin > 0 ? gemm_w4_dispatch_conv<T>(cfg, g, s) : gemm_w4_dispatch<T>(cfg, g, s);
+        const int rc = gemm_w4_run<T>(cfg, g, s);
         if (rc <= 0) return rc;
         cfg = g.conv_Cin > 0 ? 69 : 60;
     }
     if (cfg >= 50 && cfg < 60 && Tr<T>::kVec == 8) {   // ping-pong tiles; ineligible shapes (conv, K % 64) take the one-barrier 256x256 tile
-        const int rc = g.conv_Cin > 0 ? gemm_pp_dispatch_conv<T>(cfg, g, s) : gemm_pp_dispatch<T>(cfg, g, s);
+        const int rc = gemm_pp_run<T>(cfg, g, s);
         if (rc <= 0) return rc;
         cfg = g.conv_Cin > 0 ? 69 : 60;
     }
     if (cfg >= 20 && Tr<T>::kVec == 8) {
-        const int rc = g.conv_Cin > 0 ? gemm_sp_dispatch_conv<T>(cfg, g, s) : gemm_sp_dispatch<T>(cfg, g, s);
+        const int rc = gemm_sp_run<T>(cfg, g, s);
         if (rc <= 0) return rc;
-        cfg = (cfg == 21 || cfg == 68) ? 15 : (cfg == 22 || cfg == 29 || cfg == 67 || cfg == 70) ? 10 : 8;
+        const GemmTile t = sp_tile(cfg);      // the double-buffered kernel of the nearest tile: 64 rows -> 64x64, 128x64, else (and for ids that are no base tile) 128x128
+        cfg = t.BM == 64 ? 10 : (t.BM == 128 && t.BN == 64) ? 15 : 8;
     }
     switch (cfg) {
         case 1:
@@ -618,7 +613,6 @@ static int tune_shape(GemmArgs g, void* ws, size_t ws_bytes, size_t a_elems, hip
         char* p = (char*)ws;
         g.A = p; g.C = p + a_b;
         char* w0 = p + a_b + c_b;
-        g.bias = nullptr; g.residual = nullptr; g.rowvec = nullptr;
         g.epi &= SS_EPI_GEGLU_PAIR | SS_EPI_GELU;
         if (g.epi & SS_EPI_GEGLU_PAIR) g.ldc = g.N / 2;
         hipLaunchKernelGGL(tune_fill_kernel, dim3(2048), dim3(256), 0, s, (uint16_t*)g.A, a_elems, 0x1234u,
@@ -639,7 +633,7 @@ static int tune_shape(GemmArgs g, void* ws, size_t ws_bytes, size_t a_elems, hip
                 g.swz = z;
                 g.W = w0;
                 if (c >= 50 && c < 60) {   // ping-pong tiles take whole-tile / stride-1 shapes only: time the tile itself, never its fallback
-                    const int rc = g.conv_Cin > 0 ? gemm_pp_dispatch_conv<T>(c, g, s) : gemm_pp_dispatch<T>(c, g, s);
+                    const int rc = gemm_pp_run<T>(c, g, s);
                     if (rc != SS_OK) break;
                 }
                 if (gemm_dispatch_cfg<T>(c, g, s) != SS_OK) continue;   // warm-up (also faults pages in)
@@ -688,10 +682,10 @@ static void conv_geometry(GemmArgs& g, int64_t B, int64_t H, int64_t Wd, int64_t
 template <typename T>
 static int rowstat_cfg(GemmArgs& g, int* bn, int* tn) {
     int cfg = lookup_cfg<T>(g);
-    const bool has = cfg == 61 || cfg == 62 || cfg == 63 || cfg == 64 || cfg == 65 || cfg == 67 || cfg == 71 || cfg == 72;
-    if (!has) cfg = g.N % 160 == 0 ? (g.M >= 2048 ? 62 : 61) : 65;
-    *bn = (cfg == 63 || cfg == 72) ? 320 : cfg == 65 ? 128 : 160;
-    *tn = cfg == 65 ? 64 : 80;
+    if (!(sp_tile(cfg).variants & 2)) cfg = g.N % 160 == 0 ? (g.M >= 2048 ? 62 : 61) : 65;
+    const GemmTile t = sp_tile(cfg);
+    *bn = t.BN;
+    *tn = t.BN / t.WN;
     return cfg;
 }
 
@@ -741,11 +735,7 @@ int gemm_launch(const void* A, const void* W, void* C, int64_t M, int64_t N, int
     SS_REQUIRE(!(epi & SS_EPI_BIAS) || bias, "gemm: bias epilogue without bias");
     SS_REQUIRE(!(epi & SS_EPI_RESIDUAL) || residual, "gemm: residual epilogue without residual");
     if (M == 0 || N == 0) return SS_OK;
-    GemmArgs g;
-    g.A = A; g.W = W; g.C = C; g.bias = bias; g.residual = residual;
-    g.M = (int)M; g.N = (int)N; g.K = (int)K; g.lda = lda; g.ldw = ldw; g.ldc = ldc; g.ldr = ldr; g.epi = epi;
-    g.rowvec = nullptr; g.rows_per_batch = 1; g.rowvec_ld = 0;
-    g.conv_H = g.conv_W = g.conv_Cin = g.conv_stride = g.conv_up = g.conv_Ho = g.conv_Wo = 0;
+    GemmArgs g = gemm_args(A, W, C, M, N, K, lda, ldw, ldc, epi, bias, residual, ldr);
     g.swz = tuning_get("gemm_xcd_swizzle", 8);
     if (tuning_get("gemm_epi_generic", 0)) g.epi |= SS_EPI_INTERNAL_GENERIC;
     if (rowstat_out || rowpart) {
@@ -808,10 +798,7 @@ int conv3x3_launch(const void* x, const void* w, void* y, int64_t B, int64_t H, 
 
 template <typename T>
 int gemm_tune_launch(int64_t M, int64_t N, int64_t K, int epi, void* ws, size_t ws_bytes, hipStream_t s, float* us) {
-    GemmArgs g;
-    g.M = (int)((M + 127) / 128 * 128); g.N = (int)N; g.K = (int)K; g.lda = K; g.ldw = K; g.ldc = N; g.ldr = N; g.epi = epi;
-    g.rowvec = nullptr; g.rows_per_batch = 1; g.rowvec_ld = 0;
-    g.conv_H = g.conv_W = g.conv_Cin = g.conv_stride = g.conv_up = g.conv_Ho = g.conv_Wo = 0;
+    const GemmArgs g = gemm_args(nullptr, nullptr, nullptr, (M + 127) / 128 * 128, N, K, K, K, N, epi, nullptr, nullptr, N);
     return tune_shape<T>(g, ws, ws_bytes, (size_t)g.M * K, s, us);
 }
 template <typename T>
@@ -819,7 +806,6 @@ int conv_tune_launch(int64_t B, int64_t H, int64_t Wd, int64_t Cin, int64_t Cout
                      size_t ws_bytes, hipStream_t s, float* us) {
     GemmArgs g;
     conv_geometry(g, B, H, Wd, Cin, Cout, stride, up);
-    g.epi = 0; g.rowvec = nullptr; g.rowvec_ld = 0;
     return tune_shape<T>(g, ws, ws_bytes, (size_t)B * H * Wd * Cin, s, us);
 }
 
@@ -839,11 +825,7 @@ int gemm_lnfold_launch(const void* A, const void* Wg, void* C, int64_t M, int64_
         SS_REQUIRE(((rstd && shift) || (ln_part && ln_nstrip > 0 && ln_width > 0)) && colsum && (((size_t)colsum) & 15) == 0 &&
                    (((size_t)ln_part) & 7) == 0, "ss_gemm_lnfold: row statistics / column vector missing or misaligned");
         if (M == 0 || N == 0) return SS_OK;
-        GemmArgs g;
-        g.A = A; g.W = Wg; g.C = C; g.bias = bias; g.residual = nullptr;
-        g.M = (int)M; g.N = (int)N; g.K = (int)K; g.lda = K; g.ldw = K; g.ldc = ldc; g.ldr = 0; g.epi = epi;
-        g.rowvec = nullptr; g.rows_per_batch = 1; g.rowvec_ld = 0;
-        g.conv_H = g.conv_W = g.conv_Cin = g.conv_stride = g.conv_up = g.conv_Ho = g.conv_Wo = 0;
+        GemmArgs g = gemm_args(A, Wg, C, M, N, K, K, K, ldc, epi, bias);
         g.swz = tuning_get("gemm_xcd_swizzle", 8);
         g.scale_a = rstd; g.shift_a = shift; g.scale_w = colsum;
         g.ln_part = ln_part; g.ln_nstrip = (int)ln_nstrip; g.ln_inv_width = ln_width > 0 ? 1.0f / (float)ln_width : 0.f; g.ln_eps = ln_eps;
@@ -856,10 +838,8 @@ int gemm_lnfold_launch(const void* A, const void* Wg, void* C, int64_t M, int64_
         // 4 launches at [32768, 640, 640] on cfg 61 / 65 / 67 / 70, none on 62 / 68 / 60 — the fences do NOT fix it, the cause is
         // still open, the reroute stays.  The same run cleared the PRODUCER side: the rowpart statistics epilogue on the 4-wave
         // tiles 261 / 265 / 267 (and 262) gave 0 bad statistics rows and 0 bad value rows, and the plain epilogue on cfg 61 none.
-        if (!tuning_get("lnfold_w4", 0)) {
-            if (cfg == 61 || cfg == 67) cfg = 62;
-            else if (cfg == 65 || cfg == 68 || cfg == 70) cfg = N % 160 == 0 ? 62 : 66;
-        }
+        if (const GemmTile t = sp_tile(cfg); t.WM * t.WN == 4 && !tuning_get("lnfold_w4", 0))
+            cfg = (t.BN == 160 || N % 160 == 0) ? 62 : 66;
         const int rc = gemm_sp_dispatch<T>(cfg + 100, g, s);
         if (rc == 1) {
             set_error("ss_gemm_lnfold: no kernel for cfg %d / shape [%lld, %lld, %lld]", cfg + 100, (long long)M, (long long)N, (long long)K);
@@ -1007,11 +987,7 @@ int gemm_splitk_launch(const void* A, const void* W, void* C, int64_t M, int64_t
     if (!S || !ws || ws_bytes < (size_t)S * M * N * sizeof(float))
         return gemm_launch<T>(A, W, C, M, N, K, K, K, N, bias, residual, N, (bias ? SS_EPI_BIAS : 0) | (residual ? SS_EPI_RESIDUAL : 0), s);
     if constexpr (Tr<T>::kVec == 8) {
-        GemmArgs g;
-        g.A = A; g.W = W; g.C = ws; g.bias = nullptr; g.residual = nullptr;
-        g.M = (int)M; g.N = (int)N; g.K = (int)K; g.lda = K; g.ldw = K; g.ldc = N; g.ldr = N; g.epi = 0;
-        g.rowvec = nullptr; g.rows_per_batch = 1; g.rowvec_ld = 0;
-        g.conv_H = g.conv_W = g.conv_Cin = g.conv_stride = g.conv_up = g.conv_Ho = g.conv_Wo = 0;
+        GemmArgs g = gemm_args(A, W, ws, M, N, K, K, K, N, 0, nullptr, nullptr, N);
         // row-major tile ids (measured, profiles/round3_splitk_microbench.json: the XCD-grouped order that puts the 3 - 4 row
         // tiles of a W column block on one XCD is 5 - 20 % SLOWER here — the row tiles then run back to back on few CUs
         // while the W stream of the other column blocks waits; with row-major ids the repeats hit the Infinity Cache)
@@ -1093,8 +1069,7 @@ int ss_rowstats(const void* x, int64_t ld, int64_t M, int64_t K, float eps, floa
 int64_t ss_gemm_rowpart_strips(int64_t M, int64_t N, int64_t K, int dtype) {
     if (dtype != SS_BF16 && dtype != SS_F16) return 0;
     ss::GemmArgs g;
-    g.M = (int)M; g.N = (int)N; g.K = (int)K; g.conv_Cin = 0; g.epi = 0;
-    g.conv_H = g.conv_W = g.conv_stride = g.conv_up = g.conv_Ho = g.conv_Wo = 0;
+    g.M = (int)M; g.N = (int)N; g.K = (int)K;
     int bn = 0, tn = 0;
     if (dtype == SS_BF16) ss::rowstat_cfg<ss::bf16_t>(g, &bn, &tn); else ss::rowstat_cfg<ss::f16_t>(g, &bn, &tn);
     return (N % bn == 0) ? N / tn : 0;

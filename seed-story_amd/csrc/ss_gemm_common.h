@@ -110,15 +110,15 @@ template <typename T> __device__ __forceinline__ float gelu_for(float v) {
 constexpr int SS_EPI_INTERNAL_GENERIC = 1 << 30;
 
 struct GemmArgs {
-    const void* A; const void* W; void* C; const void* bias; const void* residual;
-    int M, N, K;
-    int64_t lda, ldw, ldc, ldr;
-    int epi;
+    const void* A = nullptr; const void* W = nullptr; void* C = nullptr; const void* bias = nullptr; const void* residual = nullptr;
+    int M = 0, N = 0, K = 0;
+    int64_t lda = 0, ldw = 0, ldc = 0, ldr = 0;
+    int epi = 0;
     // per-(batch, n) additive vector (the ResBlock's projected time embedding): rowvec[m / rows_per_batch][n]
-    const void* rowvec; int rows_per_batch; int64_t rowvec_ld;
+    const void* rowvec = nullptr; int rows_per_batch = 1; int64_t rowvec_ld = 0;
     // implicit-GEMM 3x3 convolution over an NHWC tensor (A = [B, H, W, Cin]); K = 9 * Cin
-    int conv_H, conv_W, conv_Cin, conv_stride, conv_up, conv_Ho, conv_Wo;
-    int swz;   // XCD-aware tile order (0 = row-major block ids)
+    int conv_H = 0, conv_W = 0, conv_Cin = 0, conv_stride = 0, conv_up = 0, conv_Ho = 0, conv_Wo = 0;
+    int swz = 0;   // XCD-aware tile order (0 = row-major block ids)
     // fp8 operands: fp32 de-quantisation scales, one per A row (token) and one per W row (output channel)
     const float* scale_a = nullptr; const float* scale_w = nullptr;
     // folded LayerNorm (16-bit operands): scale_a = rstd[m], shift_a = -mean[m] * rstd[m], scale_w = c[n] (see EM below)
@@ -140,6 +140,16 @@ struct GemmArgs {
     // splitk_reduce_kernel sums the slices and applies the epilogue
     int ksplit = 1;
 };
+static_assert(sizeof(GemmArgs) == 224, "GemmArgs is a kernel argument: its layout does not change");
+
+// the plain product C[M,N] = A[M,K] W[N,K]^T (+bias)(+residual); conv_geometry (ss_gemm.hip) is the convolution's counterpart
+static inline GemmArgs gemm_args(const void* A, const void* W, void* C, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldw,
+                          int64_t ldc, int epi, const void* bias = nullptr, const void* residual = nullptr, int64_t ldr = 0) {
+    GemmArgs g;
+    g.A = A; g.W = W; g.C = C; g.bias = bias; g.residual = residual;
+    g.M = (int)M; g.N = (int)N; g.K = (int)K; g.lda = lda; g.ldw = ldw; g.ldc = ldc; g.ldr = ldr; g.epi = epi;
+    return g;
+}
 
 // Linear workgroup id -> output tile.  MI355X deals workgroups to its 8 XCDs round-robin by linear workgroup id and
 // every XCD has a private 4 MB L2, so with row-major tile ids the blocks that share an A row-tile (or a W column-tile)
@@ -739,13 +749,141 @@ __device__ __forceinline__ void gemm_epilogue_staged_pipe(const GemmArgs& g, f32
     }
 }
 
-// Software-pipelined LDS-DMA kernels (ss_gemm_sp.inc, instantiated per dtype in ss_gemm_sp_{bf16,f16}.hip).
-// Returns SS_OK, or 1 when `cfg` is not a pipelined configuration / the shape is not eligible (the caller
-// then falls back to the double-buffered kernel).
+// ---- tile tables ------------------------------------------------------------------------------------------------------------
+// A tile — id, block shape, wave grid, pipeline parameters, epilogue variants — is ONE row of its family's list: the dispatch
+// switches (ss_gemm_sp.inc, ss_gemm_w4.inc) expand the lists into their `case` lines, the host rules that need a tile's geometry
+// (fallback tile, statistics strips, XCD group, lnfold reroute) read it through sp_tile() / fp8_tile().  (The ping-pong and the
+// 16-bit 4-wave tiles keep their five-line switches: no host rule reads their geometry.)  Columns <BM, BN, WM, WN, NH, NS, FLAGS>
+// are sp_launch's (ss_gemm_sp.inc; conv units always run NS = 2); variants: 1 = id + 100 exists (folded-LayerNorm epilogue,
+// FLAGS | 16), 2 = id + 200 (row statistics of the output, FLAGS | 32: the producers of the UNet's LayerNorm inputs — attn.to_out /
+// ff.net.2 (+ residual), proj_in; N = 640 | 1280); both GEMM only.
+// 16-bit tiles (cfg 20 .. 72).  160-wide tiles: every SDXL channel count (640 ... 10240) is a multiple of 160.
+//    id   BM   BN  WM WN NH NS FLAGS variants
+#define SS_SP_TILES(X) \
+    X(20, 128, 128, 2, 2, 1, 2,  0, 0) \
+    X(21, 128,  64, 2, 2, 1, 2,  0, 0) \
+    X(22,  64,  64, 2, 2, 1, 2,  0, 0) \
+    X(23, 256, 128, 4, 2, 1, 2,  0, 0) \
+    X(24, 256, 256, 2, 4, 2, 2,  0, 0)   /* 8 waves, 128x64 per wave, A in halves */ \
+    X(26, 128, 160, 2, 2, 1, 2,  0, 0)   /* 2 blocks per CU */ \
+    X(28, 128, 320, 2, 4, 1, 2,  0, 0)   /* 8 waves, 64x80 per wave, one block per CU */ \
+    X(29,  64, 160, 2, 2, 1, 2,  0, 0)   /* 32x80 per wave: small-M shapes */ \
+    X(30, 256, 160, 4, 2, 1, 2,  0, 0)   /* 8 waves, 64x80 per wave, uneven DMA deal */ \
+    X(31, 256, 160, 4, 2, 1, 3,  0, 0)   /* + 3-slot ring (156 KB) */ \
+    X(32, 256, 160, 4, 2, 1, 3,  1, 0)   /* + setprio */ \
+    X(33, 256, 160, 4, 2, 1, 3,  3, 0)   /* + persistent */ \
+    X(34, 256, 256, 2, 4, 2, 2,  1, 0)   /* 256x256 + setprio */ \
+    X(35, 256, 256, 2, 4, 2, 2,  2, 0)   /* 256x256 persistent */ \
+    X(36, 256, 256, 2, 4, 2, 2,  3, 0)   /* 256x256 persistent + setprio */ \
+    X(37, 128, 160, 2, 2, 1, 2,  1, 0)   /* 128x160 + setprio */ \
+    X(38, 256, 160, 4, 2, 1, 2,  2, 0)   /* 256x160 double-buffered, persistent */ \
+    X(39, 128, 320, 2, 4, 1, 2,  2, 0)   /* 128x320 persistent */ \
+    X(40, 256, 256, 2, 4, 2, 2,  6, 0)   /* 256x256 persistent, DMA spread between MFMAs */ \
+    X(41, 128, 160, 2, 2, 1, 2,  4, 0)   /* 128x160, DMA spread */ \
+    X(42, 256, 160, 4, 2, 1, 3,  4, 0)   /* 256x160 3-slot ring, DMA spread */ \
+    X(43, 256, 160, 4, 2, 1, 2,  6, 0)   /* 256x160 persistent, DMA spread */ \
+    X(44, 128, 320, 2, 4, 1, 2,  4, 0)   /* 128x320, DMA spread */ \
+    X(45, 256, 128, 4, 2, 1, 2,  4, 0)   /* 256x128, DMA spread */ \
+    X(46, 128, 128, 2, 2, 1, 2,  4, 0)   /* 128x128, DMA spread */ \
+    X(60, 256, 256, 2, 4, 2, 2, 11, 1)   /* 256x256 persistent + setprio, LDS-staged epilogue */ \
+    X(61, 128, 160, 2, 2, 1, 2,  8, 3)   /* 128x160, staged epilogue */ \
+    X(62, 256, 160, 4, 2, 1, 3, 12, 3)   /* 256x160 3-slot ring, DMA spread, staged (strips in the ring) */ \
+    X(63, 128, 320, 2, 4, 1, 2,  8, 3)   /* 128x320, staged */ \
+    X(64, 256, 160, 4, 2, 1, 2, 10, 3)   /* 256x160 persistent, staged */ \
+    X(65, 128, 128, 2, 2, 1, 2,  8, 3)   /* 128x128, staged */ \
+    X(66, 256, 128, 4, 2, 1, 2,  8, 1)   /* 256x128, staged */ \
+    X(67,  64, 160, 2, 2, 1, 2,  8, 3)   /* 64x160, staged */ \
+    X(68, 128,  64, 2, 2, 1, 2,  8, 1)   /* 128x64, staged */ \
+    X(69, 256, 256, 2, 4, 2, 2,  8, 1)   /* 256x256, staged */ \
+    X(70,  64,  64, 2, 2, 1, 2,  8, 1)   /* 64x64, staged */ \
+    X(71, 256, 160, 4, 2, 1, 2,  8, 3)   /* 256x160 double-buffered, staged (strips behind the ring) */ \
+    X(72, 128, 320, 2, 4, 1, 2, 10, 3)   /* 128x320 persistent, staged */
+// split-K tiles (grid.y K ranges, fp32 partial sums): small-M weight-streaming GEMMs of the LLaMA block continuation; GEMM only
+#define SS_SP_SPLITK_TILES(X) \
+    X(300, 128, 128, 2, 2, 1, 2, 64, 0) \
+    X(301, 128,  64, 2, 2, 1, 2, 64, 0)
+// fp8 tiles (NS = 2; wider A halving because a fragment is 8 VGPRs).  (256x256 does not fit: 128 accumulator + 96 operand
+// VGPRs per lane spill)
+#define SS_SP_FP8_TILES(X) \
+    X(80, 128, 128, 2, 2, 2, 2, 8, 0)    /* 64x64 per wave */ \
+    X(81, 128, 160, 2, 2, 2, 2, 8, 0)    /* 64x80 per wave, 2 blocks per CU */ \
+    X(82, 256, 160, 4, 2, 2, 2, 8, 0)    /* 8 waves, 64x80 per wave */ \
+    X(85,  64, 160, 2, 2, 1, 2, 8, 0)    /* small M */ \
+    X(86,  64,  64, 2, 2, 1, 2, 8, 0) \
+    X(88, 128, 160, 2, 2, 2, 2, 0, 0)    /* direct epilogue (ragged N) */
+// fp8 on the 4-wave / AGPR-accumulator tiles (ss_gemm_w4.inc): D3 / D0 (its DMA schedule) in place of NH / NS
+#define SS_W4_FP8_TILES(X) \
+    X(95, 256, 256, 2, 2, 16, 0, 2, 0)   /* persistent; the whole tile t+2 is issued in the last k-step of tile t */ \
+    X(96, 256, 256, 2, 2, 16, 0, 0, 0)
+
+struct GemmTile { int id, BM, BN, WM, WN, NH, NS, FLAGS, variants; };   // id 0: no such tile
+#define SS_TILE_ROW(id, BM, BN, WM, WN, NH, NS, FLAGS, VAR) {id, BM, BN, WM, WN, NH, NS, FLAGS, VAR},
+constexpr GemmTile kSpTiles[] = {SS_SP_TILES(SS_TILE_ROW)};
+constexpr GemmTile kFp8Tiles[] = {SS_SP_FP8_TILES(SS_TILE_ROW) SS_W4_FP8_TILES(SS_TILE_ROW)};
+template <int N> constexpr GemmTile find_tile(const GemmTile (&t)[N], int id) {
+    for (int i = 0; i < N; ++i) if (t[i].id == id) return t[i];
+    return GemmTile{};
+}
+// BASE tiles only: a variant id (+ 100 / + 200) or a split-K id is not in these lists and comes back as id 0
+constexpr GemmTile sp_tile(int id) { return find_tile(kSpTiles, id); }
+constexpr GemmTile fp8_tile(int id) { return find_tile(kFp8Tiles, id); }
+
+// ids unique and in [1, 100): the tune table stores cfg + 100 * xcd_group, and it keeps the variant ids (100 .. 299) and the
+// split-K ids clear of every base id; a tile with variants has the staged epilogue they are built on
+template <int N> constexpr bool tiles_well_formed(const GemmTile (&t)[N]) {
+    for (int i = 0; i < N; ++i) {
+        for (int j = 0; j < i; ++j) if (t[j].id == t[i].id) return false;
+        if (t[i].id < 1 || t[i].id >= 100 || (t[i].variants && !(t[i].FLAGS & 8))) return false;
+    }
+    return true;
+}
+static_assert(tiles_well_formed(kSpTiles) && tiles_well_formed(kFp8Tiles),
+              "tile lists: duplicate id, base id outside 1 .. 99, or a variant on a tile without the staged epilogue");
+
+// ---- dispatchers: one per kernel family and unit kind, instantiated per dtype in that family's translation units ----------------
+// All return SS_OK, an error code, or 1 when `cfg` is not one of the family's ids / the shape is not eligible (the caller then
+// falls back); the <float> specialisations (always 1) are in ss_gemm.hip.  Software-pipelined LDS-DMA kernels (ss_gemm_sp.inc):
 template <typename T> int gemm_sp_dispatch(int cfg, const GemmArgs& g, hipStream_t s);
-// fp8 (e4m3) operands, bf16 results: ss_gemm_sp_fp8.hip
+template <typename T> int gemm_sp_dispatch_conv(int cfg, const GemmArgs& g, hipStream_t s);
+// ping-pong 8-phase 256x256 / 256x320 tiles (ss_gemm_pp.inc): cfg 50-59
+template <typename T> int gemm_pp_dispatch(int cfg, const GemmArgs& g, hipStream_t s);
+template <typename T> int gemm_pp_dispatch_conv(int cfg, const GemmArgs& g, hipStream_t s);
+// one-stream-per-SIMD 4-wave kernels (ss_gemm_w4.inc, EXPERIMENTAL builds; ss_gemm_w4_stub.hip otherwise): cfg 90-99
+template <typename T> int gemm_w4_dispatch(int cfg, const GemmArgs& g, hipStream_t s);
+template <typename T> int gemm_w4_dispatch_conv(int cfg, const GemmArgs& g, hipStream_t s);
+// fp8 (e4m3) operands, bf16 results: ss_gemm_sp_fp8.hip / ss_gemm_w4_fp8.hip (cfg 95, 96)
 int gemm_sp_dispatch_fp8(int cfg, const GemmArgs& g, hipStream_t s);
-// fp8 on the 4-wave / AGPR-accumulator tiles (cfg 95, 96): ss_gemm_w4_fp8.hip
 int gemm_w4_dispatch_fp8(int cfg, const GemmArgs& g, hipStream_t s);
+// the family's dispatcher for the kind of unit the arguments ask for (conv_Cin > 0: implicit-GEMM convolution)
+template <typename T> static int gemm_sp_run(int cfg, const GemmArgs& g, hipStream_t s) {
+    return g.conv_Cin > 0 ? gemm_sp_dispatch_conv<T>(cfg, g, s) : gemm_sp_dispatch<T>(cfg, g, s);
+}
+template <typename T> static int gemm_pp_run(int cfg, const GemmArgs& g, hipStream_t s) {
+    return g.conv_Cin > 0 ? gemm_pp_dispatch_conv<T>(cfg, g, s) : gemm_pp_dispatch<T>(cfg, g, s);
+}
+template <typename T> static int gemm_w4_run(int cfg, const GemmArgs& g, hipStream_t s) {
+    return g.conv_Cin > 0 ? gemm_w4_dispatch_conv<T>(cfg, g, s) : gemm_w4_dispatch<T>(cfg, g, s);
+}
+
+// CUs of the current device; 256 when the query fails
+static inline int num_cus() {
+    static int n = 0;
+    if (!n) {
+        int dev = 0;
+        hipDeviceProp_t p;
+        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) n = p.multiProcessorCount;
+        if (n <= 0) n = 256;
+    }
+    return n;
+}
+// The launch every LDS-DMA family ends in: `total` output tiles on min(total, cap) workgroups (cap 0: one workgroup per tile;
+// persistent kernels pass a multiple of 8, so that tile vid and vid + grid share an XCD) x g.ksplit K ranges
+template <auto KERN> static int launch_tiles(const char* name, const GemmArgs& g, int total, int cap, int threads, size_t lds, hipStream_t s) {
+    const int grid = cap > 0 && total > cap ? cap : total;
+    if (lds > 64 * 1024) SS_DYN_LDS(KERN, lds);
+    hipLaunchKernelGGL(KERN, dim3((unsigned)grid, (unsigned)g.ksplit), dim3(threads), lds, s, g, total);
+    SS_LAUNCH_CHECK(name);
+    return SS_OK;
+}
 
 }  // namespace ss

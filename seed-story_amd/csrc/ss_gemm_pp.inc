@@ -50,16 +50,17 @@
 
 namespace ss {
 
-static int pp_num_cus() {
-    static int n = 0;
-    if (!n) {
-        int dev = 0;
-        hipDeviceProp_t p;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) n = p.multiProcessorCount;
-        if (n <= 0) n = 256;
-    }
-    return n;
-}
+// LDS layout of a BN-wide tile, for the kernel and its launcher: two K-tile buffers of four half-tiles each, and for the
+// LDS-staged epilogue (FLAGS & 8) one strip per wave — behind the ring when both fit the 160 KB of a CU, else inside buffer 0
+template <int BN, int FLAGS>
+struct PpLds {
+    static constexpr int FN = BN / 64, FN0 = (FN + 1) / 2, FN1 = FN / 2, TN = FN * 16;   // a wave's column fragments, halves
+    static constexpr int HA = 128 * 128, HB0 = 4 * FN0 * 16 * 128, HB1 = 4 * FN1 * 16 * 128;   // half-tile bytes
+    static constexpr int BUF = 2 * HA + HB0 + HB1;
+    static constexpr int STG_CR = 16, STG_WAVE = STG_CR * (TN * 2 + 16);
+    static constexpr bool STG_IN_RING = 2 * BUF + 8 * STG_WAVE > 163840;
+    static constexpr int BYTES = 2 * BUF + ((FLAGS & 8) != 0 && !STG_IN_RING ? 8 * STG_WAVE : 0);
+};
 
 static __device__ __attribute__((aligned(4096))) unsigned int g_pp_zero_page[1024];   // zero-initialised: the padding of the conv tiles (4 KB: 256 lanes x 16 B, so padded lanes do not pile onto one cache line)
 
@@ -81,17 +82,18 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmArgs g, const in
     // per CU, where 256-wide tiles waste a fifth of the chip.  BN = 320 takes whole tiles only (M % 256 == 0, N % 320 == 0:
     // the launcher refuses other shapes): 160 accumulator + 72 fragment registers leave no room for per-piece offsets, so
     // the DMA pieces of a half-tile share ONE lane offset and differ by scalar row offsets.
-    constexpr int BM = 256, FN = BN / 64, FN0 = (FN + 1) / 2, FN1 = FN / 2, TM = 128, TN = FN * 16, FM = 8;
+    using Lds = PpLds<BN, FLAGS>;
+    constexpr int BM = 256, FN = Lds::FN, FN0 = Lds::FN0, FN1 = Lds::FN1, TM = 128, TN = Lds::TN, FM = 8;
     static_assert(BN == 256 || BN == 320, "tile widths");
     constexpr bool EXACT = BN == 320 || CONV;
     constexpr bool PRIO = (FLAGS & 1) != 0, PERSIST = (FLAGS & 2) != 0, TWO = (FLAGS & 4) != 0, STAGED = (FLAGS & 8) != 0, RSTAT = (FLAGS & 32) != 0;
     constexpr int EM = ((FLAGS & 16) != 0) ? 2 : 0;
-    constexpr int HA = 128 * 128, HB0 = 4 * FN0 * 16 * 128, HB1 = 4 * FN1 * 16 * 128;   // half-tile bytes
-    constexpr int OFF_A0 = 0, OFF_A1 = HA, OFF_B0 = 2 * HA, OFF_B1 = 2 * HA + HB0, BUF = 2 * HA + HB0 + HB1;
+    constexpr int HA = Lds::HA, HB0 = Lds::HB0, HB1 = Lds::HB1, BUF = Lds::BUF;
+    constexpr int OFF_A0 = 0, OFF_A1 = HA, OFF_B0 = 2 * HA, OFF_B1 = 2 * HA + HB0;
     constexpr int NP0 = FN0, NP1 = FN1;                        // DMA pieces per wave of B-half 0 / 1 (A halves: 2 each)
     constexpr int FLY = NP0 + 2 + NP1;                         // DMA instructions in flight across the phase-4 wait
-    constexpr int STG_CR = 16, STG_WAVE = STG_CR * (TN * 2 + 16);
-    constexpr bool STG_IN_RING = 2 * BUF + 8 * STG_WAVE > 163840;
+    constexpr int STG_CR = Lds::STG_CR, STG_WAVE = Lds::STG_WAVE;
+    constexpr bool STG_IN_RING = Lds::STG_IN_RING;
     static_assert(!(PERSIST && STG_IN_RING), "persistent tiles prefetch under the epilogue: the strips need their own LDS");
     static_assert(Mma<T>::kEB == 2, "16-bit operands");
     using TO = T;
@@ -489,21 +491,8 @@ static int pp_launch(const GemmArgs& g, hipStream_t s) {
     }
     if (!ok) return 1;
     if ((g.rowstat_out || g.rowpart) && !(FLAGS & 32)) return 1;
-    constexpr int FN = BN / 64;
-    size_t lds = 2 * (2 * 128 * 128 + 4 * FN * 16 * 128);
-    const size_t stg = 8 * 16 * (FN * 16 * 2 + 16);
-    if ((FLAGS & 8) && lds + stg <= 163840) lds += stg;                   // mirrors STG_IN_RING of the kernel
-    const int total = cdiv(g.M, 256) * cdiv(g.N, BN);
-    int grid = total;
-    if (FLAGS & 2) {
-        const int cap = pp_num_cus();
-        if (grid > cap) grid = cap;
-    }
-    auto kern = gemm_pp_kernel<T, BN, FLAGS, CONV>;
-    SS_DYN_LDS(kern, lds);
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), lds, s, g, total);
-    SS_LAUNCH_CHECK("gemm_pp");
-    return SS_OK;
+    return launch_tiles<gemm_pp_kernel<T, BN, FLAGS, CONV>>("gemm_pp", g, cdiv(g.M, 256) * cdiv(g.N, BN), (FLAGS & 2) ? num_cus() : 0, 512,
+                                                            PpLds<BN, FLAGS>::BYTES, s);
 }
 
 // cfg 50 .. 59: the ping-pong tiles

@@ -36,16 +36,16 @@
 
 namespace ss {
 
-static int sp_num_cus() {
-    static int n = 0;
-    if (!n) {
-        int dev = 0;
-        hipDeviceProp_t p;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) n = p.multiProcessorCount;
-        if (n <= 0) n = 256;
-    }
-    return n;
-}
+// LDS layout of a tile, for the kernel and its launcher: an NS-slot ring of [A rows | W rows] x 128 B, and for the LDS-staged
+// epilogue (FLAGS & 8) a private strip of STG_CR rows per wave — behind the ring when both fit the 160 KB of a CU, otherwise
+// inside ring slot 0 (then the next output tile's prefetch has to wait for the epilogue)
+template <int BM, int BN, int WM, int WN, int NS, int FLAGS>
+struct SpLds {
+    static constexpr int NW = WM * WN, TILE_BYTES = (BM + BN) * 128;
+    static constexpr int STG_CR = 16, STG_WAVE = STG_CR * ((BN / WN) * 2 + 16);
+    static constexpr bool STG_IN_RING = (NW == 4 ? 2 : 1) * (NS * TILE_BYTES + NW * STG_WAVE) > 163840;   // 4-wave tiles are meant to run two workgroups per CU
+    static constexpr int BYTES = NS * TILE_BYTES + ((FLAGS & 8) != 0 && !STG_IN_RING ? NW * STG_WAVE : 0);
+};
 
 template <typename T, int BM, int BN, int WM, int WN, int NH, int NS, int FLAGS, bool CONV>
 __global__ __launch_bounds__(64 * WM * WN) void gemm_sp_kernel(const GemmArgs g, const int total_tiles) {
@@ -70,12 +70,9 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_sp_kernel(const GemmArgs g,
     constexpr int EM = F8 ? 1 : (((FLAGS & 16) != 0) ? 2 : 0);
     static_assert(!(F8 && (FLAGS & 16)), "fp8 tiles carry their own scaling epilogue");
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    constexpr int TILE_BYTES = (BM + BN) * 128;          // [A rows | W rows] x 128 B per ring slot
-    // LDS-staged epilogue (FLAGS & 8): a private strip of CR rows per wave, behind the ring when both fit the 160 KB of a
-    // CU, otherwise inside ring slot 0 (then the next output tile's prefetch has to wait for the epilogue)
-    constexpr int STG_CR = 16, STG_WAVE = STG_CR * (TN * 2 + 16);
-    constexpr int STG_BLOCKS = NW == 4 ? 2 : 1;           // 4-wave tiles are meant to run two workgroups per CU
-    constexpr bool STG_IN_RING = STG_BLOCKS * (NS * TILE_BYTES + NW * STG_WAVE) > 163840;
+    using Lds = SpLds<BM, BN, WM, WN, NS, FLAGS>;
+    constexpr int TILE_BYTES = Lds::TILE_BYTES, STG_CR = Lds::STG_CR, STG_WAVE = Lds::STG_WAVE;
+    constexpr bool STG_IN_RING = Lds::STG_IN_RING;
     constexpr bool PREFETCH_EARLY = !(STAGED && STG_IN_RING);
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -408,7 +405,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_sp_kernel(const GemmArgs g,
 template <typename T, int BM, int BN, int WM, int WN, int NH, int NS_, int FLAGS>
 static int sp_launch(const GemmArgs& g, hipStream_t s) {
     constexpr bool CONV = SS_SP_CONV != 0;
-    constexpr int NS = CONV ? 2 : NS_;
+    constexpr int NS = CONV ? 2 : NS_;            // the conv kernels drain per K tile: a third slot buys nothing there
     const bool conv = g.conv_Cin > 0;
     if (conv != CONV) return 1;
     // the pipelined kernel needs whole 64-wide K tiles (conv: one filter tap per tile) and 32-bit byte offsets
@@ -417,120 +414,47 @@ static int sp_launch(const GemmArgs& g, hipStream_t s) {
                     (conv ? (int64_t)g.M * g.conv_stride * g.conv_stride * g.conv_Cin * 2 < (1ll << 31)
                           : ((int64_t)BM * g.lda * Mma<T>::kEB < (1ll << 31))) && (int64_t)BN * g.ldw * Mma<T>::kEB < (1ll << 31);
     if (!ok) return 1;
-    size_t lds = (size_t)NS * (BM + BN) * 128;
     if ((g.rowstat_out || g.rowpart) && !(FLAGS & 32)) return 1;    // this instantiation has no statistics epilogue
-    if (FLAGS & 8) {
-        const size_t stg = (size_t)WM * WN * 16 * ((BN / WN) * 2 + 16);      // mirrors STG_IN_RING of the kernel
-        if ((WM * WN == 4 ? 2 : 1) * (lds + stg) <= 163840) lds += stg;
-    }
-    const int total = cdiv(g.M, BM) * cdiv(g.N, BN);
-    int grid = total;
-    if (FLAGS & 2) {
-        const int per_cu = lds > 80 * 1024 ? 1 : 2;
-        const int cap = sp_num_cus() * per_cu;          // multiple of 8: tile vid and vid + grid share an XCD
-        if (grid > cap) grid = cap;
-    }
-    auto kern = gemm_sp_kernel<T, BM, BN, WM, WN, NH, NS, FLAGS, CONV>;
-    if (lds > 64 * 1024) SS_DYN_LDS(kern, lds);
+    constexpr size_t lds = SpLds<BM, BN, WM, WN, NS, FLAGS>::BYTES;
     if ((g.ksplit > 1) != ((FLAGS & 64) != 0)) return 1;    // split-K runs only on its own instantiations
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid, (unsigned)g.ksplit), dim3(64 * WM * WN), lds, s, g, total);
-    SS_LAUNCH_CHECK("gemm_sp");
-    return SS_OK;
+    const int cap = (FLAGS & 2) ? num_cus() * (lds > 80 * 1024 ? 1 : 2) : 0;      // persistent: one or two workgroups per CU
+    return launch_tiles<gemm_sp_kernel<T, BM, BN, WM, WN, NH, NS, FLAGS, CONV>>("gemm_sp", g, cdiv(g.M, BM) * cdiv(g.N, BN), cap,
+                                                                                64 * WM * WN, lds, s);
 }
 
+// cfg -> sp_launch<T, BM, BN, WM, WN, NH, NS, FLAGS> through the tile lists of ss_gemm_common.h.  The variant passes come after
+// every base tile (kernels are emitted in the order they are instantiated here).
+#define SS_SP_CASE(id, BM, BN, WM, WN, NH, NS, FLAGS, VAR) case id: return sp_launch<T, BM, BN, WM, WN, NH, NS, FLAGS>(g, s);
+#define SS_SP_VARIANT(HAS, ID, BM, BN, WM, WN, NH, NS, FLAGS) \
+    if constexpr ((HAS) != 0) { if (cfg == (ID)) return sp_launch<T, BM, BN, WM, WN, NH, NS, FLAGS>(g, s); }
+#define SS_SP_LNFOLD(id, BM, BN, WM, WN, NH, NS, FLAGS, VAR) SS_SP_VARIANT((VAR) & 1, (id) + 100, BM, BN, WM, WN, NH, NS, (FLAGS) | 16)
+#define SS_SP_ROWSTAT(id, BM, BN, WM, WN, NH, NS, FLAGS, VAR) SS_SP_VARIANT((VAR) & 2, (id) + 200, BM, BN, WM, WN, NH, NS, (FLAGS) | 32)
 #if defined(SS_SP_FP8)
-// fp8 tile configurations (NS = 2; wider A halving because a fragment is 8 VGPRs): ids 80 ..
 int gemm_sp_dispatch_fp8(int cfg, const GemmArgs& g, hipStream_t s) {
     using T = fp8_t;
     switch (cfg) {
-        case 80: return sp_launch<T, 128, 128, 2, 2, 2, 2, 8>(g, s);    // 64x64 per wave
-        case 81: return sp_launch<T, 128, 160, 2, 2, 2, 2, 8>(g, s);    // 64x80 per wave, 2 blocks per CU
-        case 82: return sp_launch<T, 256, 160, 4, 2, 2, 2, 8>(g, s);    // 8 waves, 64x80 per wave
-        // (256x256 does not fit: 128 accumulator + 96 operand VGPRs per lane spill)
-        case 85: return sp_launch<T, 64, 160, 2, 2, 1, 2, 8>(g, s);     // small M
-        case 86: return sp_launch<T, 64, 64, 2, 2, 1, 2, 8>(g, s);
-        case 88: return sp_launch<T, 128, 160, 2, 2, 2, 2, 0>(g, s);    // direct epilogue (ragged N)
+        SS_SP_FP8_TILES(SS_SP_CASE)
         default: return 1;
     }
 }
 #else
-// cfg -> tile configuration <BM, BN, WM, WN, NH, NS, FLAGS>.  160-wide tiles: every SDXL channel count
-// (640 ... 10240) is a multiple of 160.
 #if SS_SP_CONV
 template <typename T> int gemm_sp_dispatch_conv(int cfg, const GemmArgs& g, hipStream_t s) {
 #else
 template <typename T> int gemm_sp_dispatch(int cfg, const GemmArgs& g, hipStream_t s) {
 #endif
     switch (cfg) {
-        case 20: return sp_launch<T, 128, 128, 2, 2, 1, 2, 0>(g, s);
-        case 21: return sp_launch<T, 128, 64, 2, 2, 1, 2, 0>(g, s);
-        case 22: return sp_launch<T, 64, 64, 2, 2, 1, 2, 0>(g, s);
-        case 23: return sp_launch<T, 256, 128, 4, 2, 1, 2, 0>(g, s);
-        case 24: return sp_launch<T, 256, 256, 2, 4, 2, 2, 0>(g, s);   // 8 waves, 128x64 per wave, A in halves
-        case 26: return sp_launch<T, 128, 160, 2, 2, 1, 2, 0>(g, s);   // 2 blocks per CU
-        case 28: return sp_launch<T, 128, 320, 2, 4, 1, 2, 0>(g, s);   // 8 waves, 64x80 per wave, one block per CU
-        case 29: return sp_launch<T, 64, 160, 2, 2, 1, 2, 0>(g, s);    // 32x80 per wave: small-M shapes
-        case 30: return sp_launch<T, 256, 160, 4, 2, 1, 2, 0>(g, s);   // 8 waves, 64x80 per wave, uneven DMA deal
-        case 31: return sp_launch<T, 256, 160, 4, 2, 1, 3, 0>(g, s);   // + 3-slot ring (156 KB)
-        case 32: return sp_launch<T, 256, 160, 4, 2, 1, 3, 1>(g, s);   // + setprio
-        case 33: return sp_launch<T, 256, 160, 4, 2, 1, 3, 3>(g, s);   // + persistent
-        case 34: return sp_launch<T, 256, 256, 2, 4, 2, 2, 1>(g, s);   // 256x256 + setprio
-        case 35: return sp_launch<T, 256, 256, 2, 4, 2, 2, 2>(g, s);   // 256x256 persistent
-        case 36: return sp_launch<T, 256, 256, 2, 4, 2, 2, 3>(g, s);   // 256x256 persistent + setprio
-        case 37: return sp_launch<T, 128, 160, 2, 2, 1, 2, 1>(g, s);   // 128x160 + setprio
-        case 38: return sp_launch<T, 256, 160, 4, 2, 1, 2, 2>(g, s);   // 256x160 double-buffered, persistent
-        case 39: return sp_launch<T, 128, 320, 2, 4, 1, 2, 2>(g, s);   // 128x320 persistent
-        case 40: return sp_launch<T, 256, 256, 2, 4, 2, 2, 6>(g, s);   // 256x256 persistent, DMA spread between MFMAs
-        case 41: return sp_launch<T, 128, 160, 2, 2, 1, 2, 4>(g, s);   // 128x160, DMA spread
-        case 42: return sp_launch<T, 256, 160, 4, 2, 1, 3, 4>(g, s);   // 256x160 3-slot ring, DMA spread
-        case 43: return sp_launch<T, 256, 160, 4, 2, 1, 2, 6>(g, s);   // 256x160 persistent, DMA spread
-        case 44: return sp_launch<T, 128, 320, 2, 4, 1, 2, 4>(g, s);   // 128x320, DMA spread
-        case 45: return sp_launch<T, 256, 128, 4, 2, 1, 2, 4>(g, s);   // 256x128, DMA spread
-        case 46: return sp_launch<T, 128, 128, 2, 2, 1, 2, 4>(g, s);   // 128x128, DMA spread
-        case 60: return sp_launch<T, 256, 256, 2, 4, 2, 2, 11>(g, s);  // 256x256 persistent + setprio, LDS-staged epilogue
-        case 61: return sp_launch<T, 128, 160, 2, 2, 1, 2, 8>(g, s);   // 128x160, staged epilogue
-        case 62: return sp_launch<T, 256, 160, 4, 2, 1, 3, 12>(g, s);  // 256x160 3-slot ring, DMA spread, staged (strips in the ring)
-        case 63: return sp_launch<T, 128, 320, 2, 4, 1, 2, 8>(g, s);   // 128x320, staged
-        case 64: return sp_launch<T, 256, 160, 4, 2, 1, 2, 10>(g, s);  // 256x160 persistent, staged
-        case 65: return sp_launch<T, 128, 128, 2, 2, 1, 2, 8>(g, s);   // 128x128, staged
-        case 66: return sp_launch<T, 256, 128, 4, 2, 1, 2, 8>(g, s);   // 256x128, staged
-        case 67: return sp_launch<T, 64, 160, 2, 2, 1, 2, 8>(g, s);    // 64x160, staged
-        case 68: return sp_launch<T, 128, 64, 2, 2, 1, 2, 8>(g, s);    // 128x64, staged
-        case 69: return sp_launch<T, 256, 256, 2, 4, 2, 2, 8>(g, s);   // 256x256, staged
-        case 70: return sp_launch<T, 64, 64, 2, 2, 1, 2, 8>(g, s);     // 64x64, staged
-        case 71: return sp_launch<T, 256, 160, 4, 2, 1, 2, 8>(g, s);   // 256x160 double-buffered, staged (strips behind the ring)
-        case 72: return sp_launch<T, 128, 320, 2, 4, 1, 2, 10>(g, s);  // 128x320 persistent, staged
+        SS_SP_TILES(SS_SP_CASE)
 #if !SS_SP_CONV
-        // split-K tiles (grid.y K ranges, fp32 partial sums): small-M weight-streaming GEMMs of the LLaMA block continuation
-        case 300: return sp_launch<T, 128, 128, 2, 2, 1, 2, 64>(g, s);
-        case 301: return sp_launch<T, 128, 64, 2, 2, 1, 2, 64>(g, s);
-        // 200 + staged id: the same tile whose epilogue also accumulates the row statistics of its output (FLAGS | 32):
-        // the producers of the UNet's LayerNorm inputs — attn.to_out / ff.net.2 (+ residual), proj_in; N = 640 | 1280
-        case 261: return sp_launch<T, 128, 160, 2, 2, 1, 2, 40>(g, s);
-        case 262: return sp_launch<T, 256, 160, 4, 2, 1, 3, 44>(g, s);
-        case 263: return sp_launch<T, 128, 320, 2, 4, 1, 2, 40>(g, s);
-        case 264: return sp_launch<T, 256, 160, 4, 2, 1, 2, 42>(g, s);
-        case 265: return sp_launch<T, 128, 128, 2, 2, 1, 2, 40>(g, s);
-        case 267: return sp_launch<T, 64, 160, 2, 2, 1, 2, 40>(g, s);
-        case 271: return sp_launch<T, 256, 160, 4, 2, 1, 2, 40>(g, s);
-        case 272: return sp_launch<T, 128, 320, 2, 4, 1, 2, 42>(g, s);
-        // 100 + staged id: the same tile with the folded-LayerNorm epilogue (FLAGS | 16)
-        case 160: return sp_launch<T, 256, 256, 2, 4, 2, 2, 27>(g, s);
-        case 161: return sp_launch<T, 128, 160, 2, 2, 1, 2, 24>(g, s);
-        case 162: return sp_launch<T, 256, 160, 4, 2, 1, 3, 28>(g, s);
-        case 163: return sp_launch<T, 128, 320, 2, 4, 1, 2, 24>(g, s);
-        case 164: return sp_launch<T, 256, 160, 4, 2, 1, 2, 26>(g, s);
-        case 165: return sp_launch<T, 128, 128, 2, 2, 1, 2, 24>(g, s);
-        case 166: return sp_launch<T, 256, 128, 4, 2, 1, 2, 24>(g, s);
-        case 167: return sp_launch<T, 64, 160, 2, 2, 1, 2, 24>(g, s);
-        case 168: return sp_launch<T, 128, 64, 2, 2, 1, 2, 24>(g, s);
-        case 169: return sp_launch<T, 256, 256, 2, 4, 2, 2, 24>(g, s);
-        case 170: return sp_launch<T, 64, 64, 2, 2, 1, 2, 24>(g, s);
-        case 171: return sp_launch<T, 256, 160, 4, 2, 1, 2, 24>(g, s);
-        case 172: return sp_launch<T, 128, 320, 2, 4, 1, 2, 26>(g, s);
+        SS_SP_SPLITK_TILES(SS_SP_CASE)
 #endif
-        default: return 1;
+        default: break;
     }
+#if !SS_SP_CONV
+    SS_SP_TILES(SS_SP_ROWSTAT)
+    SS_SP_TILES(SS_SP_LNFOLD)
+#endif
+    return 1;
 }
 
 #if SS_SP_CONV

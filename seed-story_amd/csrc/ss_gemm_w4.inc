@@ -89,16 +89,14 @@ template <> struct Mma32<fp8_t> {
 // pins a value of an accumulator block at this point of the (volatile-ordered) asm stream
 __device__ __forceinline__ void w4_tie(f32x16_t& c) { asm volatile("" : "+a"(c)); }
 
-static int w4_num_cus() {
-    static int n = 0;
-    if (!n) {
-        int dev = 0;
-        hipDeviceProp_t p;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) n = p.multiProcessorCount;
-        if (n <= 0) n = 256;
-    }
-    return n;
-}
+// LDS layout, for the kernel and its launcher: two ring slots of [A rows | W rows] x 128 B, behind them a 32-row epilogue strip per wave
+template <int BM, int BN, int WN>
+struct W4Lds {
+    static constexpr int TILE_BYTES = (BM + BN) * 128;
+    static constexpr int STG_WAVE = 32 * (BN / WN) * 2;
+    static constexpr int BYTES = 2 * TILE_BYTES + 4 * STG_WAVE;
+    static_assert(BYTES <= 163840, "LDS budget");
+};
 
 // ---- epilogues ----------------------------------------------------------------------------------------------------
 // value pipeline shared by both: t = acc + bias -> (GELU) -> round to T -> (+ rowvec, round)  [then GEGLU pair / residual]
@@ -224,9 +222,8 @@ __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(const GemmArgs g, const
     constexpr bool F8 = EB == 1;
     static_assert(KS == 4 || (KS == 2 && D0 == 0 && D1 == 0 && !CONV), "two-k-step tiles issue the whole next-but-one tile in their last k-step");
     using TO = typename OutT<T>::type;
-    constexpr int TILE_BYTES = (BM + BN) * 128;
-    constexpr int STG_WAVE = 32 * TN * 2;                    // epilogue strip of one wave
-    static_assert(2 * TILE_BYTES + 4 * STG_WAVE <= 163840, "LDS budget");
+    using Lds = W4Lds<BM, BN, WN>;
+    constexpr int TILE_BYTES = Lds::TILE_BYTES, STG_WAVE = Lds::STG_WAVE;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -494,26 +491,16 @@ static int w4_launch(const GemmArgs& g, hipStream_t s) {
     const bool staged_ok = (g.N % (BN / WN) == 0) && (((size_t)g.C | (size_t)g.residual | (size_t)g.bias | (size_t)g.rowvec) & A16) == 0 &&
                            ((g.ldc | g.ldr | g.rowvec_ld) & 7) == 0;
     if (!staged_ok) return 1;
-    const size_t lds = (size_t)2 * (BM + BN) * 128 + (size_t)4 * 32 * (BN / WN) * 2;
-    const int total = cdiv(g.M, BM) * cdiv(g.N, BN);
-    int grid = total;
-    if (FLAGS & 2) {
-        const int cap = w4_num_cus();          // multiple of 8: tile vid and vid + grid share an XCD
-        if (grid > cap) grid = cap;
-    }
-    auto kern = gemm_w4_kernel<T, BM, BN, WM, WN, D3, D0, FLAGS, CONV>;
-    SS_DYN_LDS(kern, lds);
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds, s, g, total);
-    SS_LAUNCH_CHECK("gemm_w4");
-    return SS_OK;
+    return launch_tiles<gemm_w4_kernel<T, BM, BN, WM, WN, D3, D0, FLAGS, CONV>>("gemm_w4", g, cdiv(g.M, BM) * cdiv(g.N, BN),
+                                                                                (FLAGS & 2) ? num_cus() : 0, 256, W4Lds<BM, BN, WN>::BYTES, s);
 }
 
 // cfg ids 90-99 (the tile table stores cfg + 100 * xcd_group, so ids stay below 100)
 #if defined(SS_W4_FP8)
 int gemm_w4_dispatch_fp8(int cfg, const GemmArgs& g, hipStream_t s) {
     switch (cfg) {
-        case 95: return w4_launch<fp8_t, 256, 256, 2, 2, 16, 0, 2>(g, s);   // persistent; the whole tile t+2 is issued in the last k-step of tile t
-        case 96: return w4_launch<fp8_t, 256, 256, 2, 2, 16, 0, 0>(g, s);
+#define SS_W4_CASE(id, BM, BN, WM, WN, D3, D0, FLAGS, VAR) case id: return w4_launch<fp8_t, BM, BN, WM, WN, D3, D0, FLAGS>(g, s);
+        SS_W4_FP8_TILES(SS_W4_CASE)
         default: return 1;
     }
 }

@@ -7,8 +7,6 @@
 
 namespace ss {
 
-template <typename T> int gemm_w4_dispatch(int cfg, const GemmArgs& g, hipStream_t s);
-template <typename T> int gemm_w4_dispatch_conv(int cfg, const GemmArgs& g, hipStream_t s);
 template <> int gemm_w4_dispatch<bf16_t>(int, const GemmArgs&, hipStream_t) { return 1; }
 template <> int gemm_w4_dispatch<f16_t>(int, const GemmArgs&, hipStream_t) { return 1; }
 template <> int gemm_w4_dispatch_conv<bf16_t>(int, const GemmArgs&, hipStream_t) { return 1; }
