@@ -52,7 +52,12 @@ int ss_abi_version(void);
 /* Device properties of the current HIP device: out[0]=CU count, out[1]=is_gfx950,
  * out[2]=total HBM MiB, out[3]=wavefront size. */
 int ss_device_info(int32_t out[4]);
-/* Runtime tuning knobs (grid sizes, rows per wave, …); unknown keys are accepted. */
+/* Runtime tuning knobs (kernel choices, grid sizes, arithmetic modes, …).  The complete list, with defaults and one line per
+ * knob, is csrc/ss_knobs.h; a key that is not in it does not exist.
+ *   ss_set_tuning: stores the value of a known key; an unknown or NULL key returns SS_EINVAL and ss_last_error() names it.
+ *                  Counters (gemv_split_refused) may be set too, which is how a caller resets them.
+ *   ss_get_tuning: the value of a known key that has been set or has a constant default; `dflt` for a known key that is still
+ *                  unset (gemm_fp8_swz, img_block_decode: the default is decided where the knob is read) and for an unknown key. */
 int ss_set_tuning(const char* key, int value);
 int ss_get_tuning(const char* key, int dflt);
 

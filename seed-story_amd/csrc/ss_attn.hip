@@ -1237,7 +1237,7 @@ static int flash3p_launch(const AttnArgs& a, int64_t batch, hipStream_t s) {
     // 4 / 8 / 16 waves): (16, 10 heads, 4096) 839 / 749 / 720 us; (16, 20, 1024) 120 / 112 / 124; (8, 10, 4096) 428 / 380 / 406;
     // (2, 10, 4096) 119 / 139 / 129 — small launches keep 4 waves.
     const int64_t bh = batch * a.n_heads;
-    const int aw = tuning_get("attn_waves", 0);
+    const int aw = knob(K_attn_waves);
     const bool many = a.ragged || a.kv_len >= 512;     // one- or two-tile contexts (the UNet's cross-attention) gain nothing from sharing tiles
     const bool w16 = !PIPE && (aw == 16 || (aw == 0 && many && a.q_len >= 2048 && (int64_t)cdiv(a.q_len, 512) * bh >= 1024));
     const bool w8 = !PIPE && !w16 && (aw == 8 || (aw == 0 && many && a.q_len >= 512 && (int64_t)cdiv(a.q_len, 256) * bh >= 1024));
@@ -1245,7 +1245,7 @@ static int flash3p_launch(const AttnArgs& a, int64_t batch, hipStream_t s) {
     AttnArgs a2 = a;
     dim3 grid((unsigned)nqb, (unsigned)bh);
     a2.xcd_heads = 0;
-    if (bh % 8 == 0 && nqb > 1 && tuning_get("attn_xcd", 1)) {
+    if (bh % 8 == 0 && nqb > 1 && knob(K_attn_xcd)) {
         a2.xcd_heads = nqb;
         grid = dim3((unsigned)(nqb * bh), 1);
     }
@@ -1274,7 +1274,7 @@ static int flash3_launch_hd(const AttnArgs& a, int64_t batch, hipStream_t s) {
     AttnArgs a2 = a;
     dim3 grid((unsigned)nqb, (unsigned)bh);
     a2.xcd_heads = 0;
-    if (bh % 8 == 0 && nqb > 1 && tuning_get("attn_xcd", 1)) {   // XCD k owns heads k, k+8, ...
+    if (bh % 8 == 0 && nqb > 1 && knob(K_attn_xcd)) {   // XCD k owns heads k, k+8, ...
         a2.xcd_heads = nqb;
         grid = dim3((unsigned)(nqb * bh), 1);
     }
@@ -1315,16 +1315,15 @@ int attention_launch(const AttnArgs& a, int64_t batch, hipStream_t s) {
     if (a.q_len == 0 || batch == 0) return SS_OK;
     SS_REQUIRE(a.kv_len > 0, "attention: kv_len == 0");
     if constexpr (V == 8) {
-        // v2 (DMA-staged, 32 rows per wave) whenever there is enough query work to fill its 128-row blocks
         // v3 / v2 (DMA-staged, 32 rows per wave) whenever there is enough query work to fill their 128-row blocks.
         // attn_ver: 6 (default since round 5) = v3p without the S(t+1) prefetch for head_dim <= 64 (loop-invariant DMA addresses;
         // measured -3 ... -4 % per launch on the UNet's self-attention shapes and bit-equal to v3, profiles/round5_attn_ab.json),
         // v3 for head_dim 128; 3 = v3 with the swizzled V image everywhere, 4 = v3 with the linear V image,
         // 5 = v3p WITH the prefetch (measured slower than v3: 2 waves per SIMD)
-        const int ver = tuning_get("attn_ver", 6);
+        const int ver = knob(K_attn_ver);
 #if SS_EXPERIMENTAL
         // option (1e): a short context (the UNet's cross-attention over 64 image-feature tokens) with K / V held in registers
-        if (a.hd == 64 && a.kv_len <= 64 && !a.causal_br && !a.ragged && a.q_len >= 128 && ver >= 3 && tuning_get("attn_cross64", 0))
+        if (a.hd == 64 && a.kv_len <= 64 && !a.causal_br && !a.ragged && a.q_len >= 128 && ver >= 3 && knob(K_attn_cross64))
             return cross_attn64_launch<T>(a, batch, s);
 #endif
         if (ver == 5 && a.q_len >= 32 && a.hd <= 64) return flash3p_launch<T, true>(a, batch, s);     // options: v3p (see (1d))
@@ -1552,7 +1551,7 @@ __global__ void attn_combine_kernel(const float* __restrict__ part, T* __restric
 // KV splits per (head, slot): 16 at one slot (512 blocks of ~25 keys at S = 400 — enough to fill the chip, measured
 // optimum), fewer when several story slots already multiply the block count (4 slots: 4 splits, -6 % token time)
 static inline int decode_nsplit(int nb) {
-    int n = tuning_get("attn_decode_nsplit", 0);
+    int n = knob(K_attn_decode_nsplit);
     if (n <= 0) n = 16 / (nb < 1 ? 1 : nb);
     return n <= 4 ? 4 : n <= 8 ? 8 : n <= 16 ? 16 : 32;
 }

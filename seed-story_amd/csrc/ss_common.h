@@ -14,6 +14,7 @@
 #include <atomic>
 
 #include "../../include/seedstory_hip.h"
+#include "ss_knobs.h"
 
 namespace ss {
 
@@ -224,8 +225,5 @@ inline int ensure_dyn_lds(const void* kern, size_t bytes, std::atomic<uint64_t>&
 
 inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 inline size_t dtype_size(int dt) { return dt == SS_F32 ? 4 : 2; }
-
-int tuning_get(const char* key, int dflt);
-void tuning_set(const char* key, int value);   // library-side counters readable through ss_get_tuning
 
 }  // namespace ss

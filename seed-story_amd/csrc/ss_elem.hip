@@ -205,7 +205,7 @@ int layernorm_launch(const void* x, const void* w, const void* b, void* y, int64
     SS_REQUIRE(cols % V == 0 && cols / V <= kNormMaxPacks * 256, "layernorm: cols=%lld unsupported", (long long)cols);
     if (rows == 0) return SS_OK;
     if (cols / V <= 256 && rows >= 256) {
-        const int R = rows >= 8192 ? tuning_get("layernorm_rows_per_wave", 1) : 1;
+        const int R = rows >= 8192 ? knob(K_layernorm_rows_per_wave) : 1;
         if (R == 2)
             hipLaunchKernelGGL((layernorm_wave_kernel<T, 2>), dim3((unsigned)cdiv(rows, 8)), dim3(256), 0, s, (const T*)x,
                                (const T*)w, (const T*)b, (T*)y, rows, (int)cols, eps);

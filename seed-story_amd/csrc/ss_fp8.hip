@@ -108,7 +108,7 @@ int quantize_launch(const void* x, int64_t ld, int64_t M, int64_t K, void* q, fl
 
 // closed-form tile rule for the fp8 kernels (the shapes are the UNet's: M = batch x tokens, N, K multiples of 160 / 128)
 static int pick_cfg_fp8(int64_t M, int64_t N, int64_t K) {
-    const int forced = tuning_get("gemm_fp8_cfg", 0);
+    const int forced = knob(K_gemm_fp8_cfg);
     if (forced) return forced;
     if (N % 160 != 0) {
         if (N % 16 != 0) return 88;
@@ -146,8 +146,8 @@ int ss_gemm_fp8(const void* A8, const float* scale_a, const void* W8, const floa
     // rows of the tile that will run: the id's own, or for an id the 4-wave dispatcher does not know its fallback below (82)
     const ss::GemmTile tile = ss::fp8_tile(cfg);
     const int mt = tile.id ? tile.BM : cfg >= 90 ? ss::fp8_tile(82).BM : 128;
-    g.swz = ss::tuning_get("gemm_fp8_swz", (int)((M + mt - 1) / mt) >= 16 ? 8 : 0);
-    if (ss::tuning_get("gemm_fp8_debug", 0)) fprintf(stderr, "ss_gemm_fp8 [%lld,%lld,%lld] epi %d cfg %d swz %d\n", (long long)M, (long long)N, (long long)K, epilogue, cfg, g.swz);
+    g.swz = ss::knob_or(ss::K_gemm_fp8_swz, (int)((M + mt - 1) / mt) >= 16 ? 8 : 0);
+    if (ss::knob(ss::K_gemm_fp8_debug)) fprintf(stderr, "ss_gemm_fp8 [%lld,%lld,%lld] epi %d cfg %d swz %d\n", (long long)M, (long long)N, (long long)K, epilogue, cfg, g.swz);
     int rc = 1;
     if (cfg >= 90) {        // 4-wave / AGPR-accumulator 256x256 tile (ss_gemm_w4.inc); ineligible shapes take the 8-wave 256x160 tile
         rc = ss::gemm_w4_dispatch_fp8(cfg, g, (hipStream_t)stream);

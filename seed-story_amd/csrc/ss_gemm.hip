@@ -272,7 +272,7 @@ static int gemm_launch_cfg(const GemmArgs& g, hipStream_t s) {
     const size_t lds = (size_t)(BM + BN) * LS * sizeof(T);
     dim3 grid((unsigned)cdiv(g.N, BN), (unsigned)cdiv(g.M, BM));
     if constexpr (V == 4 && KT == 1) {      // fp32 tensors: the split-bf16 "gate mode" instead of the exact fp32 FMA chain
-        if (tuning_get("gemm_f32_split", 0)) {
+        if (knob(K_gemm_f32_split)) {
             constexpr int SKT = 2;                                  // 64-wide K tiles (see the kernel's header comment)
             constexpr int SLS = 8 * SKT * V + V;
             const size_t slds = (size_t)(BM + BN) * SLS * sizeof(T);
@@ -280,7 +280,7 @@ static int gemm_launch_cfg(const GemmArgs& g, hipStream_t s) {
             GemmArgs g2 = g;
             // bands of G N tiles walked M-fastest (default 16: [7304, 12288, 4096] 2266 -> 2199 us, [7304, 22016, 4096] 4333 -> 4059 us,
             // the other MLLM shapes unchanged, profiles/round5_split_gemm_bench.json); 0 = the plain N-fastest grid
-            g2.swz = -tuning_get("gemm_f32_split_order", 16);
+            g2.swz = -knob(K_gemm_f32_split_order);
             if (slds > 64 * 1024) {
                 if (g.conv_Cin > 0) SS_DYN_LDS((gemm_kernel<T, BM, BN, WM, WN, SKT, true, true>), slds);
                 else SS_DYN_LDS((gemm_kernel<T, BM, BN, WM, WN, SKT, false, true>), slds);
@@ -491,8 +491,8 @@ static int gemm_dispatch_cfg(int cfg, const GemmArgs& g, hipStream_t s) {
                 // [7304, 12288, 4096] 2447 -> 2290 us, [7304, 22016, 4096] 4883 -> 4362 us; N = 4096 equal; the 528-row block is
                 // 40-70 % SLOWER on it, 128x256 never wins) — knob gemm_f32_split_tile: 0 = this rule, 1 / 2 = force 256x128 / 128x256,
                 // 3 = force 128x128
-                if (tuning_get("gemm_f32_split", 0)) {
-                    const int st = tuning_get("gemm_f32_split_tile", 0);
+                if (knob(K_gemm_f32_split)) {
+                    const int st = knob(K_gemm_f32_split_tile);
                     if (st == 1 || (st == 0 && g.conv_Cin == 0 && g.M >= 2048 && g.N >= 8192)) return gemm_launch_cfg<T, 256, 128, 4, 2>(g, s);
                     if (st == 2) return gemm_launch_cfg<T, 128, 256, 2, 4>(g, s);
                 }
@@ -538,7 +538,7 @@ static TuneKey make_key(int dtype, const GemmArgs& g) {
 // (narrow-N register-staged tiles); otherwise the largest tile that still yields ~one block per CU, 160-wide
 // where N is a multiple of 160 (every SDXL width), 256-row tiles once there are >= 256 of them.
 static int pick_cfg(const GemmArgs& g, bool f32) {
-    const int force = tuning_get("gemm_cfg", 0);
+    const int force = knob(K_gemm_cfg);
     if (force) return force;
     const int64_t M = g.M, N = g.N;
     if (M <= 128) return 3;
@@ -562,7 +562,7 @@ static int pick_cfg(const GemmArgs& g, bool f32) {
 template <typename T>
 static int lookup_cfg(GemmArgs& g) {
     const int fallback = pick_cfg(g, Tr<T>::kVec != 8);
-    if (Tr<T>::kVec != 8 || g.M <= 128 || tuning_get("gemm_cfg", 0) || !tuning_get("gemm_table", 1)) return fallback;
+    if (Tr<T>::kVec != 8 || g.M <= 128 || knob(K_gemm_cfg) || !knob(K_gemm_table)) return fallback;
     const TuneKey key = make_key(Tr<T>::kDtype, g);
     std::lock_guard<std::mutex> lk(g_tune_mutex);
     auto it = tune_cache().find(key);
@@ -626,7 +626,7 @@ static int tune_shape(GemmArgs g, void* ws, size_t ws_bytes, size_t a_elems, hip
         const int swzs[3] = {0, 4, 8};
         int best = -1, best_swz = 0;
         float best_ms = 1e30f;
-        const bool log = tuning_get("gemm_autotune_log", 0) != 0;
+        const bool log = knob(K_gemm_autotune_log) != 0;
         const int R = nW + nW / 2 > 12 ? nW + nW / 2 : 12;
         for (int c : kTuneCands) {
             for (int z : swzs) {
@@ -736,8 +736,8 @@ int gemm_launch(const void* A, const void* W, void* C, int64_t M, int64_t N, int
     SS_REQUIRE(!(epi & SS_EPI_RESIDUAL) || residual, "gemm: residual epilogue without residual");
     if (M == 0 || N == 0) return SS_OK;
     GemmArgs g = gemm_args(A, W, C, M, N, K, lda, ldw, ldc, epi, bias, residual, ldr);
-    g.swz = tuning_get("gemm_xcd_swizzle", 8);
-    if (tuning_get("gemm_epi_generic", 0)) g.epi |= SS_EPI_INTERNAL_GENERIC;
+    g.swz = knob(K_gemm_xcd_swizzle);
+    if (knob(K_gemm_epi_generic)) g.epi |= SS_EPI_INTERNAL_GENERIC;
     if (rowstat_out || rowpart) {
         // statistics epilogue: only the staged software-pipelined tiles 61..72 have it (ids + 200); 256x256 tiles (60 / 69)
         // and non-staged choices fall to the 160- / 128-wide staged tile of the shape
@@ -757,7 +757,7 @@ int gemm_launch(const void* A, const void* W, void* C, int64_t M, int64_t N, int
                 g.rowpart = rowpart;
                 g.rowpart_ld = (int)(N / tn);
             }
-            const bool force_fb = tuning_get("gemm_rowstat_fallback", 0) != 0;      // (tests)
+            const bool force_fb = knob(K_gemm_rowstat_fallback) != 0;      // (tests)
             int rc = force_fb ? 1 : gemm_sp_dispatch<T>(cfg + 200, g, s);
             if (rc == 1 && !rowpart && !force_fb) rc = gemm_sp_dispatch<T>(265, g, s);       // the 128x128 staged tile takes more shapes
             if (rc == 1) {
@@ -791,7 +791,7 @@ int conv3x3_launch(const void* x, const void* w, void* y, int64_t B, int64_t H, 
     conv_geometry(g, B, H, Wd, Cin, Cout, stride, up);
     g.A = x; g.W = w; g.C = y; g.bias = bias; g.residual = residual; g.epi = epi;
     g.rowvec = rowvec; g.rowvec_ld = rowvec_ld > 0 ? rowvec_ld : Cout;
-    g.swz = tuning_get("gemm_xcd_swizzle", 8);
+    g.swz = knob(K_gemm_xcd_swizzle);
     if (g.M == 0) return SS_OK;
     return gemm_dispatch_cfg<T>(lookup_cfg<T>(g), g, s);
 }
@@ -826,7 +826,7 @@ int gemm_lnfold_launch(const void* A, const void* Wg, void* C, int64_t M, int64_
                    (((size_t)ln_part) & 7) == 0, "ss_gemm_lnfold: row statistics / column vector missing or misaligned");
         if (M == 0 || N == 0) return SS_OK;
         GemmArgs g = gemm_args(A, Wg, C, M, N, K, K, K, ldc, epi, bias);
-        g.swz = tuning_get("gemm_xcd_swizzle", 8);
+        g.swz = knob(K_gemm_xcd_swizzle);
         g.scale_a = rstd; g.shift_a = shift; g.scale_w = colsum;
         g.ln_part = ln_part; g.ln_nstrip = (int)ln_nstrip; g.ln_inv_width = ln_width > 0 ? 1.0f / (float)ln_width : 0.f; g.ln_eps = ln_eps;
         int cfg = lookup_cfg<T>(g);
@@ -838,7 +838,7 @@ int gemm_lnfold_launch(const void* A, const void* Wg, void* C, int64_t M, int64_
         // 4 launches at [32768, 640, 640] on cfg 61 / 65 / 67 / 70, none on 62 / 68 / 60 — the fences do NOT fix it, the cause is
         // still open, the reroute stays.  The same run cleared the PRODUCER side: the rowpart statistics epilogue on the 4-wave
         // tiles 261 / 265 / 267 (and 262) gave 0 bad statistics rows and 0 bad value rows, and the plain epilogue on cfg 61 none.
-        if (const GemmTile t = sp_tile(cfg); t.WM * t.WN == 4 && !tuning_get("lnfold_w4", 0))
+        if (const GemmTile t = sp_tile(cfg); t.WM * t.WN == 4 && !knob(K_lnfold_w4))
             cfg = (t.BN == 160 || N % 160 == 0) ? 62 : 66;
         const int rc = gemm_sp_dispatch<T>(cfg + 100, g, s);
         if (rc == 1) {
@@ -978,12 +978,10 @@ int gemm_splitk_launch(const void* A, const void* W, void* C, int64_t M, int64_t
                        const void* residual, void* ws, size_t ws_bytes, hipStream_t s) {
     int cfg = 0, S = 0;
     if constexpr (Tr<T>::kVec == 8) {
-        if (tuning_get("gemm_splitk", 1)) splitk_plan(M, N, K, &cfg, &S);
+        if (knob(K_gemm_splitk)) splitk_plan(M, N, K, &cfg, &S);
     }
-    {
-        const int force = tuning_get("gemm_splitk_s", 0);
-        if (S && force >= 2 && force <= 8 && (size_t)force * M * N * sizeof(float) > ws_bytes) S = 0;   // forced count needs the room
-    }
+    const int force = knob(K_gemm_splitk_s);
+    if (S && force >= 2 && force <= 8 && (size_t)force * M * N * sizeof(float) > ws_bytes) S = 0;   // forced count needs the room
     if (!S || !ws || ws_bytes < (size_t)S * M * N * sizeof(float))
         return gemm_launch<T>(A, W, C, M, N, K, K, K, N, bias, residual, N, (bias ? SS_EPI_BIAS : 0) | (residual ? SS_EPI_RESIDUAL : 0), s);
     if constexpr (Tr<T>::kVec == 8) {
@@ -991,9 +989,8 @@ int gemm_splitk_launch(const void* A, const void* W, void* C, int64_t M, int64_t
         // row-major tile ids (measured, profiles/round3_splitk_microbench.json: the XCD-grouped order that puts the 3 - 4 row
         // tiles of a W column block on one XCD is 5 - 20 % SLOWER here — the row tiles then run back to back on few CUs
         // while the W stream of the other column blocks waits; with row-major ids the repeats hit the Infinity Cache)
-        g.swz = tuning_get("gemm_splitk_swz", 0);
+        g.swz = knob(K_gemm_splitk_swz);
         g.ksplit = S;
-        const int force = tuning_get("gemm_splitk_s", 0);
         if (force >= 2 && force <= 8 && force <= (int)(K / 64) / 2) g.ksplit = S = force;
         const int rc = gemm_sp_dispatch<T>(cfg, g, s);
         if (rc) {

@@ -887,12 +887,17 @@ __global__ __launch_bounds__(512) void gemv_split_f32_kernel(const GemvArgs a, c
     }
 }
 
+// MFMA forms, whole rounds: ceil(tiles / 256) tiles per workgroup on as few workgroups as that takes (688 tiles -> 230 x 3, not 256
+// workgroups of which 80 run a third round alone)
+static int gemv_mfma_grid(int ntiles) {
+    const int rounds = cdiv(ntiles, knob(K_gemv_mfma_blocks));
+    return cdiv(ntiles, rounds);
+}
+
 static int gemv_launch_split_f32(const GemvArgs& a, hipStream_t s) {
     const bool silu = (a.epi & SS_EPI_SILU_MUL) != 0;
     const int ntiles = cdiv(a.N, 16);
-    const int cus = tuning_get("gemv_mfma_blocks", 256);
-    const int rounds = cdiv(ntiles, cus);
-    const int blocks = cdiv(ntiles, rounds);
+    const int blocks = gemv_mfma_grid(ntiles);
     const int kmax = a.K < kGsSlice ? a.K : kGsSlice;
     const size_t lds = (size_t)16 * (kmax * 2 + 32) + (size_t)kGvWaves * (silu ? 2 : 1) * 256 * sizeof(float);
     auto kern = silu ? gemv_split_f32_kernel<true> : gemv_split_f32_kernel<false>;
@@ -908,8 +913,7 @@ template <typename T>
 static bool gemv_mfma_eligible(const GemvArgs& a) {
     if (a.K <= kGvWaves * kGvSteps * 32) return true;
     // the packed 43-step form: the LLaMA-7B MLP width only, <= 8 sequences, no RMSNorm prologue
-    return a.K == kGvWaves * 43 * 32 && a.nb <= 8 && !a.norm_w && !tuning_get("gemv_mfma_generic", 0) &&
-           tuning_get("gemv_mfma_long", 1);
+    return a.K == kGvWaves * 43 * 32 && a.nb <= 8 && !a.norm_w && !knob(K_gemv_mfma_generic) && knob(K_gemv_mfma_long);
 }
 
 template <typename T>
@@ -918,15 +922,11 @@ static int gemv_launch_mfma(const GemvArgs& a, hipStream_t s) {
     const int ksteps = cdiv(a.K, 32);
     const int spw = cdiv(ksteps, kGvWaves);
     const int ntiles = cdiv(a.N, 16);
-    // whole rounds: ceil(tiles / 256) tiles per workgroup on as few workgroups as that takes (688 tiles -> 230 x 3, not 256
-    // workgroups of which 80 run a third round alone)
-    const int cus = tuning_get("gemv_mfma_blocks", 256);
-    const int rounds = cdiv(ntiles, cus);
-    const int blocks = cdiv(ntiles, rounds);
-    const bool generic = tuning_get("gemv_mfma_generic", 0) != 0;
+    const int blocks = gemv_mfma_grid(ntiles);
+    const bool generic = knob(K_gemv_mfma_generic) != 0;
     // plain loads, not non-temporal ones: a fragment load touches HALF a 128-byte line per row and the next instruction the
     // other half; measured on the five LLaMA-7B shapes at 8 sequences, nt is 3 - 13 % slower (lm_head 52.0 vs 46.2 us)
-    const bool nt = tuning_get("gemv_mfma_nt", 0) != 0;
+    const bool nt = knob(K_gemv_mfma_nt) != 0;
     const dim3 g((unsigned)blocks), b(512);
 #define SS_GV_EXACT(SPW)                                                                                                  \
     do {                                                                                                                  \
@@ -954,18 +954,21 @@ static int gemv_launch_reg(const GemvArgs& a, int blocks, hipStream_t s) {
     return SS_OK;
 }
 
+// x slices live in registers while batch * NIT <= reg budget (16 packs = 64 VGPRs at batch 2, NIT = 8); else they are staged in LDS
+static bool gemv_x_in_regs(int nb, int nit) {
+    return nit <= 8 && nb * nit <= knob(K_gemv_x_reg_packs) && !knob(K_gemv_force_lds);
+}
+
 template <typename T, int NB>
 static int gemv_launch_nb(const GemvArgs& a, int nit, int64_t waves, hipStream_t s) {
     constexpr int V = Tr<T>::kVec;
-    const int max_blocks = tuning_get("gemv_max_blocks", 256 * 8);
+    const int max_blocks = knob(K_gemv_max_blocks);
     auto blocks_for = [&](int wpb) {
         int64_t b = (waves + wpb - 1) / wpb;
         if (b > max_blocks) b = max_blocks;
         return (int)(b < 1 ? 1 : b);
     };
-    // x slices live in registers while NB * NIT <= reg budget (16 packs = 64 VGPRs at NB=2, NIT=8)
-    const int reg_budget = tuning_get("gemv_x_reg_packs", 16);
-    if (nit <= 8 && NB * nit <= reg_budget && !tuning_get("gemv_force_lds", 0)) {
+    if (gemv_x_in_regs(NB, nit)) {
         const int blocks = blocks_for(4);
         if (nit <= 1) return gemv_launch_reg<T, 1, NB>(a, blocks, s);
         if (nit <= 2) return gemv_launch_reg<T, 2, NB>(a, blocks, s);
@@ -997,6 +1000,24 @@ static int gemv_launch_nb(const GemvArgs& a, int nit, int64_t waves, hipStream_t
 }
 
 template <typename T>
+int gemv_launch(const GemvArgs& a0, hipStream_t s);
+
+// two sweeps of half the sequences each
+template <typename T>
+static int gemv_launch_halves(const GemvArgs& a, hipStream_t s) {
+    const int h1 = a.nb / 2;
+    GemvArgs lo = a, hi = a;
+    lo.nb = h1;
+    hi.nb = a.nb - h1;
+    hi.x = (const T*)a.x + (int64_t)h1 * a.x_ld;
+    hi.y = (T*)a.y + (int64_t)h1 * a.y_ld;
+    if (a.residual) hi.residual = (const T*)a.residual + (int64_t)h1 * a.res_ld;
+    if (a.done_flag) hi.done_flag = a.done_flag + (int64_t)h1 * a.done_stride;
+    const int rc = gemv_launch<T>(lo, s);
+    return rc ? rc : gemv_launch<T>(hi, s);
+}
+
+template <typename T>
 int gemv_launch(const GemvArgs& a0, hipStream_t s) {
     constexpr int V = Tr<T>::kVec;
     GemvArgs a = a0;
@@ -1007,26 +1028,28 @@ int gemv_launch(const GemvArgs& a0, hipStream_t s) {
                "gemv: SILU_MUL cannot be combined with other epilogues");
     SS_REQUIRE(!(epi & SS_EPI_GELU), "gemv: GELU epilogue not supported");
     SS_REQUIRE(a.nb >= 1 && a.nb <= 16, "gemv: batch %d unsupported (1..16)", a.nb);
-    a.use_nt = tuning_get("gemv_nt", 1);
+    a.use_nt = knob(K_gemv_nt);
     // 3+ sequences (knob): the MFMA form when the shape allows it (16-bit, 8 waves x 16 steps of 32 cover K, or the packed
     // 11008-deep form).  Measured on the five LLaMA-7B projections (tools/gemv_bench.py, rotating weights, us per launch):
     // dot-product kernels at 1 | 4 sequences 20.7 9.9 32.3 19.3 46.1 | 24.4 11.0 39.0 25.7 47.8; MFMA form at 8 sequences
     // 24.2 9.9 37.3 21.9 46.2 — one sequence stays with the dot-product kernel, 3 and more go through the matrix core.
+    const bool mfma_nb = a.nb >= knob(K_gemv_mfma_min_nb);
     if constexpr (V == 8) {
-        if (a.nb >= tuning_get("gemv_mfma_min_nb", 3) && gemv_mfma_eligible<T>(a)) return gemv_launch_mfma<T>(a, s);
+        if (mfma_nb && gemv_mfma_eligible<T>(a)) return gemv_launch_mfma<T>(a, s);
     } else {
         // fp32 tensors in the gate mode: 3..8 sequences through the split-bf16 MFMA form (one sweep of the weights instead of two
         // 4-sequence sweeps of the exact dot-product kernels); the RMSNorm prologue needs the whole row in one K slice; SiLU pairs too
-        if (a.nb >= tuning_get("gemv_mfma_min_nb", 3) && a.nb <= 8 && tuning_get("gemm_f32_split", 0) && K % 8 == 0 &&
+        const bool gate = mfma_nb && a.nb <= 8 && knob(K_gemm_f32_split);
+        if (gate && K % 8 == 0 &&
             ((!a.norm_w && !(epi & SS_EPI_SILU_MUL)) || K <= kGsSlice) && (((size_t)a.x | (size_t)a.W | (size_t)a.norm_w) & 15) == 0 &&
             (a.x_ld & 3) == 0)
             return gemv_launch_split_f32(a, s);
         // the gate mode was asked for and this launch cannot take the split form (RMSNorm / SiLU row wider than one 4096 slice,
         // or 16-byte misalignment): it runs as two EXACT sweeps — correct, slower, and a different arithmetic than the rest of
-        // the run.  Counted (tuning key gemv_split_refused, readable through ss_get_tuning) and reported once.
-        if (a.nb >= tuning_get("gemv_mfma_min_nb", 3) && a.nb <= 8 && tuning_get("gemm_f32_split", 0)) {
+        // the run.  Counted (knob gemv_split_refused) and reported once.
+        if (gate) {
             static bool told = false;
-            tuning_set("gemv_split_refused", tuning_get("gemv_split_refused", 0) + 1);
+            knob_add(K_gemv_split_refused, 1);
             if (!told) {
                 told = true;
                 fprintf(stderr, "[ss] gate mode: GEMV [N=%d, K=%d, %d slots]%s%s runs as exact 4-slot sweeps (split form needs norm / SiLU rows <= %d "
@@ -1034,39 +1057,17 @@ int gemv_launch(const GemvArgs& a0, hipStream_t s) {
             }
         }
     }
-    if (a.nb > 4) {      // no MFMA form for this shape / type: two sweeps of half the sequences each
-        const int h1 = a.nb / 2;
-        GemvArgs lo = a, hi = a;
-        lo.nb = h1;
-        hi.nb = a.nb - h1;
-        hi.x = (const T*)a.x + (int64_t)h1 * a.x_ld;
-        hi.y = (T*)a.y + (int64_t)h1 * a.y_ld;
-        if (a.residual) hi.residual = (const T*)a.residual + (int64_t)h1 * a.res_ld;
-        if (a.done_flag) hi.done_flag = a.done_flag + (int64_t)h1 * a.done_stride;
-        const int rc = gemv_launch<T>(lo, s);
-        return rc ? rc : gemv_launch<T>(hi, s);
-    }
+    if (a.nb > 4) return gemv_launch_halves<T>(a, s);      // no MFMA form for this shape / type
     const int nit = cdiv(K, 64 * V);
     const int64_t groups = (epi & SS_EPI_SILU_MUL) ? N : (N + 1) / 2;
     // waves: enough to fill the chip, but several row-groups per wave so the x prologue amortises
     // auto: ~2.5k waves (8-12 per CU) measured best on MI355X for every LLaMA-7B projection
-    int gpw = tuning_get("gemv_groups_per_wave", 0);
+    int gpw = knob(K_gemv_groups_per_wave);
     if (gpw <= 0) { gpw = (int)((groups + 1280) / 2560); if (gpw < 1) gpw = 1; }
     const int64_t waves = (groups + gpw - 1) / gpw;
     // a batch whose LDS-staged activations would not fit one CU's LDS is swept in two halves
-    const bool in_regs = nit <= 8 && a.nb * nit <= tuning_get("gemv_x_reg_packs", 16) && !tuning_get("gemv_force_lds", 0);
-    if (!in_regs && a.nb > 1 && (size_t)a.nb * cdiv(K / V, 512) * 512 * 16 > 152 * 1024) {
-        const int h1 = a.nb / 2;
-        GemvArgs lo = a, hi = a;
-        lo.nb = h1;
-        hi.nb = a.nb - h1;
-        hi.x = (const T*)a.x + (int64_t)h1 * a.x_ld;
-        hi.y = (T*)a.y + (int64_t)h1 * a.y_ld;
-        if (a.residual) hi.residual = (const T*)a.residual + (int64_t)h1 * a.res_ld;
-        if (a.done_flag) hi.done_flag = a.done_flag + (int64_t)h1 * a.done_stride;
-        const int rc = gemv_launch<T>(lo, s);
-        return rc ? rc : gemv_launch<T>(hi, s);
-    }
+    if (!gemv_x_in_regs(a.nb, nit) && a.nb > 1 && (size_t)a.nb * cdiv(K / V, 512) * 512 * 16 > 152 * 1024)
+        return gemv_launch_halves<T>(a, s);
     switch (a.nb) {
         case 1: return gemv_launch_nb<T, 1>(a, nit, waves, s);
         case 2: return gemv_launch_nb<T, 2>(a, nit, waves, s);

@@ -344,7 +344,7 @@ static int read_state(ss_llama* h, hipStream_t s) {
 
 // captured decode token for slots [seq0, seq0+nb), built on first use
 static int graph_for(ss_llama* h, int seq0, int nb, hipGraphExec_t* out) {
-    const int mode = tuning_get("gemm_f32_split", 0);
+    const int mode = knob(K_gemm_f32_split);
     for (const SeqGraph& sg : h->graphs)
         if (sg.seq0 == seq0 && sg.nb == nb && sg.mode == mode) { *out = sg.exec; return SS_OK; }
     SeqGraph sg;
@@ -367,10 +367,10 @@ static int run_decode(ss_llama* h, int seq0, int nb, int64_t eff_limit, hipStrea
     int32_t* init = h->pinned + (size_t)h->n_seq * 8;
     SS_HIP(hipMemcpyAsync(h->state + (size_t)seq0 * 8, init + (size_t)seq0 * 8, (size_t)nb * 8 * sizeof(int32_t),
                           hipMemcpyHostToDevice, s));
-    const bool use_graph = tuning_get("llama_graph", 1) != 0;
+    const bool use_graph = knob(K_llama_graph) != 0;
     hipGraphExec_t exec = nullptr;
     if (use_graph) { int rc = graph_for(h, seq0, nb, &exec); if (rc) return rc; }
-    const int chunk = tuning_get("llama_done_poll", 8);
+    const int chunk = knob(K_llama_done_poll);
     int64_t launched = 0;
     while (launched < eff_limit) {
         const int64_t n = (eff_limit - launched) < chunk ? (eff_limit - launched) : chunk;
@@ -630,7 +630,7 @@ int ss_llama_prefill_batch(ss_llama* h, const void* embeds, const int64_t* host_
     const size_t e = h->esz;
     const size_t plane = (size_t)g.n_heads * g.cache_cap * hd * e;
     int rc;
-    bool uniform_rows = h->n_seq >= 2 && h->n_seq <= 8 && tuning_get("llama_batched_attn", 1) != 0;
+    bool uniform_rows = h->n_seq >= 2 && h->n_seq <= 8 && knob(K_llama_batched_attn) != 0;
     int32_t kv_lens[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     for (int b = 0; b < h->n_seq && uniform_rows; ++b) {
         if (host_rows[b] != host_rows[0] || host_rows[b] <= 0) uniform_rows = false;

@@ -3,10 +3,6 @@
 #include <stdio.h>
 #include <string.h>
 
-#include <map>
-#include <mutex>
-#include <string>
-
 #include "ss_common.h"
 
 namespace ss {
@@ -26,22 +22,17 @@ int check_hip(hipError_t e, const char* what) {
     return SS_EHIP;
 }
 
-static std::mutex g_tune_mu;
-static std::map<std::string, int>& tune_map() {
-    static std::map<std::string, int> m;
-    return m;
-}
+std::atomic<int> g_knobs[K_COUNT] = {
+#define X(name, dflt, doc) {dflt},
+    SS_KNOB_LIST(X)
+#undef X
+};
 
-int tuning_get(const char* key, int dflt) {
-    std::lock_guard<std::mutex> lk(g_tune_mu);
-    auto& m = tune_map();
-    auto it = m.find(key);
-    return it == m.end() ? dflt : it->second;
-}
-
-void tuning_set(const char* key, int value) {
-    std::lock_guard<std::mutex> lk(g_tune_mu);
-    tune_map()[key] = value;
+// the only lookup by name: the two C entry points below
+static int knob_find(const char* key) {
+    for (int k = 0; key && k < K_COUNT; ++k)
+        if (!strcmp(kKnobs[k].name, key)) return k;
+    return -1;
 }
 
 }  // namespace ss
@@ -52,12 +43,15 @@ const char* ss_last_error(void) { return ss::g_err; }
 int ss_abi_version(void) { return SS_ABI_VERSION; }
 
 int ss_set_tuning(const char* key, int value) {
-    if (!key) return SS_EINVAL;
-    std::lock_guard<std::mutex> lk(ss::g_tune_mu);
-    ss::tune_map()[key] = value;
+    const int k = ss::knob_find(key);
+    SS_REQUIRE(k >= 0, "ss_set_tuning: unknown tuning key '%s' (the list is csrc/ss_knobs.h)", key ? key : "(null)");
+    ss::g_knobs[k].store(value, std::memory_order_relaxed);
     return SS_OK;
 }
-int ss_get_tuning(const char* key, int dflt) { return key ? ss::tuning_get(key, dflt) : dflt; }
+int ss_get_tuning(const char* key, int dflt) {
+    const int k = ss::knob_find(key);
+    return k < 0 ? dflt : ss::knob_or((ss::Knob)k, dflt);
+}
 
 int ss_device_info(int32_t out[4]) {
     int dev = 0;

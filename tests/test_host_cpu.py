@@ -386,6 +386,63 @@ def test_vae_decode_dtype_policy():
         _lib.set_tuning("vae_fp32", 0)
 
 
+def test_tuning_knobs_are_a_declared_table():
+    """Knobs exist only as rows of csrc/ss_knobs.h: every key the tree's Python names is one the library accepts, a misspelt
+    key is refused (SS_EINVAL, the message names it), values round-trip, an UNSET knob answers the caller's default until it
+    is set, and the counter can be read and reset."""
+    import glob
+    from seedstory import _lib
+    lib = _lib.lib()
+    files = [os.path.join(ROOT, "bench.py")]
+    for d in ("seed-story_amd", "tests", "tools"):
+        files += glob.glob(os.path.join(ROOT, d, "**", "*.py"), recursive=True)
+    keys = {}
+    for f in files:
+        for k in re.findall(r"""[sg]et_tuning\(\s*b?["']([A-Za-z0-9_]+)["']""", open(f, encoding="utf-8").read()):
+            keys.setdefault(k, os.path.relpath(f, ROOT))
+    assert len(keys) >= 30 and "gemm_cfg" in keys and "vae_fp32" in keys, sorted(keys)      # the scan sees the tree
+    unset = -2 ** 31                                           # KNOB_UNSET
+    for k, where in sorted(keys.items()):
+        # storing a knob's own value changes nothing (an unset knob stays unset); it returns 0 only for a declared key
+        assert lib.ss_set_tuning(k.encode(), lib.ss_get_tuning(k.encode(), unset)) == 0, (k, where, lib.ss_last_error())
+
+    SS_EINVAL = -1                                             # include/seedstory_hip.h
+    bad = "attn_vre"
+    assert lib.ss_set_tuning(bad.encode(), 3) == SS_EINVAL
+    assert bad in lib.ss_last_error().decode()
+    with pytest.raises(_lib.SSError, match=bad):
+        _lib.set_tuning(bad, 3)
+    assert lib.ss_set_tuning(None, 3) == SS_EINVAL
+    assert _lib.get_tuning(bad, 17) == 17                      # unknown key: the caller's default
+
+    assert _lib.get_tuning("attn_ver", 0) == 6                 # a constant default wins over the caller's
+    _lib.set_tuning("attn_ver", 3)
+    try:
+        assert _lib.get_tuning("attn_ver", 6) == 3
+    finally:
+        _lib.set_tuning("attn_ver", 6)
+    assert _lib.get_tuning("attn_ver", 0) == 6
+
+    for k in ("gemm_fp8_swz", "img_block_decode"):
+        assert _lib.get_tuning(k, 5) == 5 and _lib.get_tuning(k, 0) == 0
+        _lib.set_tuning(k, 0)
+        try:
+            assert _lib.get_tuning(k, 5) == 0
+        finally:
+            _lib.set_tuning(k, unset)
+        assert _lib.get_tuning(k, 5) == 5
+
+    refused = _lib.get_tuning("gemv_split_refused", -1)        # the counter: always a value (0 until a launch is refused), never
+    assert refused >= 0                                        # the caller's default
+    try:
+        _lib.set_tuning("gemv_split_refused", 4)
+        assert _lib.get_tuning("gemv_split_refused", 0) == 4
+        _lib.set_tuning("gemv_split_refused", 0)               # reset
+        assert _lib.get_tuning("gemv_split_refused", 9) == 0
+    finally:
+        _lib.set_tuning("gemv_split_refused", refused)
+
+
 def test_prepare_inputs_for_generation_matches_reference_fixture():
     """``LlamaForCausalLM.prepare_inputs_for_generation`` (reference :796-852) on every branch — kv_cache_head slicing vs
     last-token slicing, embeds on the first step only, positions from ``cumsum(mask) - 1`` — against outputs of the REAL

@@ -69,7 +69,10 @@ int main(int argc, char** argv) {
             if (e == std::string::npos) e = all.size();
             std::string kv = all.substr(pos, e - pos);
             const size_t eq = kv.find('=');
-            if (eq != std::string::npos) set_tuning(kv.substr(0, eq).c_str(), atoi(kv.c_str() + eq + 1));
+            if (eq != std::string::npos && set_tuning(kv.substr(0, eq).c_str(), atoi(kv.c_str() + eq + 1)) != 0) {
+                fprintf(stderr, "UBENCH_KNOB: %s\n", last_error ? last_error() : kv.c_str());      // a knob the library does not have
+                return 2;
+            }
             pos = e + 1;
         }
     }

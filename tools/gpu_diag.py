@@ -39,21 +39,18 @@ def bench_gemv():
         x = torch.randn(K, device=DEV, dtype=torch.bfloat16)
         nw = torch.ones(K, device=DEV, dtype=torch.bfloat16)
         for gpw in (0, 1, 2, 4):
-            for nt in (1, 0):
-                _lib.set_tuning("gemv_groups_per_wave", gpw)
-                _lib.set_tuning("gemv_pipe", nt)
-                st = {"i": 0}
+            _lib.set_tuning("gemv_groups_per_wave", gpw)
+            st = {"i": 0}
 
-                def f():
-                    st["i"] += 1
-                    ops.gemv(ws[st["i"] % ncopy], x, norm_w=nw if name in ("qkv", "gateup") else None, eps=1e-5, **kw)
-                ms = timeit(f, iters=30)
-                gbs = rows * K * 2 / ms / 1e6
-                res.append(dict(name=name, N=N, K=K, gpw=gpw, pipe=nt, ms=round(ms, 4), GBps=round(gbs, 1)))
-                print(res[-1], flush=True)
+            def f():
+                st["i"] += 1
+                ops.gemv(ws[st["i"] % ncopy], x, norm_w=nw if name in ("qkv", "gateup") else None, eps=1e-5, **kw)
+            ms = timeit(f, iters=30)
+            gbs = rows * K * 2 / ms / 1e6
+            res.append(dict(name=name, N=N, K=K, gpw=gpw, ms=round(ms, 4), GBps=round(gbs, 1)))
+            print(res[-1], flush=True)
         del ws
     _lib.set_tuning("gemv_groups_per_wave", 0)
-    _lib.set_tuning("gemv_pipe", 1)
     OUT["gemv"] = res
 
 
@@ -209,21 +206,18 @@ def bench_nsplit():
 def bench_decode():
     res = {}
     eng = make_7b_engine()
-    for pipe in (1, 0):
-        _lib.set_tuning("gemv_pipe", pipe)
-        emb = torch.randn(343, 4096, device=DEV, dtype=torch.bfloat16) * 0.02
-        eng.reset(); eng.prefill(emb)
-        forced = torch.randint(3, 32000, (115,)).tolist()
-        _lib.set_tuning("llama_graph", 0)
-        eng.generate(115, 5, forced)
-        eng.set_lengths(343, 343)
-        torch.cuda.synchronize(); t0 = time.perf_counter()
-        n = eng.generate(115, 5, forced)
-        torch.cuda.synchronize()
-        res["eager_tok_ms_pipe%d" % pipe] = round((time.perf_counter() - t0) * 1e3 / n, 4)
-        _lib.set_tuning("llama_graph", 1)
-        print(res, flush=True)
-    _lib.set_tuning("gemv_pipe", int(os.environ.get("SS_GEMV_PIPE", "1")))
+    emb = torch.randn(343, 4096, device=DEV, dtype=torch.bfloat16) * 0.02
+    eng.reset(); eng.prefill(emb)
+    forced = torch.randint(3, 32000, (115,)).tolist()
+    _lib.set_tuning("llama_graph", 0)
+    eng.generate(115, 5, forced)
+    eng.set_lengths(343, 343)
+    torch.cuda.synchronize(); t0 = time.perf_counter()
+    n = eng.generate(115, 5, forced)
+    torch.cuda.synchronize()
+    res["eager_tok_ms"] = round((time.perf_counter() - t0) * 1e3 / n, 4)
+    _lib.set_tuning("llama_graph", 1)
+    print(res, flush=True)
     H = 4096
     for S in (343, 913):
         emb = torch.randn(S, H, device=DEV, dtype=torch.bfloat16) * 0.02
