@@ -478,6 +478,8 @@ static int pp_launch(const GemmArgs& g, hipStream_t s) {
     constexpr bool CONV = SS_PP_CONV != 0;
     const bool conv = g.conv_Cin > 0;
     if (conv != CONV || g.ksplit > 1) return 1;
+    // (tests/kernel_check.py pp320_eligible / conv_pp320_eligible copy the rule below to make sure their shapes reach the 320-wide
+    // tiles and not the fallback: change both together)
     bool ok = (g.K % 64 == 0) && g.K >= 64 && (int64_t)BN * g.ldw * 2 < (1ll << 31);
     if (conv) {
         // whole tiles, stride 1, no upsampling, W a power of two >= 8 (an 8-pixel DMA piece stays inside one image row), H a

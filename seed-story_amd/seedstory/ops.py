@@ -34,6 +34,17 @@ def _req(t, name="tensor"):
     return t
 
 
+def _out(out, shape, like, name):
+    """The caller's ``out=`` buffer (checked) or a fresh one: every wrapper with an ``out`` argument writes its result there."""
+    if out is None:
+        return torch.empty(shape, dtype=like.dtype, device=like.device)
+    _req(out, name + "(out=)")
+    if tuple(out.shape) != tuple(shape) or out.dtype != like.dtype or out.device != like.device:
+        raise _lib.SSError("%s(out=): expected %s %s on %s, got %s %s on %s"
+                           % (name, tuple(shape), like.dtype, like.device, tuple(out.shape), out.dtype, out.device))
+    return out
+
+
 def rmsnorm(x, w, eps):
     _req(x); _req(w)
     y = torch.empty_like(x)
@@ -120,8 +131,7 @@ def attention(q, k, v, n_heads, scale=None, causal_br=False, out=None):
     B, Lq, E = q.shape
     Lk = k.shape[1]
     hd = E // n_heads
-    if out is None:
-        out = torch.empty_like(q)
+    out = _out(out, q.shape, q, "attention")
     scale = 1.0 / math.sqrt(hd) if scale is None else scale
     kb = 0 if k.shape[0] == 1 and B > 1 else Lk * E
     check(lib().ss_attention(p(q), p(k), p(v), p(out), B, n_heads, Lq, Lk, hd, Lq * E, hd, E, kb, hd, E, kb, hd, E,
@@ -129,19 +139,19 @@ def attention(q, k, v, n_heads, scale=None, causal_br=False, out=None):
     return out
 
 
-def attention_cache(q, kcache, vcache, kv_len, causal_br=True):
+def attention_cache(q, kcache, vcache, kv_len, causal_br=True, out=None):
     """q [M, n_heads*hd] against cache planes [n_heads, cap, hd] (first kv_len slots)."""
     _req(q); _req(kcache)
     M, E = q.shape
     n_heads, cap, hd = kcache.shape
-    out = torch.empty_like(q)
+    out = _out(out, q.shape, q, "attention_cache")
     check(lib().ss_attention(p(q), p(kcache), p(vcache), p(out), 1, n_heads, M, kv_len, hd, 0, hd, E, 0, cap * hd, hd,
                              0, cap * hd, hd, 0, hd, E, 1.0 / math.sqrt(hd), int(causal_br), dt(q), stream()),
           "ss_attention")
     return out
 
 
-def attention_cache_slots(q, kcache, vcache, kv_lens, causal_br=True):
+def attention_cache_slots(q, kcache, vcache, kv_lens, causal_br=True, out=None):
     """Stacked slots: q [S * M, n_heads*hd] (M rows per slot) against caches [S, n_heads, cap, hd]; slot b attends to its
     first kv_lens[b] entries (ss_attention_ragged: one launch for the S slots)."""
     import ctypes
@@ -149,7 +159,7 @@ def attention_cache_slots(q, kcache, vcache, kv_lens, causal_br=True):
     S, n_heads, cap, hd = kcache.shape
     E = n_heads * hd
     M = q.shape[0] // S
-    out = torch.empty_like(q)
+    out = _out(out, q.shape, q, "attention_cache_slots")
     lens = (ctypes.c_int32 * S)(*[int(x) for x in kv_lens])
     check(lib().ss_attention_ragged(p(q), p(kcache), p(vcache), p(out), S, n_heads, M, ctypes.cast(lens, ctypes.c_void_p), hd,
                                     M * E, hd, E, n_heads * cap * hd, cap * hd, hd, n_heads * cap * hd, cap * hd, hd, M * E, hd, E,
@@ -157,11 +167,11 @@ def attention_cache_slots(q, kcache, vcache, kv_lens, causal_br=True):
     return out
 
 
-def attn_decode(q, kcache, vcache, kv_len_dev):
+def attn_decode(q, kcache, vcache, kv_len_dev, out=None):
     _req(q); _req(kcache)
     n_heads, cap, hd = kcache.shape
     ws = torch.empty(lib().ss_attn_decode_workspace_bytes(n_heads, hd), dtype=torch.uint8, device=q.device)
-    out = torch.empty_like(q)
+    out = _out(out, q.shape, q, "attn_decode")
     check(lib().ss_attn_decode(p(q), p(kcache), p(vcache), p(out), p(ws), p(kv_len_dev), n_heads, hd, cap, dt(q),
                                stream()), "ss_attn_decode")
     return out
@@ -173,8 +183,7 @@ def gemm(a, w, bias=None, residual=None, gelu=False, out=None, rowstat=None, row
     _req(a); _req(w)
     M, K = a.shape
     N = w.shape[0]
-    if out is None:
-        out = torch.empty(M, N, dtype=a.dtype, device=a.device)
+    out = _out(out, (M, N), a, "gemm")
     epi = (EPI_BIAS if bias is not None else 0) | (EPI_GELU if gelu else 0) | (EPI_RESIDUAL if residual is not None else 0)
     tune.ensure_gemm(M, N, K, dt(a), epi, a.device)
     if rowstat is not None:
@@ -195,24 +204,24 @@ def gemm(a, w, bias=None, residual=None, gelu=False, out=None, rowstat=None, row
     return out
 
 
-def gemm_splitk(a, w, bias=None, residual=None):
+def gemm_splitk(a, w, bias=None, residual=None, out=None):
     """Small-M weight-streaming GEMM (ss_gemm_splitk): a [M, K] @ w[N, K]^T for 128 < M <= 512; falls back to ss_gemm."""
     _req(a); _req(w)
     M, K = a.shape
     N = w.shape[0]
-    out = torch.empty(M, N, dtype=a.dtype, device=a.device)
+    out = _out(out, (M, N), a, "gemm_splitk")
     nbytes = lib().ss_gemm_splitk_workspace_bytes(M, N, K)
     ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=a.device)
     check(lib().ss_gemm_splitk(p(a), p(w), p(out), M, N, K, p(bias), p(residual), p(ws), nbytes, dt(a), stream()), "ss_gemm_splitk")
     return out
 
 
-def gemm_geglu(a, w_pairs, bias_pairs):
+def gemm_geglu(a, w_pairs, bias_pairs, out=None):
     """a [M, K] @ w_pairs[2D, K]^T with rows interleaved (value_i, gate_i) -> [M, D] = value * gelu(gate)."""
     _req(a); _req(w_pairs)
     M, K = a.shape
     N = w_pairs.shape[0]
-    out = torch.empty(M, N // 2, dtype=a.dtype, device=a.device)
+    out = _out(out, (M, N // 2), a, "gemm_geglu")
     tune.ensure_gemm(M, N, K, dt(a), _lib.EPI_GEGLU_PAIR, a.device)
     check(lib().ss_gemm(p(a), p(w_pairs), p(out), M, N, K, K, K, N // 2, p(bias_pairs), None, 0,
                         _lib.EPI_BIAS | _lib.EPI_GEGLU_PAIR, dt(a), stream()), "ss_gemm(geglu)")
@@ -242,13 +251,13 @@ def gemm_lnfold(x, wg, rstd, shift, colsum, bias_d=None, gelu=False, geglu=False
     return out
 
 
-def rowpart_strips(M, N, K, dtype, epi=0):
+def rowpart_strips(M, N, K, dtype):
     """Number of (sum, sum of squares) partials per row that ``gemm(..., rowpart=)`` writes for this shape (0: not eligible).
     The answer depends on the tile the table holds for the shape, so the shape is tuned FIRST (a first forward on a
-    shape absent from the table used to size the strip buffer from the closed-form tile and then re-tune inside `gemm`) — with
-    the PRODUCER's epilogue flags (`epi`: GELU / GEGLU), because the table key has no epilogue component and the first tune of
-    a shape is the one that sticks."""
-    tune.ensure_gemm(M, N, K, dt(dtype), int(epi), None)
+    shape absent from the table used to size the strip buffer from the closed-form tile and then re-tune inside `gemm`).  It is
+    tuned without GELU / GEGLU: a statistics producer feeds a LayerNorm, GEGLU is refused by ss_gemm_rowpart, and no producer on
+    the path applies GELU (the former `epi` argument had no caller and is gone)."""
+    tune.ensure_gemm(M, N, K, dt(dtype), 0, None)
     return int(lib().ss_gemm_rowpart_strips(M, N, K, dt(dtype)))
 
 
@@ -302,26 +311,26 @@ def gemm_fp8(a8, sa, w8, sw, bias=None, residual=None, gelu=False, geglu=False, 
     return out
 
 
-def gemv(w, x, norm_w=None, eps=0.0, bias=None, residual=None, silu_mul=False):
+def gemv(w, x, norm_w=None, eps=0.0, bias=None, residual=None, silu_mul=False, out=None):
     _req(w); _req(x)
     N, K = w.shape
     if silu_mul:
         N //= 2
-    y = torch.empty(N, dtype=x.dtype, device=x.device)
+    y = _out(out, (N,), x, "gemv")
     epi = (EPI_BIAS if bias is not None else 0) | (EPI_RESIDUAL if residual is not None else 0) | \
           (EPI_SILU_MUL if silu_mul else 0)
     check(lib().ss_gemv(p(w), p(x), p(y), N, K, p(norm_w), eps, p(bias), p(residual), epi, dt(x), stream()), "ss_gemv")
     return y
 
 
-def gemv_batched(w, x, norm_w=None, eps=0.0, bias=None, residual=None, silu_mul=False):
+def gemv_batched(w, x, norm_w=None, eps=0.0, bias=None, residual=None, silu_mul=False, out=None):
     """x [nb, K] (nb <= 4) -> y [nb, N]: one sweep of W for all rows."""
     _req(w); _req(x)
     N, K = w.shape
     if silu_mul:
         N //= 2
     nb = x.shape[0]
-    y = torch.empty(nb, N, dtype=x.dtype, device=x.device)
+    y = _out(out, (nb, N), x, "gemv_batched")
     epi = (EPI_BIAS if bias is not None else 0) | (EPI_RESIDUAL if residual is not None else 0) | \
           (EPI_SILU_MUL if silu_mul else 0)
     check(lib().ss_gemv_batched(p(w), p(x), p(y), N, K, nb, p(norm_w), eps, p(bias), p(residual), epi, dt(x),
@@ -342,14 +351,14 @@ def imgproc_argmax(logits, last_id, img_ids):
 
 
 # ---- SDXL de-tokenizer ops (NHWC activations: [B, H*W, C]) ------------------------------------------
-def conv3x3(x, w, B, H, W, stride=1, upsample=False, bias=None, rowvec=None, residual=None, rowvec_stride=0):
+def conv3x3(x, w, B, H, W, stride=1, upsample=False, bias=None, rowvec=None, residual=None, rowvec_stride=0, out=None):
     """x [B*H*W, Cin] (NHWC) -> [B*Ho*Wo, Cout]; w [Cout, 9*Cin] (tap-major, channel-minor)."""
     _req(x); _req(w)
     Cin = x.shape[-1]
     Cout = w.shape[0]
     Hin, Win = (2 * H, 2 * W) if upsample else (H, W)
     Ho, Wo = (Hin + 2 - 3) // stride + 1, (Win + 2 - 3) // stride + 1
-    y = torch.empty(B * Ho * Wo, Cout, dtype=x.dtype, device=x.device)
+    y = _out(out, (B * Ho * Wo, Cout), x, "conv3x3")
     tune.ensure_conv(B, H, W, Cin, Cout, stride, upsample, dt(x), x.device)
     check(lib().ss_conv3x3(p(x), p(w), p(y), B, H, W, Cin, Cout, stride, int(upsample), p(bias), p(rowvec),
                            rowvec_stride, p(residual), dt(x), stream()), "ss_conv3x3")
@@ -433,12 +442,12 @@ def silu(x):
     return y
 
 
-def attention_qkv_packed(qkv, B, L, n_heads):
+def attention_qkv_packed(qkv, B, L, n_heads, out=None):
     """Self-attention on a fused projection qkv [B*L, 3E] = [q | k | v] per token -> [B*L, E]."""
     _req(qkv)
     E = qkv.shape[1] // 3
     hd = E // n_heads
-    out = torch.empty(B * L, E, dtype=qkv.dtype, device=qkv.device)
+    out = _out(out, (B * L, E), qkv, "attention_qkv_packed")
     esz = qkv.element_size()
     base = qkv.data_ptr()
     check(lib().ss_attention(base, base + E * esz, base + 2 * E * esz, p(out), B, n_heads, L, L, hd, L * 3 * E, hd, 3 * E,
@@ -447,12 +456,12 @@ def attention_qkv_packed(qkv, B, L, n_heads):
     return out
 
 
-def attention_q_kvpacked(q, kv, B, Lq, Lk, n_heads):
+def attention_q_kvpacked(q, kv, B, Lq, Lk, n_heads, out=None):
     """Cross-attention: q [B*Lq, E], kv [B*Lk, 2E] = [k | v] per context token -> [B*Lq, E]."""
     _req(q); _req(kv)
     E = q.shape[1]
     hd = E // n_heads
-    out = torch.empty_like(q)
+    out = _out(out, q.shape, q, "attention_q_kvpacked")
     esz = q.element_size()
     kb = kv.data_ptr()
     check(lib().ss_attention(p(q), kb, kb + E * esz, p(out), B, n_heads, Lq, Lk, hd, Lq * E, hd, E, Lk * 2 * E, hd, 2 * E,

@@ -1,0 +1,555 @@
+"""Element-wise checker for the kernel tests: a-priori error bounds against an fp64 reference, guarded output buffers and
+exact probes.  Plain torch on the CPU; imports nothing from seed-story_amd/ (test infrastructure, like truth_cache.py).
+
+Why element-wise: a relative Frobenius norm over a [1024, 640] bf16 product is 1.7e-3 from rounding alone, and eight zeroed
+outputs, sixteen 4-ulp offsets or a K tail dropped in one 16x16 fragment all stay under the 4e-3 the sweeps assert.  Every bound
+here is PER ELEMENT and derived from the number formats, never from what a kernel returned.
+
+Notation.  u_T = unit roundoff of the stored type (2^-8 bf16, 2^-11 fp16, 2^-24 fp32); u32 = 2^-24.  Every helper carries a
+pair (v, t): v the fp64 reference value with the kernel's own intermediate roundings mirrored, t a tolerance such that a correct
+kernel's value x satisfies |x - v| <= t.  The steps (each a function below):
+
+  accumulate   v = sum_k a_k w_k exactly (fp64), S = sum_k |a_k| |w_k|.  fp32 accumulation of Kacc terms in ANY order obeys
+               |x - v| <= gamma_Kacc S with gamma_n = n u32 / (1 - n u32) ~ n u32 (Higham, Accuracy and Stability, 3.1).
+               t = 2 Kacc u32 S.  The factor 2 is the only slack in this file: MFMA's internal summation tree is not specified to
+               round after every term.  (products of two 16-bit values are exact in fp32: 8 + 8 or 11 + 11 significand bits.)
+  fp32 op      x' = fl(x + b): |x' - (v + b)| <= t + u32 |x'| <= t + u32 (|v + b| + t).
+  mid round    both sides round to T: |rnd(x) - rnd(v)| <= u_T |x| + |x - v| + u_T |v| <= 2 u_T |v| + (1 + u_T) t.  (the kernel's
+               value may land on the other side of a rounding boundary than the reference's: two half-ulps, not one.)
+  final round  only the kernel rounds; the reference stays unrounded: |rnd(x) - v| <= u_T |x| + t <= u_T |v| + (1 + u_T) t.
+               For a plain product this is the bound  |y - ref| <= u_T |ref| + (1 + u_T) e_acc.  A truncating store errs by
+               up to 2 u_T |v| and fails it.
+  subnormals   u_T |v| is the half-ulp of a NORMAL v; below the smallest normal (fp16: 6.1e-5, reached by GELU / SiLU of a negative
+               gate) the spacing stops shrinking, so every rounding also carries eta_T = half the subnormal spacing (fp16 2^-25,
+               bf16 2^-134, fp32 2^-150): 3e-8 at most, invisible next to any other term unless the value itself is that small.
+  f(x)         |f(x) - f(v)| <= L t with L = max |f'| over [v - t, v + t].  L is taken as min(Lmax, max(|f'(v - t)|, |f'(v)|,
+               |f'(v + t)|) + M2 t): every point of the interval is within t of a sample and |f''| <= M2.  erf-GELU: Lmax = 1.13
+               (f' peaks at 1.129, x = 1.41), M2 = 0.8 (f'' = phi(x) (2 - x^2) <= 2 phi(0) = 0.798).  SiLU: Lmax = 1.1, M2 = 0.5.
+               The kernel's own evaluation (16-bit GELU: Abramowitz-Stegun 7.1.26, |erf error| < 1.5e-7, on hardware rcp / exp2;
+               SiLU: expf and one division) adds at most 2^-21 max(|v|, |f(v)|): 0.5 |v| 1.5e-7 = |v| 2^-23.7 plus four fp32 ops.
+               fp32 kernels call libm's erff / expf (<= 2 ulp) and do three more fp32 operations: 2^-22 max(|v|, |f(v)|).
+               This term is not in the first-order recipe; without it the bound would charge the kernel's approximation of f to
+               its accumulation.  It is 1 / 8192 of a bf16 half-ulp.
+  a * g        |x_a x_g - a g| <= |a| t_g + |g| t_a + t_a t_g, then one fp32 op.
+
+Epilogues mirror the rounding points of the kernels (ss_gemm_common.h gemm_epilogue): bias is added in fp32 and the sum rounded;
+GELU is applied to the rounded value and rounded; a row vector (conv) and the residual are each added to the rounded value and
+rounded again; GEGLU multiplies the rounded value by the rounded GELU of the rounded gate.
+
+Attention (per query row; P = fp64 softmax of the fp64 scores, masked keys have P = 0):
+  score error   delta_s(j) = 2 hd u32 scale (|q| . |k_j|): the accumulate step above with Kacc = hd (the scale is one more fp32
+                op, inside the factor 2).
+  softmax       with scores off by d_j, P'_j = P_j e^{d_j} / sum_i P_i e^{d_i}; to first order |P'_j - P_j| <= P_j (|d_j| +
+                sum_i P_i |d_i|) <= 2 P_j max_j delta_s, so the output moves by at most 2 max_j delta_s (P @ |V|).
+  P rounded     the kernels round exp(s - m) to T before the P V product (MFMA operands) and sum the row normaliser from the same
+                values or from the unrounded ones: numerator and denominator each move by a relative u_T at most:
+                2 u_T (P @ |V|).  (fp32 kernels do not round P; u_T = u32 then and the term is noise.)
+  output        one final round: u_T |ref|.
+  bound         |out - ref| <= u_T |ref| + (2 u_T + 2 max_j delta_s) (P @ |V|).
+The fp32 accumulation of P V (kv_len terms of one sign pattern, rescaled per tile) is not budgeted on its own; it rides in the
+factor 2 of delta_s.  The constants are derived, not tuned: the GPU file records the worst error / bound ratio per family."""
+import numpy as np
+import torch
+
+U = {torch.bfloat16: 2.0 ** -8, torch.float16: 2.0 ** -11, torch.float32: 2.0 ** -24}
+U32 = 2.0 ** -24
+ETA = {torch.bfloat16: 2.0 ** -134, torch.float16: 2.0 ** -25, torch.float32: 2.0 ** -150}   # half the subnormal spacing
+NAME = {torch.bfloat16: "bf16", torch.float16: "fp16", torch.float32: "fp32"}
+
+# ---- tile ids: the one list (tests/test_kernels_gpu.py, tests/test_sdxl_gpu.py and tests/test_kernel_edges_gpu.py import these) ----
+GEMM_REG_TILES = [1, 2, 3]                                      # register-staged
+GEMM_DMA_TILES = [8, 10, 15, 20, 21, 22, 23, 24, 26, 28, 29, 30, 31, 32, 33, 34, 35, 36, 37, 38, 39, 40, 41, 42, 43, 44, 45, 46, 54, 55, 56,
+                  57, 58, 60, 61, 62, 63, 64, 65, 66, 67, 68, 69, 70, 71, 72]
+GEMM_PP_TILES = [54, 55, 56, 57, 58]                            # ping-pong
+GEMM_RING_TILES = [30, 31, 32, 33, 35, 36, 38, 39, 40, 41, 42, 43, 60, 61, 62, 64]
+GEMM_PERSISTENT_TILES = [33, 35, 36, 38, 39, 40, 43, 54, 55, 56, 57, 58, 60, 64, 72]
+GEMM_TILES = GEMM_REG_TILES + GEMM_DMA_TILES                    # every shipped GEMM tile id
+CONV_PP_TILES = [54, 55, 56, 57]
+CONV_DMA_TILES = [8, 15, 20, 21, 22, 23, 24, 26, 28, 29, 30, 33, 34, 36, 37, 38, 39, 40, 41, 42, 43, 44, 45, 46, 54, 56, 60, 61, 62, 63, 64, 65,
+                  66, 67, 68, 69, 70, 71, 72]
+CONV_PERSISTENT_TILES = [33, 36, 38, 39, 40, 43, 60, 64, 72]
+CONV_TILES = sorted(set(CONV_DMA_TILES + CONV_PP_TILES))        # every shipped conv tile id
+
+
+def rnd(x, dtype):
+    """fp64 -> T -> fp64 (round to nearest even)."""
+    return x.to(dtype).double()
+
+
+# ---- (v, t) propagation ------------------------------------------------------------------------------------------------------
+def accumulate(a, w, kacc=None):
+    """a [M, K], w [N, K] (any float dtype, exact in fp64) -> (a @ w^T, 2 Kacc u32 |a| @ |w|^T)."""
+    a, w = a.double(), w.double()
+    k = a.shape[1] if kacc is None else kacc
+    return a @ w.t(), 2.0 * k * U32 * (a.abs() @ w.abs().t())
+
+
+def op32(v, t):
+    """one fp32 operation whose exact result is v, on an operand known to t."""
+    return v, t + U32 * (v.abs() + t)
+
+
+def mid_round(v, t, dtype):
+    u = U[dtype]
+    return rnd(v, dtype), 2.0 * (u * v.abs() + ETA[dtype]) + (1.0 + u) * t
+
+
+def final_round(v, t, dtype):
+    u = U[dtype]
+    return v, u * v.abs() + ETA[dtype] + (1.0 + u) * t
+
+
+def _gelu(x):
+    return 0.5 * x * (1.0 + torch.erf(x * 0.7071067811865476))
+
+
+def _gelu_d(x):
+    return 0.5 * (1.0 + torch.erf(x * 0.7071067811865476)) + x * torch.exp(-0.5 * x * x) * 0.3989422804014327
+
+
+def _silu(x):
+    return x * torch.sigmoid(x)
+
+
+def _silu_d(x):
+    s = torch.sigmoid(x)
+    return s * (1.0 + x * (1.0 - s))
+
+
+def _apply(f, fd, lmax, m2, v, t, feval):
+    L = torch.maximum(torch.maximum(fd(v - t).abs(), fd(v).abs()), fd(v + t).abs()) + m2 * t
+    L = torch.clamp(L, max=lmax)
+    fv = f(v)
+    return fv, L * t + feval * torch.maximum(v.abs(), fv.abs())
+
+
+FEVAL = {torch.bfloat16: 2.0 ** -21, torch.float16: 2.0 ** -21, torch.float32: 2.0 ** -22}
+
+
+def gelu(v, t, dtype):
+    return _apply(_gelu, _gelu_d, 1.13, 0.8, v, t, FEVAL[dtype])
+
+
+def silu(v, t, dtype):
+    return _apply(_silu, _silu_d, 1.1, 0.5, v, t, FEVAL[dtype])
+
+
+def product(va, ta, vg, tg):
+    return op32(va * vg, va.abs() * tg + vg.abs() * ta + ta * tg)
+
+
+def epilogue(v, t, dtype, bias=None, gelu_=False, rowvec=None, residual=None, geglu=False):
+    """The rounding points of gemm_epilogue on an accumulator (v, t) -> (reference, bound) of the stored value.
+    bias [N] / rowvec [M, N] (already broadcast) / residual [M, N]: tensors of the model dtype (exact in fp64)."""
+    if bias is not None:
+        v, t = op32(v + bias.double(), t)
+    if geglu:
+        v, t = mid_round(v, t, dtype)
+        gv, gt = gelu(v[:, 1::2], t[:, 1::2], dtype)
+        gv, gt = mid_round(gv, gt, dtype)
+        v, t = product(v[:, 0::2], t[:, 0::2], gv, gt)
+        return final_round(v, t, dtype)
+    if gelu_:
+        v, t = mid_round(v, t, dtype)
+        v, t = gelu(v, t, dtype)
+    for extra in (rowvec, residual):
+        if extra is not None:
+            v, t = mid_round(v, t, dtype)
+            v, t = op32(v + extra.double(), t)
+    return final_round(v, t, dtype)
+
+
+def gemm_bound(a, w, dtype, bias=None, residual=None, gelu_=False, geglu=False):
+    """(reference, bound) [M, N] (N / 2 for GEGLU) of ss_gemm on a [M, K], w [N, K]."""
+    v, t = accumulate(a, w)
+    return epilogue(v, t, dtype, bias=bias, gelu_=gelu_, residual=residual, geglu=geglu)
+
+
+def silu_mul_bound(w, x, dtype):
+    """ss_gemv / ss_gemv_batched with the SiLU pair: w [2I, K], x [nb, K] -> y [nb, I] = round(round(silu(round(g))) * round(u))."""
+    v, t = accumulate(x, w)
+    v, t = mid_round(v, t, dtype)
+    I = w.shape[0] // 2
+    sv, st = silu(v[:, :I], t[:, :I], dtype)
+    sv, st = mid_round(sv, st, dtype)
+    v, t = product(v[:, I:], t[:, I:], sv, st)
+    return final_round(v, t, dtype)
+
+
+def conv_bound(x, w, dtype, stride=1, upsample=False, bias=None, rowvec=None, residual=None):
+    """x [B, Ci, H, W], w [Co, Ci, 3, 3], bias [Co], rowvec [B, Co], residual [B, Co, Ho, Wo] -> (reference, bound) NCHW of
+    ss_conv3x3 (padding 1; Kacc = 9 Cin, padding taps included: they add exact zeros)."""
+    F = torch.nn.functional
+    xd, wd = x.double(), w.double()
+    if upsample:
+        xd = F.interpolate(xd, scale_factor=2.0, mode="nearest")
+    v = F.conv2d(xd, wd, None, stride=stride, padding=1)
+    t = 2.0 * 9 * x.shape[1] * U32 * F.conv2d(xd.abs(), wd.abs(), None, stride=stride, padding=1)
+    return epilogue(v, t, dtype, bias=None if bias is None else bias.double()[None, :, None, None],
+                    rowvec=None if rowvec is None else rowvec.double()[:, :, None, None], residual=residual)
+
+
+def attention_bound(q, k, v, scale, allow, dtype):
+    """q [..., Lq, hd], k / v [..., Lk, hd] (per head), allow [Lq, Lk] bool or None -> (reference, bound) [..., Lq, hd]."""
+    qd, kd, vd = q.double(), k.double(), v.double()
+    hd = q.shape[-1]
+    s = qd @ kd.transpose(-1, -2) * scale
+    ds = 2.0 * hd * U32 * abs(scale) * (qd.abs() @ kd.abs().transpose(-1, -2))
+    if allow is not None:
+        s = s.masked_fill(~allow, float("-inf"))
+        ds = ds.masked_fill(~allow, 0.0)
+    P = torch.softmax(s, -1)
+    ref = P @ vd
+    u = U[dtype]
+    return ref, u * ref.abs() + (2.0 * u + 2.0 * ds.amax(-1, keepdim=True)) * (P @ vd.abs())
+
+
+def causal_allow(Lq, Lk):
+    """bottom-right aligned causal mask: query i sees keys j <= i + Lk - Lq."""
+    return torch.ones(Lq, Lk, dtype=torch.bool).tril(diagonal=Lk - Lq)
+
+
+# ---- the check ----------------------------------------------------------------------------------------------------------------
+WORST = {}   # (family, dtype name) -> worst error / bound seen by check(); the GPU file prints it
+
+
+def violations(y, ref, tol):
+    """-> (count, worst ratio, [(index tuple, ratio), ...] of the worst few).  Non-finite outputs always violate."""
+    yd = y.double().to(ref.device).reshape(ref.shape)
+    err = (yd - ref).abs()
+    err = torch.where(torch.isfinite(yd), err, torch.full_like(err, float("inf")))
+    ratio = torch.where(tol > 0, err / tol.clamp_min(1e-300), torch.where(err > 0, torch.full_like(err, float("inf")), torch.zeros_like(err)))
+    bad = ratio > 1.0
+    n = int(bad.sum())
+    worst = float(ratio.max()) if ratio.numel() else 0.0
+    coords = []
+    if n:
+        flat = ratio.flatten()
+        for i in torch.topk(flat, min(6, n)).indices.tolist():
+            coords.append((tuple(int(c) for c in np.unravel_index(i, tuple(ratio.shape))), float(flat[i])))
+    return n, worst, coords
+
+
+def report(y, ref, tol, what=""):
+    n, worst, coords = violations(y, ref, tol)
+    if not n:
+        return worst, ""
+    lines = ["%s: %d of %d elements outside the bound, worst error / bound = %.3g" % (what, n, ref.numel(), worst)]
+    for idx, r in coords:
+        rc = idx[-2:] if len(idx) >= 2 else (0,) + idx
+        lines.append("  at %s ratio %.3g   (row, col) mod 16 = (%d, %d)  mod 64 = (%d, %d)  mod 256 = (%d, %d)"
+                     % (idx, r, rc[0] % 16, rc[1] % 16, rc[0] % 64, rc[1] % 64, rc[0] % 256, rc[1] % 256))
+    return worst, "\n".join(lines)
+
+
+def check(y, ref, tol, what="", family=None, dtype=None):
+    """assert |y - ref| <= tol element-wise; records the worst ratio under (family, dtype)."""
+    worst, msg = report(y, ref, tol, what)
+    if family is not None:
+        key = (family, NAME.get(dtype, str(dtype)))
+        WORST[key] = max(WORST.get(key, 0.0), worst)
+    assert not msg, msg
+    return worst
+
+
+def worst_table():
+    return "\n".join("  %-22s %-5s worst error / bound = %.3f" % (f, d, r) for (f, d), r in sorted(WORST.items()))
+
+
+# ---- guarded outputs ----------------------------------------------------------------------------------------------------------
+SENTINEL = {torch.bfloat16: 0x7FA5, torch.float16: 0x7DA5, torch.float32: 0x7FA5A5A5}    # NaN bit patterns with a payload (compared as integers, never as floats)
+_INT = {torch.bfloat16: torch.int16, torch.float16: torch.int16, torch.float32: torch.int32}
+
+
+def _sentinel_int(dtype):
+    return SENTINEL[dtype]      # sign bit clear: the same number as int16 / int32
+
+
+class GuardedOut:
+    """One flat allocation: [front guard | offset | rows x (width payload + (ld - width) gap) | back guard], every element preset
+    to a NaN sentinel.  Guards are multiples of 16 bytes, so the payload keeps the alignment `offset` (in elements) asks for.
+    `out` is the payload view handed to the kernel ([rows, width], row stride ld); `check()` asserts guards, offset and gaps are
+    bit-identical to the sentinel and no sentinel remains in the payload, and returns the payload on the CPU."""
+    GUARD_BYTES = 1024
+
+    def __init__(self, rows, width, dtype, device="cpu", ld=None, offset=0):
+        self.rows, self.width, self.dtype = int(rows), int(width), dtype
+        self.ld = self.width if ld is None else int(ld)
+        assert self.ld >= self.width and offset >= 0
+        esz = 2 if dtype != torch.float32 else 4
+        self.guard = self.GUARD_BYTES // esz
+        self.start = self.guard + int(offset)
+        body = (self.rows - 1) * self.ld + self.width if self.rows else 0
+        self.total = self.start + body + self.guard
+        self.flat = torch.full((self.total,), _sentinel_int(dtype), dtype=_INT[dtype], device=device)
+        assert self.flat.data_ptr() % 16 == 0
+        self.out = self.flat.view(dtype).as_strided((self.rows, self.width), (self.ld, 1), self.start)
+
+    def view(self, *shape):
+        """the (contiguous, ld == width) payload under another shape"""
+        assert self.ld == self.width
+        return self.flat.view(self.dtype)[self.start:self.start + self.rows * self.width].view(*shape)
+
+    def data_ptr(self):
+        return self.out.data_ptr()
+
+    def problems(self, cpu=True):
+        """-> (messages, payload).  The comparisons run where the buffer lives (integers); the payload comes back on the CPU
+        unless cpu=False."""
+        if self.flat.is_cuda:
+            torch.cuda.synchronize()
+        f = self.flat.cpu() if cpu else self.flat
+        s = _sentinel_int(self.dtype)
+        msgs = []
+        body_end = self.start + ((self.rows - 1) * self.ld + self.width if self.rows else 0)
+        front = (f[:self.start] != s).nonzero().flatten()
+        if front.numel():
+            msgs.append("%d elements written BEFORE the output (first at element %d of %d)" % (front.numel(), int(front[0]) - self.start, self.start))
+        back = (f[body_end:] != s).nonzero().flatten()
+        if back.numel():
+            msgs.append("%d elements written PAST the output (first %d elements after its end)" % (back.numel(), int(back[0])))
+        body = f[self.start:body_end]
+        if self.ld > self.width and self.rows > 1:
+            pad = torch.full((self.rows * self.ld - body.numel(),), s, dtype=f.dtype, device=f.device)
+            grid = torch.cat([body, pad]).view(self.rows, self.ld)
+            gap = (grid[:, self.width:] != s).nonzero()
+            if gap.numel():
+                msgs.append("%d gap elements written (first: row %d, column %d of a %d-wide row)"
+                            % (gap.shape[0], int(gap[0, 0]), self.width + int(gap[0, 1]), self.width))
+            pay = grid[:, :self.width]
+        else:
+            pay = body.view(self.rows, self.width)
+        left = (pay == s).nonzero()
+        if left.numel():
+            r, c = int(left[0, 0]), int(left[0, 1])
+            msgs.append("%d payload elements never written (first at (%d, %d): mod 16 = (%d, %d), mod 64 = (%d, %d), mod 256 = (%d, %d))"
+                        % (left.shape[0], r, c, r % 16, c % 16, r % 64, c % 64, r % 256, c % 256))
+        return msgs, pay.contiguous().view(self.dtype)
+
+    def check(self, what="", cpu=True):
+        msgs, pay = self.problems(cpu)
+        assert not msgs, "%s: %s" % (what, "; ".join(msgs))
+        return pay
+
+
+# ---- exact probes -------------------------------------------------------------------------------------------------------------
+def boundary_indices(K):
+    """0, K-1 and both sides of every multiple of 32 / 64 / 128 inside [0, K)."""
+    s = {0, K - 1}
+    for step in (32, 64, 128):
+        for b in range(step, K, step):
+            s.update((b - 1, b))
+    return sorted(i for i in s if 0 <= i < K)
+
+
+def selector_probe(M, N, K, dtype, seed=0):
+    """A one-hot rows (A[m, pi(m)] = 1), W arbitrary -> (A, W, expected y[m, n] = W[n, pi(m)] exactly)."""
+    g = torch.Generator().manual_seed(1000 + seed)
+    idx = boundary_indices(K)
+    pi = torch.tensor([idx[m % len(idx)] for m in range(M)])
+    if M > len(idx):            # rows beyond the boundary list walk every k
+        pi[len(idx):] = (torch.arange(M - len(idx)) * 7 + seed) % K
+    A = torch.zeros(M, K, dtype=dtype)
+    A[torch.arange(M), pi] = 1.0
+    W = torch.randn(N, K, generator=g).to(dtype)
+    return A, W, W[:, pi].t().contiguous()
+
+
+def selector_probe_w(M, N, K, dtype, seed=0):
+    """the mirrored form: W one-hot rows, A arbitrary -> expected y[m, n] = A[m, pi(n)]."""
+    W, A, exp_t = selector_probe(N, M, K, dtype, seed + 500)
+    return A, W, exp_t.t().contiguous()
+
+
+def counter_probe(M, N, K, dtype, seed=0):
+    """A all ones, W integers in [-4, 4]: every fp32 partial sum is an exact integer (|sum| <= 4 K < 2^24), so whatever the order,
+    y = round_T(sum_k W[n, k]); a k taken twice or not at all changes the integer."""
+    assert 4 * K < 2 ** 24
+    g = torch.Generator().manual_seed(2000 + seed)
+    W = torch.randint(-4, 5, (N, K), generator=g).to(dtype)
+    A = torch.ones(M, K, dtype=dtype)
+    exp = W.double().sum(1).to(dtype)[None, :].expand(M, N).contiguous()
+    return A, W, exp
+
+
+def conv_impulse_positions(B, H, W):
+    """(b, h, w) of the impulse probes: corners, one pixel on each edge, w = W - 1 on an inner row, an interior pixel, and the
+    last pixel of the last image."""
+    hm, wm = H // 2, W // 2
+    pos = [(0, 0, 0), (0, 0, W - 1), (0, H - 1, 0), (0, H - 1, W - 1), (0, 0, wm), (0, H - 1, wm), (0, hm, 0), (0, hm, W - 1),
+           (0, max(hm - 1, 0), W - 1), (0, hm, wm), (B - 1, H - 1, W - 1), (B - 1, 0, 0)]
+    out = []
+    for p in pos:
+        if p not in out:
+            out.append(p)
+    return out
+
+
+def conv_impulse(B, Ci, H, W, pos, ci, dtype, value=1.0):
+    x = torch.zeros(B, Ci, H, W, dtype=dtype)
+    x[pos[0], ci, pos[1], pos[2]] = value
+    return x
+
+
+def conv_expected(x, w, dtype, stride=1, upsample=False):
+    """fp64 conv2d rounded to T (exact for impulse inputs: every output is one product value * weight, or a sum of the <= 4
+    products of an upsampled impulse, formed exactly in fp64)."""
+    F = torch.nn.functional
+    xd = x.double()
+    if upsample:
+        xd = F.interpolate(xd, scale_factor=2.0, mode="nearest")
+    return F.conv2d(xd, w.double(), None, stride=stride, padding=1).to(dtype)
+
+
+def attention_selector(Lq, Lk, hd, dtype, seed=0, H=1, kscale=1.0):
+    """q_i = 128 (64 e0 + e1), k_j = hi(j) e0 + lo(j) e1 with j = 64 hi + lo, scale = 1: the scores are exactly 128 j (integers
+    below 2^24 for Lk <= 4096; every operand is exact in bf16 / fp16), neighbouring keys differ by 128, and exp(-128) underflows
+    to exactly 0 in fp32 — each query selects the LAST key it may see, bit for bit.  -> (q, k, v) [H, L, hd]; expected rows are
+    v[:, j*] with j* = kv_len - 1, or i + Lk - Lq under the bottom-right causal mask.  Entry points that fix scale = 1 / sqrt(hd)
+    take kscale = 16 (k stays exact: 63 * 16 needs 6 bits): neighbouring scores are then >= 128 * 16 / sqrt(hd) >= 128 apart for
+    hd <= 256, the maximum still gets exp(0) = 1 and the rest underflow."""
+    assert Lk <= 4096 and hd >= 2
+    g = torch.Generator().manual_seed(3000 + seed)
+    q = torch.zeros(H, Lq, hd)
+    q[:, :, 0], q[:, :, 1] = 128.0 * 64.0, 128.0
+    j = torch.arange(Lk)
+    k = torch.zeros(H, Lk, hd)
+    k[:, :, 0], k[:, :, 1] = (j // 64).float() * kscale, (j % 64).float() * kscale
+    v = torch.randn(H, Lk, hd, generator=g)
+    return q.to(dtype), k.to(dtype), v.to(dtype)
+
+
+def attention_selector_expected(v, Lq, kv_len, causal):
+    """v [H, Lk, hd] -> expected [H, Lq, hd]"""
+    if causal:
+        idx = torch.arange(Lq) + (kv_len - Lq)
+    else:
+        idx = torch.full((Lq,), kv_len - 1)
+    return v[:, idx]
+
+
+def poison_(t, seed=0):
+    """fill t (any view) with alternating NaN / +Inf, in place"""
+    n = t.numel()
+    pat = torch.where(torch.arange(n) % 2 == 0, torch.tensor(float("nan")), torch.tensor(float("inf")))
+    t.copy_(pat.view(t.shape).to(device=t.device, dtype=t.dtype))
+    return t
+
+
+# ---- the cases of tests/test_kernel_edges_gpu.py (tests/test_kernel_check_cpu.py runs a simulated kernel over every one) --------
+GEMV_SHAPES = [(512, 256), (100, 512), (4096, 4096), (4096, 11008), (1000, 1664), (33, 8)]
+GEMM_SHAPES = [(1, 64, 64), (37, 100, 256), (65, 4096, 4096), (114, 1000, 4096), (343, 768, 512),
+               (130, 4992, 1664), (256, 1664, 608), (300, 256, 8192), (1024, 512, 1664)]
+# every M of {129, 255, 256, 257, 520}, N of {72, 330, 640} and K of {1 .. 7 K tiles, 8, 24, 72} at least once
+GEMM_EDGE_SHAPES = [(129, 72, 64), (255, 330, 128), (256, 640, 192), (257, 330, 256), (520, 640, 320), (520, 330, 384),
+                    (256, 72, 448), (257, 640, 8), (129, 330, 24), (255, 72, 72)]
+GEMM_EPILOGUES = ["plain", "bias", "residual", "bias+residual", "gelu", "geglu"]
+# out aliases residual (ss_models.hip vit_blocks: attention out-projection and MLP down-projection of the ViT, rows = batch * 257;
+# the resampler's toy width)
+# + whole 256 x 320 tiles: the 320-wide ping-pong tiles 56 / 58 refuse anything else and hand the launch to tile 60
+GEMM_INPLACE_SHAPES = [(257, 1664, 1664), (514, 1664, 8192), (1028, 1664, 1664), (514, 256, 512), (512, 1280, 640), (256, 320, 64)]
+GEMM_PROBE_SHAPES = [(257, 330, 448), (129, 72, 24), (520, 640, 320), (512, 640, 320)]
+GEMM_STRIDE_SHAPES = [(257, 330, 192), (256, 640, 128)]
+GEMM_PERSISTENT_SHAPES = [(8200, 3840, 192), (8192, 10240, 128), (8192, 5120, 64), (16384, 2560, 640)]
+
+
+def pp320_eligible(M, N, K):
+    """the rule of pp_launch<T, 320, ...> (ss_gemm_pp.inc): whole 256 x 320 tiles, whole K tiles.  A hand copy (the library does
+    not report which kernel ran): pp_launch carries a comment that points here, change both together."""
+    return M % 256 == 0 and N % 320 == 0 and K % 64 == 0 and K >= 64
+
+
+def conv_pp320_eligible(B, Ci, Co, H, W, stride, up):
+    """the conv form of the same rule: stride 1, no upsample, W >= 8 and H powers of two, Cin % 64 == 0"""
+    return (stride == 1 and not up and Ci % 64 == 0 and Ci <= 4096 and W >= 8 and W & (W - 1) == 0 and H & (H - 1) == 0 and (B * H * W) % 256 == 0
+            and Co % 320 == 0)
+
+
+def persistent_inputs(M, N, K, dtype, seed, device="cpu"):
+    """operands of the persistent multi-tile cases: w ~ 0.05 N(0, 1), bias and residual ~ N(0, 1)"""
+    g = torch.Generator(device=device).manual_seed(seed)
+    a = torch.randn(M, K, device=device, dtype=dtype, generator=g)
+    w = (torch.randn(N, K, device=device, generator=g) * 0.05).to(dtype)
+    bias = torch.randn(N, device=device, dtype=dtype, generator=g)
+    res = torch.randn(M, N, device=device, dtype=dtype, generator=g)
+    return a, w, bias, res
+
+# B, Cin, Cout, H, W, stride, upsample
+CONV_EDGE_CASES = [(2, 8, 16, 4, 8, 1, False), (1, 64, 96, 16, 16, 1, False), (1, 128, 8, 33, 31, 1, False), (1, 64, 64, 64, 64, 1, False),
+                   (2, 320, 64, 9, 8, 2, False), (1, 64, 40, 6, 5, 1, True), (1, 1920, 64, 8, 8, 1, False), (2, 64, 320, 16, 16, 1, False),
+                   (1, 64, 256, 16, 16, 1, False)]
+CONV_IMPULSE_CASES = [(2, 64, 32, 8, 8, 1, False), (2, 64, 32, 8, 8, 2, False), (2, 64, 32, 4, 8, 1, True), (2, 64, 256, 8, 16, 1, False),
+                      (4, 64, 320, 8, 8, 1, False)]       # the last: whole 256 x 320 tiles (conv tile 56)
+CONV_VARIANTS = [(), ("bias",), ("bias", "rowvec"), ("bias", "residual"), ("rowvec", "residual"), ("bias", "rowvec", "residual")]
+# B, heads, hd, Lq, Lk, causal: Lq / Lk on both sides of 16 / 64 / 128, causal with Lk - Lq in {0, 1, 63, 64}
+ATTN_EDGE_CASES = [(1, 2, 64, 15, 17, False), (2, 2, 64, 63, 65, False), (1, 2, 64, 129, 127, False), (1, 2, 64, 128, 128, True),
+                   (1, 2, 64, 64, 65, True), (1, 2, 64, 65, 128, True), (1, 2, 64, 64, 128, True), (1, 2, 64, 17, 17, True),
+                   (1, 2, 128, 16, 15, False), (1, 2, 128, 65, 63, False), (2, 2, 128, 127, 129, False), (1, 2, 128, 129, 129, True),
+                   (1, 2, 128, 127, 128, True), (1, 2, 128, 65, 128, True), (1, 2, 128, 63, 127, True),
+                   (1, 2, 104, 17, 64, False), (1, 2, 104, 128, 65, False), (1, 2, 104, 64, 64, True), (1, 2, 104, 33, 96, True),
+                   (1, 2, 104, 64, 65, True), (1, 2, 104, 64, 128, True),
+                   # several 128 / 256 / 512-row query blocks with a ragged last one (the 4 / 8 / 16-wave v3p kernels)
+                   (1, 2, 64, 600, 333, False), (1, 2, 64, 700, 763, True)]
+# attention_cache / attention_cache_slots: heads, hd, cap, rows per slot, kv_lens (unequal), one per slot
+ATTN_CACHE_CASES = [(2, 128, 200, 17, [17, 81, 128, 200]), (2, 64, 160, 40, [40, 41, 103, 104, 129]), (2, 128, 300, 66, [66, 67, 130, 257]),
+                    (2, 104, 96, 8, [8, 9, 71, 72]), (2, 104, 96, 40, [40, 41, 95, 96])]
+DECODE_NSPLITS = [0, 4, 8, 16, 32]
+DECODE_HEADS, DECODE_CAP = 4, 1200
+
+
+def decode_kv_lens(nsplit):
+    ns = nsplit if nsplit else 16
+    return sorted({1, ns - 1, ns, ns + 1, 500, DECODE_CAP})
+
+
+DECODE_KV_LENS = sorted({kvl for ns in DECODE_NSPLITS for kvl in decode_kv_lens(ns)})      # every length runs at every split count
+
+
+GEMV_NB = [1, 2, 3, 4, 5, 8, 16]
+GEMV_SILU_SHAPES = [(256, 256), (512, 4096), (100, 512)]        # I, K
+
+
+def epilogue_inputs(name, M, N, dtype, seed):
+    """bias / residual of a GEMM epilogue case -> kwargs of gemm_bound (CPU tensors)"""
+    g = torch.Generator().manual_seed(7000 + seed)
+    bias = (torch.randn(N, generator=g) * 0.5).to(dtype)
+    res = torch.randn(M, N, generator=g).to(dtype)
+    return {"plain": {}, "bias": {"bias": bias}, "residual": {"residual": res}, "bias+residual": {"bias": bias, "residual": res},
+            "gelu": {"bias": bias, "gelu_": True}, "geglu": {"bias": bias, "geglu": True}}[name]
+
+
+def gemm_inputs(M, N, K, dtype, seed):
+    """fresh operands per case: a ~ N(0, 1), w ~ N(0, 1 / K) so the product is O(1) in every dtype"""
+    g = torch.Generator().manual_seed(5000 + seed)
+    return torch.randn(M, K, generator=g).to(dtype), (torch.randn(N, K, generator=g) / K ** 0.5).to(dtype)
+
+
+def conv_inputs(B, Ci, Co, H, W, stride, up, dtype, seed):
+    g = torch.Generator().manual_seed(6000 + seed)
+    x = torch.randn(B, Ci, H, W, generator=g).to(dtype)
+    w = (torch.randn(Co, Ci, 3, 3, generator=g) / (9 * Ci) ** 0.5).to(dtype)
+    bias = (torch.randn(Co, generator=g) * 0.5).to(dtype)
+    tv = (torch.randn(B, Co, generator=g) * 0.5).to(dtype)
+    Hin, Win = (2 * H, 2 * W) if up else (H, W)
+    Ho, Wo = (Hin - 1) // stride + 1, (Win - 1) // stride + 1
+    res = torch.randn(B, Co, Ho, Wo, generator=g).to(dtype)
+    return x, w, bias, tv, res
+
+
+def attn_inputs(B, H, hd, Lq, Lk, dtype, seed):
+    g = torch.Generator().manual_seed(8000 + seed)
+    E = H * hd
+    return (torch.randn(B, Lq, E, generator=g).to(dtype), torch.randn(B, Lk, E, generator=g).to(dtype),
+            torch.randn(B, Lk, E, generator=g).to(dtype))
+
+
+def heads(x, H):
+    """[B, L, H * hd] -> [B, H, L, hd]"""
+    B, L, E = x.shape
+    return x.view(B, L, H, E // H).transpose(1, 2)
+
+
+def unheads(x):
+    """[B, H, L, hd] -> [B, L, H * hd]"""
+    B, H, L, hd = x.shape
+    return x.transpose(1, 2).reshape(B, L, H * hd)

@@ -12,6 +12,7 @@ import math
 import pytest
 import torch
 
+import kernel_check as KC
 import seedstory_oracle as O
 import synth
 
@@ -97,7 +98,7 @@ def test_rope_kv_append(ops, dtype):
     assert torch.equal(q2.cpu(), q2_ref)
 
 
-GEMV_SHAPES = [(512, 256), (100, 512), (4096, 4096), (4096, 11008), (1000, 1664), (33, 8)]
+GEMV_SHAPES = KC.GEMV_SHAPES
 
 
 @pytest.mark.parametrize("N,K", GEMV_SHAPES)
@@ -111,9 +112,12 @@ def test_gemv_plain_and_epilogues(ops, N, K, dtype):
     ref = w.float() @ x.float()
     y = ops.gemv(dev(w), dev(x))
     assert rel(y, ref.to(dtype)) < tol
+    acc = KC.accumulate(x[None], w)
+    KC.check(y, *KC.epilogue(*acc, dtype), "gemv plain")
     y = ops.gemv(dev(w), dev(x), bias=dev(bias), residual=dev(res))
     ref2 = ((ref + bias.float()).to(dtype) + res).to(dtype)
     assert rel(y, ref2) < tol
+    KC.check(y, *KC.epilogue(*acc, dtype, bias=bias, residual=res[None]), "gemv bias+residual")
     # fused RMSNorm prologue
     nw = synth.normal_like(11, (K,), 0.1, 1.0, dtype=dtype)
     xn = O.rmsnorm(x, nw, 1e-5)
@@ -257,8 +261,7 @@ def test_gemv_mfma_form_at_small_batches(ops, nb):
     assert rel(got, want) < 4e-3 and torch.equal(got, got_generic)
 
 
-GEMM_SHAPES = [(1, 64, 64), (37, 100, 256), (65, 4096, 4096), (114, 1000, 4096), (343, 768, 512),
-               (130, 4992, 1664), (256, 1664, 608), (300, 256, 8192), (1024, 512, 1664)]
+GEMM_SHAPES = KC.GEMM_SHAPES
 
 
 @pytest.mark.parametrize("M,N,K", GEMM_SHAPES)
@@ -272,10 +275,14 @@ def test_gemm(ops, M, N, K, dtype):
     ref = a.float() @ w.float().t()
     y = ops.gemm(dev(a), dev(w))
     assert rel(y, ref) < tol, "plain"
+    acc = KC.accumulate(a, w)
+    KC.check(y, *KC.epilogue(*acc, dtype), "gemm plain")
     y = ops.gemm(dev(a), dev(w), bias=dev(bias), residual=dev(res))
     assert rel(y, ((ref + bias.float()).to(dtype) + res).float()) < tol, "bias+residual"
+    KC.check(y, *KC.epilogue(*acc, dtype, bias=bias, residual=res), "gemm bias+residual")
     y = ops.gemm(dev(a), dev(w), bias=dev(bias), gelu=True)
     assert rel(y, torch.nn.functional.gelu((ref + bias.float()).to(dtype))) < tol * 1.5, "bias+gelu"
+    KC.check(y, *KC.epilogue(*acc, dtype, bias=bias, gelu_=True), "gemm bias+gelu")
 
 
 @pytest.mark.parametrize("M,N,K", GEMM_SHAPES + [(528, 4096, 4096), (913, 12288, 4096), (2304, 8192, 1024), (2100, 8200, 520)])
@@ -305,7 +312,7 @@ def test_gemm_f32_split_bf16_gate_mode(ops, M, N, K):
     assert rel(yg.double().cpu(), torch.nn.functional.gelu(ref + bias.double())) < 5e-5
 
 
-@pytest.mark.parametrize("cfg", [1, 2, 3])
+@pytest.mark.parametrize("cfg", KC.GEMM_REG_TILES)
 def test_gemm_every_tile_config(ops, cfg):
     from seedstory import _lib
     a = synth.normal_like(18, (200, 512), 1.0, dtype=torch.bfloat16)
@@ -318,8 +325,10 @@ def test_gemm_every_tile_config(ops, cfg):
     assert rel(y, a.float() @ w.float().t()) < 4e-3
 
 
-@pytest.mark.parametrize("cfg", [8, 10, 15, 20, 21, 22, 23, 24, 26, 28, 29, 30, 31, 32, 33, 34, 35, 36, 37, 38, 39, 40, 41, 42, 43, 44, 45, 46, 54, 55, 56, 57, 58,
-                                 60, 61, 62, 63, 64, 65, 66, 67, 68, 69, 70, 71, 72])
+_DMA_ACC = {}      # (M, N, K) -> fp64 product and accumulation bound of the sweep's operands (the same for every tile id)
+
+
+@pytest.mark.parametrize("cfg", KC.GEMM_DMA_TILES)
 @pytest.mark.parametrize("M,N,K", [(200, 300, 512), (1024, 640, 1280), (333, 1000, 64), (4096, 256, 2560), (130, 72, 192)])
 def test_gemm_dma_tile_configs_with_epilogues(ops, cfg, M, N, K):
     """Every LDS-DMA tile configuration (8/10/15 double-buffered, 20-46 / 60-72 software-pipelined, 54-58 ping-pong) on ragged and
@@ -346,9 +355,17 @@ def test_gemm_dma_tile_configs_with_epilogues(ops, cfg, M, N, K):
     if y3 is not None:
         full = (ref + bias.float()).to(dtype).float()
         assert rel(y3, full[:, 0::2] * torch.nn.functional.gelu(full[:, 1::2].to(dtype)).float()) < 8e-3
+    if (M, N, K) not in _DMA_ACC:
+        _DMA_ACC[(M, N, K)] = KC.accumulate(a.cpu(), w.cpu())
+    acc, bc, rc = _DMA_ACC[(M, N, K)], bias.cpu(), res.cpu()
+    KC.check(y0, *KC.epilogue(*acc, dtype), "cfg %d plain" % cfg)
+    KC.check(y1, *KC.epilogue(*acc, dtype, bias=bc, residual=rc), "cfg %d bias+residual" % cfg)
+    KC.check(y2, *KC.epilogue(*acc, dtype, bias=bc, gelu_=True), "cfg %d bias+gelu" % cfg)
+    if y3 is not None:
+        KC.check(y3, *KC.epilogue(*acc, dtype, bias=bc, geglu=True), "cfg %d geglu" % cfg)
 
 
-@pytest.mark.parametrize("cfg", [54, 55, 56, 57, 58])
+@pytest.mark.parametrize("cfg", KC.GEMM_PP_TILES)
 @pytest.mark.parametrize("K", [64, 128, 192, 256, 320, 448])
 @pytest.mark.parametrize("M,N", [(512, 640), (520, 330), (256, 320)])
 def test_gemm_pingpong_k_tile_edge_cases(ops, cfg, K, M, N):
@@ -373,15 +390,15 @@ def test_gemm_pingpong_k_tile_edge_cases(ops, cfg, K, M, N):
         assert torch.equal(y, y60)
 
 
-@pytest.mark.parametrize("cfg", [54, 55, 56, 57, 58])
+@pytest.mark.parametrize("cfg", KC.GEMM_PP_TILES)
 @pytest.mark.parametrize("M,N,K", [(512, 640, 256), (1000, 512, 320), (256, 320, 64), (2048, 1280, 128)])
-def test_gemm_pingpong_pipelined_epilogue_variants(ops, cfg, M, N, K):
+def test_gemm_pingpong_pipelined_epilogue_variants(ops, cfg, M, N, K, dtype=torch.bfloat16):
     """The chunk-pipelined staged epilogue of the ping-pong tiles (gemm_epilogue_staged_pipe: plain, bias, residual with its
     two-chunk prefetch, bias + residual, GELU, GEGLU pair) against the one-barrier tile 60, which keeps the chunk-serial
     gemm_epilogue_staged: bit for bit, on whole-tile shapes and on a ragged M (row predicates of the 256-wide tiles; the 320-wide
-    tiles refuse ragged shapes and the call takes their fallback), 1 .. 5 K tiles, repeated launches identical."""
+    tiles refuse ragged shapes and the call takes their fallback), 1 .. 5 K tiles, repeated launches identical.  (`dtype`: the
+    fp16 twin below runs this body too.)"""
     from seedstory import _lib
-    dtype = torch.bfloat16
     a = dev(synth.normal_like(196, (M, K), 1.0, dtype=dtype))
     w = dev(synth.normal_like(197, (N, K), 0.05, dtype=dtype))
     bias = dev(synth.normal_like(198, (N,), 0.5, dtype=dtype))
@@ -403,7 +420,14 @@ def test_gemm_pingpong_pipelined_epilogue_variants(ops, cfg, M, N, K):
             assert torch.equal(y, r)
 
 
-@pytest.mark.parametrize("cfg", [30, 31, 32, 33, 35, 36, 38, 39, 40, 41, 42, 43, 60, 61, 62, 64])
+@pytest.mark.parametrize("cfg", KC.GEMM_PP_TILES)
+@pytest.mark.parametrize("M,N,K", [(512, 640, 256), (1000, 512, 320), (256, 320, 64), (2048, 1280, 128)])
+def test_gemm_pingpong_pipelined_epilogue_variants_fp16(ops, cfg, M, N, K):
+    """the same in fp16: the pack2 / unpack2 path of ss_gemm_pp_f16.hip, bit for bit against tile 60"""
+    test_gemm_pingpong_pipelined_epilogue_variants(ops, cfg, M, N, K, dtype=torch.float16)
+
+
+@pytest.mark.parametrize("cfg", KC.GEMM_RING_TILES)
 @pytest.mark.parametrize("K", [64, 128, 192, 256, 320])
 def test_gemm_ring_depth_k_tile_edge_cases(ops, cfg, K):
     """1 .. 5 K tiles through the 2- and 3-slot LDS rings (prologue / drain paths of the counted vmcnt waits) and the
@@ -423,7 +447,7 @@ def test_gemm_ring_depth_k_tile_edge_cases(ops, cfg, K):
         assert torch.equal(y, ys[0])
 
 
-@pytest.mark.parametrize("cfg", [33, 35, 36, 38, 39, 40, 43, 54, 55, 56, 57, 58, 60, 64, 72])
+@pytest.mark.parametrize("cfg", KC.GEMM_PERSISTENT_TILES)
 @pytest.mark.parametrize("M,N,K", [(8200, 3840, 192), (8192, 10240, 128), (8192, 5120, 64), (16384, 2560, 640)])
 def test_gemm_persistent_multi_tile(ops, cfg, M, N, K):
     """Persistent configurations with several output tiles per workgroup (grid capped at the CU count): the next tile's
@@ -484,6 +508,8 @@ def test_flash_attention(ops, B, H, hd, Lq, Lk, causal, dtype):
     o = ops.attention(dev(q), dev(k), dev(v), H, scale, causal)
     ref = attn_ref(q, k, v, H, scale, causal)
     assert rel(o, ref) < (2e-5 if dtype == torch.float32 else 1e-2)
+    r64, t64 = KC.attention_bound(KC.heads(q, H), KC.heads(k, H), KC.heads(v, H), scale, KC.causal_allow(Lq, Lk) if causal else None, dtype)
+    KC.check(KC.heads(o.cpu(), H), r64, t64, "attention")
 
 
 def test_flash_attention_softmax_rescale_branch(ops):
@@ -511,6 +537,8 @@ def test_attn_decode(ops, kv_len, dtype):
     s = torch.matmul(qh, kc[:, :kv_len].float().transpose(-1, -2)) / math.sqrt(hd)
     ref = torch.matmul(torch.softmax(s, -1), vc[:, :kv_len].float()).reshape(H * hd)
     assert rel(o, ref) < (1e-5 if dtype == torch.float32 else 4e-3)
+    r64, t64 = KC.attention_bound(q.view(H, 1, hd), kc[:, :kv_len], vc[:, :kv_len], 1.0 / math.sqrt(hd), None, dtype)
+    KC.check(o.view(H, 1, hd), r64, t64, "attn_decode")
 
 
 def test_attention_cache_matches_decode(ops):

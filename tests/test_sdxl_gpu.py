@@ -13,6 +13,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import kernel_check as KC
 import sdxl_oracle as S
 import seedstory_oracle as O
 import synth
@@ -54,13 +55,15 @@ def test_conv3x3(B, Ci, Co, H, W, stride, up, dtype):
     assert (ho, wo) == (Ho, Wo)
     tol = 2e-5 if dtype == torch.float32 else 5e-3
     assert rel(nchw(y.cpu(), B, Ho, Wo), ref) < tol
+    KC.check(nchw(y.cpu(), B, Ho, Wo), *KC.conv_bound(x, w, dtype, stride, up, bias=b), "conv + bias")
     y2, _, _ = ops.conv3x3(nhwc(x).to(DEV), _conv_w(w).to(DEV), B, H, W, stride=stride, upsample=up, bias=b.to(DEV),
                            rowvec=tv.to(DEV), residual=nhwc(res).to(DEV))
     ref2 = ref + tv.float()[:, :, None, None] + res.float()
     assert rel(nchw(y2.cpu(), B, Ho, Wo), ref2) < tol * 2
+    KC.check(nchw(y2.cpu(), B, Ho, Wo), *KC.conv_bound(x, w, dtype, stride, up, bias=b, rowvec=tv, residual=res), "conv + bias + rowvec + residual")
 
 
-@pytest.mark.parametrize("cfg", [54, 55, 56, 57])
+@pytest.mark.parametrize("cfg", KC.CONV_PP_TILES)
 @pytest.mark.parametrize("B,Ci,Co,H,W", [(2, 64, 320, 16, 16), (1, 128, 640, 32, 8), (4, 320, 256, 8, 32), (1, 64, 320, 16, 16), (3, 192, 320, 16, 16),
                                          (2, 1280, 640, 16, 16)])
 def test_conv3x3_pingpong_tiles(cfg, B, Ci, Co, H, W):
@@ -90,17 +93,16 @@ def test_conv3x3_pingpong_tiles(cfg, B, Ci, Co, H, W):
         assert torch.equal(y, y69)
 
 
-@pytest.mark.parametrize("cfg", [54, 55, 56, 57])
+@pytest.mark.parametrize("cfg", KC.CONV_PP_TILES)
 @pytest.mark.parametrize("B,Ci,Co,H,W", [(2, 64, 320, 16, 16), (4, 320, 256, 8, 32), (2, 128, 640, 32, 32), (32, 64, 320, 4, 8)])
-def test_conv3x3_pingpong_pipelined_epilogue_variants(cfg, B, Ci, Co, H, W):
+def test_conv3x3_pingpong_pipelined_epilogue_variants(cfg, B, Ci, Co, H, W, dtype=torch.bfloat16):
     """The ResBlock's two convolutions as the ping-pong tiles run them since the pipelined epilogue: conv1 = bias + time-embedding
     row vector (variant 3: the vector stays packed, re-loaded when a 16-row chunk enters the next image), conv2 = bias + residual
     (variant 1 with the residual prefetch), plus the plain form — each bit for bit equal to the one-barrier tile 69 (chunk-serial
     epilogue).  (32, .., 4, 8): 32 pixels per image, so one 128-row wave tile spans four images and the vector changes every other
-    chunk."""
+    chunk.  (`dtype`: the fp16 twin below runs this body too.)"""
     from seedstory import _lib, ops
     from seedstory.diffusion import _conv_w
-    dtype = torch.bfloat16
     x = synth.normal_like(221, (B, Ci, H, W), 1.0, dtype=dtype)
     w = synth.normal_like(222, (Co, Ci, 3, 3), 1.0 / math.sqrt(9 * Ci), dtype=dtype)
     b = synth.normal_like(223, (Co,), 0.5, dtype=dtype)
@@ -126,7 +128,17 @@ def test_conv3x3_pingpong_pipelined_epilogue_variants(cfg, B, Ci, Co, H, W):
             assert torch.equal(y, r)
 
 
-@pytest.mark.parametrize("cfg", [8, 15, 20, 21, 22, 23, 24, 26, 28, 29, 30, 33, 34, 36, 37, 38, 39, 40, 41, 42, 43, 44, 45, 46, 54, 56, 60, 61, 62, 63, 64, 65, 66, 67, 68, 69, 70, 71, 72])
+@pytest.mark.parametrize("cfg", KC.CONV_PP_TILES)
+@pytest.mark.parametrize("B,Ci,Co,H,W", [(2, 64, 320, 16, 16), (4, 320, 256, 8, 32), (2, 128, 640, 32, 32), (32, 64, 320, 4, 8)])
+def test_conv3x3_pingpong_pipelined_epilogue_variants_fp16(cfg, B, Ci, Co, H, W):
+    """the same in fp16 (ss_gemm_pp_f16_conv.hip), bit for bit against tile 69"""
+    test_conv3x3_pingpong_pipelined_epilogue_variants(cfg, B, Ci, Co, H, W, dtype=torch.float16)
+
+
+_CONV_BOUND = {}      # case -> (reference, bound) of the sweep's operands (the same for every tile id)
+
+
+@pytest.mark.parametrize("cfg", KC.CONV_DMA_TILES)
 @pytest.mark.parametrize("B,Ci,Co,H,W,stride,up", [(2, 64, 96, 16, 16, 1, False), (2, 320, 64, 9, 8, 2, False),
                                                    (1, 128, 200, 6, 5, 1, True), (3, 192, 320, 13, 11, 1, False)])
 def test_conv3x3_dma_tile_configs(cfg, B, Ci, Co, H, W, stride, up):
@@ -155,9 +167,13 @@ def test_conv3x3_dma_tile_configs(cfg, B, Ci, Co, H, W, stride, up):
     assert rel(nchw(y.cpu(), B, Ho, Wo), ref + tv.float()[:, :, None, None] + res.float()) < 1e-2
     for other, _, _ in ys[1:]:
         assert torch.equal(other, y)
+    case = (B, Ci, Co, H, W, stride, up)
+    if case not in _CONV_BOUND:
+        _CONV_BOUND[case] = KC.conv_bound(x, w, dtype, stride, up, bias=b, rowvec=tv, residual=res)
+    KC.check(nchw(y.cpu(), B, Ho, Wo), *_CONV_BOUND[case], "conv cfg %d %s" % (cfg, case))
 
 
-@pytest.mark.parametrize("cfg", [33, 36, 38, 39, 40, 43, 60, 64, 72])
+@pytest.mark.parametrize("cfg", KC.CONV_PERSISTENT_TILES)
 def test_conv3x3_persistent_multi_tile(cfg):
     """Implicit-GEMM conv through the persistent configurations with > 1 output tile per workgroup."""
     from seedstory import _lib, ops
