@@ -239,6 +239,20 @@ int ss_attn_decode(const void* q, const void* kcache, const void* vcache, void* 
                    const int32_t* kv_len_dev, int64_t n_heads, int64_t hd, int64_t cache_cap, int dtype,
                    void* stream);
 
+/* Attention MAP of one head, as the reference returns it under `output_attentions`
+ * (modeling_llama_xformer.py:246-276, 299-301): PRE-softmax scores with the mask added, every rounding in the model dtype:
+ *   s = rnd_T(rnd_T(q . k) / sqrt(head_dim)), q / k post-RoPE.
+ * q [M, head_dim] rows of one head (row stride ldq), k [kv, head_dim] one head's plane of the KV cache (row stride ldk),
+ * out [M, ldo] in the model dtype.  Row i's own key is column kv - M + i (kv >= M).
+ *   row_calls = 0: the M rows are ONE reference call.  M > 1: all kv columns are written, s where j <= own(i), else
+ *                  rnd_T(s + finfo(T).min) (the additive causal mask; added and rounded, not a constant).  M == 1: all kv
+ *                  columns are written, s, and rnd_T(s + 1) on the last one (the bool mask of the one-row call).
+ *   row_calls = 1: every row is its own one-row call: row i writes columns [0, own(i)], rnd_T(s + 1) on own(i); columns
+ *                  beyond are NOT touched (the caller pre-fills them, with NaN to match the reference's merged maps).
+ * Nothing outside [M, kv] of out is written.  head_dim 128 or 64; q, k and their strides 16-byte aligned. */
+int ss_attn_scores(const void* q, int64_t ldq, const void* k, int64_t ldk, void* out, int64_t ldo, int64_t M,
+                   int64_t kv, int64_t head_dim, int row_calls, int dtype, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * Dense contractions
  * ------------------------------------------------------------------------------------- */
@@ -355,6 +369,23 @@ int ss_llama_select(ss_llama* h, int32_t seq);
  * loop's stop word holds EOS in 16 bits and this id + 1 in the 15 bits above; ss_llama_create therefore requires
  * vocab <= 65535 and eos_id < 65535 (LLaMA-2 + 66 added tokens: 32066). */
 int ss_llama_set_stop_id(ss_llama* h, int32_t token_id);
+
+/* Attention-map capture (the reference's `config.output_attentions`: one map per decoder layer, head `head`, the values
+ * ss_attn_scores documents).  maps = device memory [n_layers][n_rows][ld] in the model dtype, owned AND PRE-FILLED by the
+ * caller (NaN reproduces the reference's merged maps; the engine never clears it); buffer row r belongs to the query whose
+ * key sits at cache index row0 + r.  While capture is on,
+ *   ss_llama_prefill   writes its M rows x (kv_len + M) columns per layer; row_calls = 1 makes every multi-row prefill
+ *                      write each row as its own one-row call (the image-token block, which the reference feeds one
+ *                      token at a time); SS_EINVAL before anything is launched when the rows or columns do not fit;
+ *   ss_llama_generate  writes one row per decode token from inside the token (eager or captured; the captured graph has
+ *                      one more node per layer and is cached apart from the shipped one; it reads the buffer from a device
+ *                      descriptor, so changing buffers does not re-capture); kv_len + n_steps must fit, SS_EINVAL otherwise;
+ *   ss_llama_prefill_batch / ss_llama_generate_batch  refuse (SS_EINVAL): maps are a single-sequence tool — an n_seq > 1
+ *                      engine captures through the single-sequence entry points on the selected slot.
+ * maps = NULL turns capture off (the default): the decode token then launches exactly what it launched before.  Call it
+ * between engine calls, not while one is in flight (it updates the descriptor with a blocking copy). */
+int ss_llama_set_attn_capture(ss_llama* h, void* maps, int64_t n_rows, int64_t ld, int64_t row0, int32_t head,
+                              int32_t row_calls);
 
 /* Device pointers into the engine's workspace (views for the Python side), for the selected slot:
  * which: 0 = K cache [n_layers, n_heads, cache_cap, hd], 1 = V cache (same shape),

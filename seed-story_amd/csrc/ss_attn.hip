@@ -1367,22 +1367,7 @@ int attention_dev(const AttnArgs& a, int64_t batch, int dtype, hipStream_t s) {
 // owns position kv_len stores the rotated k and v into the cache (the torch.cat of :239-242) and
 // takes them from registers, so no other kernel (and no global read-after-write) is needed.
 // partial record per (head, split): [m, l, o[hd]] fp32; attn_combine_kernel merges the splits.
-template <typename T>
-__device__ __forceinline__ uint4 rope_pack(const T* row_h, const T* cos_t, const T* sin_t, int pos, int hd, int d0) {
-    // returns round(round(x*cos) + round(rot*sin)) for d in [d0, d0+V)
-    constexpr int V = Tr<T>::kVec;
-    const int half = hd >> 1;
-    float x[V], xp[V], c[V], sn[V], o[V];
-    unpack<T>(ld16(row_h + d0), x);
-    unpack<T>(ld16(row_h + (d0 < half ? d0 + half : d0 - half)), xp);
-    unpack<T>(ld16(cos_t + (int64_t)pos * hd + d0), c);
-    unpack<T>(ld16(sin_t + (int64_t)pos * hd + d0), sn);
-    const float sign = d0 < half ? -1.f : 1.f;
-#pragma unroll
-    for (int j = 0; j < V; ++j) o[j] = Tr<T>::rnd(Tr<T>::rnd(x[j] * c[j]) + Tr<T>::rnd(sign * xp[j] * sn[j]));
-    return pack<T>(o);
-}
-
+// (rope_pack: ss_common.h, shared with the attention-map capture kernel of ss_attn_scores.hip)
 struct DecodeArgs {
     const void* q;        // rotated q [n_heads*hd]            (plain mode)
     const void* qkv_raw;  // [3*n_heads*hd] pre-RoPE q|k|v      (fused mode) or NULL

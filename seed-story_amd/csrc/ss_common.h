@@ -171,6 +171,35 @@ __device__ __forceinline__ uint4 ld_nt16(const void* p) {
 __device__ __forceinline__ uint4 ld16(const void* p) { return *reinterpret_cast<const uint4*>(p); }
 __device__ __forceinline__ void st16(void* p, const uint4& v) { *reinterpret_cast<uint4*>(p) = v; }
 
+// ---- RoPE of one 16-byte pack -------------------------------------------------------------
+// rotate_half / apply_rotary_pos_emb (modeling_llama_xformer.py:158-173) in the model dtype, for the V elements [d0, d0+V) of
+// one head's row: the decode attention kernel (ss_attn.hip) and the attention-map capture kernel (ss_attn_scores.hip) rotate
+// the raw q / k of the decode token with the same arithmetic.
+template <typename T>
+__device__ __forceinline__ uint4 rope_pack(const T* row_h, const T* cos_t, const T* sin_t, int pos, int hd, int d0) {
+    // returns round(round(x*cos) + round(rot*sin)) for d in [d0, d0+V)
+    constexpr int V = Tr<T>::kVec;
+    const int half = hd >> 1;
+    float x[V], xp[V], c[V], sn[V], o[V];
+    unpack<T>(ld16(row_h + d0), x);
+    unpack<T>(ld16(row_h + (d0 < half ? d0 + half : d0 - half)), xp);
+    unpack<T>(ld16(cos_t + (int64_t)pos * hd + d0), c);
+    unpack<T>(ld16(sin_t + (int64_t)pos * hd + d0), sn);
+    const float sign = d0 < half ? -1.f : 1.f;
+#pragma unroll
+    for (int j = 0; j < V; ++j) o[j] = Tr<T>::rnd(Tr<T>::rnd(x[j] * c[j]) + Tr<T>::rnd(sign * xp[j] * sn[j]));
+    return pack<T>(o);
+}
+
+// Where the attention-map capture of the LLaMA engine writes (ss_llama_set_attn_capture): lives in device memory so that ONE
+// captured "capture on" decode graph serves every buffer the caller hands over.
+struct AttnCaptureDesc {
+    void* maps;            // [n_layers][n_rows][ld] model dtype, caller-owned; NULL = nothing is written
+    int32_t n_rows, ld;
+    int32_t row0;          // buffer row r <-> the query whose key sits at cache index row0 + r
+    int32_t head;
+};
+
 // ---- host side ------------------------------------------------------------------------------
 void set_error(const char* fmt, ...);
 int check_hip(hipError_t e, const char* what);

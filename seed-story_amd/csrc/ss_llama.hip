@@ -39,6 +39,12 @@ int attn_decode_fused_dev(const void* qkv_raw, void* kc, void* vc, const void* c
                           void* ws, const int32_t* kv_len_dev, const int32_t* pos_dev, const int32_t* done_flag,
                           int64_t n_heads, int64_t hd, int64_t cache_cap, int nb, int state_stride,
                           int64_t cache_stride, int dtype, hipStream_t s);
+int attn_scores_dev(const void* q, int64_t ldq, const void* k, int64_t ldk, void* out, int64_t ldo, int64_t M, int64_t kv,
+                    int64_t hd, int row_calls, int dtype, hipStream_t s);
+int attn_scores_decode_dev(const void* qkv_raw, const void* kplane, const void* cos_t, const void* sin_t,
+                           const int32_t* kv_len_dev, const int32_t* pos_dev, const int32_t* done_flag,
+                           const AttnCaptureDesc* desc, int layer, int64_t n_heads, int64_t hd, int64_t cap, int dtype,
+                           hipStream_t s);
 
 // device state words
 enum { ST_KV_LEN = 0, ST_POS = 1, ST_NGEN = 2, ST_DONE = 3, ST_LAST = 4, ST_NFORCED = 5, ST_LIMIT = 6, ST_EOS = 7 };
@@ -168,6 +174,7 @@ static int prefill_proj(void* splitk_ws, size_t splitk_bytes, const void* A, con
 struct SeqGraph {
     int seq0, nb;
     int mode;                // arithmetic knobs the captured kernels were chosen under (gemm_f32_split): part of the cache key
+    int capture;             // attention-map capture on: one more launch per layer (a different graph; the buffer is NOT part of the key)
     hipGraph_t graph;
     hipGraphExec_t exec;
 };
@@ -199,6 +206,10 @@ struct ss_llama {
     hipStream_t cap_stream;
     std::vector<SeqGraph> graphs;
     int32_t* pinned;         // [2][n_seq][8] ints of pinned host memory: state read-back | state upload
+    // attention-map capture (ss_llama_set_attn_capture): host copy + the device descriptor the decode-token kernel reads
+    AttnCaptureDesc cap = {nullptr, 0, 0, 0, 0};
+    int cap_row_calls = 0;
+    AttnCaptureDesc* cap_desc = nullptr;
     size_t seq_kv_bytes() const { return (size_t)cfg.n_layers * cfg.n_heads * cfg.cache_cap * hd * esz; }
 };
 
@@ -246,6 +257,7 @@ static void carve(ss_llama* h, Carver& c) {
     }
     h->splitk_bytes = sk;
     h->splitk_ws = sk ? c.take(sk) : nullptr;
+    h->cap_desc = (AttnCaptureDesc*)c.take(sizeof(AttnCaptureDesc));     // zeroed with the workspace: capture off
 }
 
 static int cfg_n_seq(const ss_llama_config* cfg) { return cfg->n_seq > 0 ? cfg->n_seq : 1; }
@@ -307,6 +319,11 @@ static int decode_token(ss_llama* h, hipStream_t s, ProfSink* prof, int seq0, in
         rc = attn_decode_fused_dev(h->qkv, kc, vc, h->w.rope_cos, h->w.rope_sin, h->attn, attn_ws, st + ST_KV_LEN,
                                    st + ST_POS, done, g.n_heads, hd, g.cache_cap, nb, 8, cache_stride, dt, s);
         if (rc) return rc;
+        if (h->cap.maps && nb == 1) {   // attention-map capture: this layer's row of head cap.head (capture off: no launch)
+            rc = attn_scores_decode_dev(h->qkv, kc, h->w.rope_cos, h->w.rope_sin, st + ST_KV_LEN, st + ST_POS, done, h->cap_desc,
+                                        l, g.n_heads, hd, g.cache_cap, dt, s);
+            if (rc) return rc;
+        }
         MARK(1);
         rc = gemv_batched_dev(L.wo, h->attn, h->xn, H, H, nullptr, 0.f, nullptr, h->x, SS_EPI_RESIDUAL, done, 8, nb, H,
                               H, H, dt, s);
@@ -345,10 +362,11 @@ static int read_state(ss_llama* h, hipStream_t s) {
 // captured decode token for slots [seq0, seq0+nb), built on first use
 static int graph_for(ss_llama* h, int seq0, int nb, hipGraphExec_t* out) {
     const int mode = knob(K_gemm_f32_split);
+    const int capture = (h->cap.maps && nb == 1) ? 1 : 0;
     for (const SeqGraph& sg : h->graphs)
-        if (sg.seq0 == seq0 && sg.nb == nb && sg.mode == mode) { *out = sg.exec; return SS_OK; }
+        if (sg.seq0 == seq0 && sg.nb == nb && sg.mode == mode && sg.capture == capture) { *out = sg.exec; return SS_OK; }
     SeqGraph sg;
-    sg.seq0 = seq0; sg.nb = nb; sg.mode = mode; sg.graph = nullptr; sg.exec = nullptr;
+    sg.seq0 = seq0; sg.nb = nb; sg.mode = mode; sg.capture = capture; sg.graph = nullptr; sg.exec = nullptr;
     SS_HIP(hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
     int rc = decode_token(h, h->cap_stream, nullptr, seq0, nb);
     hipError_t ce = hipStreamEndCapture(h->cap_stream, &sg.graph);
@@ -475,6 +493,39 @@ int ss_llama_set_stop_id(ss_llama* h, int32_t token_id) {
     return SS_OK;
 }
 
+int ss_llama_set_attn_capture(ss_llama* h, void* maps, int64_t n_rows, int64_t ld, int64_t row0, int32_t head,
+                              int32_t row_calls) {
+    SS_REQUIRE(h, "llama_set_attn_capture: null handle");
+    AttnCaptureDesc d = {nullptr, 0, 0, 0, 0};
+    if (maps) {
+        SS_REQUIRE(n_rows > 0 && ld > 0 && n_rows < (1ll << 30) && ld < (1ll << 30) && row0 >= 0 && row0 <= h->cfg.cache_cap,
+                   "llama_set_attn_capture: bad buffer (n_rows=%lld ld=%lld row0=%lld)", (long long)n_rows, (long long)ld,
+                   (long long)row0);
+        SS_REQUIRE(head >= 0 && head < h->cfg.n_heads, "llama_set_attn_capture: head %d out of range (%d heads)", (int)head,
+                   h->cfg.n_heads);
+        SS_REQUIRE(row_calls == 0 || row_calls == 1, "llama_set_attn_capture: row_calls must be 0 or 1");
+        SS_REQUIRE(h->hd == 128 || h->hd == 64, "llama_set_attn_capture: head dim %d unsupported (64, 128)", h->hd);
+        d.maps = maps; d.n_rows = (int32_t)n_rows; d.ld = (int32_t)ld; d.row0 = (int32_t)row0; d.head = head;
+    }
+    // every decode loop of this engine has synchronised before it returned: nothing in flight reads the descriptor
+    SS_HIP(hipMemcpy(h->cap_desc, &d, sizeof(d), hipMemcpyHostToDevice));
+    h->cap = d;
+    h->cap_row_calls = maps ? row_calls : 0;
+    return SS_OK;
+}
+
+// capture on: the rows [kv0, kv0 + n) x columns [0, kv0 + n) must lie inside the caller's buffer
+static int capture_fits(const ss_llama* h, int64_t kv0, int64_t n, const char* who) {
+    if (!h->cap.maps) return SS_OK;
+    SS_REQUIRE(kv0 >= h->cap.row0, "%s: attention capture starts at cache index %d, the cache holds only %lld", who,
+               (int)h->cap.row0, (long long)kv0);
+    SS_REQUIRE(kv0 + n - h->cap.row0 <= h->cap.n_rows, "%s: attention-capture buffer has %d rows, %lld needed", who,
+               (int)h->cap.n_rows, (long long)(kv0 + n - h->cap.row0));
+    SS_REQUIRE(kv0 + n <= h->cap.ld, "%s: attention-capture buffer has %d columns, %lld needed", who, (int)h->cap.ld,
+               (long long)(kv0 + n));
+    return SS_OK;
+}
+
 int ss_llama_select(ss_llama* h, int32_t seq) {
     SS_REQUIRE(h && seq >= 0 && seq < h->n_seq, "llama_select: sequence slot %d out of range", (int)seq);
     h->cur = seq;
@@ -557,6 +608,7 @@ int ss_llama_prefill(ss_llama* h, const void* embeds, int64_t M, const int32_t* 
     SS_REQUIRE(cur_kv + M <= h->cfg.cache_cap, "llama_prefill: KV cache overflow (%lld + %lld > %d)",
                (long long)cur_kv, (long long)M, h->cfg.cache_cap);
     SS_REQUIRE(pos_ids || cur_pos + M <= h->cfg.max_pos, "llama_prefill: position overflow");
+    if (int crc = capture_fits(h, cur_kv, M, "llama_prefill")) return crc;
     const ss_llama_config& g = h->cfg;
     hipStream_t s = (hipStream_t)stream;
     const int dt = g.dtype;
@@ -578,6 +630,12 @@ int ss_llama_prefill(ss_llama* h, const void* embeds, int64_t M, const int32_t* 
         if ((rc = ss_rope_kv_append(h->qkv, h->q, kc, vc, h->w.rope_cos, h->w.rope_sin, pos_ids, cur_pos, M, g.n_heads,
                                     hd, kv0, g.cache_cap, dt, stream)))
             return rc;
+        if (h->cap.maps) {      // head cap.head's pre-softmax scores of these M rows against the cache (prefix included)
+            char* rows = (char*)h->cap.maps + (((size_t)l * h->cap.n_rows + (size_t)(kv0 - h->cap.row0)) * h->cap.ld) * e;
+            if ((rc = attn_scores_dev(h->q + (size_t)h->cap.head * hd * e, H, kc + (size_t)h->cap.head * g.cache_cap * hd * e, hd,
+                                      rows, h->cap.ld, M, kv1, hd, M > 1 ? h->cap_row_calls : 0, dt, s)))
+                return rc;
+        }
         if ((rc = ss_attention(h->q, kc, vc, h->attn, 1, g.n_heads, M, kv1, hd, 0, hd, H, 0, (int64_t)g.cache_cap * hd,
                                hd, 0, (int64_t)g.cache_cap * hd, hd, 0, hd, H, 1.0f / sqrtf((float)hd), 1, dt, stream)))
             return rc;
@@ -606,6 +664,7 @@ int ss_llama_prefill(ss_llama* h, const void* embeds, int64_t M, const int32_t* 
 // continuation of lock-step stories (4 x 66 rows) and for their prompt prefill (4 x S rows).
 int ss_llama_prefill_batch(ss_llama* h, const void* embeds, const int64_t* host_rows, void* hidden_out, void* stream) {
     SS_REQUIRE(h && embeds && host_rows, "llama_prefill_batch: bad arguments");
+    SS_REQUIRE(!h->cap.maps, "llama_prefill_batch: attention capture is a single-sequence tool (use ss_llama_prefill on the selected slot)");
     const ss_llama_config& g = h->cfg;
     int64_t M = 0;
     for (int b = 0; b < h->n_seq; ++b) {
@@ -725,6 +784,7 @@ int ss_llama_generate(ss_llama* h, int64_t n_steps, int32_t last_prompt_id, cons
                (long long)h->kv_len[q], (long long)limit, g.cache_cap);
     SS_REQUIRE(h->pos[q] + limit <= g.max_pos, "llama_generate: position overflow (%lld + %lld > %d)", (long long)h->pos[q],
                (long long)limit, g.max_pos);
+    if (int crc = capture_fits(h, h->kv_len[q], limit, "llama_generate")) return crc;
     if (n_forced > 0)
         SS_HIP(hipMemcpyAsync(h->forced + (size_t)q * g.max_new, host_forced, (size_t)n_forced * sizeof(int32_t),
                               hipMemcpyHostToDevice, s));
@@ -740,6 +800,7 @@ int ss_llama_generate_batch(ss_llama* h, int64_t n_steps, const int32_t* last_pr
                             int64_t forced_ld, const int64_t* n_forced, const int32_t* active,
                             int64_t* host_n_generated, void* stream) {
     SS_REQUIRE(h && n_steps > 0 && last_prompt_ids, "llama_generate_batch: bad arguments");
+    SS_REQUIRE(!h->cap.maps, "llama_generate_batch: attention capture is a single-sequence tool (use ss_llama_generate on the selected slot)");
     const ss_llama_config& g = h->cfg;
     hipStream_t s = (hipStream_t)stream;
     const int64_t limit = n_steps < g.max_new ? n_steps : g.max_new;

@@ -93,6 +93,7 @@ PROTOTYPES = {
     "ss_attention_ragged": (C.c_int, [vp, vp, vp, vp] + [i64] * 3 + [vp] + [i64] * 13 + [f32, C.c_int, C.c_int, vp]),
     "ss_attn_decode_workspace_bytes": (sz, [i64, i64]),
     "ss_attn_decode": (C.c_int, [vp, vp, vp, vp, vp, vp, i64, i64, i64, C.c_int, vp]),
+    "ss_attn_scores": (C.c_int, [vp, i64, vp, i64, vp, i64, i64, i64, i64, C.c_int, C.c_int, vp]),
     "ss_gemm": (C.c_int, [vp, vp, vp, i64, i64, i64, i64, i64, i64, vp, vp, i64, C.c_int, C.c_int, vp]),
     "ss_gemm_tune_workspace_bytes": (sz, [i64, i64, i64, C.c_int]),
     "ss_gemm_tune": (C.c_int, [i64, i64, i64, C.c_int, C.c_int, vp, sz, vp, C.POINTER(f32)]),
@@ -111,6 +112,7 @@ PROTOTYPES = {
     "ss_llama_destroy": (None, [vp]),
     "ss_llama_select": (C.c_int, [vp, i32]),
     "ss_llama_set_stop_id": (C.c_int, [vp, i32]),
+    "ss_llama_set_attn_capture": (C.c_int, [vp, vp, i64, i64, i64, i32, i32]),
     "ss_llama_buffer": (vp, [vp, C.c_int]),
     "ss_llama_set_lengths": (C.c_int, [vp, i64, i64, vp]),
     "ss_llama_get_lengths": (C.c_int, [vp, C.POINTER(i64), C.POINTER(i64)]),

@@ -5,6 +5,7 @@ KV-cache slab and activation workspace — and exposes the KV cache in the refer
 (``past_key_values``: tuple over layers of ``(k, v)`` each ``[1, n_heads, len, head_dim]``, keys
 post-RoPE) as zero-copy views.
 """
+import contextlib
 import ctypes as C
 
 import torch
@@ -122,6 +123,7 @@ class LlamaEngine:
         self._h = h
         self._views = {}
         self._cur = 0
+        self._capture = None       # (maps, row0, head) while attention-map capture is on
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -207,6 +209,45 @@ class LlamaEngine:
         idx = torch.as_tensor(keep_idx, dtype=torch.int32, device=self.device).contiguous()
         check(lib().ss_llama_kv_gather(self._h, idx.data_ptr(), idx.numel(), ops.stream()), "ss_llama_kv_gather")
 
+    # ---- attention maps (the reference's config.output_attentions) --------------------------------------
+    def attn_capture_on(self, rows, cols, head=0, row0=None):
+        """Start recording head ``head``'s attention map of every layer (pre-softmax scores + mask in the model dtype, as the
+        reference's ``output_attentions`` returns them; include/seedstory_hip.h).  Allocates and returns
+        ``[n_layers, rows, cols]`` filled with NaN: row r belongs to the query whose key sits at cache index ``row0 + r``
+        (default: the current cache length), so ``prefill`` / ``generate`` / ``generate_img_block`` of the selected slot fill
+        one row per fed token, real up to that call's key count and NaN beyond — the reference's merged map.  The lock-step
+        batch entry points raise while capture is on."""
+        if row0 is None:
+            row0 = self.lengths()[0]
+        maps = torch.full((self.n_layers, int(rows), int(cols)), float("nan"), dtype=self.dtype, device=self.device)
+        self._set_capture(maps, int(row0), int(head), 0)
+        self._capture = (maps, int(row0), int(head))
+        return maps
+
+    def attn_capture_off(self):
+        if self._capture is not None:
+            self._capture = None
+            check(lib().ss_llama_set_attn_capture(self._h, None, 0, 0, 0, 0, 0), "ss_llama_set_attn_capture")
+
+    @contextlib.contextmanager
+    def attn_capture(self, rows, cols, head=0):
+        """``with eng.attn_capture(rows, cols) as maps: ...`` — ``attn_capture_on`` / ``attn_capture_off`` as a context."""
+        maps = self.attn_capture_on(rows, cols, head)
+        try:
+            yield maps
+        finally:
+            self.attn_capture_off()
+
+    def _set_capture(self, maps, row0, head, row_calls):
+        torch.cuda.current_stream(self.device).synchronize()       # the NaN fill precedes the engine's (blocking) descriptor copy
+        check(lib().ss_llama_set_attn_capture(self._h, maps.data_ptr(), maps.shape[1], maps.shape[2], row0, head, row_calls),
+              "ss_llama_set_attn_capture")
+
+    def _refuse_capture(self, what):
+        if self._capture is not None:
+            raise _lib.SSError("%s: attention capture is a single-sequence tool (use the single-sequence methods on the "
+                               "selected slot)" % what)
+
     # ---- forward paths ---------------------------------------------------------------------------------
     def prefill(self, embeds, pos_ids=None, want_hidden=False):
         """embeds [M, hidden] rows appended after the cached prefix.  Returns the post-final-norm
@@ -227,6 +268,7 @@ class LlamaEngine:
         """``prefill`` for several sequence slots in ONE sweep of the weights (ss_llama_prefill_batch): ``embeds[b]`` =
         slot b's new rows [M_b, hidden] or None.  Returns the per-slot hidden rows (or None) — each slot's last row's
         logits land in that slot's logits buffer and its lengths advance by M_b."""
+        self._refuse_capture("prefill_batch")
         S = self.n_seq
         assert len(embeds) == S
         rows = [0 if e is None else int(e.shape[0]) for e in embeds]
@@ -274,6 +316,7 @@ class LlamaEngine:
         """Greedy decode of all ``n_seq`` slots in lock-step (one sweep of the weights per token
         for the whole batch).  ``last_prompt_ids[b]``, optional ``forced[b]`` token lists and
         ``active[b]`` flags are per slot; returns the per-slot generated-token counts."""
+        self._refuse_capture("generate_batch")
         S = self.n_seq
         assert len(last_prompt_ids) == S
         forced = [[] for _ in range(S)] if forced is None else [[int(t) for t in (f or [])] for f in forced]
@@ -324,8 +367,15 @@ class LlamaEngine:
         ids = torch.tensor(blk[:rows], dtype=torch.int32, device=self.device)
         emb = ops.gather_rows(self.embed, ids)
         step = int(self.max_rows)                                   # rows per prefill call the engine was sized for
-        hb = torch.cat([self.prefill(emb[i:i + step], want_hidden=True).clone() for i in range(0, rows, step)]) \
-            if rows > step else self.prefill(emb, want_hidden=True)
+        capture = getattr(self, "_capture", None)     # getattr: tests/test_host_cpu.py binds this method onto a stand-in engine
+        if capture is not None:             # the reference feeds these rows one call each: every map row is a one-row call
+            self._set_capture(*capture, 1)
+        try:
+            hb = torch.cat([self.prefill(emb[i:i + step], want_hidden=True).clone() for i in range(0, rows, step)]) \
+                if rows > step else self.prefill(emb, want_hidden=True)
+        finally:
+            if capture is not None:
+                self._set_capture(*capture, 0)
         if _lib.get_tuning("img_block_logits", 1):
             ops.gemm(hb, self.lm_head)                             # the reference's per-position logits (unused: forced)
         return blk[1:m + 1], hb, (blk[rows - 1] if rows == m + 1 else None)

@@ -177,6 +177,25 @@ def attn_decode(q, kcache, vcache, kv_len_dev, out=None):
     return out
 
 
+def attn_scores(q, k, out, row_calls=False):
+    """Attention map of one head, the reference's ``output_attentions`` values (ss_attn_scores): q [M, hd] rows of one head
+    (post-RoPE), k [kv, hd] one head's plane of the KV cache, out [M, >= kv] in the same dtype — any of them may be a strided
+    view with unit inner stride.  Writes ``out[:, :kv]`` in place (``row_calls``: each row only up to its own key, the rest is
+    left as the caller filled it) and returns ``out``."""
+    for t, name in ((q, "q"), (k, "k"), (out, "out")):
+        if not t.is_cuda:
+            raise _lib.SSError("%s must live on the GPU (there is no CPU path)" % name)
+        if t.dim() != 2 or t.stride(1) != 1 or t.dtype != q.dtype:
+            raise _lib.SSError("%s must be a 2-D view with unit inner stride, in q's dtype" % name)
+    M, hd = q.shape
+    kv = k.shape[0]
+    if k.shape[1] != hd or out.shape[0] != M or out.shape[1] < kv:
+        raise _lib.SSError("attn_scores: q %s, k %s, out %s do not fit" % (tuple(q.shape), tuple(k.shape), tuple(out.shape)))
+    check(lib().ss_attn_scores(p(q), q.stride(0), p(k), k.stride(0), p(out), out.stride(0), M, kv, hd, 1 if row_calls else 0,
+                               dt(q), stream()), "ss_attn_scores")
+    return out
+
+
 def gemm(a, w, bias=None, residual=None, gelu=False, out=None, rowstat=None, rowpart=None):
     """a [M, K] @ w[N, K]^T (+bias)(+gelu)(+residual) -> [M, N].  ``rowstat`` (fp64 [M, 2], zeroed by the caller): the
     epilogue also accumulates (sum, sum of squares) of every stored output row into it (ss_gemm_rowstat)."""

@@ -167,6 +167,9 @@ def run_story(args, j, question, image, tokenizer, transform, vit, agent, adapte
             ctx.start(tokenizer.encode(question, add_special_tokens=False), vit(image_tensor))   # gen_george.py:168-188
     llama = agent.llm.base_model.model if hasattr(agent.llm, "base_model") else agent.llm
     llama.use_kv_cache_head = False                                                         # :165
+    if args.save_attn:                                           # the reference's switch: one merged attention map per layer
+        llama.config.output_attentions = True
+        os.makedirs(args.save_attn, exist_ok=True)
     size = args.image_size
     forced = None
     for step in range(1, args.steps + 1):
@@ -177,6 +180,9 @@ def run_story(args, j, question, image, tokenizer, transform, vit, agent, adapte
         out = agent.generate(tokenizer=tokenizer, input_ids=ctx.input_ids(device), image_embeds=ctx.image_embeds,
                              embeds_cmp_mask=emb_mask, ids_cmp_mask=ids_mask, max_new_tokens=500, num_img_gen_tokens=64,
                              forced_tokens=forced)
+        if args.save_attn:                                       # [layers, rows, width], head 0 (NaN beyond each row's keys)
+            torch.save(torch.stack([a[0] for a in out['attn_weights']]).cpu(),
+                       os.path.join(args.save_attn, "val_%d_step_%02d.pt" % (j, step)))
         text = re.sub(r'\s*<[^>]*>\s*', ' ', out['text']).strip()
         with open(os.path.join(save_folder, "text.txt"), "a+") as f:
             f.write(text + "\n")
@@ -207,6 +213,9 @@ def main():
     ap.add_argument("--tiny", action="store_true")
     ap.add_argument("--caption-tokens", type=int, default=48)
     ap.add_argument("--stories", type=int, default=1)
+    ap.add_argument("--save-attn", default=None, metavar="DIR",
+                    help="run the LLM with config.output_attentions and torch.save each step's attn_weights (head 0's "
+                         "pre-softmax maps) into DIR")
     ap.add_argument("--parity", action="store_true",
                     help="string-level prompt bookkeeping exactly as the reference driver (decode -> scrub -> re-tokenise, "
                          "'[INST]'-length skip on eviction) instead of the id-level context")

@@ -35,6 +35,9 @@ def run_story(args, j, start_text, captions, image, tokenizer, transform, vit, a
     llama.past_key_values = None
     sink = args.cache_mode == "img_head_tail"
     llama.use_kv_cache_head = sink
+    if args.save_attn:                                           # the reference's switch: one merged attention map per layer
+        llama.config.output_attentions = True
+        os.makedirs(args.save_attn, exist_ok=True)
     ctx = StoryContext(tokenizer.bos_token_id, boi, eoi, img_all[1:-1], window=args.window)
     with torch.no_grad():
         ctx.start(enc(start_text), vit(transform(image).unsqueeze(0).to(device, dtype=dtype)))
@@ -51,6 +54,9 @@ def run_story(args, j, start_text, captions, image, tokenizer, transform, vit, a
                              past_key_values=past, forced_tokens=forced)
         with open(os.path.join(save_folder, "token.txt"), "a+") as f:
             f.write("context token: {} cached: {} sink: {}\n".format((1, len(ctx.ids)), cached, ctx.sink_len))
+        if args.save_attn:                                       # [layers, rows, width], head 0 (NaN beyond each row's keys)
+            torch.save(torch.stack([a[0] for a in out['attn_weights']]).cpu(),
+                       os.path.join(args.save_attn, "val_%d_step_%02d.pt" % (j, step)))
         if not out['has_img_output']:
             break
         images = adapter.generate(image_embeds=out['img_gen_feat'], num_inference_steps=args.diffusion_steps,
@@ -95,6 +101,9 @@ def main():
     ap.add_argument("--tiny", action="store_true")
     ap.add_argument("--caption-tokens", type=int, default=48)
     ap.add_argument("--stories", type=int, default=1)
+    ap.add_argument("--save-attn", default=None, metavar="DIR",
+                    help="run the LLM with config.output_attentions and torch.save each step's attn_weights (head 0's "
+                         "pre-softmax maps, the evidence behind the attention sink) into DIR")
     args = ap.parse_args()
     device = "cuda:0"
     dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float16

@@ -37,6 +37,7 @@ class LlamaConfig:
         self.eos_token_id = eos_token_id
         self.bos_token_id = bos_token_id
         self.use_cache = True
+        self.output_attentions = bool(kwargs.get("output_attentions", False))    # the reference's switch for attention maps
 
     @classmethod
     def from_pretrained(cls, path):
@@ -205,9 +206,11 @@ class LlamaForCausalLM(nn.Module):
         (lm_head on every row, :759), the grown cache, and — unlike the reference, which can return every layer's input —
         ``hidden_states = (last,)``: the post-final-norm states, the only entry the path reads (models.py:182-197 uses
         ``hidden_states[-1]``).  Side effects as the reference: ``self.past_key_values`` (:778), ``kv_cache_head``
-        (:780-784).  With ``labels`` or a batch of sequences: `_forward_sequences` (loss :761-772, forward only)."""
-        if output_attentions:
-            raise NotImplementedError("attention probabilities are never materialised (flash attention)")
+        (:780-784).  With ``labels`` or a batch of sequences: `_forward_sequences` (loss :761-772, forward only).
+        ``output_attentions`` (default ``config.output_attentions``): ``attentions`` = tuple over layers of ``[1, q, kv + q]``,
+        what the reference returns there (:299-301, 591-596) — head 0's PRE-softmax scores with the mask added in the model
+        dtype; computed by a kernel of their own next to the flash attention (ss_attn_scores), not on the default path."""
+        want_attn = bool(getattr(self.config, "output_attentions", False) if output_attentions is None else output_attentions)
         eng = self.engine_for_generation(tuple(getattr(self, "_img_ids", ())))
         dev = eng.device
         if inputs_embeds is None:
@@ -215,6 +218,8 @@ class LlamaForCausalLM(nn.Module):
         if labels is not None or inputs_embeds.shape[0] != 1:
             if past_key_values is not None:
                 raise ValueError("the batched / loss forward takes whole sequences (no past_key_values)")
+            if want_attn:
+                raise ValueError("attention maps are returned by single-sequence calls only (not by the batched / loss forward)")
             return self._forward_sequences(eng, inputs_embeds.to(dev), labels, position_ids, output_hidden_states, return_dict)
         rows = inputs_embeds[0].to(dev)
         q = rows.shape[0]
@@ -229,7 +234,12 @@ class LlamaForCausalLM(nn.Module):
             pos = position_ids.reshape(-1).to(device=dev, dtype=torch.int32)
         elif kv:
             pos = torch.arange(kv, kv + q, dtype=torch.int32, device=dev)
-        hid = eng.prefill(rows, pos_ids=pos, want_hidden=True)                    # [q, H], post final norm
+        maps = eng.attn_capture_on(q, kv + q, row0=kv) if want_attn else None
+        try:
+            hid = eng.prefill(rows, pos_ids=pos, want_hidden=True)                # [q, H], post final norm
+        finally:
+            if want_attn:
+                eng.attn_capture_off()
         from seedstory import ops as _ops
         logits = _ops.gemm(hid.contiguous(), self.lm_head.weight).unsqueeze(0)     # [1, q, V]
         pkv = eng.past_key_values()
@@ -237,10 +247,12 @@ class LlamaForCausalLM(nn.Module):
         if self.use_kv_cache_head and not self.training:
             n_in = q if input_ids is None else input_ids.shape[1]
             self.kv_cache_head = n_in if self.kv_cache_head is None else self.kv_cache_head + n_in
+        attentions = tuple(maps[l].unsqueeze(0) for l in range(maps.shape[0])) if want_attn else None
         out = CausalLMOutputWithPast(logits=logits, past_key_values=pkv,
-                                     hidden_states=(hid.unsqueeze(0),) if output_hidden_states else None)
+                                     hidden_states=(hid.unsqueeze(0),) if output_hidden_states else None,
+                                     attentions=attentions)
         if return_dict is False:
-            return (logits, pkv) + ((out.hidden_states,) if output_hidden_states else ())
+            return (logits, pkv) + ((out.hidden_states,) if output_hidden_states else ()) + ((attentions,) if want_attn else ())
         return out
 
 
@@ -321,10 +333,15 @@ class LlamaForCausalLM(nn.Module):
     @torch.no_grad()
     def generate(self, input_ids=None, inputs_embeds=None, logits_processor=None, past_key_values=None,
                  max_new_tokens=120, output_hidden_states=True, return_dict_in_generate=True, forced_tokens=None,
-                 **unused):
+                 output_attentions=None, **unused):
         """Greedy search as ``ContinuousLVLM.generate`` drives it (reference models.py:146-153):
         ``inputs_embeds`` feed step 0, ``input_ids`` is the running sequence, ``do_sample=False``
-        (temperature / top_p are inert), the image-token logits processor is applied on device."""
+        (temperature / top_p are inert), the image-token logits processor is applied on device.
+        ``output_attentions`` (default ``config.output_attentions``, the reference's switch): ``attentions`` = tuple over steps
+        of tuple over layers — step 0 ``[1, q0, kv0 + q0]``, step j ``[1, 1, kv0 + q0 + j]``, as many as ``hidden_states`` —
+        all VIEWS of one capture buffer, which ``attention_maps`` [layers, rows, width] hands out whole (one row per fed token,
+        NaN beyond each row's key count: what the reference's pad-and-concatenate merge builds, models.py:164-179)."""
+        want_attn = bool(getattr(self.config, "output_attentions", False) if output_attentions is None else output_attentions)
         img_ids = ()
         for proc in (logits_processor or []):
             img_ids = tuple(getattr(proc, "img_ids_list", ()))
@@ -335,14 +352,30 @@ class LlamaForCausalLM(nn.Module):
         if inputs_embeds is None:
             inputs_embeds = self.model.embed_tokens(input_ids)
         rows = inputs_embeds[0]
+        try:
+            return self._generate(eng, input_ids, rows, S, img_ids, past_key_values, max_new_tokens, output_hidden_states,
+                                  forced_tokens, want_attn)
+        finally:
+            if want_attn:
+                eng.attn_capture_off()
+
+    def _generate(self, eng, input_ids, rows, S, img_ids, past_key_values, max_new_tokens, output_hidden_states,
+                  forced_tokens, want_attn):
+        dev = eng.device
+        maps, kv0 = None, 0
         if past_key_values is None:
             eng.reset()
             fed0 = S
+            if want_attn:
+                maps = eng.attn_capture_on(fed0 + max_new_tokens, fed0 + max_new_tokens, row0=0)
             hid0 = eng.prefill(rows, want_hidden=output_hidden_states)
         else:
             head = self.kv_cache_head if (self.use_kv_cache_head and self.kv_cache_head is not None) else S - 1
             eng.load_past_key_values(past_key_values)
             fed0 = S - head
+            kv0 = eng.lengths()[0]
+            if want_attn:
+                maps = eng.attn_capture_on(fed0 + max_new_tokens, kv0 + fed0 + max_new_tokens, row0=kv0)
             pos = torch.arange(head, S, dtype=torch.int32, device=dev)      # cumsum(mask)-1 sliced (:811-816)
             hid0 = eng.prefill(rows[head:], pos_ids=pos, want_hidden=output_hidden_states)
             eng.set_lengths(eng.lengths()[0], S)
@@ -368,7 +401,24 @@ class LlamaForCausalLM(nn.Module):
         if self.use_kv_cache_head:
             adv = fed0 + max(n - 1, 0)
             self.kv_cache_head = adv if self.kv_cache_head is None else self.kv_cache_head + adv
-        return GenerateOutput(sequences=sequences, hidden_states=hidden_states, attentions=None)
+        attentions = attention_maps = None
+        if want_attn:
+            fed = fed0 + max(n - 1, 0)
+            attentions = attention_step_views(maps, kv0, fed0, fed)
+            attention_maps = maps[:, :fed, :kv0 + fed]
+        return GenerateOutput(sequences=sequences, hidden_states=hidden_states, attentions=attentions,
+                              attention_maps=attention_maps)
+
+
+def attention_step_views(maps, kv0, fed0, fed):
+    """HF's ``attentions`` of a greedy run as views of the capture buffer ``maps`` [layers, rows, width] (row r = the r-th fed
+    token, cache length ``kv0`` before the run): tuple over steps of tuple over layers, step 0 = the ``fed0`` rows of the first
+    call ``[1, fed0, kv0 + fed0]``, step j = row ``fed0 + j - 1`` as ``[1, 1, kv0 + fed0 + j]``, up to ``fed`` rows in all."""
+    L = maps.shape[0]
+    steps = [tuple(maps[l, :fed0, :kv0 + fed0].unsqueeze(0) for l in range(L))]
+    steps += [tuple(maps[l, fed0 + j - 1:fed0 + j, :kv0 + fed0 + j].unsqueeze(0) for l in range(L))
+              for j in range(1, fed - fed0 + 1)]
+    return tuple(steps)
 
 
 class CausalLMOutputWithPast:
@@ -383,7 +433,8 @@ class CausalLMOutputWithPast:
 
 
 class GenerateOutput:
-    def __init__(self, sequences, hidden_states, attentions):
+    def __init__(self, sequences, hidden_states, attentions, attention_maps=None):
         self.sequences = sequences
         self.hidden_states = hidden_states
         self.attentions = attentions
+        self.attention_maps = attention_maps      # [layers, rows, width]: the buffer every entry of `attentions` is a view of

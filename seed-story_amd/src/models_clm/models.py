@@ -159,13 +159,19 @@ class ContinuousLVLM(nn.Module):
         else:
             img_gen_feat = None
         generate_text = tokenizer.decode(generate_ids, skip_special_tokens=False)
+        # one merged attention map per decoder layer when the LLM ran with config.output_attentions (:162-179): the reference
+        # pads the running map with a NaN column per step and concatenates; here every step wrote its row into one NaN-filled
+        # buffer, so the merged map is a slice of it
+        attn_weights = ()
+        if output.attentions is not None:
+            attn_weights = tuple(output.attention_maps[l].unsqueeze(0) for l in range(output.attention_maps.shape[0]))
         return {
             'text': generate_text,
             'generate_ids': generate_ids,
             'has_img_output': has_img_output,
             'img_gen_feat': img_gen_feat,
             'num_gen_imgs': num_gen_imgs,
-            'attn_weights': (),
+            'attn_weights': attn_weights,
             'past_key_values': output_past_key_values
         }
 
