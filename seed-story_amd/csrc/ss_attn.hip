@@ -482,6 +482,43 @@ __device__ __forceinline__ float max3_asm(float a, float b, float c) {
 template <typename T> struct OnesFrag;
 template <> struct OnesFrag<bf16_t> { static constexpr uint32_t kPair = 0x3F803F80u; };
 template <> struct OnesFrag<f16_t> { static constexpr uint32_t kPair = 0x3C003C00u; };
+// Workgroup -> (batch*head, query block).  Workgroups are dealt to the 8 XCDs round-robin by linear id and every XCD
+// has its own 4 MB L2: with the plain (x = query block, y = head) order the 32 query blocks that share one head's
+// K/V (1 MB at 4096 x 64) land on all eight L2s and every XCD streams every head (PMC: 4.5x the algorithmic bytes
+// from the fabric, L2 hit 74 %).  With a 1-D grid, XCD k owns heads k, k+8, ... and walks each head's query blocks
+// back to back, so a head's K/V is fetched into ONE L2 once.
+__device__ __forceinline__ void attn_block_of_grid(const AttnArgs& a, int& bh, int& qblk) {
+    if (gridDim.y == 1 && a.xcd_heads > 0) {
+        const int id = blockIdx.x, xcd = id & 7, j = id >> 3;
+        const int nqb = a.xcd_heads;                 // query blocks per head
+        bh = (j / nqb) * 8 + xcd;
+        qblk = j - (j / nqb) * nqb;
+    } else {
+        bh = blockIdx.y; qblk = blockIdx.x;
+    }
+}
+
+// S^T = K Q^T of the K tile at Kb (rows of HD elements, 16-byte chunks XOR-swizzled by key row), both
+// 16-row query blocks of the wave.  Called by v3 and v3p; takes everything but the fragments by value: in
+// this form both kernels compile to the code of the statements written out in their bodies (checked per
+// opcode; re-check after touching the signature).
+template <typename T, int HD>
+__device__ __forceinline__ void flash_compute_s(const char* Kb, int l15, int grp, const uint4 (&qf)[2][HD / 32],
+                                                f32x4_t (&s)[2][kBKV / 16]) {
+    constexpr int CPR = HD / 8, ROWB = HD * 2;   // 16-byte chunks, bytes per key row
+#pragma unroll
+    for (int kb = 0; kb < kBKV / 16; ++kb) {
+        s[0][kb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+        s[1][kb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+        const int r = kb * 16 + l15;
+#pragma unroll
+        for (int ks = 0; ks < HD / 32; ++ks) {
+            const uint4 kf = *reinterpret_cast<const uint4*>(Kb + r * ROWB + (((ks * 4 + grp) ^ (r & (CPR - 1))) << 4));
+            s[0][kb] = AttnMma<T>::run(kf, qf[0][ks], s[0][kb]);
+            s[1][kb] = AttnMma<T>::run(kf, qf[1][ks], s[1][kb]);
+        }
+    }
+}
 
 template <typename T, int HD, bool VSWZ>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HD <= 64 ? 3 : 2)))
@@ -501,20 +538,8 @@ void flash_attn3_kernel(const AttnArgs a) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l15 = lane & 15, grp = lane >> 4;
-    // Workgroup -> (batch*head, query block).  Workgroups are dealt to the 8 XCDs round-robin by linear id and every XCD
-    // has its own 4 MB L2: with the plain (x = query block, y = head) order the 32 query blocks that share one head's
-    // K/V (1 MB at 4096 x 64) land on all eight L2s and every XCD streams every head (PMC: 4.5x the algorithmic bytes
-    // from the fabric, L2 hit 74 %).  With a 1-D grid, XCD k owns heads k, k+8, ... and walks each head's query blocks
-    // back to back, so a head's K/V is fetched into ONE L2 once.
     int bh, qblk;
-    if (gridDim.y == 1 && a.xcd_heads > 0) {
-        const int id = blockIdx.x, xcd = id & 7, j = id >> 3;
-        const int nqb = a.xcd_heads;                 // query blocks per head
-        bh = (j / nqb) * 8 + xcd;
-        qblk = j - (j / nqb) * nqb;
-    } else {
-        bh = blockIdx.y; qblk = blockIdx.x;
-    }
+    attn_block_of_grid(a, bh, qblk);
     const int b = bh / a.n_heads, h = bh % a.n_heads;
     const int kvl = a.ragged ? a.kv_len_b[b] : a.kv_len;      // per-batch key count (stacked story slots)
     const int q0 = qblk * BQ2;
@@ -608,20 +633,8 @@ void flash_attn3_kernel(const AttnArgs a) {
         if (++stage == NSTAGE) stage = 0;
         const int t0 = t * kBKV;
 
-        // ---- S^T = K Q^T for both 16-row query blocks ---------------------------------------------
         f32x4_t s[2][NKB];
-#pragma unroll
-        for (int kb = 0; kb < NKB; ++kb) {
-            s[0][kb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-            s[1][kb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-            const int r = kb * 16 + l15;
-#pragma unroll
-            for (int ks = 0; ks < NKS; ++ks) {
-                const uint4 kf = *reinterpret_cast<const uint4*>(Kb + r * ROWB + (((ks * 4 + grp) ^ (r & (CPR - 1))) << 4));
-                s[0][kb] = AttnMma<T>::run(kf, qf[0][ks], s[0][kb]);
-                s[1][kb] = AttnMma<T>::run(kf, qf[1][ks], s[1][kb]);
-            }
-        }
+        flash_compute_s<T, HD>(Kb, l15, grp, qf, s);
         // ---- softmax numerators (log2 domain, deferred rescale) ----------------------------------------
         uint4 pfrag[2][NKB / 2];
         const bool need_mask = a.causal_br || (t0 + kBKV > kvl);   // wave-uniform
@@ -761,14 +774,7 @@ void flash_attn3p_kernel(const AttnArgs a) {
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l15 = lane & 15, grp = lane >> 4;
     int bh, qblk;
-    if (gridDim.y == 1 && a.xcd_heads > 0) {      // XCD-aware 1-D grid, as v3
-        const int id = blockIdx.x, xcd = id & 7, j = id >> 3;
-        const int nqb = a.xcd_heads;
-        bh = (j / nqb) * 8 + xcd;
-        qblk = j - (j / nqb) * nqb;
-    } else {
-        bh = blockIdx.y; qblk = blockIdx.x;
-    }
+    attn_block_of_grid(a, bh, qblk);
     const int b = bh / a.n_heads, h = bh % a.n_heads;
     const int kvl = a.ragged ? a.kv_len_b[b] : a.kv_len;
     const int q0 = qblk * BQ2;
@@ -871,18 +877,7 @@ void flash_attn3p_kernel(const AttnArgs a) {
     // S^T = K Q^T of the tile in ring slot `slot`, both 16-row query blocks
     auto compute_s = [&](int slot, f32x4_t (&s)[2][NKB]) {
         const char* Kb = smem_raw + slot * 2 * TILE_B;
-#pragma unroll
-        for (int kb = 0; kb < NKB; ++kb) {
-            s[0][kb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-            s[1][kb] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-            const int r = kb * 16 + l15;
-#pragma unroll
-            for (int ks = 0; ks < NKS; ++ks) {
-                const uint4 kf = *reinterpret_cast<const uint4*>(Kb + r * ROWB + (((ks * 4 + grp) ^ (r & (CPR - 1))) << 4));
-                s[0][kb] = AttnMma<T>::run(kf, qf[0][ks], s[0][kb]);
-                s[1][kb] = AttnMma<T>::run(kf, qf[1][ks], s[1][kb]);
-            }
-        }
+        flash_compute_s<T, HD>(Kb, l15, grp, qf, s);
     };
 
     // softmax numerators of tile t from its scores + O^T += V^T P^T, l += 1^T P^T (v3's statements, unchanged)
@@ -1226,6 +1221,18 @@ static int cross_attn64_launch(const AttnArgs& a, int64_t batch, hipStream_t s) 
 
 #endif  // SS_EXPERIMENTAL (cross_attn64)
 
+// grid of the v3 / v3p kernels over nqb query blocks x bh (batch, head) pairs: plain 2-D, or (bh a multiple of
+// the 8 XCDs, more than one query block, knob attn_xcd) flattened to 1-D so that XCD k owns pairs k, k+8, ...;
+// attn_block_of_grid undoes it
+static dim3 flash_grid(AttnArgs& a, int nqb, int64_t bh) {
+    a.xcd_heads = 0;
+    if (bh % 8 == 0 && nqb > 1 && knob(K_attn_xcd)) {
+        a.xcd_heads = nqb;
+        return dim3((unsigned)(nqb * bh), 1);
+    }
+    return dim3((unsigned)nqb, (unsigned)bh);
+}
+
 template <typename T, bool PIPE>
 static int flash3p_launch(const AttnArgs& a, int64_t batch, hipStream_t s) {
     // ring of 3 (K, V) tiles — or as many as the context has: a one-tile context (the UNet's cross-attention, 64 image-feature tokens)
@@ -1243,12 +1250,7 @@ static int flash3p_launch(const AttnArgs& a, int64_t batch, hipStream_t s) {
     const bool w8 = !PIPE && !w16 && (aw == 8 || (aw == 0 && many && a.q_len >= 512 && (int64_t)cdiv(a.q_len, 256) * bh >= 1024));
     const int nqb = cdiv(a.q_len, w16 ? 512 : w8 ? 256 : 128);
     AttnArgs a2 = a;
-    dim3 grid((unsigned)nqb, (unsigned)bh);
-    a2.xcd_heads = 0;
-    if (bh % 8 == 0 && nqb > 1 && knob(K_attn_xcd)) {
-        a2.xcd_heads = nqb;
-        grid = dim3((unsigned)(nqb * bh), 1);
-    }
+    const dim3 grid = flash_grid(a2, nqb, bh);
     if constexpr (!PIPE) {
         if (w16) {
             hipLaunchKernelGGL((flash_attn3p_kernel<T, 64, false, 16>), grid, dim3(1024), lds, s, a2);
@@ -1272,12 +1274,7 @@ static int flash3_launch_hd(const AttnArgs& a, int64_t batch, hipStream_t s) {
     const int nqb = cdiv(a.q_len, 128);
     const int64_t bh = batch * a.n_heads;
     AttnArgs a2 = a;
-    dim3 grid((unsigned)nqb, (unsigned)bh);
-    a2.xcd_heads = 0;
-    if (bh % 8 == 0 && nqb > 1 && knob(K_attn_xcd)) {   // XCD k owns heads k, k+8, ...
-        a2.xcd_heads = nqb;
-        grid = dim3((unsigned)(nqb * bh), 1);
-    }
+    const dim3 grid = flash_grid(a2, nqb, bh);
     hipLaunchKernelGGL((flash_attn3_kernel<T, HD, VSWZ>), grid, dim3(256), lds, s, a2);
     SS_LAUNCH_CHECK("flash_attn3");
     return SS_OK;
@@ -1570,15 +1567,24 @@ int attn_decode_launch(const DecodeArgs& a0, void* out, int64_t n_heads, int64_t
     return SS_OK;
 }
 
+// (positional: mind the order at the call sites, the nullptr arguments carry no type protection)
+// one sequence (nb = 1, no strides); nsplit and scale are filled in by attn_decode_launch
+static DecodeArgs decode_args(const void* q, const void* qkv_raw, void* kc, void* vc, const void* cos_t, const void* sin_t, void* ws,
+                              const int32_t* kv_len_dev, const int32_t* pos_dev, const int32_t* done_flag, int64_t n_heads, int64_t hd,
+                              int64_t cache_cap) {
+    DecodeArgs a;
+    a.q = q; a.qkv_raw = qkv_raw; a.kc = kc; a.vc = vc; a.cos_t = cos_t; a.sin_t = sin_t;
+    a.part = (float*)ws; a.kv_len_dev = kv_len_dev; a.pos_dev = pos_dev; a.done_flag = done_flag;
+    a.hd = (int)hd; a.n_heads = (int)n_heads; a.cap = (int)cache_cap; a.nsplit = 0; a.scale = 0.f;
+    a.nb = 1; a.state_stride = 0; a.q_stride = a.cache_stride = a.part_stride = a.out_stride = 0;
+    return a;
+}
+
 // plain: rotated q given, cache already holds kv_len entries
 int attn_decode_dev(const void* q, const void* kc, const void* vc, void* out, void* ws, const int32_t* kv_len_dev,
                     const int32_t* done_flag, int64_t n_heads, int64_t hd, int64_t cache_cap, int dtype,
                     hipStream_t s) {
-    DecodeArgs a;
-    a.q = q; a.qkv_raw = nullptr; a.kc = (void*)kc; a.vc = (void*)vc; a.cos_t = a.sin_t = nullptr;
-    a.part = (float*)ws; a.kv_len_dev = kv_len_dev; a.pos_dev = nullptr; a.done_flag = done_flag;
-    a.hd = (int)hd; a.n_heads = (int)n_heads; a.cap = (int)cache_cap; a.nsplit = 0; a.scale = 0.f;
-    a.nb = 1; a.state_stride = 0; a.q_stride = a.cache_stride = a.part_stride = a.out_stride = 0;
+    const DecodeArgs a = decode_args(q, nullptr, (void*)kc, (void*)vc, nullptr, nullptr, ws, kv_len_dev, nullptr, done_flag, n_heads, hd, cache_cap);
     return SS_DISPATCH(dtype, attn_decode_launch, a, out, n_heads, hd, s);
 }
 
@@ -1589,14 +1595,24 @@ int attn_decode_fused_dev(const void* qkv_raw, void* kc, void* vc, const void* c
                           void* ws, const int32_t* kv_len_dev, const int32_t* pos_dev, const int32_t* done_flag,
                           int64_t n_heads, int64_t hd, int64_t cache_cap, int nb, int state_stride,
                           int64_t cache_stride, int dtype, hipStream_t s) {
-    DecodeArgs a;
+    DecodeArgs a = decode_args(nullptr, qkv_raw, kc, vc, cos_t, sin_t, ws, kv_len_dev, pos_dev, done_flag, n_heads, hd, cache_cap);
     a.nb = nb; a.state_stride = state_stride; a.q_stride = 3 * n_heads * hd; a.cache_stride = cache_stride;
     a.part_stride = (int64_t)(ss_attn_decode_workspace_bytes(n_heads, hd) / sizeof(float));
     a.out_stride = n_heads * hd;
-    a.q = nullptr; a.qkv_raw = qkv_raw; a.kc = kc; a.vc = vc; a.cos_t = cos_t; a.sin_t = sin_t;
-    a.part = (float*)ws; a.kv_len_dev = kv_len_dev; a.pos_dev = pos_dev; a.done_flag = done_flag;
-    a.hd = (int)hd; a.n_heads = (int)n_heads; a.cap = (int)cache_cap; a.nsplit = 0; a.scale = 0.f;
     return SS_DISPATCH(dtype, attn_decode_launch, a, out, n_heads, hd, s);
+}
+
+// everything but the key count(s): kv_len, ragged and kv_len_b are the caller's
+static AttnArgs attn_args(const void* q, const void* k, const void* v, void* out, int64_t n_heads, int64_t q_len, int64_t hd, int64_t q_sb,
+                          int64_t q_sh, int64_t q_ss, int64_t k_sb, int64_t k_sh, int64_t k_ss, int64_t v_sb, int64_t v_sh, int64_t v_ss,
+                          int64_t o_sb, int64_t o_sh, int64_t o_ss, float scale, int causal_br) {
+    AttnArgs a;
+    a.q = q; a.k = k; a.v = v; a.out = out;
+    a.q_len = (int)q_len; a.kv_len = 0; a.hd = (int)hd; a.n_heads = (int)n_heads;
+    a.q_sb = q_sb; a.q_sh = q_sh; a.q_ss = q_ss; a.k_sb = k_sb; a.k_sh = k_sh; a.k_ss = k_ss;
+    a.v_sb = v_sb; a.v_sh = v_sh; a.v_ss = v_ss; a.o_sb = o_sb; a.o_sh = o_sh; a.o_ss = o_ss;
+    a.scale = scale; a.causal_br = causal_br; a.xcd_heads = 0; a.ragged = 0;
+    return a;
 }
 
 }  // namespace ss
@@ -1609,12 +1625,8 @@ int ss_attention(const void* q, const void* k, const void* v, void* out, int64_t
                  int64_t q_len, int64_t kv_len, int64_t hd, int64_t q_sb, int64_t q_sh, int64_t q_ss, int64_t k_sb,
                  int64_t k_sh, int64_t k_ss, int64_t v_sb, int64_t v_sh, int64_t v_ss, int64_t o_sb, int64_t o_sh,
                  int64_t o_ss, float scale, int causal_br, int dtype, void* stream) {
-    AttnArgs a;
-    a.q = q; a.k = k; a.v = v; a.out = out;
-    a.q_len = (int)q_len; a.kv_len = (int)kv_len; a.hd = (int)hd; a.n_heads = (int)n_heads;
-    a.q_sb = q_sb; a.q_sh = q_sh; a.q_ss = q_ss; a.k_sb = k_sb; a.k_sh = k_sh; a.k_ss = k_ss;
-    a.v_sb = v_sb; a.v_sh = v_sh; a.v_ss = v_ss; a.o_sb = o_sb; a.o_sh = o_sh; a.o_ss = o_ss;
-    a.scale = scale; a.causal_br = causal_br; a.xcd_heads = 0; a.ragged = 0;
+    AttnArgs a = attn_args(q, k, v, out, n_heads, q_len, hd, q_sb, q_sh, q_ss, k_sb, k_sh, k_ss, v_sb, v_sh, v_ss, o_sb, o_sh, o_ss, scale, causal_br);
+    a.kv_len = (int)kv_len;
     return attention_dev(a, batch, dtype, (hipStream_t)stream);
 }
 
@@ -1625,12 +1637,8 @@ int ss_attention_ragged(const void* q, const void* k, const void* v, void* out, 
                         int64_t k_sh, int64_t k_ss, int64_t v_sb, int64_t v_sh, int64_t v_ss, int64_t o_sb, int64_t o_sh,
                         int64_t o_ss, float scale, int causal_br, int dtype, void* stream) {
     SS_REQUIRE(host_kv_lens && batch >= 1 && batch <= 8, "attention_ragged: 1..8 batch elements");
-    AttnArgs a;
-    a.q = q; a.k = k; a.v = v; a.out = out;
-    a.q_len = (int)q_len; a.hd = (int)hd; a.n_heads = (int)n_heads;
-    a.q_sb = q_sb; a.q_sh = q_sh; a.q_ss = q_ss; a.k_sb = k_sb; a.k_sh = k_sh; a.k_ss = k_ss;
-    a.v_sb = v_sb; a.v_sh = v_sh; a.v_ss = v_ss; a.o_sb = o_sb; a.o_sh = o_sh; a.o_ss = o_ss;
-    a.scale = scale; a.causal_br = causal_br; a.xcd_heads = 0; a.ragged = 1;
+    AttnArgs a = attn_args(q, k, v, out, n_heads, q_len, hd, q_sb, q_sh, q_ss, k_sb, k_sh, k_ss, v_sb, v_sh, v_ss, o_sb, o_sh, o_ss, scale, causal_br);
+    a.ragged = 1;
     int mx = 0;
     for (int b = 0; b < 8; ++b) {
         a.kv_len_b[b] = b < batch ? host_kv_lens[b] : 0;

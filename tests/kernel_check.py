@@ -489,7 +489,9 @@ ATTN_EDGE_CASES = [(1, 2, 64, 15, 17, False), (2, 2, 64, 63, 65, False), (1, 2, 
                    (1, 2, 104, 17, 64, False), (1, 2, 104, 128, 65, False), (1, 2, 104, 64, 64, True), (1, 2, 104, 33, 96, True),
                    (1, 2, 104, 64, 65, True), (1, 2, 104, 64, 128, True),
                    # several 128 / 256 / 512-row query blocks with a ragged last one (the 4 / 8 / 16-wave v3p kernels)
-                   (1, 2, 64, 600, 333, False), (1, 2, 64, 700, 763, True)]
+                   (1, 2, 64, 600, 333, False), (1, 2, 64, 700, 763, True),
+                   # batch x heads = 8 with several ragged query blocks: the XCD-aware 1-D work-group mapping (v3 at 128 rows, v3p at 128 / 256 / 512)
+                   (1, 8, 64, 600, 333, False), (1, 8, 64, 600, 763, True), (1, 8, 128, 300, 333, True)]
 # attention_cache / attention_cache_slots: heads, hd, cap, rows per slot, kv_lens (unequal), one per slot
 ATTN_CACHE_CASES = [(2, 128, 200, 17, [17, 81, 128, 200]), (2, 64, 160, 40, [40, 41, 103, 104, 129]), (2, 128, 300, 66, [66, 67, 130, 257]),
                     (2, 104, 96, 8, [8, 9, 71, 72]), (2, 104, 96, 40, [40, 41, 95, 96])]
