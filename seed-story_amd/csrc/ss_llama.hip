@@ -46,8 +46,8 @@ int attn_scores_decode_dev(const void* qkv_raw, const void* kplane, const void* 
                            const AttnCaptureDesc* desc, int layer, int64_t n_heads, int64_t hd, int64_t cap, int dtype,
                            hipStream_t s);
 
-// device state words
-enum { ST_KV_LEN = 0, ST_POS = 1, ST_NGEN = 2, ST_DONE = 3, ST_LAST = 4, ST_NFORCED = 5, ST_LIMIT = 6, ST_EOS = 7 };
+// device state words (ST_WORDS per sequence slot)
+enum { ST_KV_LEN = 0, ST_POS = 1, ST_NGEN = 2, ST_DONE = 3, ST_LAST = 4, ST_NFORCED = 5, ST_LIMIT = 6, ST_EOS = 7, ST_WORDS = 8 };
 
 // ---- engine kernels ---------------------------------------------------------------------------
 
@@ -63,7 +63,7 @@ __global__ __launch_bounds__(1024) void sample_embed_kernel(T* logits, int vocab
     {
         const int b = blockIdx.x;
         logits += (int64_t)b * vocab;
-        st += b * 8;
+        st += b * ST_WORDS;
         forced += (int64_t)b * max_new;
         gen_ids += (int64_t)b * max_new;
         x += (int64_t)b * hidden;
@@ -105,7 +105,7 @@ __global__ __launch_bounds__(256) void final_norm_advance_kernel(const T* __rest
         x += (int64_t)b * hidden;
         xn += (int64_t)b * hidden;
         hid_rows += (int64_t)b * max_new * hidden;
-        st += b * 8;
+        st += b * ST_WORDS;
     }
     if (st[ST_DONE]) return;
     const int npack = hidden / V;
@@ -191,7 +191,7 @@ struct ss_llama {
     size_t esz;
     // device buffers (carved from the caller's workspace); every per-sequence array is [n_seq][...]
     char *kc, *vc;           // [n_seq][L][H][cap][hd]
-    int32_t* state;          // [n_seq][8]
+    int32_t* state;          // [n_seq][ST_WORDS]
     int32_t* gen_ids;        // [n_seq][max_new]
     int32_t* forced;         // [n_seq][max_new]
     int32_t* img_ids;        // [n_img_ids]
@@ -205,13 +205,23 @@ struct ss_llama {
     std::vector<int64_t> kv_len, pos;
     hipStream_t cap_stream;
     std::vector<SeqGraph> graphs;
-    int32_t* pinned;         // [2][n_seq][8] ints of pinned host memory: state read-back | state upload
+    int32_t* pinned;         // [2][n_seq][ST_WORDS] ints of pinned host memory: state read-back | state upload
     // attention-map capture (ss_llama_set_attn_capture): host copy + the device descriptor the decode-token kernel reads
     AttnCaptureDesc cap = {nullptr, 0, 0, 0, 0};
     int cap_row_calls = 0;
     AttnCaptureDesc* cap_desc = nullptr;
-    size_t seq_kv_bytes() const { return (size_t)cfg.n_layers * cfg.n_heads * cfg.cache_cap * hd * esz; }
+    size_t plane_bytes() const { return (size_t)cfg.n_heads * cfg.cache_cap * hd * esz; }       // one layer of one slot
+    size_t seq_kv_bytes() const { return (size_t)cfg.n_layers * plane_bytes(); }
+    int32_t* upload() const { return pinned + (size_t)n_seq * ST_WORDS; }                        // the state upload area
 };
+
+// layer `layer`'s K / V plane [n_heads][cache_cap][hd] of sequence slot `slot`
+static inline char* slot_k(const ss_llama* h, int slot, int layer) {
+    return h->kc + (size_t)slot * h->seq_kv_bytes() + (size_t)layer * h->plane_bytes();
+}
+static inline char* slot_v(const ss_llama* h, int slot, int layer) {
+    return h->vc + (size_t)slot * h->seq_kv_bytes() + (size_t)layer * h->plane_bytes();
+}
 
 static size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
 
@@ -226,7 +236,7 @@ static void carve(ss_llama* h, Carver& c) {
     const size_t H = g.hidden, I = g.inter, R = (size_t)h->max_rows, S = (size_t)h->n_seq;
     h->kc = c.take(S * h->seq_kv_bytes());
     h->vc = c.take(S * h->seq_kv_bytes());
-    h->state = (int32_t*)c.take(S * 8 * sizeof(int32_t));
+    h->state = (int32_t*)c.take(S * ST_WORDS * sizeof(int32_t));
     h->gen_ids = (int32_t*)c.take(S * (size_t)g.max_new * sizeof(int32_t));
     h->forced = (int32_t*)c.take(S * (size_t)g.max_new * sizeof(int32_t));
     h->img_ids = (int32_t*)c.take((size_t)(g.n_img_ids > 0 ? g.n_img_ids : 1) * sizeof(int32_t));
@@ -277,47 +287,54 @@ struct ProfSink {
     }
 };
 
+template <typename T>
+static int sample_embed_launch(ss_llama* h, int seq0, int nb, hipStream_t s) {
+    const ss_llama_config& g = h->cfg;
+    hipLaunchKernelGGL(sample_embed_kernel<T>, dim3((unsigned)nb), dim3(1024), 0, s, (T*)h->logits + (size_t)seq0 * g.vocab,
+                       g.vocab, h->state + (size_t)seq0 * ST_WORDS, h->img_ids, g.n_img_ids,
+                       h->forced + (size_t)seq0 * g.max_new, h->gen_ids + (size_t)seq0 * g.max_new, (const T*)h->w.embed,
+                       (T*)h->x, g.hidden, g.max_new);
+    SS_LAUNCH_CHECK("sample_embed");
+    return SS_OK;
+}
+
+template <typename T>
+static int final_norm_advance_launch(ss_llama* h, int seq0, int nb, hipStream_t s) {
+    const ss_llama_config& g = h->cfg;
+    hipLaunchKernelGGL(final_norm_advance_kernel<T>, dim3((unsigned)nb), dim3(256), 0, s, (const T*)h->x,
+                       (const T*)h->w.final_norm, (T*)h->xn, (T*)h->hid_rows + (size_t)seq0 * g.max_new * g.hidden,
+                       h->state + (size_t)seq0 * ST_WORDS, g.hidden, g.rms_eps, g.max_new);
+    SS_LAUNCH_CHECK("final_norm_advance");
+    return SS_OK;
+}
+
 static int decode_token(ss_llama* h, hipStream_t s, ProfSink* prof, int seq0, int nb) {
     const ss_llama_config& g = h->cfg;
     const int dt = g.dtype;
     const int H = g.hidden, I = g.inter, hd = h->hd;
     const size_t e = h->esz;
-    int32_t* st = h->state + (size_t)seq0 * 8;
+    int32_t* st = h->state + (size_t)seq0 * ST_WORDS;
     const int32_t* done = st + ST_DONE;
-    const size_t plane = (size_t)g.n_heads * g.cache_cap * hd * e;
-    const size_t seq_kv = h->seq_kv_bytes();
-    const int64_t cache_stride = (int64_t)(seq_kv / e);
+    const int64_t cache_stride = (int64_t)(h->seq_kv_bytes() / e);
     char* logits = h->logits + (size_t)seq0 * g.vocab * e;
-    int32_t* forced = h->forced + (size_t)seq0 * g.max_new;
-    int32_t* gen_ids = h->gen_ids + (size_t)seq0 * g.max_new;
-    char* hid_rows = h->hid_rows + (size_t)seq0 * g.max_new * H * e;
     float* attn_ws = (float*)((char*)h->attn_ws + (size_t)seq0 * ss_attn_decode_workspace_bytes(g.n_heads, hd));
+    int rc;
 #define MARK(c) do { if (prof) prof->mark(c); } while (0)
-#define SAMPLE(T)                                                                                                  \
-    hipLaunchKernelGGL(sample_embed_kernel<T>, dim3((unsigned)nb), dim3(1024), 0, s, (T*)logits, g.vocab, st,        \
-                       h->img_ids, g.n_img_ids, forced, gen_ids, (const T*)h->w.embed, (T*)h->x, H, g.max_new)
-#define FINAL(T)                                                                                                   \
-    hipLaunchKernelGGL(final_norm_advance_kernel<T>, dim3((unsigned)nb), dim3(256), 0, s, (const T*)h->x,            \
-                       (const T*)h->w.final_norm, (T*)h->xn, (T*)hid_rows, st, H, g.rms_eps, g.max_new)
     MARK(-1);
-    if (dt == SS_BF16) SAMPLE(bf16_t);
-    else if (dt == SS_F32) SAMPLE(float);
-    else SAMPLE(f16_t);
-    SS_LAUNCH_CHECK("sample_embed");
+    if ((rc = SS_DISPATCH(dt, sample_embed_launch, h, seq0, nb, s))) return rc;
     MARK(3);
     for (int l = 0; l < g.n_layers; ++l) {
         const ss_llama_layer_weights& L = h->layers[l];
-        char* kc = h->kc + (size_t)seq0 * seq_kv + (size_t)l * plane;
-        char* vc = h->vc + (size_t)seq0 * seq_kv + (size_t)l * plane;
-        int rc;
+        char* kc = slot_k(h, seq0, l);
+        char* vc = slot_v(h, seq0, l);
         MARK(-1);
-        rc = gemv_batched_dev(L.wqkv, h->x, h->qkv, 3 * H, H, L.ln1, g.rms_eps, nullptr, nullptr, SS_EPI_NONE, done, 8,
-                              nb, H, 3 * H, 0, dt, s);
+        rc = gemv_batched_dev(L.wqkv, h->x, h->qkv, 3 * H, H, L.ln1, g.rms_eps, nullptr, nullptr, SS_EPI_NONE, done,
+                              ST_WORDS, nb, H, 3 * H, 0, dt, s);
         if (rc) return rc;
         MARK(0);
         // RoPE(q,k) + KV append + split-KV attention in one kernel (+ the split merge)
         rc = attn_decode_fused_dev(h->qkv, kc, vc, h->w.rope_cos, h->w.rope_sin, h->attn, attn_ws, st + ST_KV_LEN,
-                                   st + ST_POS, done, g.n_heads, hd, g.cache_cap, nb, 8, cache_stride, dt, s);
+                                   st + ST_POS, done, g.n_heads, hd, g.cache_cap, nb, ST_WORDS, cache_stride, dt, s);
         if (rc) return rc;
         if (h->cap.maps && nb == 1) {   // attention-map capture: this layer's row of head cap.head (capture off: no launch)
             rc = attn_scores_decode_dev(h->qkv, kc, h->w.rope_cos, h->w.rope_sin, st + ST_KV_LEN, st + ST_POS, done, h->cap_desc,
@@ -325,37 +342,37 @@ static int decode_token(ss_llama* h, hipStream_t s, ProfSink* prof, int seq0, in
             if (rc) return rc;
         }
         MARK(1);
-        rc = gemv_batched_dev(L.wo, h->attn, h->xn, H, H, nullptr, 0.f, nullptr, h->x, SS_EPI_RESIDUAL, done, 8, nb, H,
-                              H, H, dt, s);
+        rc = gemv_batched_dev(L.wo, h->attn, h->xn, H, H, nullptr, 0.f, nullptr, h->x, SS_EPI_RESIDUAL, done, ST_WORDS, nb,
+                              H, H, H, dt, s);
         if (rc) return rc;
         MARK(0);
-        rc = gemv_batched_dev(L.wgu, h->xn, h->hm, I, H, L.ln2, g.rms_eps, nullptr, nullptr, SS_EPI_SILU_MUL, done, 8,
-                              nb, H, I, 0, dt, s);
+        rc = gemv_batched_dev(L.wgu, h->xn, h->hm, I, H, L.ln2, g.rms_eps, nullptr, nullptr, SS_EPI_SILU_MUL, done,
+                              ST_WORDS, nb, H, I, 0, dt, s);
         if (rc) return rc;
         MARK(0);
-        rc = gemv_batched_dev(L.wdown, h->hm, h->x, H, I, nullptr, 0.f, nullptr, h->xn, SS_EPI_RESIDUAL, done, 8, nb, I,
-                              H, H, dt, s);
+        rc = gemv_batched_dev(L.wdown, h->hm, h->x, H, I, nullptr, 0.f, nullptr, h->xn, SS_EPI_RESIDUAL, done, ST_WORDS, nb,
+                              I, H, H, dt, s);
         if (rc) return rc;
         MARK(2);
     }
-    if (dt == SS_BF16) FINAL(bf16_t);
-    else if (dt == SS_F32) FINAL(float);
-    else FINAL(f16_t);
-    SS_LAUNCH_CHECK("final_norm_advance");
+    if ((rc = SS_DISPATCH(dt, final_norm_advance_launch, h, seq0, nb, s))) return rc;
     MARK(3);
-    int rc = gemv_batched_dev(h->w.lm_head, h->xn, logits, g.vocab, H, nullptr, 0.f, nullptr, nullptr, SS_EPI_NONE, done,
-                              8, nb, H, g.vocab, 0, dt, s);
+    rc = gemv_batched_dev(h->w.lm_head, h->xn, logits, g.vocab, H, nullptr, 0.f, nullptr, nullptr, SS_EPI_NONE, done,
+                          ST_WORDS, nb, H, g.vocab, 0, dt, s);
     if (rc) return rc;
     MARK(0);
 #undef MARK
-#undef SAMPLE
-#undef FINAL
     return SS_OK;
 }
 
-static int read_state(ss_llama* h, hipStream_t s) {
-    SS_HIP(hipMemcpyAsync(h->pinned, h->state, (size_t)h->n_seq * 8 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+// device state -> pinned read-back area (synchronises), then the host mirrors of slots [seq0, seq0+nb)
+static int sync_lengths(ss_llama* h, int seq0, int nb, hipStream_t s) {
+    SS_HIP(hipMemcpyAsync(h->pinned, h->state, (size_t)h->n_seq * ST_WORDS * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     SS_HIP(hipStreamSynchronize(s));
+    for (int b = seq0; b < seq0 + nb; ++b) {
+        h->kv_len[b] = h->pinned[b * ST_WORDS + ST_KV_LEN];
+        h->pos[b] = h->pinned[b * ST_WORDS + ST_POS];
+    }
     return SS_OK;
 }
 
@@ -382,9 +399,8 @@ static int graph_for(ss_llama* h, int seq0, int nb, hipGraphExec_t* out) {
 // [seq0, seq0+nb) have been staged in h->pinned[upload area]; replays the decode graph until every
 // slot reports done or `eff_limit` tokens were launched.
 static int run_decode(ss_llama* h, int seq0, int nb, int64_t eff_limit, hipStream_t s) {
-    int32_t* init = h->pinned + (size_t)h->n_seq * 8;
-    SS_HIP(hipMemcpyAsync(h->state + (size_t)seq0 * 8, init + (size_t)seq0 * 8, (size_t)nb * 8 * sizeof(int32_t),
-                          hipMemcpyHostToDevice, s));
+    SS_HIP(hipMemcpyAsync(h->state + (size_t)seq0 * ST_WORDS, h->upload() + (size_t)seq0 * ST_WORDS,
+                          (size_t)nb * ST_WORDS * sizeof(int32_t), hipMemcpyHostToDevice, s));
     const bool use_graph = knob(K_llama_graph) != 0;
     hipGraphExec_t exec = nullptr;
     if (use_graph) { int rc = graph_for(h, seq0, nb, &exec); if (rc) return rc; }
@@ -397,16 +413,144 @@ static int run_decode(ss_llama* h, int seq0, int nb, int64_t eff_limit, hipStrea
             else { int rc = decode_token(h, s, nullptr, seq0, nb); if (rc) return rc; }
         }
         launched += n;
-        int rc = read_state(h, s);
+        int rc = sync_lengths(h, seq0, nb, s);
         if (rc) return rc;
         bool all = true;
-        for (int b = seq0; b < seq0 + nb; ++b) all = all && h->pinned[b * 8 + ST_DONE];
+        for (int b = seq0; b < seq0 + nb; ++b) all = all && h->pinned[b * ST_WORDS + ST_DONE];
         if (all) break;
     }
-    if (launched == 0) { int rc = read_state(h, s); if (rc) return rc; }
-    for (int b = seq0; b < seq0 + nb; ++b) {
-        h->kv_len[b] = h->pinned[b * 8 + ST_KV_LEN];
-        h->pos[b] = h->pinned[b * 8 + ST_POS];
+    return launched ? SS_OK : sync_lengths(h, seq0, nb, s);
+}
+
+// kv_len / pos of one slot: the device state words and the host mirrors (the callers have checked the range)
+static int set_lengths_slot(ss_llama* h, int slot, int64_t kv_len, int64_t pos, hipStream_t s) {
+    hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(64), 0, s, h->state + (size_t)slot * ST_WORDS, (int)ST_KV_LEN,
+                       (int)kv_len, (int)ST_POS, (int)pos);
+    SS_LAUNCH_CHECK("set_state");
+    h->kv_len[slot] = kv_len;
+    h->pos[slot] = pos;
+    return SS_OK;
+}
+
+// one cache plane: rows keep[0 .. n_keep) packed to the front, through the qkv activation buffer as scratch
+template <typename T>
+static int kv_repack_launch(ss_llama* h, char* plane, const int32_t* keep, int n_keep, hipStream_t s) {
+    const int cap = h->cfg.cache_cap, hd = h->hd;
+    const int blocks = cdiv((int64_t)n_keep * (hd / Tr<T>::kVec), 256);
+    const dim3 grid((unsigned)(blocks > 0 ? blocks : 1), (unsigned)h->cfg.n_heads);
+    hipLaunchKernelGGL(kv_gather_kernel<T>, grid, dim3(256), 0, s, (const T*)plane, (T*)h->qkv, keep, n_keep, cap, hd, n_keep);
+    hipLaunchKernelGGL(kv_gather_kernel<T>, grid, dim3(256), 0, s, (const T*)h->qkv, (T*)plane, (const int32_t*)nullptr, n_keep,
+                       n_keep, hd, cap);
+    SS_LAUNCH_CHECK("kv_gather");
+    return SS_OK;
+}
+
+// capture on: the rows [kv0, kv0 + n) x columns [0, kv0 + n) must lie inside the caller's buffer
+static int capture_fits(const ss_llama* h, int64_t kv0, int64_t n, const char* who) {
+    if (!h->cap.maps) return SS_OK;
+    SS_REQUIRE(kv0 >= h->cap.row0, "%s: attention capture starts at cache index %d, the cache holds only %lld", who,
+               (int)h->cap.row0, (long long)kv0);
+    SS_REQUIRE(kv0 + n - h->cap.row0 <= h->cap.n_rows, "%s: attention-capture buffer has %d rows, %lld needed", who,
+               (int)h->cap.n_rows, (long long)(kv0 + n - h->cap.row0));
+    SS_REQUIRE(kv0 + n <= h->cap.ld, "%s: attention-capture buffer has %d columns, %lld needed", who, (int)h->cap.ld,
+               (long long)(kv0 + n));
+    return SS_OK;
+}
+
+// The stride list of "stacked rows [rows, hidden] of one slot against that slot's cache planes [n_heads][cache_cap][hd],
+// bottom-right causal", and its sibling for every slot of the engine at once (slot b: rows [b*rows, (b+1)*rows) against
+// kv_lens[b] keys of its own planes of layer `layer`).
+static int cache_attention(const ss_llama* h, const void* q, const void* kc, const void* vc, void* out, int64_t rows,
+                           int64_t kv_len, void* stream) {
+    const int64_t H = h->cfg.hidden, hd = h->hd, head = (int64_t)h->cfg.cache_cap * hd;
+    return ss_attention(q, kc, vc, out, 1, h->cfg.n_heads, rows, kv_len, hd, 0, hd, H, 0, head, hd, 0, head, hd, 0, hd, H,
+                        1.0f / sqrtf((float)hd), 1, h->cfg.dtype, stream);
+}
+static int cache_attention_all_slots(const ss_llama* h, int layer, int64_t rows, const int32_t* kv_lens, void* stream) {
+    const int64_t H = h->cfg.hidden, hd = h->hd, head = (int64_t)h->cfg.cache_cap * hd;
+    const int64_t slot = (int64_t)(h->seq_kv_bytes() / h->esz);
+    return ss_attention_ragged(h->q, slot_k(h, 0, layer), slot_v(h, 0, layer), h->attn, h->n_seq, h->cfg.n_heads, rows, kv_lens,
+                               hd, rows * H, hd, H, slot, head, hd, slot, head, hd, rows * H, hd, H, 1.0f / sqrtf((float)hd), 1,
+                               h->cfg.dtype, stream);
+}
+
+// The prefill / continuation forward: segment i feeds segs[i].rows new rows of `embeds` (stacked in segment order) to
+// sequence slot segs[i].slot.  Every projection runs ONCE on the stack (M = sum of the rows: the 13.2 GB of layer weights
+// are streamed once per call, not once per slot); RoPE / KV append and the bottom-right causal attention stay per slot
+// (each slot's rows against its own cache).  One segment = the single-slot ss_llama_prefill; several = the image-token
+// block continuation of lock-step stories (4 x 66 rows) and their prompt prefill (4 x S rows).  The callers have checked
+// every segment's KV and position bounds, so nothing fails after the first launch for a reason known beforehand.
+struct PrefillSeg {
+    int slot;
+    int64_t rows;               // > 0
+    const int32_t* pos_ids;     // explicit RoPE positions (device), or null: pos, pos + 1, ...; the slot's pos then stays
+};
+
+static int prefill_forward(ss_llama* h, const PrefillSeg* segs, int nseg, const void* embeds, void* hidden_out,
+                           const char* who, void* stream) {
+    const ss_llama_config& g = h->cfg;
+    hipStream_t s = (hipStream_t)stream;
+    const int dt = g.dtype;
+    const int64_t H = g.hidden, I = g.inter;
+    const int hd = h->hd;
+    const size_t e = h->esz;
+    int rc;
+    int64_t M = 0;
+    // every slot of the engine feeds the same number of rows (the lock-step image-token block, equal-length prompts): ONE
+    // attention launch over the slots, slot b attending to its own kv_len[b] + r keys (measured at 8 x 66 rows: 256 launches
+    // of 24 us per pass = a third of the block's time, before)
+    bool ragged = nseg == h->n_seq && nseg >= 2 && nseg <= 8 && knob(K_llama_batched_attn) != 0;
+    int32_t kv_lens[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int i = 0; i < nseg; ++i) {
+        const PrefillSeg& sg = segs[i];
+        if ((rc = capture_fits(h, h->kv_len[sg.slot], sg.rows, who))) return rc;
+        if (sg.rows != segs[0].rows) ragged = false;
+        if (ragged) kv_lens[i] = (int32_t)(h->kv_len[sg.slot] + sg.rows);       // nseg == n_seq: segment i is slot i
+        M += sg.rows;
+    }
+    SS_HIP(hipMemcpyAsync(h->x, embeds, (size_t)M * H * e, hipMemcpyDeviceToDevice, s));
+    for (int l = 0; l < g.n_layers; ++l) {
+        const ss_llama_layer_weights& L = h->layers[l];
+        if ((rc = rmsnorm_rows(h->x, L.ln1, h->xn, M, H, g.rms_eps, dt, s))) return rc;
+        if ((rc = prefill_proj(h->splitk_ws, h->splitk_bytes, h->xn, L.wqkv, h->qkv, M, 3 * H, H, nullptr, dt, s))) return rc;
+        int64_t r0 = 0;
+        for (int i = 0; i < nseg; ++i) {
+            const PrefillSeg& sg = segs[i];
+            char *kc = slot_k(h, sg.slot, l), *vc = slot_v(h, sg.slot, l);
+            const int64_t r = sg.rows, kv0 = h->kv_len[sg.slot], kv1 = kv0 + r;
+            char* q_b = h->q + (size_t)r0 * H * e;
+            if ((rc = ss_rope_kv_append(h->qkv + (size_t)r0 * 3 * H * e, q_b, kc, vc, h->w.rope_cos, h->w.rope_sin, sg.pos_ids,
+                                        h->pos[sg.slot], r, g.n_heads, hd, kv0, g.cache_cap, dt, stream)))
+                return rc;
+            if (h->cap.maps) {      // head cap.head's pre-softmax scores of these rows against the cache (prefix included)
+                char* rows = (char*)h->cap.maps + (((size_t)l * h->cap.n_rows + (size_t)(kv0 - h->cap.row0)) * h->cap.ld) * e;
+                if ((rc = attn_scores_dev(q_b + (size_t)h->cap.head * hd * e, H, kc + (size_t)h->cap.head * g.cache_cap * hd * e, hd,
+                                          rows, h->cap.ld, r, kv1, hd, r > 1 ? h->cap_row_calls : 0, dt, s)))
+                    return rc;
+            }
+            if (!ragged && (rc = cache_attention(h, q_b, kc, vc, h->attn + (size_t)r0 * H * e, r, kv1, stream))) return rc;
+            r0 += r;
+        }
+        if (ragged && (rc = cache_attention_all_slots(h, l, segs[0].rows, kv_lens, stream))) return rc;
+        if ((rc = prefill_proj(h->splitk_ws, h->splitk_bytes, h->attn, L.wo, h->x, M, H, H, h->x, dt, s))) return rc;
+        if ((rc = rmsnorm_rows(h->x, L.ln2, h->xn, M, H, g.rms_eps, dt, s))) return rc;
+        if ((rc = prefill_proj(h->splitk_ws, h->splitk_bytes, h->xn, L.wgu, h->gu, M, 2 * I, H, nullptr, dt, s))) return rc;
+        if ((rc = ss_silu_mul(h->gu, h->hm, M, I, dt, stream))) return rc;
+        if ((rc = prefill_proj(h->splitk_ws, h->splitk_bytes, h->hm, L.wdown, h->x, M, H, I, h->x, dt, s))) return rc;
+    }
+    // final norm (:652) for all rows, lm_head for each segment's last row only (greedy consumes logits[:, -1])
+    void* hid = hidden_out ? hidden_out : (void*)h->xn;
+    if ((rc = rmsnorm_rows(h->x, h->w.final_norm, hid, M, H, g.rms_eps, dt, s))) return rc;
+    int64_t r0 = 0;
+    for (int i = 0; i < nseg; ++i) {
+        const PrefillSeg& sg = segs[i];
+        const char* last = (const char*)hid + (size_t)(r0 + sg.rows - 1) * H * e;
+        if ((rc = gemv_dev(h->w.lm_head, last, h->logits + (size_t)sg.slot * g.vocab * e, g.vocab, H, nullptr, 0.f, nullptr,
+                           nullptr, SS_EPI_NONE, nullptr, dt, s)))
+            return rc;
+        const int64_t pos = h->pos[sg.slot] + (sg.pos_ids ? 0 : sg.rows);        // explicit pos_ids: the caller sets pos afterwards
+        if ((rc = set_lengths_slot(h, sg.slot, h->kv_len[sg.slot] + sg.rows, pos, s))) return rc;
+        r0 += sg.rows;
     }
     return SS_OK;
 }
@@ -463,7 +607,7 @@ int ss_llama_create(const ss_llama_config* cfg, const ss_llama_weights* w, void*
     h->pos.assign(h->n_seq, 0);
     hipError_t e = hipStreamCreateWithFlags(&h->cap_stream, hipStreamNonBlocking);
     if (e == hipSuccess)
-        e = hipHostMalloc((void**)&h->pinned, (size_t)h->n_seq * 16 * sizeof(int32_t) + 64, hipHostMallocDefault);
+        e = hipHostMalloc((void**)&h->pinned, (size_t)h->n_seq * 2 * ST_WORDS * sizeof(int32_t) + 64, hipHostMallocDefault);
     // the whole workspace starts as zeros: a cache row a caller declares valid without having written it (set_lengths on a
     // fresh slot: profiling runs, KV mirrors) then holds zeros, not the allocator's residue — NaN bit patterns there turn
     // every logit into NaN
@@ -514,18 +658,6 @@ int ss_llama_set_attn_capture(ss_llama* h, void* maps, int64_t n_rows, int64_t l
     return SS_OK;
 }
 
-// capture on: the rows [kv0, kv0 + n) x columns [0, kv0 + n) must lie inside the caller's buffer
-static int capture_fits(const ss_llama* h, int64_t kv0, int64_t n, const char* who) {
-    if (!h->cap.maps) return SS_OK;
-    SS_REQUIRE(kv0 >= h->cap.row0, "%s: attention capture starts at cache index %d, the cache holds only %lld", who,
-               (int)h->cap.row0, (long long)kv0);
-    SS_REQUIRE(kv0 + n - h->cap.row0 <= h->cap.n_rows, "%s: attention-capture buffer has %d rows, %lld needed", who,
-               (int)h->cap.n_rows, (long long)(kv0 + n - h->cap.row0));
-    SS_REQUIRE(kv0 + n <= h->cap.ld, "%s: attention-capture buffer has %d columns, %lld needed", who, (int)h->cap.ld,
-               (long long)(kv0 + n));
-    return SS_OK;
-}
-
 int ss_llama_select(ss_llama* h, int32_t seq) {
     SS_REQUIRE(h && seq >= 0 && seq < h->n_seq, "llama_select: sequence slot %d out of range", (int)seq);
     h->cur = seq;
@@ -542,7 +674,7 @@ void* ss_llama_buffer(ss_llama* h, int which) {
         case 2: return h->gen_ids + q * g.max_new;
         case 3: return h->hid_rows + q * (size_t)g.max_new * g.hidden * h->esz;
         case 4: return h->logits + q * (size_t)g.vocab * h->esz;
-        case 5: return h->state + q * 8;
+        case 5: return h->state + q * ST_WORDS;
         default: return nullptr;
     }
 }
@@ -550,12 +682,7 @@ void* ss_llama_buffer(ss_llama* h, int which) {
 int ss_llama_set_lengths(ss_llama* h, int64_t kv_len, int64_t pos, void* stream) {
     SS_REQUIRE(h && kv_len >= 0 && kv_len <= h->cfg.cache_cap && pos >= 0 && pos <= h->cfg.max_pos,
                "llama_set_lengths: out of range (kv_len=%lld pos=%lld)", (long long)kv_len, (long long)pos);
-    hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, h->state + (size_t)h->cur * 8,
-                       (int)ST_KV_LEN, (int)kv_len, (int)ST_POS, (int)pos);
-    SS_LAUNCH_CHECK("set_state");
-    h->kv_len[h->cur] = kv_len;
-    h->pos[h->cur] = pos;
-    return SS_OK;
+    return set_lengths_slot(h, h->cur, kv_len, pos, (hipStream_t)stream);
 }
 
 int ss_llama_get_lengths(ss_llama* h, int64_t* kv_len, int64_t* pos) {
@@ -568,34 +695,13 @@ int ss_llama_get_lengths(ss_llama* h, int64_t* kv_len, int64_t* pos) {
 int ss_llama_kv_gather(ss_llama* h, const int32_t* keep_idx_dev, int64_t n_keep, void* stream) {
     SS_REQUIRE(h && keep_idx_dev && n_keep >= 0 && n_keep <= h->kv_len[h->cur], "llama_kv_gather: bad arguments");
     const ss_llama_config& g = h->cfg;
-    const size_t e = h->esz;
     // scratch = qkv activation buffer: [max_rows][3*hidden] elements >= n_heads * n_keep * hd = n_keep * hidden
     SS_REQUIRE(n_keep <= 3 * h->max_rows, "llama_kv_gather: n_keep %lld exceeds scratch (3 x %lld rows)",
                (long long)n_keep, (long long)h->max_rows);
-    hipStream_t s = (hipStream_t)stream;
-    const size_t plane = (size_t)g.n_heads * g.cache_cap * h->hd * e;
-    char* kbase = h->kc + (size_t)h->cur * h->seq_kv_bytes();
-    char* vbase = h->vc + (size_t)h->cur * h->seq_kv_bytes();
-    const int V = g.dtype == SS_F32 ? 4 : 8;
-    dim3 grid((unsigned)cdiv(n_keep * (h->hd / V), 256) > 0 ? (unsigned)cdiv(n_keep * (h->hd / V), 256) : 1,
-              (unsigned)g.n_heads);
-    if (n_keep > 0) {
-        for (int l = 0; l < g.n_layers; ++l) {
-            for (int kv = 0; kv < 2; ++kv) {
-                char* plane_p = (kv ? vbase : kbase) + (size_t)l * plane;
-#define GATHER(T)                                                                                                  \
-    hipLaunchKernelGGL(kv_gather_kernel<T>, grid, dim3(256), 0, s, (const T*)plane_p, (T*)h->qkv, keep_idx_dev,     \
-                       (int)n_keep, g.cache_cap, h->hd, (int)n_keep);                                               \
-    hipLaunchKernelGGL(kv_gather_kernel<T>, grid, dim3(256), 0, s, (const T*)h->qkv, (T*)plane_p,                   \
-                       (const int32_t*)nullptr, (int)n_keep, (int)n_keep, h->hd, g.cache_cap)
-                if (g.dtype == SS_BF16) { GATHER(bf16_t); }
-                else if (g.dtype == SS_F32) { GATHER(float); }
-                else { GATHER(f16_t); }
-#undef GATHER
-                SS_LAUNCH_CHECK("kv_gather");
-            }
-        }
-    }
+    for (int l = 0; l < g.n_layers && n_keep > 0; ++l)
+        for (char* plane : {slot_k(h, h->cur, l), slot_v(h, h->cur, l)})
+            if (int rc = SS_DISPATCH(g.dtype, kv_repack_launch, h, plane, keep_idx_dev, (int)n_keep, (hipStream_t)stream))
+                return rc;
     return ss_llama_set_lengths(h, n_keep, h->pos[h->cur], stream);
 }
 
@@ -608,152 +714,42 @@ int ss_llama_prefill(ss_llama* h, const void* embeds, int64_t M, const int32_t* 
     SS_REQUIRE(cur_kv + M <= h->cfg.cache_cap, "llama_prefill: KV cache overflow (%lld + %lld > %d)",
                (long long)cur_kv, (long long)M, h->cfg.cache_cap);
     SS_REQUIRE(pos_ids || cur_pos + M <= h->cfg.max_pos, "llama_prefill: position overflow");
-    if (int crc = capture_fits(h, cur_kv, M, "llama_prefill")) return crc;
-    const ss_llama_config& g = h->cfg;
-    hipStream_t s = (hipStream_t)stream;
-    const int dt = g.dtype;
-    const int64_t H = g.hidden, I = g.inter;
-    const int hd = h->hd;
-    const size_t e = h->esz;
-    const size_t plane = (size_t)g.n_heads * g.cache_cap * hd * e;
-    char* kbase = h->kc + (size_t)h->cur * h->seq_kv_bytes();
-    char* vbase = h->vc + (size_t)h->cur * h->seq_kv_bytes();
-    const int64_t kv0 = cur_kv, kv1 = cur_kv + M;
-    int rc;
-    SS_HIP(hipMemcpyAsync(h->x, embeds, (size_t)M * H * e, hipMemcpyDeviceToDevice, s));
-    for (int l = 0; l < g.n_layers; ++l) {
-        const ss_llama_layer_weights& L = h->layers[l];
-        char* kc = kbase + (size_t)l * plane;
-        char* vc = vbase + (size_t)l * plane;
-        if ((rc = rmsnorm_rows(h->x, L.ln1, h->xn, M, H, g.rms_eps, dt, s))) return rc;
-        if ((rc = prefill_proj(h->splitk_ws, h->splitk_bytes, h->xn, L.wqkv, h->qkv, M, 3 * H, H, nullptr, dt, s))) return rc;
-        if ((rc = ss_rope_kv_append(h->qkv, h->q, kc, vc, h->w.rope_cos, h->w.rope_sin, pos_ids, cur_pos, M, g.n_heads,
-                                    hd, kv0, g.cache_cap, dt, stream)))
-            return rc;
-        if (h->cap.maps) {      // head cap.head's pre-softmax scores of these M rows against the cache (prefix included)
-            char* rows = (char*)h->cap.maps + (((size_t)l * h->cap.n_rows + (size_t)(kv0 - h->cap.row0)) * h->cap.ld) * e;
-            if ((rc = attn_scores_dev(h->q + (size_t)h->cap.head * hd * e, H, kc + (size_t)h->cap.head * g.cache_cap * hd * e, hd,
-                                      rows, h->cap.ld, M, kv1, hd, M > 1 ? h->cap_row_calls : 0, dt, s)))
-                return rc;
-        }
-        if ((rc = ss_attention(h->q, kc, vc, h->attn, 1, g.n_heads, M, kv1, hd, 0, hd, H, 0, (int64_t)g.cache_cap * hd,
-                               hd, 0, (int64_t)g.cache_cap * hd, hd, 0, hd, H, 1.0f / sqrtf((float)hd), 1, dt, stream)))
-            return rc;
-        if ((rc = prefill_proj(h->splitk_ws, h->splitk_bytes, h->attn, L.wo, h->x, M, H, H, h->x, dt, s))) return rc;
-        if ((rc = rmsnorm_rows(h->x, L.ln2, h->xn, M, H, g.rms_eps, dt, s))) return rc;
-        if ((rc = prefill_proj(h->splitk_ws, h->splitk_bytes, h->xn, L.wgu, h->gu, M, 2 * I, H, nullptr, dt, s))) return rc;
-        if ((rc = ss_silu_mul(h->gu, h->hm, M, I, dt, stream))) return rc;
-        if ((rc = prefill_proj(h->splitk_ws, h->splitk_bytes, h->hm, L.wdown, h->x, M, H, I, h->x, dt, s))) return rc;
-    }
-    // final norm (:652) for all rows, lm_head for the last row only (greedy consumes logits[:, -1])
-    void* hid = hidden_out ? hidden_out : (void*)h->xn;
-    if ((rc = rmsnorm_rows(h->x, h->w.final_norm, hid, M, H, g.rms_eps, dt, s))) return rc;
-    const char* last = (const char*)hid + (size_t)(M - 1) * H * e;
-    char* logits = h->logits + (size_t)h->cur * g.vocab * e;
-    if ((rc = gemv_dev(h->w.lm_head, last, logits, g.vocab, H, nullptr, 0.f, nullptr, nullptr, SS_EPI_NONE, nullptr,
-                       dt, s)))
-        return rc;
-    const int64_t new_pos = pos_ids ? cur_pos : cur_pos + M;  // explicit pos_ids: caller sets pos afterwards
-    return ss_llama_set_lengths(h, kv1, new_pos, stream);
+    const PrefillSeg seg = {h->cur, M, pos_ids};
+    return prefill_forward(h, &seg, 1, embeds, hidden_out, "llama_prefill", stream);
 }
 
-// The same forward for SEVERAL sequence slots in one sweep of the weights: the rows of all participating slots are
-// stacked (slot-major) and every projection runs ONCE on the stack (M = sum of the slots' rows: the 13.2 GB of layer
-// weights are streamed once per call instead of once per slot, and the GEMMs see 4x the rows); RoPE / KV append and the
-// bottom-right causal attention stay per slot (each slot's rows against its own cache).  Used for the image-token block
-// continuation of lock-step stories (4 x 66 rows) and for their prompt prefill (4 x S rows).
+// several sequence slots in one sweep of the weights: host_rows[b] rows of `embeds` (stacked slot-major) for slot b
 int ss_llama_prefill_batch(ss_llama* h, const void* embeds, const int64_t* host_rows, void* hidden_out, void* stream) {
     SS_REQUIRE(h && embeds && host_rows, "llama_prefill_batch: bad arguments");
     SS_REQUIRE(!h->cap.maps, "llama_prefill_batch: attention capture is a single-sequence tool (use ss_llama_prefill on the selected slot)");
     const ss_llama_config& g = h->cfg;
+    PrefillSeg segs[8];         // n_seq <= 8 (ss_llama_create)
+    int nseg = 0;
     int64_t M = 0;
     for (int b = 0; b < h->n_seq; ++b) {
         const int64_t r = host_rows[b];
         SS_REQUIRE(r >= 0, "llama_prefill_batch: negative row count for slot %d", b);
         SS_REQUIRE(h->kv_len[b] + r <= g.cache_cap, "llama_prefill_batch: KV cache overflow in slot %d (%lld + %lld > %d)", b,
                    (long long)h->kv_len[b], (long long)r, g.cache_cap);
-        // (the bound of ss_llama_set_lengths, checked for EVERY slot before anything is launched: a slot that fails there
-        // after the forward would leave host and device lengths inconsistent across the slots)
+        // (checked for EVERY slot before anything is launched: a slot that failed after the forward would leave host and
+        // device lengths inconsistent across the slots)
         // (`<=`: the last RoPE position used is pos + r - 1, so a prompt may exactly fill the position table — the same bound as
         // the single-slot ss_llama_prefill; decoding further is refused by the generate entry points)
         SS_REQUIRE(r == 0 || h->pos[b] + r <= g.max_pos, "llama_prefill_batch: position overflow in slot %d (%lld + %lld > %d)", b,
                    (long long)h->pos[b], (long long)r, g.max_pos);
+        if (r) segs[nseg++] = {b, r, nullptr};
         M += r;
     }
     SS_REQUIRE(M > 0 && M <= h->max_rows, "llama_prefill_batch: %lld stacked rows (max_prefill_rows=%lld)", (long long)M,
                (long long)h->max_rows);
-    hipStream_t s = (hipStream_t)stream;
-    const int dt = g.dtype;
-    const int64_t H = g.hidden, I = g.inter;
-    const int hd = h->hd;
-    const size_t e = h->esz;
-    const size_t plane = (size_t)g.n_heads * g.cache_cap * hd * e;
-    int rc;
-    bool uniform_rows = h->n_seq >= 2 && h->n_seq <= 8 && knob(K_llama_batched_attn) != 0;
-    int32_t kv_lens[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int b = 0; b < h->n_seq && uniform_rows; ++b) {
-        if (host_rows[b] != host_rows[0] || host_rows[b] <= 0) uniform_rows = false;
-        else kv_lens[b] = (int32_t)(h->kv_len[b] + host_rows[b]);
-    }
-    SS_HIP(hipMemcpyAsync(h->x, embeds, (size_t)M * H * e, hipMemcpyDeviceToDevice, s));
-    for (int l = 0; l < g.n_layers; ++l) {
-        const ss_llama_layer_weights& L = h->layers[l];
-        if ((rc = rmsnorm_rows(h->x, L.ln1, h->xn, M, H, g.rms_eps, dt, s))) return rc;
-        if ((rc = prefill_proj(h->splitk_ws, h->splitk_bytes, h->xn, L.wqkv, h->qkv, M, 3 * H, H, nullptr, dt, s))) return rc;
-        int64_t r0 = 0;
-        for (int b = 0; b < h->n_seq; ++b) {
-            const int64_t r = host_rows[b];
-            if (!r) continue;
-            char* kc = h->kc + (size_t)b * h->seq_kv_bytes() + (size_t)l * plane;
-            char* vc = h->vc + (size_t)b * h->seq_kv_bytes() + (size_t)l * plane;
-            const int64_t kv0 = h->kv_len[b], kv1 = kv0 + r;
-            char* qkv_b = h->qkv + (size_t)r0 * 3 * H * e;
-            char* q_b = h->q + (size_t)r0 * H * e;
-            if ((rc = ss_rope_kv_append(qkv_b, q_b, kc, vc, h->w.rope_cos, h->w.rope_sin, nullptr, h->pos[b], r, g.n_heads,
-                                        hd, kv0, g.cache_cap, dt, stream)))
-                return rc;
-            if (!uniform_rows &&
-                (rc = ss_attention(q_b, kc, vc, h->attn + (size_t)r0 * H * e, 1, g.n_heads, r, kv1, hd, 0, hd, H, 0,
-                                   (int64_t)g.cache_cap * hd, hd, 0, (int64_t)g.cache_cap * hd, hd, 0, hd, H,
-                                   1.0f / sqrtf((float)hd), 1, dt, stream)))
-                return rc;
-            r0 += r;
-        }
-        if (uniform_rows) {
-            // every slot feeds the same number of rows (the lock-step image-token block, equal-length prompts): ONE attention
-            // launch over the slots, slot b attending to its own kv_len[b] + r keys (measured at 8 x 66 rows: 256 launches of
-            // 24 us per pass = a third of the block's time, before)
-            const int64_t r = host_rows[0];
-            const int64_t seq_stride = (int64_t)(h->seq_kv_bytes() / e);
-            if ((rc = ss_attention_ragged(h->q, h->kc + (size_t)l * plane, h->vc + (size_t)l * plane, h->attn, h->n_seq, g.n_heads,
-                                          r, kv_lens, hd, r * H, hd, H, seq_stride, (int64_t)g.cache_cap * hd, hd, seq_stride,
-                                          (int64_t)g.cache_cap * hd, hd, r * H, hd, H, 1.0f / sqrtf((float)hd), 1, dt, stream)))
-                return rc;
-        }
-        if ((rc = prefill_proj(h->splitk_ws, h->splitk_bytes, h->attn, L.wo, h->x, M, H, H, h->x, dt, s))) return rc;
-        if ((rc = rmsnorm_rows(h->x, L.ln2, h->xn, M, H, g.rms_eps, dt, s))) return rc;
-        if ((rc = prefill_proj(h->splitk_ws, h->splitk_bytes, h->xn, L.wgu, h->gu, M, 2 * I, H, nullptr, dt, s))) return rc;
-        if ((rc = ss_silu_mul(h->gu, h->hm, M, I, dt, stream))) return rc;
-        if ((rc = prefill_proj(h->splitk_ws, h->splitk_bytes, h->hm, L.wdown, h->x, M, H, I, h->x, dt, s))) return rc;
-    }
-    void* hid = hidden_out ? hidden_out : (void*)h->xn;
-    if ((rc = rmsnorm_rows(h->x, h->w.final_norm, hid, M, H, g.rms_eps, dt, s))) return rc;
-    const int keep_cur = h->cur;
-    int64_t r0 = 0;
-    for (int b = 0; b < h->n_seq; ++b) {
-        const int64_t r = host_rows[b];
-        if (!r) continue;
-        const char* last = (const char*)hid + (size_t)(r0 + r - 1) * H * e;
-        char* logits = h->logits + (size_t)b * g.vocab * e;
-        if ((rc = gemv_dev(h->w.lm_head, last, logits, g.vocab, H, nullptr, 0.f, nullptr, nullptr, SS_EPI_NONE, nullptr, dt, s)))
-            return rc;
-        h->cur = b;
-        rc = ss_llama_set_lengths(h, h->kv_len[b] + r, h->pos[b] + r, stream);
-        h->cur = keep_cur;
-        if (rc) return rc;
-        r0 += r;
-    }
-    return SS_OK;
+    return prefill_forward(h, segs, nseg, embeds, hidden_out, "llama_prefill_batch", stream);
+}
+
+// one slot's initial decode state words
+static void fill_state(int32_t* init, int64_t kv_len, int64_t pos, bool done, int32_t last, int64_t n_forced, int64_t limit,
+                       int32_t eos_word) {
+    init[ST_KV_LEN] = (int32_t)kv_len; init[ST_POS] = (int32_t)pos; init[ST_NGEN] = 0; init[ST_DONE] = done ? 1 : 0;
+    init[ST_LAST] = last; init[ST_NFORCED] = (int32_t)n_forced; init[ST_LIMIT] = (int32_t)limit; init[ST_EOS] = eos_word;
 }
 
 // stage one slot's initial decode state in the pinned upload area; returns the launch bound
@@ -764,11 +760,8 @@ static int64_t stage_seq(ss_llama* h, int b, int64_t n_steps, int32_t last_id, c
     int64_t eff = limit;
     for (int64_t i = 0; i < n_forced && i < eff; ++i)
         if (forced[i] == g.eos_id || forced[i] == h->stop2) { eff = i + 1; break; }  // the host already knows where it stops
-    int32_t* init = h->pinned + (size_t)h->n_seq * 8 + (size_t)b * 8;
-    init[ST_KV_LEN] = (int32_t)h->kv_len[b]; init[ST_POS] = (int32_t)h->pos[b]; init[ST_NGEN] = 0;
-    init[ST_DONE] = active ? 0 : 1; init[ST_LAST] = last_id; init[ST_NFORCED] = (int32_t)n_forced;
-    init[ST_LIMIT] = (int32_t)limit;
-    init[ST_EOS] = (g.eos_id >= 0 ? (g.eos_id & 0xFFFF) : 0xFFFF) | ((h->stop2 + 1) << 16);
+    fill_state(h->upload() + (size_t)b * ST_WORDS, h->kv_len[b], h->pos[b], !active, last_id, n_forced, limit,
+               (g.eos_id >= 0 ? (g.eos_id & 0xFFFF) : 0xFFFF) | ((h->stop2 + 1) << 16));
     return active ? eff : 0;
 }
 
@@ -788,11 +781,11 @@ int ss_llama_generate(ss_llama* h, int64_t n_steps, int32_t last_prompt_id, cons
     if (n_forced > 0)
         SS_HIP(hipMemcpyAsync(h->forced + (size_t)q * g.max_new, host_forced, (size_t)n_forced * sizeof(int32_t),
                               hipMemcpyHostToDevice, s));
-    // state upload staged in pinned memory; consumed before this call returns (read_state syncs)
+    // state upload staged in pinned memory; consumed before this call returns (sync_lengths syncs)
     const int64_t eff_limit = stage_seq(h, q, n_steps, last_prompt_id, host_forced, n_forced, true);
     int rc = run_decode(h, q, 1, eff_limit, s);
     if (rc) return rc;
-    if (host_n_generated) *host_n_generated = h->pinned[q * 8 + ST_NGEN];
+    if (host_n_generated) *host_n_generated = h->pinned[q * ST_WORDS + ST_NGEN];
     return SS_OK;
 }
 
@@ -824,7 +817,7 @@ int ss_llama_generate_batch(ss_llama* h, int64_t n_steps, const int32_t* last_pr
     int rc = run_decode(h, 0, h->n_seq, eff_limit, s);
     if (rc) return rc;
     if (host_n_generated)
-        for (int b = 0; b < h->n_seq; ++b) host_n_generated[b] = h->pinned[b * 8 + ST_NGEN];
+        for (int b = 0; b < h->n_seq; ++b) host_n_generated[b] = h->pinned[b * ST_WORDS + ST_NGEN];
     return SS_OK;
 }
 
@@ -832,14 +825,11 @@ int ss_llama_profile_decode(ss_llama* h, int64_t n_tokens, float out_ms[8], doub
     SS_REQUIRE(h && n_tokens > 0 && out_ms && out_bytes, "llama_profile_decode: bad arguments");
     const ss_llama_config& g = h->cfg;
     hipStream_t s = (hipStream_t)stream;
-    int32_t* init = h->pinned + (size_t)h->n_seq * 8;
     for (int b = 0; b < h->n_seq; ++b) {
         SS_REQUIRE(h->kv_len[b] + n_tokens + 1 <= g.cache_cap, "llama_profile_decode: KV cache too full (slot %d)", b);
-        int32_t* st = init + b * 8;
-        st[ST_KV_LEN] = (int32_t)h->kv_len[b]; st[ST_POS] = (int32_t)h->pos[b]; st[ST_NGEN] = 0; st[ST_DONE] = 0;
-        st[ST_LAST] = 0; st[ST_NFORCED] = 0; st[ST_LIMIT] = g.max_new; st[ST_EOS] = -1;
+        fill_state(h->upload() + (size_t)b * ST_WORDS, h->kv_len[b], h->pos[b], false, 0, 0, g.max_new, -1);
     }
-    SS_HIP(hipMemcpyAsync(h->state, init, (size_t)h->n_seq * 8 * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    SS_HIP(hipMemcpyAsync(h->state, h->upload(), (size_t)h->n_seq * ST_WORDS * sizeof(int32_t), hipMemcpyHostToDevice, s));
     for (int i = 0; i < 8; ++i) out_ms[i] = 0.f;
     double cnt[4] = {0, 0, 0, 0};
     for (int64_t t = 0; t < n_tokens && t < g.max_new - 1; ++t) {
@@ -868,13 +858,7 @@ int ss_llama_profile_decode(ss_llama* h, int64_t n_tokens, float out_ms[8], doub
     out_bytes[1] = cnt[0] / (double)n_tokens;
     out_bytes[2] = (double)g.n_layers * H * I * (double)h->esz;
     out_bytes[3] = cnt[2] / (double)n_tokens;
-    int rc = read_state(h, s);
-    if (rc) return rc;
-    for (int b = 0; b < h->n_seq; ++b) {
-        h->kv_len[b] = h->pinned[b * 8 + ST_KV_LEN];
-        h->pos[b] = h->pinned[b * 8 + ST_POS];
-    }
-    return SS_OK;
+    return sync_lengths(h, 0, h->n_seq, s);
 }
 
 }  // extern "C"

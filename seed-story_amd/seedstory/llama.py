@@ -37,6 +37,13 @@ def _merged(sd, name, dtype, device, lora_scaling):
     return w.to(dtype).contiguous()
 
 
+def _prefill_chunked(eng, emb, want_hidden):
+    """``eng.prefill`` of ``emb`` on the selected slot, ``max_rows`` (what the engine was sized for) rows per call."""
+    step = int(eng.max_rows)
+    parts = [eng.prefill(emb[i:i + step], want_hidden=want_hidden) for i in range(0, emb.shape[0], step)]
+    return torch.cat([p.clone() for p in parts]) if want_hidden and len(parts) > 1 else parts[0]
+
+
 class LlamaEngine:
     def __init__(self, state_dict, *, hidden, n_heads, n_layers, inter, vocab, dtype=torch.bfloat16, device="cuda:0",
                  rms_eps=1e-5, max_pos=4096, cache_cap=2048, max_new=512, max_prefill_rows=1024, img_ids=(),
@@ -249,6 +256,12 @@ class LlamaEngine:
                                "selected slot)" % what)
 
     # ---- forward paths ---------------------------------------------------------------------------------
+    def _ensure_prefill_tiles(self, M):
+        if M > 128:      # the four prefill projections of this row-count bucket (tile table: seedstory/tune.py)
+            code, Hd, I = ops.dt(self.dtype), self.hidden, self.inter
+            for n, k in ((3 * Hd, Hd), (Hd, Hd), (2 * I, Hd), (Hd, I)):
+                tune.ensure_gemm(M, n, k, code, 0, self.device)
+
     def prefill(self, embeds, pos_ids=None, want_hidden=False):
         """embeds [M, hidden] rows appended after the cached prefix.  Returns the post-final-norm
         hidden rows [M, hidden] if want_hidden; the last row's logits land in ``self.logits``."""
@@ -256,10 +269,7 @@ class LlamaEngine:
         M = embeds.shape[0]
         hid = torch.empty(M, self.hidden, dtype=self.dtype, device=self.device) if want_hidden else None
         pid = None if pos_ids is None else pos_ids.to(device=self.device, dtype=torch.int32).contiguous()
-        if M > 128:      # the four prefill projections of this row-count bucket (tile table: seedstory/tune.py)
-            code, Hd, I = ops.dt(self.dtype), self.hidden, self.inter
-            for n, k in ((3 * Hd, Hd), (Hd, Hd), (2 * I, Hd), (Hd, I)):
-                tune.ensure_gemm(M, n, k, code, 0, self.device)
+        self._ensure_prefill_tiles(M)
         check(lib().ss_llama_prefill(self._h, embeds.data_ptr(), M, ops.p(pid), ops.p(hid), ops.stream()),
               "ss_llama_prefill")
         return hid
@@ -277,22 +287,13 @@ class LlamaEngine:
             return [None] * S
         M = sum(rows)
         if M > self.max_rows:                      # engine sized for fewer stacked rows: slot by slot, max_rows at a time
-            out, step, keep = [], int(self.max_rows), self._cur
-            for b, e in enumerate(embeds):
-                if not rows[b]:
-                    out.append(None)
-                    continue
-                self.select(b)
-                parts = [self.prefill(e[i:i + step], want_hidden=want_hidden) for i in range(0, rows[b], step)]
-                out.append(None if not want_hidden else (parts[0] if len(parts) == 1 else torch.cat([p.clone() for p in parts])))
+            keep = self._cur
+            out = [_prefill_chunked(self.select(b), e, want_hidden) if rows[b] else None for b, e in enumerate(embeds)]
             self.select(keep)
             return out
         stack = live[0].contiguous() if len(live) == 1 else torch.cat(live, dim=0)
         hid = torch.empty(M, self.hidden, dtype=self.dtype, device=self.device) if want_hidden else None
-        if M > 128:
-            code, Hd, I = ops.dt(self.dtype), self.hidden, self.inter
-            for n, k in ((3 * Hd, Hd), (Hd, Hd), (2 * I, Hd), (Hd, I)):
-                tune.ensure_gemm(M, n, k, code, 0, self.device)
+        self._ensure_prefill_tiles(M)
         arr = (C.c_int64 * S)(*rows)
         check(lib().ss_llama_prefill_batch(self._h, stack.data_ptr(), arr, ops.p(hid), ops.stream()), "ss_llama_prefill_batch")
         if not want_hidden:
@@ -366,13 +367,11 @@ class LlamaEngine:
         m, rows = self._img_block_plan(remaining, forced)
         ids = torch.tensor(blk[:rows], dtype=torch.int32, device=self.device)
         emb = ops.gather_rows(self.embed, ids)
-        step = int(self.max_rows)                                   # rows per prefill call the engine was sized for
         capture = getattr(self, "_capture", None)     # getattr: tests/test_host_cpu.py binds this method onto a stand-in engine
         if capture is not None:             # the reference feeds these rows one call each: every map row is a one-row call
             self._set_capture(*capture, 1)
         try:
-            hb = torch.cat([self.prefill(emb[i:i + step], want_hidden=True).clone() for i in range(0, rows, step)]) \
-                if rows > step else self.prefill(emb, want_hidden=True)
+            hb = _prefill_chunked(self, emb, True)
         finally:
             if capture is not None:
                 self._set_capture(*capture, 0)

@@ -639,6 +639,34 @@ def test_prefill_batch_uniform_rows_one_attention_launch(golden, dtype, tol, n_s
         assert torch.equal(outs[0][1][b], outs[1][1][b])
 
 
+@pytest.mark.parametrize("dtype,first", [(torch.float32, 37), (torch.bfloat16, 37), (torch.bfloat16, 130)])
+def test_prefill_single_equals_stacked_single_segment_bitwise(golden, dtype, first):
+    """``prefill`` on the selected slot and ``prefill_batch`` with only that slot live are the same forward (one segment of
+    the stacked entry): same launches, so hidden rows, logits and the KV prefix are equal bit for bit — prompt, then a 12-row
+    continuation against the cache.  130 rows = the smallest count on the split-K projection path (128 < M <= 512)."""
+    from seedstory.llama import LlamaEngine
+    g, meta = golden
+    d = meta["LLAMA"]
+    wd = synth.llama_weights(11, d["hidden"], d["n_heads"], d["n_layers"], d["inter"], d["vocab"], dtype=dtype)
+    kw = dict(hidden=d["hidden"], n_heads=d["n_heads"], n_layers=d["n_layers"], inter=d["inter"], vocab=d["vocab"], dtype=dtype,
+              device=DEV, cache_cap=256, max_new=128, max_prefill_rows=256, img_ids=_img_ids(meta), n_seq=3)
+    emb = wd["model.embed_tokens.weight"]
+    calls = [emb[synth.randint(950, (first,), 3, 250)], emb[synth.randint(951, (12,), 3, 250)]]
+    a, b = LlamaEngine(wd, **kw), LlamaEngine(wd, **kw)
+    a.select(1)
+    ha = [a.prefill(rows, want_hidden=True) for rows in calls]
+    hb = [b.prefill_batch([None, rows, None], want_hidden=True)[1] for rows in calls]
+    n = first + 12
+    for x, y in zip(ha, hb):
+        assert x.shape == y.shape and torch.equal(x, y)
+    b.select(1)
+    assert a.lengths() == (n, n) and b.lengths() == (n, n)
+    assert torch.equal(a.logits, b.logits)
+    assert torch.equal(a.k_cache[:, :, :n], b.k_cache[:, :, :n]) and torch.equal(a.v_cache[:, :, :n], b.v_cache[:, :, :n])
+    for e in (a, b):
+        assert e.select(0).lengths() == (0, 0) and e.select(2).lengths() == (0, 0)
+
+
 class _ProcStub:
     """Carries the 66 image-token ids the way AutoImageTokenGenerationProcessor does (generation.py:17)."""
 
