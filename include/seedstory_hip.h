@@ -302,6 +302,19 @@ int ss_gemv(const void* W, const void* x, void* y, int64_t N, int64_t K, const v
 int ss_gemv_batched(const void* W, const void* x, void* y, int64_t N, int64_t K, int64_t nb,
                     const void* norm_w, float eps, const void* bias, const void* residual, int epilogue,
                     int dtype, void* stream);
+/* Host only (no GPU needed): which kernels the two calls above would launch for this shape under the current tuning knobs.
+ * One row of SS_GEMV_PLAN_COLS ints per launch, in launch order: first sequence, sequence count, form (SS_GEMV_FORM_*),
+ * NIT of the register form | k-steps per wave of the MFMA forms | 0, workgroups, threads per workgroup, dynamic LDS bytes,
+ * non-temporal weight loads (0 / 1), SiLU pair (0 / 1), refused (1: gemm_f32_split asked for the split form and this launch is
+ * an exact one instead).  has_norm: a norm_w would be passed; aligned16: W, x and norm_w are 16-byte aligned and the row stride
+ * of x is a multiple of 4 elements (what the split form needs).  rows has room for max_rows rows (SS_GEMV_PLAN_MAX always
+ * suffices).  Returns the number of launches, or a negative error code. */
+#define SS_GEMV_PLAN_COLS 10
+#define SS_GEMV_PLAN_MAX 16
+enum { SS_GEMV_FORM_REG = 0, SS_GEMV_FORM_LDSX = 1, SS_GEMV_FORM_MFMA = 2, SS_GEMV_FORM_MFMA_EXACT16 = 3,
+       SS_GEMV_FORM_MFMA_EXACT43 = 4, SS_GEMV_FORM_SPLIT_F32 = 5 };
+int ss_gemv_plan(int64_t N, int64_t K, int64_t nb, int dtype, int epilogue, int has_norm, int aligned16, int32_t* rows,
+                 int64_t max_rows);
 
 /* ---------------------------------------------------------------------------------------
  * Sampling: lm_head logits -> AutoImageTokenGenerationProcessor -> greedy argmax

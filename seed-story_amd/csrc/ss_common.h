@@ -213,7 +213,7 @@ int check_hip(hipError_t e, const char* what);
 // code object, so a process that drives several devices must set it on each — with the return code checked (a part with
 // less LDS fails here, by name, not later as a generic launch error).  `done` = the call site's static device mask (atomic: host
 // threads launch concurrently; two that race both set the attribute, which is harmless).  The attribute is set ONCE, with the first
-// caller's byte count: `bytes` must be the MAXIMUM the call site ever launches that kernel with (gemv_launch_nb, whose size varies, sets it per launch).
+// caller's byte count: `bytes` must be the MAXIMUM the call site ever launches that kernel with (gemv_run's LDS-staged kernels, whose size varies, set it per launch).
 inline int ensure_dyn_lds(const void* kern, size_t bytes, std::atomic<uint64_t>& done) {
     int dev = 0;
     int rc = check_hip(hipGetDevice(&dev), "hipGetDevice");

@@ -1,0 +1,15 @@
+// Device-pointer entry points of the decode projection (ss_gemv.hip) for the other translation units of the library.
+#pragma once
+#include "ss_common.h"
+
+namespace ss {
+
+// y[b][N] = W[N,K] . x[b][K] for nb <= 16 sequences, rows x_ld / y_ld / res_ld elements apart; done_flag: optional device flags,
+// one per sequence and done_stride ints apart: the launch is skipped when every sequence's flag is set
+int gemv_batched_dev(const void* W, const void* x, void* y, int64_t N, int64_t K, const void* norm_w, float eps,
+                     const void* bias, const void* residual, int epi, const int32_t* done_flag, int done_stride,
+                     int nb, int64_t x_ld, int64_t y_ld, int64_t res_ld, int dtype, hipStream_t s);
+int gemv_dev(const void* W, const void* x, void* y, int64_t N, int64_t K, const void* norm_w, float eps,
+             const void* bias, const void* residual, int epi, const int32_t* done_flag, int dtype, hipStream_t s);
+
+}  // namespace ss

@@ -15,8 +15,11 @@
 //     SiLU(gate)·up for the fused [gate; up] projection (LlamaMLP.forward, :190-191).
 // Reference call sites: modeling_llama_xformer.py:228-230 (q/k/v), :297 (o), :191 (MLP),
 // :759 (lm_head); LlamaRMSNorm :107-115 for the prologue.
-#include "ss_common.h"
+#include "ss_gemv.h"
 
+#include <string.h>
+#include <algorithm>
+#include <type_traits>
 #include <utility>
 
 namespace ss {
@@ -46,29 +49,103 @@ __device__ __forceinline__ bool gemv_all_done(const GemvArgs& a) {
     return true;
 }
 
-// epilogue of one finished row-group for sequence b (lane 0 of the wave)
-template <typename T, int ROWS>
-__device__ __forceinline__ void gemv_store(const GemvArgs& a, int b, int g, const float (&acc)[ROWS], bool silu) {
-    const int N = a.N;
-    T* y = (T*)a.y + (int64_t)b * a.y_ld;
-    if (silu) {
-        // gate = round(acc0), up = round(acc1); y = round(round(silu(gate)) * up)
-        const float gt = Tr<T>::rnd(acc[0]), up = Tr<T>::rnd(acc[ROWS > 1 ? 1 : 0]);
-        Tr<T>::st(y + g, Tr<T>::rnd(silu_g(gt)) * up);
+// ---- the one output epilogue -----------------------------------------------------------------------------------------------------
+// y = round(acc + bias) + residual (in T, like `residual + hidden`), or for the fused [gate; up] projection
+// y = round(round(silu(round gate)) * round up) (the store rounds once more).  bias / res are callables: an absent operand is
+// never read.  Tr<float>::rnd is the identity, so the fp32 forms share the text.
+template <typename T>
+__device__ __forceinline__ float gv_silu_pair(float g, float u) { return Tr<T>::rnd(silu_g(Tr<T>::rnd(g))) * Tr<T>::rnd(u); }
+template <typename T, typename FB, typename FR>
+__device__ __forceinline__ float gv_epilogue(float acc, FB&& bias, FR&& res, int epi) {
+    if (epi & SS_EPI_BIAS) acc += bias();
+    acc = Tr<T>::rnd(acc);
+    if (epi & SS_EPI_RESIDUAL) acc += res();
+    return acc;
+}
+// rows row0 .. row0 + 3 of sequence seq: ONE 8- / 16-byte store when the four rows exist and row stride, row0 and the base of y
+// are aligned to it (an `out=` view at an odd element offset takes the scalar stores)
+template <typename T>
+__device__ __forceinline__ void gv_store4(const GemvArgs& a, int seq, int row0, const float (&o)[4]) {
+    using V4 = std::conditional_t<sizeof(T) == 4, uint4, uint2>;
+    T* y = (T*)a.y + (int64_t)seq * a.y_ld;
+    if (row0 + 3 < a.N && ((a.y_ld | row0) & 3) == 0 && ((size_t)a.y & (sizeof(V4) - 1)) == 0) {
+        alignas(16) T tmp[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) Tr<T>::st(tmp + r, o[r]);
+        *reinterpret_cast<V4*>(y + row0) = *reinterpret_cast<const V4*>(tmp);
     } else {
 #pragma unroll
-        for (int r = 0; r < ROWS; ++r) {
-            const int64_t row = (int64_t)g * ROWS + r;
-            if (row >= N) continue;
-            float v = acc[r];
-            if (a.epi & SS_EPI_BIAS) v += Tr<T>::ld((const T*)a.bias + row);
-            v = Tr<T>::rnd(v);
-            if (a.epi & SS_EPI_RESIDUAL) v += Tr<T>::ld((const T*)a.residual + (int64_t)b * a.res_ld + row);
-            Tr<T>::st(y + row, v);
+        for (int r = 0; r < 4; ++r)
+            if (row0 + r < a.N) Tr<T>::st(y + row0 + r, o[r]);
+    }
+}
+
+// ---- the one RMSNorm prologue (LlamaRMSNorm: gw * round(x * rstd), statistic in fp32), per 16-byte pack ----------------------------
+template <typename T>
+__device__ __forceinline__ float gv_pack_ssq(const uint4& x, float ssq) {
+    constexpr int V = Tr<T>::kVec;
+    float f[V];
+    unpack<T>(x, f);
+#pragma unroll
+    for (int j = 0; j < V; ++j) ssq = fmaf(f[j], f[j], ssq);
+    return ssq;
+}
+__device__ __forceinline__ float gv_rstd(float ssq, int K, float eps) { return 1.0f / sqrtf(ssq / (float)K + eps); }
+template <typename T>
+__device__ __forceinline__ uint4 gv_pack_norm(const uint4& x, const uint4& gain, float rstd) {
+    constexpr int V = Tr<T>::kVec;
+    float f[V], gw[V];
+    unpack<T>(x, f);
+    unpack<T>(gain, gw);
+#pragma unroll
+    for (int j = 0; j < V; ++j) f[j] = gw[j] * Tr<T>::rnd(f[j] * rstd);
+    return pack<T>(f);
+}
+
+// ---- row groups of the dot-product kernels: what a wave owns per trip ---------------------------------------------------------------
+// silu -> N groups, each the pair (n, n + N) of W;  else ROWS consecutive rows.
+template <int ROWS>
+struct GvRowGroups {
+    int N; bool silu;
+    __device__ __forceinline__ int count() const { return silu ? N : (N + ROWS - 1) / ROWS; }
+    __device__ __forceinline__ int64_t row(int g, int r) const { return silu ? (int64_t)g + (int64_t)r * N : (int64_t)g * ROWS + r; }
+    __device__ __forceinline__ bool valid(int64_t row) const { return silu || row < N; }
+};
+// a pack of weights (row / pack out of range: zeros)
+template <typename T>
+__device__ __forceinline__ uint4 gv_load_w(const T* p, bool ok, int nt) {
+    if (!ok) return make_uint4(0, 0, 0, 0);
+    return nt ? ld_nt16(p) : ld16(p);
+}
+// lane sums of a finished group -> wave sums -> epilogue and store by lane 0
+template <typename T, int ROWS, int NB>
+__device__ __forceinline__ void gv_reduce_store(const GemvArgs& a, const GvRowGroups<ROWS>& rg, int g, float (&acc)[NB][ROWS], int lane) {
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+#pragma unroll
+        for (int r = 0; r < ROWS; ++r) acc[b][r] = wave_sum(acc[b][r]);
+        if (lane != 0) continue;
+        T* y = (T*)a.y + (int64_t)b * a.y_ld;
+        if (rg.silu) {
+            Tr<T>::st(y + g, gv_silu_pair<T>(acc[b][0], acc[b][ROWS > 1 ? 1 : 0]));
+        } else {
+#pragma unroll
+            for (int r = 0; r < ROWS; ++r) {
+                const int64_t row = rg.row(g, r);
+                if (row >= a.N) continue;
+                Tr<T>::st(y + row, gv_epilogue<T>(acc[b][r], [&] { return Tr<T>::ld((const T*)a.bias + row); },
+                                                  [&] { return Tr<T>::ld((const T*)a.residual + (int64_t)b * a.res_ld + row); }, a.epi));
+            }
         }
     }
 }
 
+// LDS staging of gemv_ldsx_kernel (kernel and launch plan): nb rows of K / V packs, padded to whole chunks of 8 x 64 packs
+struct GvLdsxStage {
+    int npack, nchunk, npack_pad;
+    __host__ __device__ GvLdsxStage(int K, int V) : npack(K / V), nchunk((npack + 511) / 512), npack_pad(nchunk * 512) {}
+    __host__ __device__ size_t bytes(int nb) const { return (size_t)nb * npack_pad * 16; }
+};
 // NB = sequences sharing one sweep of W (the decode batch: every weight pack is dotted with NB
 // resident x slices, so the HBM traffic per generated token falls as 1/NB).
 template <typename T, int NIT, int ROWS, int NB>
@@ -81,24 +158,16 @@ __global__ __launch_bounds__(256) void gemv_kernel(const GemvArgs a) {
     const T* __restrict__ W = (const T*)a.W;
     const int K = a.K, N = a.N;
     const bool silu = (a.epi & SS_EPI_SILU_MUL) != 0;
-
-    // logical rows: silu -> N rows, each the pair (n, n+N) of W;  else ROWS consecutive rows.
-    const int ngroups = silu ? N : (N + ROWS - 1) / ROWS;
-    auto row_of = [&](int g, int r) -> int64_t { return silu ? (int64_t)g + (int64_t)r * N : (int64_t)g * ROWS + r; };
+    const GvRowGroups<ROWS> rg{N, silu};
     auto load_group = [&](int g, uint4 (&wv)[ROWS][NIT]) {
 #pragma unroll
         for (int r = 0; r < ROWS; ++r) {
-            const int64_t row = row_of(g, r);
-            const bool ok = silu || row < N;
+            const int64_t row = rg.row(g, r);
+            const bool ok = rg.valid(row);
 #pragma unroll
             for (int it = 0; it < NIT; ++it) {
                 const int k = (it * 64 + lane) * V;
-                if (ok && k < K) {
-                    const T* p = W + row * K + k;
-                    wv[r][it] = a.use_nt ? ld_nt16(p) : ld16(p);
-                } else {
-                    wv[r][it] = make_uint4(0, 0, 0, 0);
-                }
+                wv[r][it] = gv_load_w<T>(W + row * K + k, ok && k < K, a.use_nt);
             }
         }
     };
@@ -141,36 +210,17 @@ __global__ __launch_bounds__(256) void gemv_kernel(const GemvArgs a) {
         for (int b = 0; b < NB; ++b) {
             float ssq = 0.f;
 #pragma unroll
-            for (int it = 0; it < NIT; ++it) {
-                float f[V];
-                unpack<T>(xr[b][it], f);
-#pragma unroll
-                for (int j = 0; j < V; ++j) ssq = fmaf(f[j], f[j], ssq);
-            }
-            ssq = wave_sum(ssq);
-            const float rstd = 1.0f / sqrtf(ssq / (float)K + a.eps);
+            for (int it = 0; it < NIT; ++it) ssq = gv_pack_ssq<T>(xr[b][it], ssq);
+            const float rstd = gv_rstd(wave_sum(ssq), K, a.eps);
             if constexpr (COOP) {
 #pragma unroll
-                for (int j4 = 0; j4 < NQ; ++j4) {
-                    float f[V], gw[V];
-                    unpack<T>(xq[b][j4], f);
-                    unpack<T>(gq[j4], gw);
-#pragma unroll
-                    for (int j = 0; j < V; ++j) f[j] = gw[j] * Tr<T>::rnd(f[j] * rstd);
-                    xn_s[(b * NIT + wid * NQ + j4) * 64 + lane] = pack<T>(f);   // k >= K packs are zeros already
-                }
+                for (int j4 = 0; j4 < NQ; ++j4)      // k >= K packs are zeros already
+                    xn_s[(b * NIT + wid * NQ + j4) * 64 + lane] = gv_pack_norm<T>(xq[b][j4], gq[j4], rstd);
             } else {
 #pragma unroll
                 for (int it = 0; it < NIT; ++it) {
                     const int k = (it * 64 + lane) * V;
-                    if (k < K) {
-                        float f[V], gw[V];
-                        unpack<T>(xr[b][it], f);
-                        unpack<T>(ld16((const T*)a.norm_w + k), gw);
-#pragma unroll
-                        for (int j = 0; j < V; ++j) f[j] = gw[j] * Tr<T>::rnd(f[j] * rstd);
-                        xr[b][it] = pack<T>(f);
-                    }
+                    if (k < K) xr[b][it] = gv_pack_norm<T>(xr[b][it], ld16((const T*)a.norm_w + k), rstd);
                 }
             }
         }
@@ -188,7 +238,7 @@ __global__ __launch_bounds__(256) void gemv_kernel(const GemvArgs a) {
     // (requesting the first group's weights before the prologue was measured: the 64 extra live VGPRs
     // cost two waves/SIMD of occupancy and more than the overlap gains)
     uint4 wv[ROWS][NIT];
-    for (int g = wave; g < ngroups; g += nwaves) {
+    for (int g = wave; g < rg.count(); g += nwaves) {
         load_group(g, wv);
         float acc[NB][ROWS];
 #pragma unroll
@@ -201,12 +251,7 @@ __global__ __launch_bounds__(256) void gemv_kernel(const GemvArgs a) {
             for (int r = 0; r < ROWS; ++r)
 #pragma unroll
                 for (int b = 0; b < NB; ++b) acc[b][r] = dot_pack<T>(wv[r][it], xr[b][it], acc[b][r]);
-#pragma unroll
-        for (int b = 0; b < NB; ++b) {
-#pragma unroll
-            for (int r = 0; r < ROWS; ++r) acc[b][r] = wave_sum(acc[b][r]);
-            if (lane == 0) gemv_store<T, ROWS>(a, b, g, acc[b], silu);
-        }
+        gv_reduce_store<T, ROWS, NB>(a, rg, g, acc, lane);
     }
 }
 
@@ -227,26 +272,18 @@ __global__ __launch_bounds__(1024) void gemv_ldsx_kernel(const GemvArgs a) {
     const T* __restrict__ W = (const T*)a.W;
     const int K = a.K, N = a.N;
     const bool silu = (a.epi & SS_EPI_SILU_MUL) != 0;
-    const int npack = K / V;
-    const int nchunk = (npack + 511) / 512;  // chunks of 8 wave-iterations
-    const int npack_pad = nchunk * 512;
-
-    const int ngroups = silu ? N : (N + ROWS - 1) / ROWS;
-    auto row_of = [&](int g, int r) -> int64_t { return silu ? (int64_t)g + (int64_t)r * N : (int64_t)g * ROWS + r; };
+    const GvLdsxStage st(K, V);
+    const int npack = st.npack, nchunk = st.nchunk, npack_pad = st.npack_pad;
+    const GvRowGroups<ROWS> rg{N, silu};
     auto load_tile = [&](int g, int c, uint4 (&wv)[ROWS][8]) {
 #pragma unroll
         for (int r = 0; r < ROWS; ++r) {
-            const int64_t row = row_of(g, r);
-            const bool ok = silu || row < N;
+            const int64_t row = rg.row(g, r);
+            const bool ok = rg.valid(row);
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 const int p = (c * 8 + i) * 64 + lane;
-                if (ok && p < npack) {
-                    const T* ptr = W + row * K + (int64_t)p * V;
-                    wv[r][i] = a.use_nt ? ld_nt16(ptr) : ld16(ptr);
-                } else {
-                    wv[r][i] = make_uint4(0, 0, 0, 0);
-                }
+                wv[r][i] = gv_load_w<T>(W + row * K + (int64_t)p * V, ok && p < npack, a.use_nt);
             }
         }
     };
@@ -263,12 +300,7 @@ __global__ __launch_bounds__(1024) void gemv_ldsx_kernel(const GemvArgs a) {
 #pragma unroll
         for (int b = 0; b < NB; ++b) {
             const uint4 v = ok ? ld16((const T*)a.x + (int64_t)b * a.x_ld + (int64_t)p * V) : make_uint4(0, 0, 0, 0);
-            if (a.norm_w) {
-                float f[V];
-                unpack<T>(v, f);
-#pragma unroll
-                for (int j = 0; j < V; ++j) ssq[b] = fmaf(f[j], f[j], ssq[b]);
-            }
+            if (a.norm_w) ssq[b] = gv_pack_ssq<T>(v, ssq[b]);
             xs[(size_t)b * npack_pad + p] = v;
         }
     }
@@ -287,25 +319,18 @@ __global__ __launch_bounds__(1024) void gemv_ldsx_kernel(const GemvArgs a) {
         for (int b = 0; b < NB; ++b) {
             float t = 0.f;
             for (int w = 0; w < wpb; ++w) t += red[b][w];
-            rstd[b] = 1.0f / sqrtf(t / (float)K + a.eps);
+            rstd[b] = gv_rstd(t, K, a.eps);
         }
         for (int p = threadIdx.x; p < npack; p += blockDim.x) {
-            float gw[V];
-            unpack<T>(ld16((const T*)a.norm_w + (int64_t)p * V), gw);
+            const uint4 gw = ld16((const T*)a.norm_w + (int64_t)p * V);
 #pragma unroll
-            for (int b = 0; b < NB; ++b) {
-                float f[V];
-                unpack<T>(xs[(size_t)b * npack_pad + p], f);
-#pragma unroll
-                for (int j = 0; j < V; ++j) f[j] = gw[j] * Tr<T>::rnd(f[j] * rstd[b]);
-                xs[(size_t)b * npack_pad + p] = pack<T>(f);
-            }
+            for (int b = 0; b < NB; ++b) xs[(size_t)b * npack_pad + p] = gv_pack_norm<T>(xs[(size_t)b * npack_pad + p], gw, rstd[b]);
         }
     }
     __syncthreads();
 
     uint4 wv[ROWS][8];
-    for (int g = wave; g < ngroups; g += nwaves) {
+    for (int g = wave; g < rg.count(); g += nwaves) {
         float acc[NB][ROWS];
 #pragma unroll
         for (int b = 0; b < NB; ++b)
@@ -323,12 +348,7 @@ __global__ __launch_bounds__(1024) void gemv_ldsx_kernel(const GemvArgs a) {
                 }
             }
         }
-#pragma unroll
-        for (int b = 0; b < NB; ++b) {
-#pragma unroll
-            for (int r = 0; r < ROWS; ++r) acc[b][r] = wave_sum(acc[b][r]);
-            if (lane == 0) gemv_store<T, ROWS>(a, b, g, acc[b], silu);
-        }
+        gv_reduce_store<T, ROWS, NB>(a, rg, g, acc, lane);
     }
 }
 
@@ -346,7 +366,7 @@ __global__ __launch_bounds__(1024) void gemv_ldsx_kernel(const GemvArgs a) {
 //     requested before the MFMAs of the current one (two register buffers of 8 steps), also across tile boundaries
 //     and across the barrier: 8 - 16 KB per wave stay in flight the whole launch;
 //   * per tile the 8 partial accumulators meet in LDS (double-buffered: one barrier per tile) and wave 0 applies the
-//     epilogue of gemv_store (bias, rounding, residual | SiLU(gate) * up with the [gate; up] rows as two MFMA chains).
+//     epilogue (gv_epilogue: bias, rounding, residual | gv_silu_pair with the [gate; up] rows as two MFMA chains).
 template <int N, typename F, int... I>
 __device__ __forceinline__ void gv_static_for_impl(F&& f, std::integer_sequence<int, I...>) {
     (f(std::integral_constant<int, I>{}), ...);
@@ -364,8 +384,8 @@ template <> __device__ __forceinline__ f32x4_t gv_mfma<f16_t>(const uint4& a, co
 
 constexpr int kGvWaves = 8, kGvSteps = 16, kGvChunk = 8;
 
-// the 8 waves' partial accumulators of one row tile -> LDS -> (barrier) -> wave 0 folds them in wave order and applies the
-// epilogue of gemv_store.  `part` = [8 waves][M][256] floats of this tile's parity.
+// The 8 waves' partial accumulators of one row tile meet in LDS (`part` = [8 waves][M][256] floats), wave 0 folds them in wave
+// order and applies the epilogue.
 // The epilogue's residual / bias values of wave 0 are requested at the TOP of the tile (gv_epi_prefetch), ahead of the weight
 // loads: a load issued in the epilogue itself would have to be waited for with every younger weight prefetch in front of
 // it (vmcnt is in-order), which stalls wave 0 — and through the next barrier the whole workgroup — once per tile.
@@ -396,57 +416,69 @@ template <typename T> __device__ __forceinline__ float gv_elem(const uint2& v, i
     return Tr<T>::ld(&t);
 }
 
-template <typename T, bool SILU>
-__device__ __forceinline__ void gv_fold_store(const GemvArgs& a, float* part, const f32x4_t (&acc)[SILU ? 2 : 1], int tile,
-                                              int wave, int lane, const GvEpi& epi) {
-    constexpr int M = SILU ? 2 : 1;
-    const int i = lane & 15, q = lane >> 4;
-    const int N = a.N;
+template <int M>
+__device__ __forceinline__ void gv_write_partials(float* part, const f32x4_t (&acc)[M], int wave, int lane) {
 #pragma unroll
     for (int m = 0; m < M; ++m) *reinterpret_cast<f32x4_t*>(part + (wave * M + m) * 256 + lane * 4) = acc[m];
-    __syncthreads();
-    if (wave != 0) return;
-    f32x4_t v[M];
+}
+template <int M>
+__device__ __forceinline__ void gv_fold(const float* part, int lane, f32x4_t (&v)[M]) {
 #pragma unroll
     for (int m = 0; m < M; ++m) {
         v[m] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int w = 0; w < kGvWaves; ++w) v[m] += *reinterpret_cast<const f32x4_t*>(part + (w * M + m) * 256 + lane * 4);
     }
-    const int row0 = tile * 16 + q * 4;                       // D[row 4q + r][sequence i]
+}
+// epilogue + store of a folded tile: lane l holds D[row 4q + r][sequence i], i = l & 15, q = l >> 4
+template <typename T, bool SILU>
+__device__ __forceinline__ void gv_tile_store(const GemvArgs& a, const f32x4_t (&v)[SILU ? 2 : 1], int tile, int lane, const GvEpi& epi) {
+    constexpr int M = SILU ? 2 : 1;
+    const int i = lane & 15, q = lane >> 4;
+    const int N = a.N;
+    const int row0 = tile * 16 + q * 4;
     if (i >= a.nb || row0 >= N) return;
-    T* y = (T*)a.y + (int64_t)i * a.y_ld;
     float o[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int row = row0 + r < N ? row0 + r : N - 1;
         if constexpr (SILU) {
-            const float gt = Tr<T>::rnd(v[0][r]), up = Tr<T>::rnd(v[M - 1][r]);
-            o[r] = Tr<T>::rnd(silu_g(gt)) * up;
+            o[r] = gv_silu_pair<T>(v[0][r], v[M - 1][r]);
         } else {
-            float t = v[0][r];
-            if (epi.vec) {
-                if (a.epi & SS_EPI_BIAS) t += gv_elem<T>(epi.bias, r);
-                t = Tr<T>::rnd(t);
-                if (a.epi & SS_EPI_RESIDUAL) t += gv_elem<T>(epi.res, r);
-            } else {
-                if (a.epi & SS_EPI_BIAS) t += Tr<T>::ld((const T*)a.bias + row);
-                t = Tr<T>::rnd(t);
-                if (a.epi & SS_EPI_RESIDUAL) t += Tr<T>::ld((const T*)a.residual + (int64_t)i * a.res_ld + row);
+            if constexpr (sizeof(T) == 2) {
+                if (epi.vec) {
+                    o[r] = gv_epilogue<T>(v[0][r], [&] { return gv_elem<T>(epi.bias, r); }, [&] { return gv_elem<T>(epi.res, r); }, a.epi);
+                    continue;
+                }
             }
-            o[r] = t;
+            o[r] = gv_epilogue<T>(v[0][r], [&] { return Tr<T>::ld((const T*)a.bias + row); },
+                                  [&] { return Tr<T>::ld((const T*)a.residual + (int64_t)i * a.res_ld + row); }, a.epi);
         }
     }
-    if (row0 + 3 < N && ((a.y_ld | row0) & 3) == 0) {
-        T tmp[4];
+    gv_store4<T>(a, i, row0, o);
+}
+template <typename T, bool SILU>
+__device__ __forceinline__ void gv_fold_store(const GemvArgs& a, float* part, const f32x4_t (&acc)[SILU ? 2 : 1], int tile,
+                                              int wave, int lane, const GvEpi& epi) {
+    gv_write_partials(part, acc, wave, lane);
+    __syncthreads();
+    if (wave != 0) return;
+    f32x4_t v[SILU ? 2 : 1];
+    gv_fold(part, lane, v);
+    gv_tile_store<T, SILU>(a, v, tile, lane, epi);
+}
+
+// RMSNorm statistic of the MFMA forms: a lane's sum over its k-chunks -> the four k-chunk lanes of a sequence -> the 8 waves in
+// wave order (through red[8][16]; one barrier)
+__device__ __forceinline__ float gv_rstd_across_waves(float ssq, float (*red)[16], int wave, int lane, int K, float eps) {
+    ssq += __shfl_xor(ssq, 16, 64);
+    ssq += __shfl_xor(ssq, 32, 64);
+    if (lane < 16) red[wave][lane] = ssq;
+    __syncthreads();
+    float tot = 0.f;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) Tr<T>::st(tmp + r, o[r]);
-        *reinterpret_cast<uint2*>(y + row0) = *reinterpret_cast<const uint2*>(tmp);
-    } else {
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-            if (row0 + r < N) Tr<T>::st(y + row0 + r, o[r]);
-    }
+    for (int w = 0; w < kGvWaves; ++w) tot += red[w][lane & 15];
+    return gv_rstd(tot, K, eps);
 }
 
 // any K <= 4096 (multiple of 8), any N: predicated loads — correct for every shape, with the prefetch serialised by the
@@ -476,32 +508,12 @@ __global__ __launch_bounds__(512) void gemv_mfma_kernel(const GemvArgs a, const 
         });
         if (a.norm_w) {
             float ssq = 0.f;
-            gv_static_for<NS>([&](auto s_) {
-                constexpr int s = decltype(s_)::value;
-                float f[8];
-                unpack<T>(xf[s], f);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) ssq = fmaf(f[j], f[j], ssq);
-            });
-            ssq += __shfl_xor(ssq, 16, 64);
-            ssq += __shfl_xor(ssq, 32, 64);
-            if (lane < 16) red[wave][lane] = ssq;
-            __syncthreads();
-            float tot = 0.f;
-#pragma unroll
-            for (int w = 0; w < kGvWaves; ++w) tot += red[w][i];
-            const float rstd = 1.0f / sqrtf(tot / (float)K + a.eps);
+            gv_static_for<NS>([&](auto s_) { ssq = gv_pack_ssq<T>(xf[decltype(s_)::value], ssq); });
+            const float rstd = gv_rstd_across_waves(ssq, red, wave, lane, K, a.eps);
             const T* gw = (const T*)a.norm_w + k0;
             gv_static_for<NS>([&](auto s_) {
                 constexpr int s = decltype(s_)::value;
-                if (s < nvalid) {
-                    float f[8], g[8];
-                    unpack<T>(xf[s], f);
-                    unpack<T>(ld16(gw + s * 32), g);
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) f[j] = g[j] * Tr<T>::rnd(f[j] * rstd);
-                    xf[s] = pack<T>(f);
-                }
+                if (s < nvalid) xf[s] = gv_pack_norm<T>(xf[s], ld16(gw + s * 32), rstd);
             });
         }
     }
@@ -595,27 +607,11 @@ __global__ __launch_bounds__(512) void gemv_mfma_exact_kernel(const GemvArgs a, 
         __builtin_amdgcn_sched_barrier(0);
         if (a.norm_w) {
             float ssq = 0.f;
-            gv_static_for<HALF>([&](auto s_) {
-                constexpr int s = decltype(s_)::value;
-                float f[8];
-                unpack<T>(xf[s], f);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) ssq = fmaf(f[j], f[j], ssq);
-            });
+            gv_static_for<HALF>([&](auto s_) { ssq = gv_pack_ssq<T>(xf[decltype(s_)::value], ssq); });
             // (the fragments are unpacked AGAIN below: without this fence hipcc keeps the 128 unpacked floats alive across
             // the barrier and spills)
-            gv_static_for<HALF>([&](auto s_) {
-                constexpr int s = decltype(s_)::value;
-                gv_fence(xf[s]);
-            });
-            ssq += __shfl_xor(ssq, 16, 64);
-            ssq += __shfl_xor(ssq, 32, 64);
-            if (lane < 16) red[wave][lane] = ssq;
-            __syncthreads();
-            float tot = 0.f;
-#pragma unroll
-            for (int w = 0; w < kGvWaves; ++w) tot += red[w][i];
-            const float rstd = 1.0f / sqrtf(tot / (float)K + a.eps);
+            gv_static_for<HALF>([&](auto s_) { gv_fence(xf[decltype(s_)::value]); });
+            const float rstd = gv_rstd_across_waves(ssq, red, wave, lane, K, a.eps);
             const T* gw = (const T*)a.norm_w + k0;
             // the gain in two batches of 8 fragments (32 VGPRs in flight, not 64: with the activations and the first weights
             // resident the single batch spills)
@@ -625,12 +621,7 @@ __global__ __launch_bounds__(512) void gemv_mfma_exact_kernel(const GemvArgs a, 
                 gv_static_for<HALF / 2>([&](auto s_) { constexpr int s = decltype(s_)::value; gf[s] = ld16(gw + (h * (HALF / 2) + s) * 32); });
                 gv_static_for<HALF / 2>([&](auto s_) {
                     constexpr int s = decltype(s_)::value, t = h * (HALF / 2) + s;
-                    float f[8], g[8];
-                    unpack<T>(xf[t], f);
-                    unpack<T>(gf[s], g);
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) f[j] = g[j] * Tr<T>::rnd(f[j] * rstd);
-                    xf[t] = pack<T>(f);
+                    xf[t] = gv_pack_norm<T>(xf[t], gf[s], rstd);
                 });
                 __builtin_amdgcn_sched_barrier(0);
             });
@@ -704,6 +695,20 @@ __global__ __launch_bounds__(512) void gemv_mfma_exact_kernel(const GemvArgs a, 
 //     write of y (the first version ran three launches: 70 us against ~48 for the same bytes);
 //   * persistent workgroups of 8 waves = 8 K ranges of a 16-row tile; partial sums meet in LDS, wave 0 applies the epilogue.
 constexpr int kGsSlice = 4096;
+
+// LDS of gemv_split_f32_kernel (kernel and launch plan): two bf16 planes of 8 sequences, SS bytes apart, then ONE buffer of partial sums
+// (a second one would push the SiLU instantiation past the 160 KB of a CU: the kernel pays a barrier per tile instead)
+struct GvSplitLds {
+    int SS, xl, part, bytes;
+    __host__ __device__ GvSplitLds(int K, bool silu) {
+        const int kmax = K < kGsSlice ? K : kGsSlice;
+        SS = kmax * 2 + 32;                                  // bytes between sequences of a plane
+        xl = 8 * SS;
+        part = 16 * SS;                                      // [8 waves][M][256] floats
+        bytes = part + kGvWaves * (silu ? 2 : 1) * 256 * (int)sizeof(float);
+    }
+};
+
 template <bool SILU>
 __global__ __launch_bounds__(512) void gemv_split_f32_kernel(const GemvArgs a, const int ntiles) {
     constexpr int CH = 4, NCH = kGvSteps / CH, M = SILU ? 2 : 1;
@@ -712,12 +717,12 @@ __global__ __launch_bounds__(512) void gemv_split_f32_kernel(const GemvArgs a, c
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int i = lane & 15, q = lane >> 4;
     const int K = a.K, N = a.N, nb = a.nb;
-    const int kmax = K < kGsSlice ? K : kGsSlice;
-    const int SS = kmax * 2 + 32;                            // bytes between sequences of a plane
+    const GvSplitLds lds(K, SILU);
+    const int SS = lds.SS;
     const int nslices = (K + kGsSlice - 1) / kGsSlice;       // K > 4096 (the 11008-deep down projection): slices walked INSIDE the tile
     char* xh = gs_smem;
-    char* xl = gs_smem + 8 * SS;
-    float* part = reinterpret_cast<float*>(gs_smem + 16 * SS);   // [8 waves][M][256]
+    char* xl = gs_smem + lds.xl;
+    float* part = reinterpret_cast<float*>(gs_smem + lds.part);
     const float* __restrict__ W = (const float*)a.W;
 
     // ---- the activations of K slice [kbase, kbase + kslice) -> the two bf16 planes: wave w <-> sequence w -----------------
@@ -728,13 +733,10 @@ __global__ __launch_bounds__(512) void gemv_split_f32_kernel(const GemvArgs a, c
         const float* xr = (const float*)a.x + (int64_t)(live ? wave : 0) * a.x_ld;
         if (norm) {
             float ssq = 0.f;
-            for (int k = lane * 4; k < K; k += 256) {
-                const float4 v = *reinterpret_cast<const float4*>(xr + k);
-                ssq = fmaf(v.x, v.x, ssq); ssq = fmaf(v.y, v.y, ssq); ssq = fmaf(v.z, v.z, ssq); ssq = fmaf(v.w, v.w, ssq);
-            }
+            for (int k = lane * 4; k < K; k += 256) ssq = gv_pack_ssq<float>(ld16(xr + k), ssq);
 #pragma unroll
             for (int off = 1; off < 64; off <<= 1) ssq += __shfl_xor(ssq, off, 64);
-            rstd = 1.0f / sqrtf(ssq / (float)K + a.eps);
+            rstd = gv_rstd(ssq, K, a.eps);
         }
     }
     auto stage = [&](int kbase, int kslice) {
@@ -742,11 +744,9 @@ __global__ __launch_bounds__(512) void gemv_split_f32_kernel(const GemvArgs a, c
         const bool live = seq < nb;
         const float* xr = (const float*)a.x + (int64_t)(live ? seq : 0) * a.x_ld;
         for (int k = lane * 4; k < kslice; k += 256) {
-            float4 v = live ? *reinterpret_cast<const float4*>(xr + kbase + k) : make_float4(0.f, 0.f, 0.f, 0.f);
-            if (norm) {
-                const float4 gw = *reinterpret_cast<const float4*>((const float*)a.norm_w + kbase + k);
-                v.x = gw.x * (v.x * rstd); v.y = gw.y * (v.y * rstd); v.z = gw.z * (v.z * rstd); v.w = gw.w * (v.w * rstd);
-            }
+            uint4 u = live ? ld16(xr + kbase + k) : make_uint4(0, 0, 0, 0);
+            if (norm) u = gv_pack_norm<float>(u, ld16((const float*)a.norm_w + kbase + k), rstd);
+            const float4 v = make_float4(__uint_as_float(u.x), __uint_as_float(u.y), __uint_as_float(u.z), __uint_as_float(u.w));
             const uint32_t h01 = f32x2_to_bf16x2_bits(v.x, v.y), h23 = f32x2_to_bf16x2_bits(v.z, v.w);
             const float r0 = v.x - __uint_as_float(h01 << 16), r1 = v.y - __uint_as_float(h01 & 0xffff0000u);
             const float r2 = v.z - __uint_as_float(h23 << 16), r3 = v.w - __uint_as_float(h23 & 0xffff0000u);
@@ -887,203 +887,194 @@ __global__ __launch_bounds__(512) void gemv_split_f32_kernel(const GemvArgs a, c
     }
 }
 
-// MFMA forms, whole rounds: ceil(tiles / 256) tiles per workgroup on as few workgroups as that takes (688 tiles -> 230 x 3, not 256
-// workgroups of which 80 run a third round alone)
-static int gemv_mfma_grid(int ntiles) {
-    const int rounds = cdiv(ntiles, knob(K_gemv_mfma_blocks));
-    return cdiv(ntiles, rounds);
-}
+// ---- launch plan ----------------------------------------------------------------------------------------------------------------------
+// Which kernels serve a call is decided by gemv_plan, a pure function of the shape, the dtype, the epilogue and the tuning knobs (no
+// HIP call: ss_gemv_plan exposes it to machines without a GPU); gemv_run is the only code that launches.
+// one launch = one sweep of W for the sequences [seq0, seq0 + nseq); the row layout of ss_gemv_plan
+struct GemvLaunch {
+    int seq0, nseq;
+    int form;                   // SS_GEMV_FORM_*
+    int param;                  // SS_GEMV_FORM_REG: NIT (16-byte packs of x per lane); MFMA forms: steps of 32 k per wave; else 0
+    int blocks, threads, lds;   // workgroups, workgroup size, dynamic LDS bytes
+    int nt, silu;               // non-temporal weight loads; the SiLU(gate) * up pair
+    int refused;                // the gate mode was asked for and this sweep runs an exact form instead
+};
+static_assert(sizeof(GemvLaunch) == SS_GEMV_PLAN_COLS * sizeof(int32_t), "ss_gemv_plan row layout");
+struct GemvPlan { int n = 0; GemvLaunch l[SS_GEMV_PLAN_MAX]; };   // worst case: 16 sequences whose staged rows fit the LDS one at a time
+constexpr size_t kGvLdsxMaxBytes = 152 * 1024;          // LDS-staged activations of one sweep
 
-static int gemv_launch_split_f32(const GemvArgs& a, hipStream_t s) {
-    const bool silu = (a.epi & SS_EPI_SILU_MUL) != 0;
-    const int ntiles = cdiv(a.N, 16);
-    const int blocks = gemv_mfma_grid(ntiles);
-    const int kmax = a.K < kGsSlice ? a.K : kGsSlice;
-    const size_t lds = (size_t)16 * (kmax * 2 + 32) + (size_t)kGvWaves * (silu ? 2 : 1) * 256 * sizeof(float);
-    auto kern = silu ? gemv_split_f32_kernel<true> : gemv_split_f32_kernel<false>;
-    // (the largest request of either instantiation: a full 4096-wide slice, SiLU pair)
-    const size_t lds_max = (size_t)16 * (kGsSlice * 2 + 32) + (size_t)kGvWaves * 2 * 256 * sizeof(float);
-    if (silu) SS_DYN_LDS(gemv_split_f32_kernel<true>, lds_max); else SS_DYN_LDS(gemv_split_f32_kernel<false>, lds_max);
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(512), lds, s, a, ntiles);
-    SS_LAUNCH_CHECK("gemv_split_f32");
-    return SS_OK;
-}
-
-template <typename T>
-static bool gemv_mfma_eligible(const GemvArgs& a) {
-    if (a.K <= kGvWaves * kGvSteps * 32) return true;
-    // the packed 43-step form: the LLaMA-7B MLP width only, <= 8 sequences, no RMSNorm prologue
-    return a.K == kGvWaves * 43 * 32 && a.nb <= 8 && !a.norm_w && !knob(K_gemv_mfma_generic) && knob(K_gemv_mfma_long);
-}
-
-template <typename T>
-static int gemv_launch_mfma(const GemvArgs& a, hipStream_t s) {
-    const bool silu = (a.epi & SS_EPI_SILU_MUL) != 0;
-    const int ksteps = cdiv(a.K, 32);
-    const int spw = cdiv(ksteps, kGvWaves);
-    const int ntiles = cdiv(a.N, 16);
-    const int blocks = gemv_mfma_grid(ntiles);
-    const bool generic = knob(K_gemv_mfma_generic) != 0;
-    // plain loads, not non-temporal ones: a fragment load touches HALF a 128-byte line per row and the next instruction the
-    // other half; measured on the five LLaMA-7B shapes at 8 sequences, nt is 3 - 13 % slower (lm_head 52.0 vs 46.2 us)
-    const bool nt = knob(K_gemv_mfma_nt) != 0;
-    const dim3 g((unsigned)blocks), b(512);
-#define SS_GV_EXACT(SPW)                                                                                                  \
-    do {                                                                                                                  \
-        if (silu) { if (nt) hipLaunchKernelGGL((gemv_mfma_exact_kernel<T, true, SPW, true>), g, b, 0, s, a, ntiles);      \
-                    else hipLaunchKernelGGL((gemv_mfma_exact_kernel<T, true, SPW, false>), g, b, 0, s, a, ntiles); }       \
-        else { if (nt) hipLaunchKernelGGL((gemv_mfma_exact_kernel<T, false, SPW, true>), g, b, 0, s, a, ntiles);          \
-               else hipLaunchKernelGGL((gemv_mfma_exact_kernel<T, false, SPW, false>), g, b, 0, s, a, ntiles); }           \
-    } while (0)
-    if (!generic && a.K == kGvWaves * kGvSteps * 32) SS_GV_EXACT(16);
-    else if (!generic && a.K == kGvWaves * 43 * 32) {
-        SS_GV_EXACT(43);
-    }
-    else if (silu) hipLaunchKernelGGL((gemv_mfma_kernel<T, true>), g, b, 0, s, a, spw, ntiles);
-    else hipLaunchKernelGGL((gemv_mfma_kernel<T, false>), g, b, 0, s, a, spw, ntiles);
-#undef SS_GV_EXACT
-    SS_LAUNCH_CHECK("gemv_mfma");
-    return SS_OK;
-}
-
-template <typename T, int NIT, int NB>
-static int gemv_launch_reg(const GemvArgs& a, int blocks, hipStream_t s) {
-    // ROWS=2 keeps 16 x 16 B per lane in flight at NIT=8 (and SiLU pairs need exactly 2 rows)
-    hipLaunchKernelGGL((gemv_kernel<T, NIT, 2, NB>), dim3((unsigned)blocks), dim3(256), 0, s, a);
-    SS_LAUNCH_CHECK("gemv");
-    return SS_OK;
-}
-
-// x slices live in registers while batch * NIT <= reg budget (16 packs = 64 VGPRs at batch 2, NIT = 8); else they are staged in LDS
-static bool gemv_x_in_regs(int nb, int nit) {
-    return nit <= 8 && nb * nit <= knob(K_gemv_x_reg_packs) && !knob(K_gemv_force_lds);
-}
-
-template <typename T, int NB>
-static int gemv_launch_nb(const GemvArgs& a, int nit, int64_t waves, hipStream_t s) {
-    constexpr int V = Tr<T>::kVec;
-    const int max_blocks = knob(K_gemv_max_blocks);
-    auto blocks_for = [&](int wpb) {
-        int64_t b = (waves + wpb - 1) / wpb;
-        if (b > max_blocks) b = max_blocks;
-        return (int)(b < 1 ? 1 : b);
-    };
-    if (gemv_x_in_regs(NB, nit)) {
-        const int blocks = blocks_for(4);
-        if (nit <= 1) return gemv_launch_reg<T, 1, NB>(a, blocks, s);
-        if (nit <= 2) return gemv_launch_reg<T, 2, NB>(a, blocks, s);
-        if (nit <= 4) return gemv_launch_reg<T, 4, NB>(a, blocks, s);
-        return gemv_launch_reg<T, 8, NB>(a, blocks, s);
-    }
-    const size_t lds = (size_t)NB * cdiv(a.K / V, 512) * 512 * 16;
-    SS_REQUIRE(lds <= 152 * 1024, "gemv: K=%d x batch %d too large for LDS staging", a.K, NB);
-    int threads, blocks;
-    if (NB == 1) {
-        // batch 1 (the reference configuration): several 256-thread blocks per CU, ~2.5k waves (measured optimum)
-        threads = lds <= 36 * 1024 ? 256 : lds <= 72 * 1024 ? 512 : 1024;
-        blocks = blocks_for(threads / 64);
-    } else {
-        // every block stages all NB rows of x, so blocks are fat and their count is a whole number per CU
-        // (no CU ends up with one block more than its neighbour): 2 x 512 threads per CU, or 1 x 1024 when the
-        // staged activations exceed half the LDS
-        const int per_cu = lds <= 76 * 1024 ? 2 : 1;
-        threads = per_cu == 2 ? 512 : 1024;
-        blocks = 256 * per_cu;
-        const int64_t max_b = (waves * 2 + threads / 64 - 1) / (threads / 64);   // keep >= ~2 row groups per wave
-        if (blocks > max_b) blocks = (int)(max_b < 1 ? 1 : max_b);
-    }
-    if (lds > 64 * 1024)     // (the request depends on K: set per launch, return code checked)
-        SS_HIP(hipFuncSetAttribute((const void*)gemv_ldsx_kernel<T, 2, NB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((gemv_ldsx_kernel<T, 2, NB>), dim3((unsigned)blocks), dim3((unsigned)threads), lds, s, a);
-    SS_LAUNCH_CHECK("gemv_ldsx");
-    return SS_OK;
-}
-
-template <typename T>
-int gemv_launch(const GemvArgs& a0, hipStream_t s);
-
-// two sweeps of half the sequences each
-template <typename T>
-static int gemv_launch_halves(const GemvArgs& a, hipStream_t s) {
-    const int h1 = a.nb / 2;
-    GemvArgs lo = a, hi = a;
-    lo.nb = h1;
-    hi.nb = a.nb - h1;
-    hi.x = (const T*)a.x + (int64_t)h1 * a.x_ld;
-    hi.y = (T*)a.y + (int64_t)h1 * a.y_ld;
-    if (a.residual) hi.residual = (const T*)a.residual + (int64_t)h1 * a.res_ld;
-    if (a.done_flag) hi.done_flag = a.done_flag + (int64_t)h1 * a.done_stride;
-    const int rc = gemv_launch<T>(lo, s);
-    return rc ? rc : gemv_launch<T>(hi, s);
-}
-
-template <typename T>
-int gemv_launch(const GemvArgs& a0, hipStream_t s) {
-    constexpr int V = Tr<T>::kVec;
-    GemvArgs a = a0;
-    const int64_t N = a.N, K = a.K;
-    const int epi = a.epi;
+static int gemv_plan(int64_t N, int64_t K, int nb, int dtype, int epi, bool norm, bool aligned16, GemvPlan& plan) {
+    SS_REQUIRE(dtype == SS_F32 || dtype == SS_BF16 || dtype == SS_F16, "unsupported dtype %d", dtype);
+    const int V = dtype == SS_F32 ? 4 : 8;
     SS_REQUIRE(K % V == 0 && K > 0 && N > 0, "gemv: K=%lld must be a positive multiple of %d", (long long)K, V);
     SS_REQUIRE(!(epi & SS_EPI_SILU_MUL) || !(epi & (SS_EPI_BIAS | SS_EPI_RESIDUAL | SS_EPI_GELU)),
                "gemv: SILU_MUL cannot be combined with other epilogues");
     SS_REQUIRE(!(epi & SS_EPI_GELU), "gemv: GELU epilogue not supported");
-    SS_REQUIRE(a.nb >= 1 && a.nb <= 16, "gemv: batch %d unsupported (1..16)", a.nb);
-    a.use_nt = knob(K_gemv_nt);
-    // 3+ sequences (knob): the MFMA form when the shape allows it (16-bit, 8 waves x 16 steps of 32 cover K, or the packed
-    // 11008-deep form).  Measured on the five LLaMA-7B projections (tools/gemv_bench.py, rotating weights, us per launch):
-    // dot-product kernels at 1 | 4 sequences 20.7 9.9 32.3 19.3 46.1 | 24.4 11.0 39.0 25.7 47.8; MFMA form at 8 sequences
-    // 24.2 9.9 37.3 21.9 46.2 — one sequence stays with the dot-product kernel, 3 and more go through the matrix core.
-    const bool mfma_nb = a.nb >= knob(K_gemv_mfma_min_nb);
-    if constexpr (V == 8) {
-        if (mfma_nb && gemv_mfma_eligible<T>(a)) return gemv_launch_mfma<T>(a, s);
-    } else {
-        // fp32 tensors in the gate mode: 3..8 sequences through the split-bf16 MFMA form (one sweep of the weights instead of two
-        // 4-sequence sweeps of the exact dot-product kernels); the RMSNorm prologue needs the whole row in one K slice; SiLU pairs too
-        const bool gate = mfma_nb && a.nb <= 8 && knob(K_gemm_f32_split);
-        if (gate && K % 8 == 0 &&
-            ((!a.norm_w && !(epi & SS_EPI_SILU_MUL)) || K <= kGsSlice) && (((size_t)a.x | (size_t)a.W | (size_t)a.norm_w) & 15) == 0 &&
-            (a.x_ld & 3) == 0)
-            return gemv_launch_split_f32(a, s);
-        // the gate mode was asked for and this launch cannot take the split form (RMSNorm / SiLU row wider than one 4096 slice,
-        // or 16-byte misalignment): it runs as two EXACT sweeps — correct, slower, and a different arithmetic than the rest of
-        // the run.  Counted (knob gemv_split_refused) and reported once.
-        if (gate) {
-            static bool told = false;
-            knob_add(K_gemv_split_refused, 1);
-            if (!told) {
-                told = true;
-                fprintf(stderr, "[ss] gate mode: GEMV [N=%d, K=%d, %d slots]%s%s runs as exact 4-slot sweeps (split form needs norm / SiLU rows <= %d "
-                                "wide and 16-byte alignment)\n", N, K, a.nb, a.norm_w ? " +RMSNorm" : "", (epi & SS_EPI_SILU_MUL) ? " +SiLU" : "", kGsSlice);
-            }
-        }
-    }
-    if (a.nb > 4) return gemv_launch_halves<T>(a, s);      // no MFMA form for this shape / type
+    SS_REQUIRE(nb >= 1 && nb <= 16, "gemv: batch %d unsupported (1..16)", nb);
+    const bool silu = (epi & SS_EPI_SILU_MUL) != 0;
+    // MFMA forms, whole rounds: ceil(tiles / 256) tiles per workgroup on as few workgroups as that takes (688 tiles -> 230 x 3, not
+    // 256 workgroups of which 80 run a third round alone)
+    const int ntiles = cdiv(N, 16), mfma_blocks = cdiv(ntiles, cdiv(ntiles, knob(K_gemv_mfma_blocks)));
+    // dot-product forms: several row groups per wave so the x prologue amortises; auto: ~2.5k waves (8-12 per CU) measured best
     const int nit = cdiv(K, 64 * V);
-    const int64_t groups = (epi & SS_EPI_SILU_MUL) ? N : (N + 1) / 2;
-    // waves: enough to fill the chip, but several row-groups per wave so the x prologue amortises
-    // auto: ~2.5k waves (8-12 per CU) measured best on MI355X for every LLaMA-7B projection
+    const int64_t groups = silu ? N : (N + 1) / 2;
     int gpw = knob(K_gemv_groups_per_wave);
     if (gpw <= 0) { gpw = (int)((groups + 1280) / 2560); if (gpw < 1) gpw = 1; }
     const int64_t waves = (groups + gpw - 1) / gpw;
-    // a batch whose LDS-staged activations would not fit one CU's LDS is swept in two halves
-    if (!gemv_x_in_regs(a.nb, nit) && a.nb > 1 && (size_t)a.nb * cdiv(K / V, 512) * 512 * 16 > 152 * 1024)
-        return gemv_launch_halves<T>(a, s);
-    switch (a.nb) {
-        case 1: return gemv_launch_nb<T, 1>(a, nit, waves, s);
-        case 2: return gemv_launch_nb<T, 2>(a, nit, waves, s);
-        case 3: return gemv_launch_nb<T, 3>(a, nit, waves, s);
-        default: return gemv_launch_nb<T, 4>(a, nit, waves, s);
+    auto blocks_for = [&](int wpb) { return (int)std::clamp<int64_t>((waves + wpb - 1) / wpb, 1, std::max(1, knob(K_gemv_max_blocks))); };
+    const GvLdsxStage stage((int)K, V);
+
+    // ranges of sequences still to place, first on top: a range no form takes in one sweep is swept as its two halves (every
+    // launch takes >= 1 of <= 16 sequences: at most SS_GEMV_PLAN_MAX launches, and the stack holds one range per halving level)
+    struct Range { int seq0, nseq, refused; } todo[8] = {{0, nb, 0}};
+    int top = 1;
+    while (top > 0) {
+        const Range r = todo[--top];
+        const int n = r.nseq;
+        GemvLaunch l = {r.seq0, n, SS_GEMV_FORM_REG, 0, 0, 0, 0, 0, silu, r.refused};
+        // 3+ sequences (knob): the MFMA form when the shape allows it (16-bit, 8 waves x 16 steps of 32 cover K, or the packed
+        // 11008-deep form: <= 8 sequences, no RMSNorm prologue).  Measured on the five LLaMA-7B projections (tools/gemv_bench.py,
+        // rotating weights, us per launch): dot-product kernels at 1 | 4 sequences 20.7 9.9 32.3 19.3 46.1 | 24.4 11.0 39.0 25.7 47.8;
+        // MFMA form at 8 sequences 24.2 9.9 37.3 21.9 46.2 — one sequence stays with the dot-product kernel.
+        const bool mfma_nb = n >= knob(K_gemv_mfma_min_nb);
+        const bool generic = knob(K_gemv_mfma_generic) != 0;
+        const bool exact43 = K == kGvWaves * 43 * 32 && n <= 8 && !norm && !generic && knob(K_gemv_mfma_long);
+        // fp32 tensors in the gate mode: 3..8 sequences through the split-bf16 MFMA form (one sweep of W instead of two exact ones)
+        const bool gate = V == 4 && mfma_nb && n <= 8 && knob(K_gemm_f32_split);
+        if (V == 8 && mfma_nb && (K <= kGvWaves * kGvSteps * 32 || exact43)) {
+            l.form = exact43 ? SS_GEMV_FORM_MFMA_EXACT43 : (!generic && K == kGvWaves * kGvSteps * 32) ? SS_GEMV_FORM_MFMA_EXACT16 : SS_GEMV_FORM_MFMA;
+            l.param = exact43 ? 43 : cdiv(cdiv(K, 32), kGvWaves);
+            l.blocks = mfma_blocks, l.threads = 512;
+            // plain loads, not non-temporal ones: a fragment load touches HALF a 128-byte line per row and the next instruction the
+            // other half; measured on the five LLaMA-7B shapes at 8 sequences, nt is 3 - 13 % slower (lm_head 52.0 vs 46.2 us)
+            l.nt = l.form != SS_GEMV_FORM_MFMA && knob(K_gemv_mfma_nt) != 0;
+        } else if (gate && K % 8 == 0 && ((!norm && !silu) || K <= kGsSlice) && aligned16) {
+            // (the RMSNorm prologue needs the whole row in one K slice; SiLU pairs too)
+            l.form = SS_GEMV_FORM_SPLIT_F32;
+            l.blocks = mfma_blocks, l.threads = 512;
+            l.lds = GvSplitLds((int)K, silu).bytes;
+        } else {
+            // a refused gate-mode sweep (RMSNorm / SiLU row wider than one 4096 slice, or 16-byte misalignment) runs EXACT forms
+            if (gate) l.refused = 1;
+            // x slices live in registers while batch * NIT <= reg budget (16 packs = 64 VGPRs at batch 2, NIT = 8); else in LDS
+            const bool in_regs = nit <= 8 && n * nit <= knob(K_gemv_x_reg_packs) && !knob(K_gemv_force_lds);
+            const size_t lds = in_regs ? 0 : stage.bytes(n);
+            if (n > 4 || (n > 1 && lds > kGvLdsxMaxBytes)) {     // no form for this many sequences, or their activations overflow the LDS
+                todo[top++] = {r.seq0 + n / 2, n - n / 2, l.refused};
+                todo[top++] = {r.seq0, n / 2, l.refused};
+                continue;
+            }
+            SS_REQUIRE(lds <= kGvLdsxMaxBytes, "gemv: K=%lld x batch %d too large for LDS staging", (long long)K, n);
+            l.nt = knob(K_gemv_nt), l.lds = (int)lds;
+            if (in_regs) {
+                for (l.param = 1; l.param < nit;) l.param *= 2;    // gemv_kernel is instantiated for NIT 1, 2, 4, 8
+                l.blocks = blocks_for(4), l.threads = 256;
+            } else if (n == 1) {
+                // batch 1 (the reference configuration): several 256-thread blocks per CU, ~2.5k waves (measured optimum)
+                l.form = SS_GEMV_FORM_LDSX;
+                l.threads = lds <= 36 * 1024 ? 256 : lds <= 72 * 1024 ? 512 : 1024;
+                l.blocks = blocks_for(l.threads / 64);
+            } else {
+                // every block stages all rows of x, so blocks are fat and their count is a whole number per CU (no CU ends up with one
+                // block more than its neighbour): 2 x 512 threads per CU, or 1 x 1024 when the staged activations exceed half the LDS
+                const int per_cu = lds <= 76 * 1024 ? 2 : 1;
+                l.form = SS_GEMV_FORM_LDSX;
+                l.threads = per_cu == 2 ? 512 : 1024;
+                l.blocks = 256 * per_cu;
+                const int64_t max_b = (waves * 2 + l.threads / 64 - 1) / (l.threads / 64);   // keep >= ~2 row groups per wave
+                if (l.blocks > max_b) l.blocks = (int)(max_b < 1 ? 1 : max_b);
+            }
+        }
+        plan.l[plan.n++] = l;
     }
+    return SS_OK;
+}
+
+// ---- kernel tables --------------------------------------------------------------------------------------------------------------------
+using GemvKern = void (*)(GemvArgs);
+using GemvTileKern = void (*)(GemvArgs, int);
+// ROWS = 2 keeps 16 x 16 B per lane in flight at NIT = 8 (and SiLU pairs need exactly 2 rows)
+template <typename T, int NB>
+static GemvKern gv_dot_kernel_nb(const GemvLaunch& l) {
+    if (l.form == SS_GEMV_FORM_LDSX) return gemv_ldsx_kernel<T, 2, NB>;
+    static constexpr GemvKern by_nit[9] = {nullptr, gemv_kernel<T, 1, 2, NB>, gemv_kernel<T, 2, 2, NB>, nullptr, gemv_kernel<T, 4, 2, NB>,
+                                           nullptr, nullptr, nullptr, gemv_kernel<T, 8, 2, NB>};
+    return by_nit[l.param];
+}
+template <typename T>
+static GemvKern gv_dot_kernel(const GemvLaunch& l) {
+    static constexpr GemvKern (*by_nb[4])(const GemvLaunch&) = {gv_dot_kernel_nb<T, 1>, gv_dot_kernel_nb<T, 2>, gv_dot_kernel_nb<T, 3>, gv_dot_kernel_nb<T, 4>};
+    return by_nb[l.nseq - 1](l);
+}
+template <typename T, int SPW>
+static GemvTileKern gv_exact_kernel(const GemvLaunch& l) {
+    static constexpr GemvTileKern k[2][2] = {{gemv_mfma_exact_kernel<T, false, SPW, false>, gemv_mfma_exact_kernel<T, false, SPW, true>},
+                                             {gemv_mfma_exact_kernel<T, true, SPW, false>, gemv_mfma_exact_kernel<T, true, SPW, true>}};
+    return k[l.silu][l.nt];
+}
+template <bool SILU>
+static int gemv_run_split(const GemvLaunch& l, const GemvArgs& a, hipStream_t s) {
+    SS_DYN_LDS(gemv_split_f32_kernel<SILU>, (size_t)GvSplitLds(kGsSlice, true).bytes);   // the largest request: full slice, SiLU pair
+    hipLaunchKernelGGL(gemv_split_f32_kernel<SILU>, dim3((unsigned)l.blocks), dim3((unsigned)l.threads), (size_t)l.lds, s, a, cdiv(a.N, 16));
+    return SS_OK;
+}
+
+template <typename T>
+static int gemv_run(const GemvPlan& plan, const GemvArgs& args, hipStream_t s) {
+    for (int j = 0; j < plan.n; ++j) {
+        const GemvLaunch& l = plan.l[j];
+        GemvArgs a = args;
+        a.nb = l.nseq, a.use_nt = l.nt;
+        a.x = (const T*)args.x + (int64_t)l.seq0 * args.x_ld;
+        a.y = (T*)args.y + (int64_t)l.seq0 * args.y_ld;
+        if (args.residual) a.residual = (const T*)args.residual + (int64_t)l.seq0 * args.res_ld;
+        if (args.done_flag) a.done_flag = args.done_flag + (int64_t)l.seq0 * args.done_stride;
+        const dim3 g((unsigned)l.blocks), b((unsigned)l.threads);
+        if (l.form == SS_GEMV_FORM_REG || l.form == SS_GEMV_FORM_LDSX) {
+            const GemvKern k = gv_dot_kernel<T>(l);
+            if (l.lds > 64 * 1024)     // (the request depends on K: set per launch, return code checked)
+                SS_HIP(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, l.lds));
+            hipLaunchKernelGGL(k, g, b, (size_t)l.lds, s, a);
+        } else if constexpr (sizeof(T) == 4) {
+            const int rc = l.silu ? gemv_run_split<true>(l, a, s) : gemv_run_split<false>(l, a, s);
+            if (rc) return rc;
+        } else if (l.form == SS_GEMV_FORM_MFMA) {
+            void (*const k)(GemvArgs, int, int) = l.silu ? gemv_mfma_kernel<T, true> : gemv_mfma_kernel<T, false>;
+            hipLaunchKernelGGL(k, g, b, 0, s, a, l.param, cdiv(a.N, 16));
+        } else {
+            const GemvTileKern k = l.form == SS_GEMV_FORM_MFMA_EXACT16 ? gv_exact_kernel<T, 16>(l) : gv_exact_kernel<T, 43>(l);
+            hipLaunchKernelGGL(k, g, b, 0, s, a, cdiv(a.N, 16));
+        }
+        static const char* const what[] = {"gemv", "gemv_ldsx", "gemv_mfma", "gemv_mfma", "gemv_mfma", "gemv_split_f32"};
+        SS_LAUNCH_CHECK(what[l.form]);
+    }
+    return SS_OK;
 }
 
 int gemv_batched_dev(const void* W, const void* x, void* y, int64_t N, int64_t K, const void* norm_w, float eps,
                      const void* bias, const void* residual, int epi, const int32_t* done_flag, int done_stride,
                      int nb, int64_t x_ld, int64_t y_ld, int64_t res_ld, int dtype, hipStream_t s) {
+    GemvPlan plan;
+    const bool aligned16 = (((size_t)x | (size_t)W | (size_t)norm_w) & 15) == 0 && (x_ld & 3) == 0;     // what the split form needs
+    const int rc = gemv_plan(N, K, nb, dtype, epi, norm_w != nullptr, aligned16, plan);
+    if (rc) return rc;
+    bool refused = false;
+    for (int j = 0; j < plan.n; ++j) refused |= plan.l[j].refused != 0;
+    if (refused) {      // counted once per call (knob gemv_split_refused) and reported once per process
+        static bool told = false;
+        knob_add(K_gemv_split_refused, 1);
+        if (!told) {
+            told = true;
+            fprintf(stderr, "[ss] gate mode: GEMV [N=%lld, K=%lld, %d slots]%s%s runs as exact 4-slot sweeps (split form needs norm / SiLU "
+                            "rows <= %d wide and 16-byte alignment)\n", (long long)N, (long long)K, nb, norm_w ? " +RMSNorm" : "",
+                    (epi & SS_EPI_SILU_MUL) ? " +SiLU" : "", kGsSlice);
+        }
+    }
     GemvArgs a;
     a.W = W; a.x = x; a.y = y; a.norm_w = norm_w; a.bias = bias; a.residual = residual; a.done_flag = done_flag;
-    a.N = (int)N; a.K = (int)K; a.epi = epi; a.eps = eps; a.use_nt = 1;
+    a.N = (int)N; a.K = (int)K; a.epi = epi; a.eps = eps; a.use_nt = 0;
     a.nb = nb; a.done_stride = done_stride; a.x_ld = x_ld; a.y_ld = y_ld; a.res_ld = res_ld;
-    return SS_DISPATCH(dtype, gemv_launch, a, s);
+    return SS_DISPATCH(dtype, gemv_run, plan, a, s);
 }
 
 int gemv_dev(const void* W, const void* x, void* y, int64_t N, int64_t K, const void* norm_w, float eps,
@@ -1098,9 +1089,17 @@ extern "C" int ss_gemv(const void* W, const void* x, void* y, int64_t N, int64_t
     return ss::gemv_dev(W, x, y, N, K, norm_w, eps, bias, residual, epilogue, nullptr, dtype, (hipStream_t)stream);
 }
 
-extern "C" int ss_gemv_batched(const void* W, const void* x, void* y, int64_t N, int64_t K, int64_t nb,
-                               const void* norm_w, float eps, const void* bias, const void* residual, int epilogue,
-                               int dtype, void* stream) {
-    return ss::gemv_batched_dev(W, x, y, N, K, norm_w, eps, bias, residual, epilogue, nullptr, 0, (int)nb, K, N, N,
-                                dtype, (hipStream_t)stream);
+extern "C" int ss_gemv_batched(const void* W, const void* x, void* y, int64_t N, int64_t K, int64_t nb, const void* norm_w, float eps,
+                               const void* bias, const void* residual, int epilogue, int dtype, void* stream) {
+    return ss::gemv_batched_dev(W, x, y, N, K, norm_w, eps, bias, residual, epilogue, nullptr, 0, (int)nb, K, N, N, dtype, (hipStream_t)stream);
+}
+
+extern "C" int ss_gemv_plan(int64_t N, int64_t K, int64_t nb, int dtype, int epilogue, int has_norm, int aligned16, int32_t* rows,
+                            int64_t max_rows) {
+    ss::GemvPlan plan;
+    const int rc = ss::gemv_plan(N, K, (int)nb, dtype, epilogue, has_norm != 0, aligned16 != 0, plan);
+    if (rc) return rc;
+    SS_REQUIRE(rows && max_rows >= plan.n, "ss_gemv_plan: %d rows needed, room for %lld", plan.n, (long long)max_rows);
+    memcpy(rows, plan.l, (size_t)plan.n * sizeof(ss::GemvLaunch));
+    return plan.n;
 }

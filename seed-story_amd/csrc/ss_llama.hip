@@ -18,15 +18,11 @@
 #include <vector>
 
 #include "ss_common.h"
+#include "ss_gemv.h"
 #include "ss_sample.h"
 
 namespace ss {
 
-int gemv_dev(const void* W, const void* x, void* y, int64_t N, int64_t K, const void* norm_w, float eps,
-             const void* bias, const void* residual, int epi, const int32_t* done_flag, int dtype, hipStream_t s);
-int gemv_batched_dev(const void* W, const void* x, void* y, int64_t N, int64_t K, const void* norm_w, float eps,
-                     const void* bias, const void* residual, int epi, const int32_t* done_flag, int done_stride,
-                     int nb, int64_t x_ld, int64_t y_ld, int64_t res_ld, int dtype, hipStream_t s);
 size_t gemm_splitk_workspace_bytes(int64_t M, int64_t N, int64_t K);
 int gemm_splitk_dev(const void* A, const void* W, void* C, int64_t M, int64_t N, int64_t K, const void* bias,
                     const void* residual, void* ws, size_t ws_bytes, int dtype, hipStream_t s);

@@ -693,3 +693,85 @@ def test_splitk_plan_and_bench_slot_groups():
     import bench
     assert [bench.slot_groups(n) for n in (1, 2, 3, 4, 6, 8, 9, 16)] == [[1], [2], [3], [4], [6], [8], [5, 4], [8, 8]]
     assert [bench.slot_groups(n, 4) for n in (4, 6, 8)] == [[4], [3, 3], [4, 4]]         # the round-3 grouping (--max-slots 4)
+
+
+def test_gemv_plan_matches_recorded_launches():
+    """ss_gemv_plan (host only) names the launches ss_gemv / ss_gemv_batched make.  tests/golden/gemv_launches.json is a kernel
+    trace of the library BEFORE the launch plan existed (tools/gemv_launch_table.py on an MI355X: dtypes x 1..16 sequences x
+    the LLaMA-7B projections and odd shapes x prologues / epilogues x knob sets): for every case the plan must give the
+    recorded kernels, workgroups and threads, over sequence ranges that tile [0, nb) in order (a dot-product kernel's name
+    carries its sequence count; the trace's LDS column holds static LDS only, so the dynamic request is held by the rows
+    derived by hand from the launch rules below)."""
+    import ctypes
+    import json
+    from seedstory import _lib
+    lib = _lib.lib()
+    DT = {"bf16": (_lib.SS_BF16, "bf16_t"), "fp16": (_lib.SS_F16, "f16_t"), "fp32": (_lib.SS_F32, "float")}
+    REG, LDSX, MFMA, EXACT16, EXACT43, SPLIT = range(6)
+    tf = ("false", "true")
+
+    def plan(dtype, nb, N, K, epi=0, norm=False, aligned=True, **knobs):
+        """-> [(kernel name, first sequence, sequences, workgroups, threads, dynamic LDS, refused)]"""
+        rows = (ctypes.c_int32 * 160)()
+        old = {k: _lib.get_tuning(k) for k in knobs}
+        try:
+            for k, v in knobs.items():
+                _lib.set_tuning(k, v)
+            n = lib.ss_gemv_plan(N, K, nb, DT[dtype][0], epi, int(norm), int(aligned), rows, 16)
+        finally:
+            for k, v in old.items():
+                _lib.set_tuning(k, v)
+        assert 1 <= n <= 16, (n, lib.ss_last_error())
+        out, T = [], DT[dtype][1]
+        for j in range(n):
+            seq0, nseq, form, param, blocks, threads, lds, nt, silu, refused = rows[10 * j:10 * j + 10]
+            name = {REG: "gemv_kernel<%s,%d,2,%d>" % (T, param, nseq), LDSX: "gemv_ldsx_kernel<%s,2,%d>" % (T, nseq),
+                    MFMA: "gemv_mfma_kernel<%s,%s>" % (T, tf[silu]), EXACT16: "gemv_mfma_exact_kernel<%s,%s,16,%s>" % (T, tf[silu], tf[nt]),
+                    EXACT43: "gemv_mfma_exact_kernel<%s,%s,43,%s>" % (T, tf[silu], tf[nt]), SPLIT: "gemv_split_f32_kernel<%s>" % tf[silu]}[form]
+            assert param == {EXACT16: 16, EXACT43: 43}.get(form, param)
+            out.append((name, seq0, nseq, blocks, threads, lds, refused))
+        assert [r[1] for r in out] == [sum(q[2] for q in out[:j]) for j in range(n)] and sum(r[2] for r in out) == nb, out
+        return out
+
+    rec = json.load(open(os.path.join(ROOT, "tests", "golden", "gemv_launches.json")))
+    ncases = 0
+    for key, per_nb in rec["table"].items():
+        dtypes, rows, K, variant = key.split()
+        silu = "silu" in variant
+        epi = _lib.EPI_SILU_MUL if silu else (_lib.EPI_BIAS | _lib.EPI_RESIDUAL) if variant == "bias+res" else 0
+        for dtype in dtypes.split("|"):
+            for nb, (dflt, other) in zip(rec["nbs"], per_nb):
+                for ks, knobs in enumerate(rec["knob_sets"]):
+                    got = plan(dtype, nb, int(rows) // 2 if silu else int(rows), int(K), epi, "norm" in variant, **knobs)
+                    want = [(rec["kernels"][k].replace("T16", DT[dtype][1]), wgs, threads) for k, wgs, threads, _ in other.get(str(ks), dflt)]
+                    assert [(g[0], g[3], g[4]) for g in got] == want, (dtype, nb, rows, K, variant, knobs, got, want)
+                    ncases += 1
+    assert ncases == 5166
+
+    # rows that follow from the launch rules under default knobs (H = 4096, I = 11008, vocabulary 32066)
+    H, I, SILU = 4096, 11008, _lib.EPI_SILU_MUL
+    assert plan("bf16", 1, H, H) == [("gemv_kernel<bf16_t,8,2,1>", 0, 1, 512, 256, 0, 0)]
+    assert plan("bf16", 1, H, I) == [("gemv_ldsx_kernel<bf16_t,2,1>", 0, 1, 512, 256, 24576, 0)]
+    assert [r[3] for r in plan("bf16", 1, I, H, SILU, True)] == [688]
+    assert [r[3] for r in plan("bf16", 1, 32066, H)] == [669]
+    assert plan("bf16", 8, I, H, SILU, True) == [("gemv_mfma_exact_kernel<bf16_t,true,16,false>", 0, 8, 230, 512, 0, 0)]
+    assert plan("bf16", 8, H, I) == [("gemv_mfma_exact_kernel<bf16_t,false,43,false>", 0, 8, 256, 512, 0, 0)]
+    assert plan("bf16", 8, H, I, 0, True) == [("gemv_ldsx_kernel<bf16_t,2,4>", s, 4, 256, 1024, 98304, 0) for s in (0, 4)]
+    assert plan("bf16", 16, H, I) == [("gemv_mfma_exact_kernel<bf16_t,false,43,false>", s, 8, 256, 512, 0, 0) for s in (0, 8)]
+    assert plan("fp32", 8, H, H) == [("gemv_ldsx_kernel<float,2,4>", s, 4, 512, 512, 65536, 0) for s in (0, 4)]
+    assert 4 * 49152 == 196608 > 152 * 1024       # four staged fp32 rows of 11008 overflow the LDS: two sweeps of two
+    assert [(r[1], r[2], r[5]) for r in plan("fp32", 4, H, I)] == [(0, 2, 98304), (2, 2, 98304)]
+    assert plan("fp32", 8, H, H, gemm_f32_split=1) == [("gemv_split_f32_kernel<false>", 0, 8, 256, 512, 139776, 0)]
+    assert plan("fp32", 8, I, H, SILU, True, gemm_f32_split=1) == [("gemv_split_f32_kernel<true>", 0, 8, 230, 512, 147968, 0)]
+    # the dynamic LDS of the staged forms at 2 / 3 sequences, and a register form (none)
+    assert plan("bf16", 2, H, I) == [("gemv_ldsx_kernel<bf16_t,2,2>", 0, 2, 512, 512, 2 * 24576, 0)]
+    assert plan("fp16", 3, H, I, 0, True) == [("gemv_ldsx_kernel<f16_t,2,3>", 0, 3, 512, 512, 3 * 24576, 0)]
+    assert plan("bf16", 2, H, H) == [("gemv_kernel<bf16_t,8,2,2>", 0, 2, 512, 256, 0, 0)]
+    # the worst case of the halving: two staged fp32 rows of 20480 (2 x 81920 B) overflow the LDS, so 16 sequences are swept one
+    # at a time (64 rows = 32 groups = 32 waves: 2 workgroups of 1024 threads)
+    assert plan("fp32", 16, 64, 20480) == [("gemv_ldsx_kernel<float,2,1>", s, 1, 2, 1024, 81920, 0) for s in range(16)]
+    assert len(plan("bf16", 16, 64, 40960)) == 16 and len(plan("fp32", 9, 64, 20480)) == 9
+    refused = plan("fp32", 8, H, I, 0, True, gemm_f32_split=1)       # an RMSNorm row wider than one 4096 slice: exact sweeps
+    assert [(r[0], r[1], r[2], r[6]) for r in refused] == [("gemv_ldsx_kernel<float,2,2>", s, 2, 1) for s in (0, 2, 4, 6)]
+    assert [r[6] for r in plan("fp32", 8, H, H, aligned=False, gemm_f32_split=1)] == [1, 1]     # misaligned operands too
+    assert lib.ss_gemv_plan(H, H + 4, 1, _lib.SS_BF16, 0, 0, 1, None, 0) == -1 and b"multiple of 8" in lib.ss_last_error()

@@ -48,6 +48,13 @@ this table; a ratio above 1 fails the case that produced it):
   gemv                   bf16  worst error / bound = 0.958
   gemv                   fp16  worst error / bound = 0.977
   gemv                   fp32  worst error / bound = 0.154
+  gemv multi-tile        bf16  worst error / bound = 0.905
+  gemv multi-tile        fp16  worst error / bound = 0.670
+  gemv multi-tile        fp32  worst error / bound = 0.001
+  gemv multi-tile silu_mul bf16  worst error / bound = 0.149
+  gemv multi-tile silu_mul fp16  worst error / bound = 0.152
+  gemv multi-tile silu_mul fp32  worst error / bound = 0.001
+  gemv multi-tile split  fp32  worst error / bound = 0.001
   gemv silu_mul          bf16  worst error / bound = 0.166
   gemv silu_mul          fp16  worst error / bound = 0.174
   gemv silu_mul          fp32  worst error / bound = 0.001
@@ -500,6 +507,74 @@ def test_gemv_silu_mul_bound(ops, I, K, dtype):
             g = guarded(1, I, dtype)
             ops.gemv(wd, xd[0], silu_mul=True, out=g.view(I))
             KC.check(g.check("ss_gemv silu_mul"), ref, tol, "ss_gemv silu_mul %s" % ((I, K),), family="gemv silu_mul", dtype=dtype)
+
+
+GEMV_MULTI_SHAPES = [(100, 256), (37, 4096), (40, 11008)]       # N, K: generic MFMA / exact 16-step / packed 43-step depths
+
+
+def rmsnorm_inputs(x, K, dtype, seed):
+    """(gain [K] of the model dtype, fp64 reference of the RMS-normalised activations, bound of their error).
+    The kernels form rstd = 1 / sqrt(sum x^2 / K + eps) in fp32 (K positive terms, then a division, an addition, a square root
+    and a reciprocal: relative error <= (K + 8) u32 together with the product x * rstd), round x * rstd to T, multiply by the gain
+    in fp32 and round to T again when the pack is formed (fp32: both roundings are the fp32 operation's own)."""
+    g = torch.Generator().manual_seed(8000 + seed)
+    gain = (1.0 + 0.1 * torch.randn(K, generator=g)).to(dtype)
+    xd = x.double()
+    v = xd / torch.sqrt((xd * xd).mean(dim=1, keepdim=True) + 1e-5)
+    v, t = KC.mid_round(v, (K + 8) * KC.U32 * v.abs(), dtype)
+    v, t = KC.product(v, t, gain.double().expand_as(v), torch.zeros_like(v))
+    v, t = KC.mid_round(v, t, dtype)
+    return gain, v, t
+
+
+@pytest.mark.parametrize("dtype", D16 + [F32], ids=dname)
+def test_gemv_multi_tile_bound(ops, dtype):
+    """gemv_mfma_blocks = 2 and gemv_max_blocks = 1: every persistent workgroup of the MFMA forms walks several row tiles (two
+    register buffers, LDS parity, the prefetch across the tile boundary) and every wave of the dot-product forms several row
+    groups, at sizes where only the LLaMA-sized shapes do under the default knobs.  Plain, bias + residual, the fused RMSNorm
+    prologue and the SiLU pair (I = 24, and I = 40: three tiles on two workgroups) at 1 / 4 / 8 sequences, against the same bounds as the other GEMV tests; with the
+    RMSNorm the activations themselves carry an error (rmsnorm_inputs), which enters the accumulator's bound as t_x |w|.
+    fp32 also runs the split-bf16 form (gemm_f32_split = 1) over two K slices, (37, 4104): its operands are hi + lo bf16 pairs
+    with the lo x lo term dropped, 2^-16 per product relative, far inside the 2 K u32 = 2^-11 of the exact chain's bound."""
+    with knobs(gemv_mfma_blocks=2, gemv_max_blocks=1):
+        for (N, K) in GEMV_MULTI_SHAPES:
+            for nb in (1, 4, 8):
+                seed = N + K + nb
+                x, w = KC.gemm_inputs(nb, N, K, dtype, seed)
+                kw = KC.epilogue_inputs("bias+residual", nb, N, dtype, seed)
+                gain, xn, tx = rmsnorm_inputs(x, K, dtype, seed)
+                wd, xd = padded(w, 3), padded(x, 1)
+                what = "gemv multi-tile %s %s nb %d" % ((N, K), dname(dtype), nb)
+                run = lambda g, **k: (ops.gemv(wd, xd[0], out=g.view(N), **k) if nb == 1 else ops.gemv_batched(wd, xd, out=g.out, **k))  # noqa: E731
+                g = guarded(nb, N, dtype)
+                run(g)
+                KC.check(g.check(what), *KC.gemm_bound(x, w, dtype), what, family="gemv multi-tile", dtype=dtype)
+                g = guarded(nb, N, dtype)
+                run(g, bias=dev(kw["bias"]), residual=dev(kw["residual"])[0] if nb == 1 else dev(kw["residual"]))
+                KC.check(g.check(what), *KC.gemm_bound(x, w, dtype, **kw), what + " bias+residual", family="gemv multi-tile", dtype=dtype)
+                g = guarded(nb, N, dtype)
+                run(g, norm_w=dev(gain), eps=1e-5)
+                v, t = KC.accumulate(xn, w)
+                ref, tol = KC.epilogue(v, t + (1.0 + 2.0 * K * KC.U32) * (tx @ w.double().abs().t()), dtype)
+                KC.check(g.check(what), ref, tol, what + " rmsnorm", family="gemv multi-tile", dtype=dtype)
+                for I in (24, 40):
+                    xs, ws = KC.gemm_inputs(nb, 2 * I, K, dtype, seed + I)
+                    g = guarded(nb, I, dtype)
+                    if nb == 1:
+                        ops.gemv(padded(ws, 3), padded(xs, 1)[0], silu_mul=True, out=g.view(I))
+                    else:
+                        ops.gemv_batched(padded(ws, 3), padded(xs, 1), silu_mul=True, out=g.out)
+                    KC.check(g.check(what), *KC.silu_mul_bound(ws, xs, dtype), what + " silu_mul I %d" % I, family="gemv multi-tile silu_mul", dtype=dtype)
+        if dtype == F32:
+            N, K, nb = 37, 4104, 8
+            x, w = KC.gemm_inputs(nb, N, K, dtype, N + K)
+            kw = KC.epilogue_inputs("bias+residual", nb, N, dtype, N + K)
+            with knobs(gemm_f32_split=1):
+                for name, k in (("plain", {}), ("bias+residual", kw)):
+                    g = guarded(nb, N, dtype)
+                    ops.gemv_batched(padded(w, 3), padded(x, 1), out=g.out, **{n: dev(v) for n, v in k.items()})
+                    what = "gemv multi-tile split %s %s" % ((N, K), name)
+                    KC.check(g.check(what), *KC.gemm_bound(x, w, dtype, **k), what, family="gemv multi-tile split", dtype=dtype)
 
 
 def test_out_argument_is_checked(ops):
