@@ -312,9 +312,25 @@ int ss_gemv_batched(const void* W, const void* x, void* y, int64_t N, int64_t K,
 #define SS_GEMV_PLAN_COLS 10
 #define SS_GEMV_PLAN_MAX 16
 enum { SS_GEMV_FORM_REG = 0, SS_GEMV_FORM_LDSX = 1, SS_GEMV_FORM_MFMA = 2, SS_GEMV_FORM_MFMA_EXACT16 = 3,
-       SS_GEMV_FORM_MFMA_EXACT43 = 4, SS_GEMV_FORM_SPLIT_F32 = 5 };
+       SS_GEMV_FORM_MFMA_EXACT43 = 4, SS_GEMV_FORM_SPLIT_F32 = 5,
+       SS_GEMV_FORM_W8 = 6, SS_GEMV_FORM_W8_EXACT16 = 7, SS_GEMV_FORM_W8_EXACT43 = 8 /* ss_gemv_w8 only */ };
 int ss_gemv_plan(int64_t N, int64_t K, int64_t nb, int dtype, int epilogue, int has_norm, int aligned16, int32_t* rows,
                  int64_t max_rows);
+
+/* The decode projection over fp8 weights (weight-only: activations and outputs stay in the 16-bit model dtype):
+ *   y[b][n] = epilogue( w_scale[n] * sum_k dec(Wq[n][k]) * x[b][k] ),  b < nb <= 16
+ * Wq [N, K] bytes of OCP e4m3fn in the 16-bit weights' row layout ([2N, K] = [gate; up] for SS_EPI_SILU_MUL, w_scale [2N]),
+ * w_scale fp32, one per row of Wq (ops.quantize_weight_rows_fp8: amax / 448); x [nb, K], y / residual [nb, N] contiguous,
+ * bias [N], norm_w [K] (RMSNorm prologue as ss_gemv) in `dtype` = SS_BF16 | SS_F16.  Every code is converted exactly to the
+ * 16-bit type in registers and multiplied in the bf16 / f16 MFMA with fp32 accumulation; the scale is one fp32 multiply on the
+ * finished sum, then the epilogue of ss_gemv (NONE, BIAS, RESIDUAL, BIAS | RESIDUAL, SILU_MUL alone).  Half the weight bytes
+ * of ss_gemv_batched per call.  Shapes: K % 16 == 0 and K <= 4096, or K == 11008 (no norm_w there; 9..16 sequences run as two
+ * sweeps); Wq, x and norm_w 16-byte aligned.  Anything else returns SS_EINVAL with a message before a launch.
+ * ss_gemv_w8_plan: host only, the launches of that call as rows of ss_gemv_plan's layout (forms SS_GEMV_FORM_W8*; the
+ * parameter column holds MFMA steps of 32 k per wave). */
+int ss_gemv_w8(const void* Wq, const float* w_scale, const void* x, void* y, int64_t N, int64_t K, int64_t nb,
+               const void* norm_w, float eps, const void* bias, const void* residual, int epilogue, int dtype, void* stream);
+int ss_gemv_w8_plan(int64_t N, int64_t K, int64_t nb, int dtype, int epilogue, int has_norm, int32_t* rows, int64_t max_rows);
 
 /* ---------------------------------------------------------------------------------------
  * Sampling: lm_head logits -> AutoImageTokenGenerationProcessor -> greedy argmax
@@ -400,6 +416,23 @@ int ss_llama_set_stop_id(ss_llama* h, int32_t token_id);
 int ss_llama_set_attn_capture(ss_llama* h, void* maps, int64_t n_rows, int64_t ld, int64_t row0, int32_t head,
                               int32_t row_calls);
 
+/* fp8 (OCP e4m3fn) weight-only decode.  Per layer: the four byte planes in the 16-bit weights' layouts (wqkv [3*hidden, hidden],
+ * wo [hidden, hidden], wgu [2*inter, hidden] = [gate; up], wdown [hidden, inter]) and one fp32 scale per row of each
+ * (s_qkv [3*hidden], s_o [hidden], s_gu [2*inter], s_down [hidden]); lm_head_q [vocab, hidden] bytes + lm_head_scale [vocab].
+ * Device memory owned by the caller and kept alive while the option is on; `layers` is a host array[n_layers] (copied).
+ * While it is set, the five decode projections of ss_llama_generate / ss_llama_generate_batch (and of
+ * ss_llama_profile_decode) run ss_gemv_w8 on these planes: eager or captured, with attention-map capture too; half the
+ * weight bytes per generated token.  ss_llama_prefill*, the one-row lm_head at the end of a prefill and the image-token block
+ * keep the 16-bit weights, which therefore stay resident.  layers = NULL turns it off (the default).  Call it between
+ * engine calls; the captured fp8 decode graph is cached apart from the 16-bit one and dropped when the planes change.
+ * SS_EINVAL: an fp32 engine, or a projection shape ss_gemv_w8 does not take (hidden / inter not a multiple of 16, wider than
+ * 4096 and not 11008, ...), a NULL or misaligned plane. */
+typedef struct ss_llama_layer_w8 {
+    const void *wqkv, *wo, *wgu, *wdown;
+    const float *s_qkv, *s_o, *s_gu, *s_down;
+} ss_llama_layer_w8;
+int ss_llama_set_decode_w8(ss_llama* h, const ss_llama_layer_w8* layers, const void* lm_head_q, const float* lm_head_scale);
+
 /* Device pointers into the engine's workspace (views for the Python side), for the selected slot:
  * which: 0 = K cache [n_layers, n_heads, cache_cap, hd], 1 = V cache (same shape),
  * 2 = generated ids int32[max_new], 3 = hidden rows [max_new, hidden] (post final norm,
@@ -456,7 +489,8 @@ int ss_llama_generate_batch(ss_llama* h, int64_t n_steps, const int32_t* last_pr
  *             ss::gemv_kernel), [1] = attention (+split merge), [2] = sum over the down-projection
  *             GEMV launches (ss::gemv_ldsx_kernel), [3] = sampling + final norm, [4] = whole token;
  * out_bytes[0] = weight bytes streamed by the class-0 launches of one token, [1] = their count,
- * out_bytes[2] / [3] = the same for class 2. */
+ * out_bytes[2] / [3] = the same for class 2.  With ss_llama_set_decode_w8 on, the token is the fp8 one and the bytes are
+ * the bytes it streams: one per weight plus the fp32 row scales. */
 int ss_llama_profile_decode(ss_llama* h, int64_t n_tokens, float out_ms[8], double out_bytes[4],
                             void* stream);
 

@@ -13,6 +13,8 @@
 //     statistic redundantly from its registers: cheaper than a kernel boundary);
 //   * epilogues: +bias, +residual (in T, like `residual + hidden`, :352,:359),
 //     SiLU(gate)·up for the fused [gate; up] projection (LlamaMLP.forward, :190-191).
+// fp8 (OCP e4m3fn) weight-only variant (ss_gemv_w8, the opt-in decode_weights="fp8" of the LLaMA engine): the MFMA family below
+// over byte planes + one fp32 scale per row, codes converted to the 16-bit type in registers — see "fp8 weight forms".
 // Reference call sites: modeling_llama_xformer.py:228-230 (q/k/v), :297 (o), :191 (MLP),
 // :759 (lm_head); LlamaRMSNorm :107-115 for the prologue.
 #include "ss_gemv.h"
@@ -457,15 +459,22 @@ __device__ __forceinline__ void gv_tile_store(const GemvArgs& a, const f32x4_t (
     }
     gv_store4<T>(a, i, row0, o);
 }
-template <typename T, bool SILU>
+// (`post` sees the folded sums before the epilogue: the fp8-weight forms apply their row scales there)
+template <typename T, bool SILU, typename P>
 __device__ __forceinline__ void gv_fold_store(const GemvArgs& a, float* part, const f32x4_t (&acc)[SILU ? 2 : 1], int tile,
-                                              int wave, int lane, const GvEpi& epi) {
+                                              int wave, int lane, const GvEpi& epi, P&& post) {
     gv_write_partials(part, acc, wave, lane);
     __syncthreads();
     if (wave != 0) return;
     f32x4_t v[SILU ? 2 : 1];
     gv_fold(part, lane, v);
+    post(v);
     gv_tile_store<T, SILU>(a, v, tile, lane, epi);
+}
+template <typename T, bool SILU>
+__device__ __forceinline__ void gv_fold_store(const GemvArgs& a, float* part, const f32x4_t (&acc)[SILU ? 2 : 1], int tile,
+                                              int wave, int lane, const GvEpi& epi) {
+    gv_fold_store<T, SILU>(a, part, acc, tile, wave, lane, epi, [](auto&) {});
 }
 
 // RMSNorm statistic of the MFMA forms: a lane's sum over its k-chunks -> the four k-chunk lanes of a sequence -> the 8 waves in
@@ -564,6 +573,29 @@ __device__ __forceinline__ uint4 gv_row_shift8(const uint4& v) {
     return r;
 }
 
+// RMSNorm of the resident activation fragments of a stream loop; fragment t sits koff(t) elements behind gw / its x pointer
+template <typename T, int NF, typename KO>
+__device__ __forceinline__ void gv_norm_frags(uint4 (&xf)[NF], const T* gw, KO&& koff, float (*red)[16], int wave, int lane, int K,
+                                              float eps) {
+    float ssq = 0.f;
+    gv_static_for<NF>([&](auto s_) { ssq = gv_pack_ssq<T>(xf[decltype(s_)::value], ssq); });
+    // (the fragments are unpacked AGAIN below: without this fence hipcc keeps the 128 unpacked floats alive across
+    // the barrier and spills)
+    gv_static_for<NF>([&](auto s_) { gv_fence(xf[decltype(s_)::value]); });
+    const float rstd = gv_rstd_across_waves(ssq, red, wave, lane, K, eps);
+    // the gain in two batches of 8 fragments (32 VGPRs in flight, not 64: with the activations and the first weights
+    // resident the single batch spills)
+    gv_static_for<2>([&](auto h_) {
+        constexpr int h = decltype(h_)::value;
+        uint4 gf[NF / 2];
+        gv_static_for<NF / 2>([&](auto s_) { constexpr int s = decltype(s_)::value; gf[s] = ld16(gw + koff(h * (NF / 2) + s)); });
+        gv_static_for<NF / 2>([&](auto s_) {
+            constexpr int s = decltype(s_)::value, t = h * (NF / 2) + s;
+            xf[t] = gv_pack_norm<T>(xf[t], gf[s], rstd);
+        });
+        __builtin_amdgcn_sched_barrier(0);
+    });
+}
 template <typename T, bool SILU, int SPW, bool NT>
 __global__ __launch_bounds__(512) void gemv_mfma_exact_kernel(const GemvArgs a, const int ntiles) {
     constexpr int CH = kGvChunk, M = SILU ? 2 : 1;
@@ -605,27 +637,7 @@ __global__ __launch_bounds__(512) void gemv_mfma_exact_kernel(const GemvArgs a, 
         gv_static_for<HALF>([&](auto s_) { constexpr int s = decltype(s_)::value; xf[s] = ld16(xr + s * 32); });
         load_chunk(std::integral_constant<int, 0>{}, tile);         // the first weights travel while the statistic is formed
         __builtin_amdgcn_sched_barrier(0);
-        if (a.norm_w) {
-            float ssq = 0.f;
-            gv_static_for<HALF>([&](auto s_) { ssq = gv_pack_ssq<T>(xf[decltype(s_)::value], ssq); });
-            // (the fragments are unpacked AGAIN below: without this fence hipcc keeps the 128 unpacked floats alive across
-            // the barrier and spills)
-            gv_static_for<HALF>([&](auto s_) { gv_fence(xf[decltype(s_)::value]); });
-            const float rstd = gv_rstd_across_waves(ssq, red, wave, lane, K, a.eps);
-            const T* gw = (const T*)a.norm_w + k0;
-            // the gain in two batches of 8 fragments (32 VGPRs in flight, not 64: with the activations and the first weights
-            // resident the single batch spills)
-            gv_static_for<2>([&](auto h_) {
-                constexpr int h = decltype(h_)::value;
-                uint4 gf[HALF / 2];
-                gv_static_for<HALF / 2>([&](auto s_) { constexpr int s = decltype(s_)::value; gf[s] = ld16(gw + (h * (HALF / 2) + s) * 32); });
-                gv_static_for<HALF / 2>([&](auto s_) {
-                    constexpr int s = decltype(s_)::value, t = h * (HALF / 2) + s;
-                    xf[t] = gv_pack_norm<T>(xf[t], gf[s], rstd);
-                });
-                __builtin_amdgcn_sched_barrier(0);
-            });
-        }
+        if (a.norm_w) gv_norm_frags<T>(xf, (const T*)a.norm_w + k0, [](int t) { return t * 32; }, red, wave, lane, K, a.eps);
     } else {
         const int seq = i & 7, upper = i >> 3;
         const T* xr = (const T*)a.x + (int64_t)(seq < nb ? seq : 0) * a.x_ld + k0 + upper * HALF * 32;
@@ -672,6 +684,238 @@ __global__ __launch_bounds__(512) void gemv_mfma_exact_kernel(const GemvArgs a, 
             __builtin_amdgcn_sched_barrier(0);
         });
         gv_fold_store<T, SILU>(a, &part[itn & 1][0][0][0], acc, tl, wave, lane, epi);
+    };
+    for (; tile + (int)gridDim.x < ntiles; tile += gridDim.x, ++it) tile_body(tile, it, std::true_type{});
+    tile_body(tile, it, std::false_type{});
+}
+
+// ---- fp8 (OCP e4m3fn) weight forms: half the bytes per k, the same matrix instruction ----------------------------------------------
+// y[b][n] = epilogue( s[n] * sum_k dec(Wq[n][k]) * x[b][k] ):  Wq is [N, K] bytes in the 16-bit weights' row layout, s one fp32 scale
+// per row.  A lane's 16-byte load now holds 16 consecutive k = TWO MFMA steps (lane l: row l & 15, bytes (l >> 4) * 16 .. + 15 of
+// the load's 64 k; step 0 takes bytes 0..7, step 1 bytes 8..15), the codes are converted to the model's 16-bit type in registers
+// (v_cvt_scalef32_pk_{bf16,f16}_fp8 with unit scale, two codes per instruction, exact: e4m3 is a subset of both types) and fed to
+// gv_mfma<T>; the activation fragments are laid out to match (fragment 2L + h = x[load L's 64 k + 16 q + 8 h .. + 8]).  Every
+// product of an e4m3 value and a 16-bit value is exact in fp32; the row scale is ONE fp32 multiply on the folded sum in front of
+// the shared epilogue (gate and up rows of the SiLU pair have their own scales).  One sequence takes these forms too.
+typedef __attribute__((ext_vector_type(2))) __bf16 gv_bf16x2_t;
+typedef __attribute__((ext_vector_type(2))) _Float16 gv_f16x2_t;
+template <typename T> __device__ __forceinline__ uint4 gv_dec8(uint32_t lo, uint32_t hi);      // 8 codes -> 8 values of T
+template <> __device__ __forceinline__ uint4 gv_dec8<bf16_t>(uint32_t lo, uint32_t hi) {
+    return make_uint4(__builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, 1.0f, false)),
+                      __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, 1.0f, true)),
+                      __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, 1.0f, false)),
+                      __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, 1.0f, true)));
+}
+template <> __device__ __forceinline__ uint4 gv_dec8<f16_t>(uint32_t lo, uint32_t hi) {
+    return make_uint4(__builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(lo, 1.0f, false)),
+                      __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(lo, 1.0f, true)),
+                      __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(hi, 1.0f, false)),
+                      __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(hi, 1.0f, true)));
+}
+
+// the row scales of wave 0's four output rows (lane l: rows 4 (l >> 4) + r of the tile), requested at the top of the tile like
+// gv_epi_prefetch and for the same reason.  vec (kernel-uniform): N % 4 == 0 and a 16-byte aligned scale vector -> one load.
+template <int M> struct GvScale { f32x4_t s[M]; };
+template <int M>
+__device__ __forceinline__ GvScale<M> gv_scale_prefetch(const float* w_scale, int N, int tile, int lane, bool vec) {
+    GvScale<M> r;
+    const int row0 = tile * 16 + (lane >> 4) * 4;
+#pragma unroll
+    for (int m = 0; m < M; ++m) {
+        const float* sp = w_scale + (int64_t)m * N;
+        if (vec) {
+            r.s[m] = *reinterpret_cast<const f32x4_t*>(sp + (row0 > N - 4 ? N - 4 : row0));
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) r.s[m][j] = sp[row0 + j < N ? row0 + j : N - 1];
+        }
+    }
+    return r;
+}
+__device__ __forceinline__ bool gv_scale_vec_ok(const float* w_scale, int N) { return (N & 3) == 0 && N >= 4 && ((size_t)w_scale & 15) == 0; }
+
+// any K <= 4096 (multiple of 16), any N: predicated loads, LPW <= 8 loads of 64 k per wave (gemv_mfma_kernel's role)
+template <typename T, bool SILU>
+__global__ __launch_bounds__(512) void gemv_w8_kernel(const GemvArgs a, const float* __restrict__ w_scale, const int lpw, const int ntiles) {
+    constexpr int NL = kGvSteps / 2, M = SILU ? 2 : 1;
+    __shared__ __attribute__((aligned(16))) float part[2][kGvWaves][M][256];
+    __shared__ float red[kGvWaves][16];
+    if (gemv_all_done(a)) return;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int i = lane & 15, q = lane >> 4;
+    const int K = a.K, N = a.N, nb = a.nb;
+    const uint8_t* __restrict__ W = (const uint8_t*)a.W;
+    const int k0 = wave * lpw * 64 + q * 16;                        // this lane's k at the wave's load 0
+    int nvalid = k0 < K ? (K - k0 + 63) / 64 : 0;                   // loads of this lane that lie inside K (K % 16 == 0: whole or not)
+    if (nvalid > lpw) nvalid = lpw;
+
+    uint4 xf[2 * NL];
+    {
+        const T* xr = (const T*)a.x + (int64_t)(i < nb ? i : 0) * a.x_ld + k0;
+        gv_static_for<2 * NL>([&](auto s_) {
+            constexpr int s = decltype(s_)::value;
+            xf[s] = (s >> 1) < nvalid ? ld16(xr + (s >> 1) * 64 + (s & 1) * 8) : make_uint4(0, 0, 0, 0);
+        });
+        if (a.norm_w) {
+            float ssq = 0.f;
+            gv_static_for<2 * NL>([&](auto s_) { ssq = gv_pack_ssq<T>(xf[decltype(s_)::value], ssq); });
+            const float rstd = gv_rstd_across_waves(ssq, red, wave, lane, K, a.eps);
+            const T* gw = (const T*)a.norm_w + k0;
+            gv_static_for<2 * NL>([&](auto s_) {
+                constexpr int s = decltype(s_)::value;
+                if ((s >> 1) < nvalid) xf[s] = gv_pack_norm<T>(xf[s], ld16(gw + (s >> 1) * 64 + (s & 1) * 8), rstd);
+            });
+        }
+    }
+    const bool svec = gv_scale_vec_ok(w_scale, N);
+    uint4 wa[M][NL];
+    int it = 0;
+    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x, ++it) {
+        int row = tile * 16 + i;
+        if (row >= N) row = N - 1;
+        const GvScale<M> sc = gv_scale_prefetch<M>(w_scale, N, tile, lane, svec);
+        f32x4_t acc[M];
+#pragma unroll
+        for (int m = 0; m < M; ++m) {
+            acc[m] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+            const uint8_t* p = W + ((int64_t)row + (int64_t)m * N) * K + k0;
+            gv_static_for<NL>([&](auto s_) {
+                constexpr int s = decltype(s_)::value;
+                wa[m][s] = s < nvalid ? ld16(p + s * 64) : make_uint4(0, 0, 0, 0);      // code 0 is +0
+            });
+        }
+        gv_static_for<NL>([&](auto s_) {
+            constexpr int s = decltype(s_)::value;
+#pragma unroll
+            for (int m = 0; m < M; ++m) {
+                acc[m] = gv_mfma<T>(gv_dec8<T>(wa[m][s].x, wa[m][s].y), xf[2 * s], acc[m]);
+                acc[m] = gv_mfma<T>(gv_dec8<T>(wa[m][s].z, wa[m][s].w), xf[2 * s + 1], acc[m]);
+            }
+        });
+        GvEpi epi;
+        epi.vec = false;
+        gv_fold_store<T, SILU>(a, &part[it & 1][0][0][0], acc, tile, wave, lane, epi, [&](f32x4_t (&v)[M]) {
+#pragma unroll
+            for (int m = 0; m < M; ++m) v[m] = v[m] * sc.s[m];
+        });
+    }
+}
+
+// the predicate-free stream loops: K == 8 waves x SPW MFMA steps x 32 (SPW = 16: K = 4096; SPW = 43: K = 11008), the structure of
+// gemv_mfma_exact_kernel with half the loads.  A wave's K slice is SPW * 32 bytes per row = SPW / 2 loads of 16 bytes per lane, and
+// for the odd SPW one last load of 8 bytes (one step: lane l bytes (l >> 4) * 8 .. + 7 of the slice's last 32): every load of every
+// lane is in range, no predicate, no branch.  Load slots are walked in chunks of CH through two register buffers; the loads of
+// chunk c + 1 (or of the next tile's chunk 0) are issued before the MFMAs of chunk c.
+// SPW = 43 keeps the nb <= 8 packing of the 16-bit form (lanes 8..15 of a row carry the fragments of steps 22..42 of sequences
+// 0..7, handed down by a row_shl:8 move): 88 VGPRs of activations; the halved load count leaves the rule as it was because the
+// activations, not the weights, fill the registers.  No RMSNorm in that form.
+template <typename T, bool SILU, int SPW>
+__global__ __launch_bounds__(512) void gemv_w8_exact_kernel(const GemvArgs a, const float* __restrict__ w_scale, const int ntiles) {
+    constexpr int M = SILU ? 2 : 1;
+    constexpr bool PACK = SPW > kGvSteps, TAIL = (SPW & 1) != 0;
+    constexpr int NSLOT = (SPW + 1) / 2;                    // loads per lane and row: SPW / 2 of 16 bytes (+ one of 8)
+    constexpr int CH = PACK ? 6 : 4;                        // load slots per chunk
+    constexpr int NCH = (NSLOT + CH - 1) / CH;
+    constexpr int HALF = PACK ? (SPW + 1) / 2 : SPW;        // fragments a lane holds
+    static_assert(NCH % 2 == 0, "an even number of chunks keeps the buffer parity across tiles");
+    __shared__ __attribute__((aligned(16))) float part[2][kGvWaves][M][256];
+    __shared__ float red[kGvWaves][16];
+    if (gemv_all_done(a)) return;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int i = lane & 15, q = lane >> 4;
+    const int K = a.K, N = a.N, nb = a.nb;
+    const uint8_t* __restrict__ W = (const uint8_t*)a.W;
+    const int kw = wave * SPW * 32;                                 // the wave's K slice
+    // k of MFMA step s of this lane, relative to kw
+    auto koff = [&](int s) { return (TAIL && s == SPW - 1) ? s * 32 + q * 8 : (s >> 1) * 64 + (s & 1) * 8 + q * 16; };
+    int tile = blockIdx.x, it = 0;
+    if (tile >= ntiles) return;
+
+    uint4 wa[2][M][CH];
+    auto load_chunk = [&](auto c_, int tl) {                        // chunk c of row tile tl -> buffer c & 1
+        constexpr int c = decltype(c_)::value;
+        int row = tl * 16 + i;
+        if (row >= N) row = N - 1;
+#pragma unroll
+        for (int m = 0; m < M; ++m) {
+            const uint8_t* p = W + ((int64_t)row + (int64_t)m * N) * K + kw;
+            gv_static_for<CH>([&](auto e_) {
+                constexpr int e = decltype(e_)::value, L = c * CH + e;
+                if constexpr (TAIL && L == NSLOT - 1) {
+                    const uint2 t = *reinterpret_cast<const uint2*>(p + (SPW - 1) * 32 + q * 8);
+                    wa[c & 1][m][e] = make_uint4(t.x, t.y, 0, 0);
+                } else if constexpr (L < NSLOT) {
+                    wa[c & 1][m][e] = ld16(p + L * 64 + q * 16);
+                }
+            });
+        }
+    };
+
+    // ---- the wave's slice of the activations, in B-operand order (+ fused RMSNorm) -----------------------------------
+    uint4 xf[HALF];
+    if constexpr (!PACK) {
+        // (lanes of sequences >= nb read sequence 0: their columns of D are never stored)
+        const T* xr = (const T*)a.x + (int64_t)(i < nb ? i : 0) * a.x_ld + kw;
+        gv_static_for<HALF>([&](auto s_) { constexpr int s = decltype(s_)::value; xf[s] = ld16(xr + koff(s)); });
+        load_chunk(std::integral_constant<int, 0>{}, tile);         // the first weights travel while the statistic is formed
+        __builtin_amdgcn_sched_barrier(0);
+        if (a.norm_w) gv_norm_frags<T>(xf, (const T*)a.norm_w + kw, koff, red, wave, lane, K, a.eps);
+    } else {
+        const int seq = i & 7, upper = i >> 3;
+        const T* xr = (const T*)a.x + (int64_t)(seq < nb ? seq : 0) * a.x_ld + kw;
+        gv_static_for<HALF>([&](auto s_) {
+            constexpr int s = decltype(s_)::value;
+            if constexpr (s + HALF < SPW) xf[s] = ld16(xr + (upper ? koff(s + HALF) : koff(s)));
+            else {                                                  // step s + HALF does not exist: the upper lanes hold zeros
+                const uint4 v = ld16(xr + koff(s));
+                xf[s] = upper ? make_uint4(0, 0, 0, 0) : v;
+            }
+        });
+        load_chunk(std::integral_constant<int, 0>{}, tile);
+    }
+    const bool vec_ok = ((a.y_ld | a.res_ld | N) & 3) == 0 && N >= 4 && (a.epi & (SS_EPI_RESIDUAL | SS_EPI_BIAS)) &&
+                        ((((size_t)a.y | (size_t)a.residual | (size_t)a.bias) & 7) == 0);
+    const bool svec = gv_scale_vec_ok(w_scale, N);
+
+    auto tile_body = [&](int tl, int itn, auto has_next_) {
+        constexpr bool has_next = decltype(has_next_)::value;
+        f32x4_t acc[M];
+#pragma unroll
+        for (int m = 0; m < M; ++m) acc[m] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+        GvEpi epi;
+        epi.vec = false;
+        if constexpr (!SILU) epi = gv_epi_prefetch<T>(a, tl, lane, vec_ok);
+        const GvScale<M> sc = gv_scale_prefetch<M>(w_scale, N, tl, lane, svec);
+        gv_static_for<NCH>([&](auto c_) {
+            constexpr int c = decltype(c_)::value;
+            if constexpr (c + 1 < NCH) load_chunk(std::integral_constant<int, c + 1>{}, tl);
+            else if constexpr (has_next) load_chunk(std::integral_constant<int, 0>{}, tl + (int)gridDim.x);
+            __builtin_amdgcn_sched_barrier(0);      // (as in gemv_mfma_exact_kernel: keeps two buffers in flight)
+            gv_static_for<CH>([&](auto e_) {
+                constexpr int e = decltype(e_)::value, L = c * CH + e;
+                if constexpr (L < NSLOT) {
+                    gv_static_for<2>([&](auto h_) {
+                        constexpr int h = decltype(h_)::value, s = 2 * L + h;
+                        if constexpr (s < SPW) {
+                            uint4 b;
+                            if constexpr (!PACK) b = xf[s];
+                            else if constexpr (s < HALF) b = xf[s];
+                            else b = gv_row_shift8(xf[s - HALF]);
+#pragma unroll
+                            for (int m = 0; m < M; ++m) {
+                                const uint4& w = wa[c & 1][m][e];
+                                acc[m] = gv_mfma<T>(h ? gv_dec8<T>(w.z, w.w) : gv_dec8<T>(w.x, w.y), b, acc[m]);
+                            }
+                        }
+                    });
+                }
+            });
+            __builtin_amdgcn_sched_barrier(0);
+        });
+        gv_fold_store<T, SILU>(a, &part[itn & 1][0][0][0], acc, tl, wave, lane, epi, [&](f32x4_t (&v)[M]) {
+#pragma unroll
+            for (int m = 0; m < M; ++m) v[m] = v[m] * sc.s[m];
+        });
     };
     for (; tile + (int)gridDim.x < ntiles; tile += gridDim.x, ++it) tile_body(tile, it, std::true_type{});
     tile_body(tile, it, std::false_type{});
@@ -990,6 +1234,36 @@ static int gemv_plan(int64_t N, int64_t K, int nb, int dtype, int epi, bool norm
     return SS_OK;
 }
 
+// The fp8-weight call: always an MFMA form (one sequence too).  K = 4096 and K = 11008 take the stream loops, every other
+// K <= 4096 (and the knob gemv_mfma_generic) the predicated kernel; the packed 11008-deep loop takes <= 8 sequences, so 9..16
+// run as two sweeps.  Anything else is refused here, before a launch.
+static int gemv_w8_plan(int64_t N, int64_t K, int nb, int dtype, int epi, bool norm, GemvPlan& plan) {
+    SS_REQUIRE(dtype == SS_BF16 || dtype == SS_F16, "gemv_w8: the model dtype must be bf16 or fp16 (got %d)", dtype);
+    constexpr int64_t K16 = kGvWaves * kGvSteps * 32, K43 = kGvWaves * 43 * 32;
+    SS_REQUIRE(N > 0 && K > 0 && K % 16 == 0 && (K <= K16 || K == K43),
+               "gemv_w8: K=%lld must be a positive multiple of 16, at most %lld or exactly %lld (N=%lld)", (long long)K, (long long)K16,
+               (long long)K43, (long long)N);
+    SS_REQUIRE(N < (1ll << 30), "gemv_w8: N=%lld too large", (long long)N);
+    SS_REQUIRE(!(epi & SS_EPI_SILU_MUL) || !(epi & (SS_EPI_BIAS | SS_EPI_RESIDUAL | SS_EPI_GELU)),
+               "gemv_w8: SILU_MUL cannot be combined with other epilogues");
+    SS_REQUIRE(!(epi & ~(SS_EPI_BIAS | SS_EPI_RESIDUAL | SS_EPI_SILU_MUL)), "gemv_w8: epilogue %d not supported", epi);
+    SS_REQUIRE(nb >= 1 && nb <= 16, "gemv_w8: batch %d unsupported (1..16)", nb);
+    SS_REQUIRE(K != K43 || !norm, "gemv_w8: no RMSNorm prologue at K=%lld", (long long)K);
+    const bool silu = (epi & SS_EPI_SILU_MUL) != 0;
+    const int ntiles = cdiv(N, 16), blocks = cdiv(ntiles, cdiv(ntiles, knob(K_gemv_mfma_blocks)));
+    const bool exact16 = K == K16 && !knob(K_gemv_mfma_generic);
+    const int sweeps = (K == K43 && nb > 8) ? 2 : 1;
+    for (int j = 0; j < sweeps; ++j) {
+        const int seq0 = j * (nb / 2), n = sweeps == 1 ? nb : (j ? nb - nb / 2 : nb / 2);
+        GemvLaunch l = {seq0, n, SS_GEMV_FORM_W8, 0, blocks, 512, 0, 0, silu, 0};
+        if (K == K43) l.form = SS_GEMV_FORM_W8_EXACT43, l.param = 43;
+        else if (exact16) l.form = SS_GEMV_FORM_W8_EXACT16, l.param = kGvSteps;
+        else l.param = 2 * cdiv(cdiv(K, 64), kGvWaves);          // MFMA steps per wave: two per 16-byte load
+        plan.l[plan.n++] = l;
+    }
+    return SS_OK;
+}
+
 // ---- kernel tables --------------------------------------------------------------------------------------------------------------------
 using GemvKern = void (*)(GemvArgs);
 using GemvTileKern = void (*)(GemvArgs, int);
@@ -1012,6 +1286,11 @@ static GemvTileKern gv_exact_kernel(const GemvLaunch& l) {
                                              {gemv_mfma_exact_kernel<T, true, SPW, false>, gemv_mfma_exact_kernel<T, true, SPW, true>}};
     return k[l.silu][l.nt];
 }
+using GemvW8Kern = void (*)(GemvArgs, const float*, int);
+template <typename T, int SPW>
+static GemvW8Kern gv_w8_exact_kernel(const GemvLaunch& l) {
+    return l.silu ? gemv_w8_exact_kernel<T, true, SPW> : gemv_w8_exact_kernel<T, false, SPW>;
+}
 template <bool SILU>
 static int gemv_run_split(const GemvLaunch& l, const GemvArgs& a, hipStream_t s) {
     SS_DYN_LDS(gemv_split_f32_kernel<SILU>, (size_t)GvSplitLds(kGsSlice, true).bytes);   // the largest request: full slice, SiLU pair
@@ -1020,7 +1299,7 @@ static int gemv_run_split(const GemvLaunch& l, const GemvArgs& a, hipStream_t s)
 }
 
 template <typename T>
-static int gemv_run(const GemvPlan& plan, const GemvArgs& args, hipStream_t s) {
+static int gemv_run(const GemvPlan& plan, const GemvArgs& args, hipStream_t s, const float* w_scale = nullptr) {
     for (int j = 0; j < plan.n; ++j) {
         const GemvLaunch& l = plan.l[j];
         GemvArgs a = args;
@@ -1038,6 +1317,12 @@ static int gemv_run(const GemvPlan& plan, const GemvArgs& args, hipStream_t s) {
         } else if constexpr (sizeof(T) == 4) {
             const int rc = l.silu ? gemv_run_split<true>(l, a, s) : gemv_run_split<false>(l, a, s);
             if (rc) return rc;
+        } else if (l.form == SS_GEMV_FORM_W8) {
+            void (*const k)(GemvArgs, const float*, int, int) = l.silu ? gemv_w8_kernel<T, true> : gemv_w8_kernel<T, false>;
+            hipLaunchKernelGGL(k, g, b, 0, s, a, w_scale, l.param / 2, cdiv(a.N, 16));
+        } else if (l.form == SS_GEMV_FORM_W8_EXACT16 || l.form == SS_GEMV_FORM_W8_EXACT43) {
+            const GemvW8Kern k = l.form == SS_GEMV_FORM_W8_EXACT16 ? gv_w8_exact_kernel<T, 16>(l) : gv_w8_exact_kernel<T, 43>(l);
+            hipLaunchKernelGGL(k, g, b, 0, s, a, w_scale, cdiv(a.N, 16));
         } else if (l.form == SS_GEMV_FORM_MFMA) {
             void (*const k)(GemvArgs, int, int) = l.silu ? gemv_mfma_kernel<T, true> : gemv_mfma_kernel<T, false>;
             hipLaunchKernelGGL(k, g, b, 0, s, a, l.param, cdiv(a.N, 16));
@@ -1045,7 +1330,7 @@ static int gemv_run(const GemvPlan& plan, const GemvArgs& args, hipStream_t s) {
             const GemvTileKern k = l.form == SS_GEMV_FORM_MFMA_EXACT16 ? gv_exact_kernel<T, 16>(l) : gv_exact_kernel<T, 43>(l);
             hipLaunchKernelGGL(k, g, b, 0, s, a, cdiv(a.N, 16));
         }
-        static const char* const what[] = {"gemv", "gemv_ldsx", "gemv_mfma", "gemv_mfma", "gemv_mfma", "gemv_split_f32"};
+        static const char* const what[] = {"gemv", "gemv_ldsx", "gemv_mfma", "gemv_mfma", "gemv_mfma", "gemv_split_f32", "gemv_w8", "gemv_w8", "gemv_w8"};
         SS_LAUNCH_CHECK(what[l.form]);
     }
     return SS_OK;
@@ -1077,6 +1362,29 @@ int gemv_batched_dev(const void* W, const void* x, void* y, int64_t N, int64_t K
     return SS_DISPATCH(dtype, gemv_run, plan, a, s);
 }
 
+int gemv_w8_check(int64_t N, int64_t K, int nb, int dtype, int epi, bool norm) {
+    GemvPlan plan;
+    return gemv_w8_plan(N, K, nb, dtype, epi, norm, plan);
+}
+
+int gemv_w8_batched_dev(const void* Wq, const float* w_scale, const void* x, void* y, int64_t N, int64_t K, const void* norm_w,
+                        float eps, const void* bias, const void* residual, int epi, const int32_t* done_flag, int done_stride,
+                        int nb, int64_t x_ld, int64_t y_ld, int64_t res_ld, int dtype, hipStream_t s) {
+    GemvPlan plan;
+    const int rc = gemv_w8_plan(N, K, nb, dtype, epi, norm_w != nullptr, plan);
+    if (rc) return rc;
+    SS_REQUIRE(Wq && w_scale && x && y, "gemv_w8: NULL argument");
+    SS_REQUIRE(!(epi & SS_EPI_BIAS) || bias, "gemv_w8: BIAS epilogue without a bias");
+    SS_REQUIRE(!(epi & SS_EPI_RESIDUAL) || residual, "gemv_w8: RESIDUAL epilogue without a residual");
+    SS_REQUIRE((((size_t)Wq | (size_t)x | (size_t)norm_w) & 15) == 0 && (x_ld & 7) == 0 && ((size_t)w_scale & 3) == 0,
+               "gemv_w8: Wq, x and norm_w must be 16-byte aligned (x row stride a multiple of 8 elements)");
+    GemvArgs a;
+    a.W = Wq; a.x = x; a.y = y; a.norm_w = norm_w; a.bias = bias; a.residual = residual; a.done_flag = done_flag;
+    a.N = (int)N; a.K = (int)K; a.epi = epi; a.eps = eps; a.use_nt = 0;
+    a.nb = nb; a.done_stride = done_stride; a.x_ld = x_ld; a.y_ld = y_ld; a.res_ld = res_ld;
+    return dtype == SS_BF16 ? gemv_run<bf16_t>(plan, a, s, w_scale) : gemv_run<f16_t>(plan, a, s, w_scale);
+}
+
 int gemv_dev(const void* W, const void* x, void* y, int64_t N, int64_t K, const void* norm_w, float eps,
              const void* bias, const void* residual, int epi, const int32_t* done_flag, int dtype, hipStream_t s) {
     return gemv_batched_dev(W, x, y, N, K, norm_w, eps, bias, residual, epi, done_flag, 0, 1, K, N, N, dtype, s);
@@ -1100,6 +1408,23 @@ extern "C" int ss_gemv_plan(int64_t N, int64_t K, int64_t nb, int dtype, int epi
     const int rc = ss::gemv_plan(N, K, (int)nb, dtype, epilogue, has_norm != 0, aligned16 != 0, plan);
     if (rc) return rc;
     SS_REQUIRE(rows && max_rows >= plan.n, "ss_gemv_plan: %d rows needed, room for %lld", plan.n, (long long)max_rows);
+    memcpy(rows, plan.l, (size_t)plan.n * sizeof(ss::GemvLaunch));
+    return plan.n;
+}
+
+extern "C" int ss_gemv_w8(const void* Wq, const float* w_scale, const void* x, void* y, int64_t N, int64_t K, int64_t nb,
+                          const void* norm_w, float eps, const void* bias, const void* residual, int epilogue, int dtype, void* stream) {
+    SS_REQUIRE(nb >= 1 && nb <= 16, "gemv_w8: batch %lld unsupported (1..16)", (long long)nb);
+    return ss::gemv_w8_batched_dev(Wq, w_scale, x, y, N, K, norm_w, eps, bias, residual, epilogue, nullptr, 0, (int)nb, K, N, N, dtype,
+                                   (hipStream_t)stream);
+}
+
+extern "C" int ss_gemv_w8_plan(int64_t N, int64_t K, int64_t nb, int dtype, int epilogue, int has_norm, int32_t* rows, int64_t max_rows) {
+    ss::GemvPlan plan;
+    SS_REQUIRE(nb >= 1 && nb <= 16, "gemv_w8: batch %lld unsupported (1..16)", (long long)nb);
+    const int rc = ss::gemv_w8_plan(N, K, (int)nb, dtype, epilogue, has_norm != 0, plan);
+    if (rc) return rc;
+    SS_REQUIRE(rows && max_rows >= plan.n, "ss_gemv_w8_plan: %d rows needed, room for %lld", plan.n, (long long)max_rows);
     memcpy(rows, plan.l, (size_t)plan.n * sizeof(ss::GemvLaunch));
     return plan.n;
 }

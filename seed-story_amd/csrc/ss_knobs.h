@@ -56,7 +56,8 @@
     X(unet_graph, 1, "denoising steps replay a captured graph")                                                                      \
     X(gemm_autotune, 1, "tune unseen GEMM shapes on first use")                                                                      \
     X(img_block_logits, 1, "image-token blocks also compute the reference's (unused) per-position logits")                           \
-    X(img_block_decode, KNOB_UNSET, "forced image-token blocks decode as one block; unset = the SEEDSTORY_IMG_BLOCK environment rule")
+    X(img_block_decode, KNOB_UNSET, "forced image-token blocks decode as one block; unset = the SEEDSTORY_IMG_BLOCK environment rule")                \
+    X(llama_decode_w8, 0, "LlamaEngine default of decode_weights: 1 = fp8 (e4m3) weight-only decode projections")
 
 namespace ss {
 
@@ -75,7 +76,7 @@ inline constexpr KnobInfo kKnobs[] = {
     SS_KNOB_LIST(X)
 #undef X
 };
-static_assert(sizeof(kKnobs) / sizeof(kKnobs[0]) == K_COUNT && K_COUNT == 42, "knob list and enum out of step");
+static_assert(sizeof(kKnobs) / sizeof(kKnobs[0]) == K_COUNT && K_COUNT == 43, "knob list and enum out of step");
 
 extern std::atomic<int> g_knobs[K_COUNT];   // ss_runtime.hip, constant-initialised from the defaults
 

@@ -171,6 +171,7 @@ struct SeqGraph {
     int seq0, nb;
     int mode;                // arithmetic knobs the captured kernels were chosen under (gemm_f32_split): part of the cache key
     int capture;             // attention-map capture on: one more launch per layer (a different graph; the buffer is NOT part of the key)
+    int w8;                  // fp8 decode weights on (ss_llama_set_decode_w8): other kernels, other weight pointers
     hipGraph_t graph;
     hipGraphExec_t exec;
 };
@@ -206,6 +207,10 @@ struct ss_llama {
     AttnCaptureDesc cap = {nullptr, 0, 0, 0, 0};
     int cap_row_calls = 0;
     AttnCaptureDesc* cap_desc = nullptr;
+    // fp8 decode weights (ss_llama_set_decode_w8): empty = off
+    std::vector<ss_llama_layer_w8> w8;
+    const void* w8_lm_head = nullptr;
+    const float* w8_lm_scale = nullptr;
     size_t plane_bytes() const { return (size_t)cfg.n_heads * cfg.cache_cap * hd * esz; }       // one layer of one slot
     size_t seq_kv_bytes() const { return (size_t)cfg.n_layers * plane_bytes(); }
     int32_t* upload() const { return pinned + (size_t)n_seq * ST_WORDS; }                        // the state upload area
@@ -315,17 +320,26 @@ static int decode_token(ss_llama* h, hipStream_t s, ProfSink* prof, int seq0, in
     char* logits = h->logits + (size_t)seq0 * g.vocab * e;
     float* attn_ws = (float*)((char*)h->attn_ws + (size_t)seq0 * ss_attn_decode_workspace_bytes(g.n_heads, hd));
     int rc;
+    // the five decode projections: the 16-bit weights, or their fp8 planes + row scales while ss_llama_set_decode_w8 is on
+    const bool w8 = !h->w8.empty();
+    auto proj = [&](const void* W, const void* Wq, const float* sc, const char* x, char* y, int64_t N, int64_t K, const void* norm_w,
+                    const void* residual, int epi, int64_t y_ld, int64_t res_ld) {
+        if (w8)
+            return gemv_w8_batched_dev(Wq, sc, x, y, N, K, norm_w, g.rms_eps, nullptr, residual, epi, done, ST_WORDS, nb, K, y_ld, res_ld, dt, s);
+        return gemv_batched_dev(W, x, y, N, K, norm_w, norm_w ? g.rms_eps : 0.f, nullptr, residual, epi, done, ST_WORDS, nb, K, y_ld, res_ld, dt, s);
+    };
+    static const ss_llama_layer_w8 kNoW8 = {};
 #define MARK(c) do { if (prof) prof->mark(c); } while (0)
     MARK(-1);
     if ((rc = SS_DISPATCH(dt, sample_embed_launch, h, seq0, nb, s))) return rc;
     MARK(3);
     for (int l = 0; l < g.n_layers; ++l) {
         const ss_llama_layer_weights& L = h->layers[l];
+        const ss_llama_layer_w8& Q = w8 ? h->w8[l] : kNoW8;
         char* kc = slot_k(h, seq0, l);
         char* vc = slot_v(h, seq0, l);
         MARK(-1);
-        rc = gemv_batched_dev(L.wqkv, h->x, h->qkv, 3 * H, H, L.ln1, g.rms_eps, nullptr, nullptr, SS_EPI_NONE, done,
-                              ST_WORDS, nb, H, 3 * H, 0, dt, s);
+        rc = proj(L.wqkv, Q.wqkv, Q.s_qkv, h->x, h->qkv, 3 * H, H, L.ln1, nullptr, SS_EPI_NONE, 3 * H, 0);
         if (rc) return rc;
         MARK(0);
         // RoPE(q,k) + KV append + split-KV attention in one kernel (+ the split merge)
@@ -338,23 +352,19 @@ static int decode_token(ss_llama* h, hipStream_t s, ProfSink* prof, int seq0, in
             if (rc) return rc;
         }
         MARK(1);
-        rc = gemv_batched_dev(L.wo, h->attn, h->xn, H, H, nullptr, 0.f, nullptr, h->x, SS_EPI_RESIDUAL, done, ST_WORDS, nb,
-                              H, H, H, dt, s);
+        rc = proj(L.wo, Q.wo, Q.s_o, h->attn, h->xn, H, H, nullptr, h->x, SS_EPI_RESIDUAL, H, H);
         if (rc) return rc;
         MARK(0);
-        rc = gemv_batched_dev(L.wgu, h->xn, h->hm, I, H, L.ln2, g.rms_eps, nullptr, nullptr, SS_EPI_SILU_MUL, done,
-                              ST_WORDS, nb, H, I, 0, dt, s);
+        rc = proj(L.wgu, Q.wgu, Q.s_gu, h->xn, h->hm, I, H, L.ln2, nullptr, SS_EPI_SILU_MUL, I, 0);
         if (rc) return rc;
         MARK(0);
-        rc = gemv_batched_dev(L.wdown, h->hm, h->x, H, I, nullptr, 0.f, nullptr, h->xn, SS_EPI_RESIDUAL, done, ST_WORDS, nb,
-                              I, H, H, dt, s);
+        rc = proj(L.wdown, Q.wdown, Q.s_down, h->hm, h->x, H, I, nullptr, h->xn, SS_EPI_RESIDUAL, H, H);
         if (rc) return rc;
         MARK(2);
     }
     if ((rc = SS_DISPATCH(dt, final_norm_advance_launch, h, seq0, nb, s))) return rc;
     MARK(3);
-    rc = gemv_batched_dev(h->w.lm_head, h->xn, logits, g.vocab, H, nullptr, 0.f, nullptr, nullptr, SS_EPI_NONE, done,
-                          ST_WORDS, nb, H, g.vocab, 0, dt, s);
+    rc = proj(h->w.lm_head, h->w8_lm_head, h->w8_lm_scale, h->xn, logits, g.vocab, H, nullptr, nullptr, SS_EPI_NONE, g.vocab, 0);
     if (rc) return rc;
     MARK(0);
 #undef MARK
@@ -376,10 +386,11 @@ static int sync_lengths(ss_llama* h, int seq0, int nb, hipStream_t s) {
 static int graph_for(ss_llama* h, int seq0, int nb, hipGraphExec_t* out) {
     const int mode = knob(K_gemm_f32_split);
     const int capture = (h->cap.maps && nb == 1) ? 1 : 0;
+    const int w8 = h->w8.empty() ? 0 : 1;
     for (const SeqGraph& sg : h->graphs)
-        if (sg.seq0 == seq0 && sg.nb == nb && sg.mode == mode && sg.capture == capture) { *out = sg.exec; return SS_OK; }
+        if (sg.seq0 == seq0 && sg.nb == nb && sg.mode == mode && sg.capture == capture && sg.w8 == w8) { *out = sg.exec; return SS_OK; }
     SeqGraph sg;
-    sg.seq0 = seq0; sg.nb = nb; sg.mode = mode; sg.capture = capture; sg.graph = nullptr; sg.exec = nullptr;
+    sg.seq0 = seq0; sg.nb = nb; sg.mode = mode; sg.capture = capture; sg.w8 = w8; sg.graph = nullptr; sg.exec = nullptr;
     SS_HIP(hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
     int rc = decode_token(h, h->cap_stream, nullptr, seq0, nb);
     hipError_t ce = hipStreamEndCapture(h->cap_stream, &sg.graph);
@@ -654,6 +665,53 @@ int ss_llama_set_attn_capture(ss_llama* h, void* maps, int64_t n_rows, int64_t l
     return SS_OK;
 }
 
+// the captured fp8 graphs hold the weight pointers of the planes they were captured over: dropped when the planes change
+static void drop_w8_graphs(ss_llama* h) {
+    size_t keep = 0;
+    for (SeqGraph& sg : h->graphs) {
+        if (!sg.w8) { h->graphs[keep++] = sg; continue; }
+        if (sg.exec) hipGraphExecDestroy(sg.exec);
+        if (sg.graph) hipGraphDestroy(sg.graph);
+    }
+    h->graphs.resize(keep);
+}
+
+int ss_llama_set_decode_w8(ss_llama* h, const ss_llama_layer_w8* layers, const void* lm_head_q, const float* lm_head_scale) {
+    SS_REQUIRE(h, "llama_set_decode_w8: null handle");
+    if (!layers) {      // off: the 16-bit graphs are still cached; the fp8 ones go with their planes
+        drop_w8_graphs(h);
+        h->w8.clear();
+        h->w8_lm_head = nullptr;
+        h->w8_lm_scale = nullptr;
+        return SS_OK;
+    }
+    const ss_llama_config& g = h->cfg;
+    SS_REQUIRE(g.dtype == SS_BF16 || g.dtype == SS_F16, "llama_set_decode_w8: fp8 decode weights need a bf16 / fp16 engine (dtype %d)", g.dtype);
+    SS_REQUIRE(lm_head_q && lm_head_scale, "llama_set_decode_w8: NULL lm_head plane or scales");
+    const int64_t H = g.hidden, I = g.inter;
+    // the five projections, at one sequence and at all slots: every shape the decode loop will launch
+    const struct { int64_t N, K; int epi; bool norm; } shapes[5] = {
+        {3 * H, H, SS_EPI_NONE, true}, {H, H, SS_EPI_RESIDUAL, false}, {I, H, SS_EPI_SILU_MUL, true}, {H, I, SS_EPI_RESIDUAL, false},
+        {g.vocab, H, SS_EPI_NONE, false}};
+    for (const auto& sh : shapes) {
+        int rc = gemv_w8_check(sh.N, sh.K, 1, g.dtype, sh.epi, sh.norm);
+        if (!rc) rc = gemv_w8_check(sh.N, sh.K, h->n_seq, g.dtype, sh.epi, sh.norm);
+        if (rc) return rc;
+    }
+    for (int l = 0; l < g.n_layers; ++l) {
+        const ss_llama_layer_w8& Q = layers[l];
+        SS_REQUIRE(Q.wqkv && Q.wo && Q.wgu && Q.wdown && Q.s_qkv && Q.s_o && Q.s_gu && Q.s_down, "llama_set_decode_w8: NULL pointer in layer %d", l);
+        SS_REQUIRE((((size_t)Q.wqkv | (size_t)Q.wo | (size_t)Q.wgu | (size_t)Q.wdown) & 15) == 0,
+                   "llama_set_decode_w8: layer %d: the byte planes must be 16-byte aligned", l);
+    }
+    SS_REQUIRE(((size_t)lm_head_q & 15) == 0, "llama_set_decode_w8: the lm_head plane must be 16-byte aligned");
+    drop_w8_graphs(h);
+    h->w8.assign(layers, layers + g.n_layers);
+    h->w8_lm_head = lm_head_q;
+    h->w8_lm_scale = lm_head_scale;
+    return SS_OK;
+}
+
 int ss_llama_select(ss_llama* h, int32_t seq) {
     SS_REQUIRE(h && seq >= 0 && seq < h->n_seq, "llama_select: sequence slot %d out of range", (int)seq);
     h->cur = seq;
@@ -850,9 +908,16 @@ int ss_llama_profile_decode(ss_llama* h, int64_t n_tokens, float out_ms[8], doub
     for (int i = 0; i < 8; ++i) out_ms[i] /= (float)n_tokens;
     const double H = g.hidden, I = g.inter;
     // class 0 = every GEMV except the down projection (qkv, o, gate|up per layer + lm_head); class 2 = down
-    out_bytes[0] = ((double)g.n_layers * (4.0 * H * H + 2.0 * H * I) + (double)g.vocab * H) * (double)h->esz;
+    // (fp8 decode weights: one byte per weight + the fp32 row scales)
+    const bool w8 = !h->w8.empty();
+    const double wb = w8 ? 1.0 : (double)h->esz;
+    out_bytes[0] = ((double)g.n_layers * (4.0 * H * H + 2.0 * H * I) + (double)g.vocab * H) * wb;
     out_bytes[1] = cnt[0] / (double)n_tokens;
-    out_bytes[2] = (double)g.n_layers * H * I * (double)h->esz;
+    out_bytes[2] = (double)g.n_layers * H * I * wb;
+    if (w8) {
+        out_bytes[0] += 4.0 * ((double)g.n_layers * (4.0 * H + 2.0 * I) + (double)g.vocab);
+        out_bytes[2] += 4.0 * (double)g.n_layers * H;
+    }
     out_bytes[3] = cnt[2] / (double)n_tokens;
     return sync_lengths(h, 0, h->n_seq, s);
 }

@@ -31,6 +31,10 @@ class LlamaLayerWeights(C.Structure):
     _fields_ = [("wqkv", vp), ("wo", vp), ("wgu", vp), ("wdown", vp), ("ln1", vp), ("ln2", vp)]
 
 
+class LlamaLayerW8(C.Structure):
+    _fields_ = [("wqkv", vp), ("wo", vp), ("wgu", vp), ("wdown", vp), ("s_qkv", vp), ("s_o", vp), ("s_gu", vp), ("s_down", vp)]
+
+
 class LlamaWeights(C.Structure):
     _fields_ = [("embed", vp), ("lm_head", vp), ("final_norm", vp), ("rope_cos", vp), ("rope_sin", vp),
                 ("layers", C.POINTER(LlamaLayerWeights))]
@@ -106,6 +110,8 @@ PROTOTYPES = {
     "ss_gemv": (C.c_int, [vp, vp, vp, i64, i64, vp, f32, vp, vp, C.c_int, C.c_int, vp]),
     "ss_gemv_batched": (C.c_int, [vp, vp, vp, i64, i64, i64, vp, f32, vp, vp, C.c_int, C.c_int, vp]),
     "ss_gemv_plan": (C.c_int, [i64, i64, i64, C.c_int, C.c_int, C.c_int, C.c_int, i32p, i64]),
+    "ss_gemv_w8": (C.c_int, [vp, vp, vp, vp, i64, i64, i64, vp, f32, vp, vp, C.c_int, C.c_int, vp]),
+    "ss_gemv_w8_plan": (C.c_int, [i64, i64, i64, C.c_int, C.c_int, C.c_int, i32p, i64]),
     "ss_imgproc_argmax": (C.c_int, [vp, i64, vp, vp, i64, vp, C.c_int, vp]),
     "ss_llama_workspace_bytes": (sz, [C.POINTER(LlamaConfig), i64]),
     "ss_llama_create": (C.c_int, [C.POINTER(LlamaConfig), C.POINTER(LlamaWeights), vp, sz, i64, i32p,
@@ -114,6 +120,7 @@ PROTOTYPES = {
     "ss_llama_select": (C.c_int, [vp, i32]),
     "ss_llama_set_stop_id": (C.c_int, [vp, i32]),
     "ss_llama_set_attn_capture": (C.c_int, [vp, vp, i64, i64, i64, i32, i32]),
+    "ss_llama_set_decode_w8": (C.c_int, [vp, C.POINTER(LlamaLayerW8), vp, vp]),
     "ss_llama_buffer": (vp, [vp, C.c_int]),
     "ss_llama_set_lengths": (C.c_int, [vp, i64, i64, vp]),
     "ss_llama_get_lengths": (C.c_int, [vp, C.POINTER(i64), C.POINTER(i64)]),

@@ -47,7 +47,9 @@ def _prefill_chunked(eng, emb, want_hidden):
 class LlamaEngine:
     def __init__(self, state_dict, *, hidden, n_heads, n_layers, inter, vocab, dtype=torch.bfloat16, device="cuda:0",
                  rms_eps=1e-5, max_pos=4096, cache_cap=2048, max_new=512, max_prefill_rows=1024, img_ids=(),
-                 eos_id=2, lora_scaling=2.0, n_seq=1):
+                 eos_id=2, lora_scaling=2.0, n_seq=1, decode_weights=None):
+        """``decode_weights``: None = the ``llama_decode_w8`` tuning knob decides (default off), "fp8" = decode tokens
+        stream e4m3 copies of the five projections (``enable_decode_fp8``), "16bit" = off whatever the knob says."""
         self.n_seq = int(n_seq)
         self.device = torch.device(device)
         self.dtype = dtype
@@ -59,6 +61,7 @@ class LlamaEngine:
         sd = state_dict
         dev = self.device
         self._keep = []  # tensors the engine points into
+        self._proj = []  # per layer (wqkv, wo, wgu, wdown): what enable_decode_fp8 quantises
 
         def own(t):
             t = t.to(device=dev, dtype=dtype).contiguous()
@@ -80,16 +83,18 @@ class LlamaEngine:
             ln1 = own(sd[pfx + "input_layernorm.weight"])
             ln2 = own(sd[pfx + "post_attention_layernorm.weight"])
             self._keep += [wqkv, o, wgu, d]
+            self._proj.append((wqkv, o, wgu, d))
             layers[l] = _lib.LlamaLayerWeights(wqkv.data_ptr(), o.data_ptr(), wgu.data_ptr(), d.data_ptr(),
                                                ln1.data_ptr(), ln2.data_ptr())
             del q, k, v, g, u
         self._layers = layers
         self._init_engine(max_pos, rms_eps)
+        self._init_decode_weights(decode_weights)
 
     @classmethod
     def from_prebuilt(cls, *, embed, lm_head, final_norm, layers, hidden, n_heads, n_layers, inter, vocab,
                       dtype=torch.bfloat16, device="cuda:0", rms_eps=1e-5, max_pos=4096, cache_cap=2048, max_new=512,
-                      max_prefill_rows=1024, img_ids=(), eos_id=2, n_seq=1):
+                      max_prefill_rows=1024, img_ids=(), eos_id=2, n_seq=1, decode_weights=None):
         """Engine over already merged/concatenated device tensors: ``layers`` is a list of
         ``(wqkv, wo, wgu, wdown, ln1, ln2)`` (used by the synthetic-weight benchmark, which
         creates the 13.5 GB of weights directly on the GPU)."""
@@ -106,11 +111,13 @@ class LlamaEngine:
         cos, sin = rope_tables(self.hd, max_pos, dtype)
         self.rope_cos, self.rope_sin = cos.to(self.device), sin.to(self.device)
         self._keep = [embed, lm_head, final_norm, self.rope_cos, self.rope_sin, layers]
+        self._proj = [tuple(t[:4]) for t in layers]
         arr = (_lib.LlamaLayerWeights * n_layers)()
         for l, t in enumerate(layers):
             arr[l] = _lib.LlamaLayerWeights(*[x.data_ptr() for x in t])
         self._layers = arr
         self._init_engine(max_pos, rms_eps)
+        self._init_decode_weights(decode_weights)
         return self
 
     def _init_engine(self, max_pos, rms_eps):
@@ -131,6 +138,8 @@ class LlamaEngine:
         self._views = {}
         self._cur = 0
         self._capture = None       # (maps, row0, head) while attention-map capture is on
+        self._w8 = None            # tensors of the fp8 decode planes while the option is on
+        self.decode_weights = None
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -254,6 +263,61 @@ class LlamaEngine:
         if self._capture is not None:
             raise _lib.SSError("%s: attention capture is a single-sequence tool (use the single-sequence methods on the "
                                "selected slot)" % what)
+
+    # ---- fp8 (e4m3) weight-only decode -------------------------------------------------------------------
+    def _init_decode_weights(self, decode_weights):
+        if decode_weights is None:      # the knob is a default for the engines that can take it: fp32 (gate mode) engines stay as they are
+            on = _lib.get_tuning("llama_decode_w8", 0) and self.dtype in (torch.bfloat16, torch.float16)
+            decode_weights = "fp8" if on else None
+        if decode_weights not in (None, "16bit", "fp8"):
+            raise ValueError("decode_weights must be None, '16bit' or 'fp8', not %r" % (decode_weights,))
+        if decode_weights == "fp8":
+            self.enable_decode_fp8()
+
+    def enable_decode_fp8(self):
+        """Quantise the engine's own merged weights on the device (one e4m3 scale per output row, ``amax / 448``) and
+        switch the decode projections to them: ``generate`` / ``generate_batch`` / ``profile_decode`` then stream half the
+        weight bytes per token.  Prefill, the image-token block and the one-row lm_head at the end of a prefill keep the
+        16-bit weights, so those stay resident: the option COSTS memory, one byte per projection weight on top (about 6.7 GB
+        for LLaMA-7B).  Off by default: what e4m3 weights do to stories on a real checkpoint has not been measured."""
+        layers = [tuple(ops.quantize_weight_rows_fp8(w) for w in lw) for lw in self._proj]
+        self.set_decode_fp8(layers, ops.quantize_weight_rows_fp8(self.lm_head))
+
+    def set_decode_fp8(self, layers, lm_head):
+        """Caller-supplied planes: ``layers[l]`` = four ``(q uint8 [N, K], scale fp32 [N])`` pairs for wqkv, wo, wgu
+        (= [gate; up]) and wdown in the engine's layouts, ``lm_head`` one such pair.  ``layers=None`` switches the option off.
+        Raises ``SSError`` on an fp32 engine or a projection shape the fp8 kernel does not take."""
+        if layers is None:
+            return self.disable_decode_fp8()
+        shapes = ((3 * self.hidden, self.hidden), (self.hidden, self.hidden), (2 * self.inter, self.hidden), (self.hidden, self.inter))
+        if len(layers) != self.n_layers:
+            raise _lib.SSError("set_decode_fp8: %d layers given, the engine has %d" % (len(layers), self.n_layers))
+        keep = []
+
+        def plane(pair, shape, what):
+            q, s = pair
+            if q.dtype != torch.uint8 or tuple(q.shape) != shape or s.numel() != shape[0]:
+                raise _lib.SSError("set_decode_fp8: %s must be (uint8 %s, scale [%d])" % (what, list(shape), shape[0]))
+            q = q.to(self.device).contiguous()
+            s = s.to(device=self.device, dtype=torch.float32).contiguous()
+            keep.extend((q, s))
+            return q, s
+
+        arr = (_lib.LlamaLayerW8 * self.n_layers)()
+        for l, lw in enumerate(layers):
+            qs = [plane(pr, sh, "layer %d projection %d" % (l, j)) for j, (pr, sh) in enumerate(zip(lw, shapes))]
+            arr[l] = _lib.LlamaLayerW8(*([q.data_ptr() for q, _ in qs] + [s.data_ptr() for _, s in qs]))
+        ql, sl = plane(lm_head, (self.vocab, self.hidden), "lm_head")
+        torch.cuda.current_stream(self.device).synchronize()
+        check(lib().ss_llama_set_decode_w8(self._h, arr, ql.data_ptr(), sl.data_ptr()), "ss_llama_set_decode_w8")
+        self._w8 = keep
+        self.decode_weights = "fp8"
+
+    def disable_decode_fp8(self):
+        torch.cuda.current_stream(self.device).synchronize()
+        check(lib().ss_llama_set_decode_w8(self._h, None, None, None), "ss_llama_set_decode_w8")
+        self._w8 = None
+        self.decode_weights = None
 
     # ---- forward paths ---------------------------------------------------------------------------------
     def _ensure_prefill_tiles(self, M):

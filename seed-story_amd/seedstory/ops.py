@@ -357,6 +357,33 @@ def gemv_batched(w, x, norm_w=None, eps=0.0, bias=None, residual=None, silu_mul=
     return y
 
 
+def gemv_w8(wq, w_scale, x, norm_w=None, eps=0.0, bias=None, residual=None, silu_mul=False, out=None):
+    """``gemv_batched`` over fp8 weights: wq uint8 [N, K] of OCP e4m3fn codes ([2N, K] = [gate; up] with ``silu_mul``), w_scale
+    fp32 with one entry per row of wq; x [nb, K] (nb <= 16) or [K] in bf16 / fp16 -> y [nb, N] or [N] in x's dtype:
+    ``epilogue(w_scale[n] * sum_k dec(wq[n, k]) * x[b, k])``.  K % 16 == 0 and K <= 4096, or K == 11008."""
+    _req(wq); _req(x); _req(w_scale)
+    if wq.dtype != torch.uint8 or w_scale.dtype != torch.float32 or w_scale.numel() != wq.shape[0]:
+        raise _lib.SSError("gemv_w8: wq must be uint8 [N, K] and w_scale fp32 [N]")
+    N, K = wq.shape
+    if silu_mul:
+        N //= 2
+    one = x.dim() == 1
+    nb = 1 if one else x.shape[0]
+    y = _out(out, (N,) if one else (nb, N), x, "gemv_w8")
+    epi = (EPI_BIAS if bias is not None else 0) | (EPI_RESIDUAL if residual is not None else 0) | \
+          (EPI_SILU_MUL if silu_mul else 0)
+    check(lib().ss_gemv_w8(p(wq), p(w_scale), p(x), p(y), N, K, nb, p(norm_w), eps, p(bias), p(residual), epi, dt(x), stream()),
+          "ss_gemv_w8")
+    return y
+
+
+def quantize_weight_rows_fp8(w):
+    """w [N, K] (bf16 / fp16 on the GPU) -> (q uint8 [N, K] of OCP e4m3fn codes, scale fp32 [N] = amax(row) / 448) for
+    ``gemv_w8`` / ``LlamaEngine.set_decode_fp8``: ``scale[n] * dec(q[n])`` is w[n] rounded to e4m3 on the row's own grid.  An
+    all-zero row gets scale 0 and codes 0 (``ss_quantize_rows_fp8`` does that itself), so its output is 0."""
+    return quantize_rows_fp8(w.contiguous())
+
+
 def imgproc_argmax(logits, last_id, img_ids):
     """In-place processor + argmax; returns an int32 device scalar tensor."""
     _req(logits)

@@ -115,6 +115,7 @@ class LlamaForCausalLM(nn.Module):
         self.cache_cap = 2048
         self.max_new = 512
         self.max_prefill_rows = 1280
+        self.decode_weights = None      # "fp8": e4m3 weight-only decode projections (LlamaEngine.enable_decode_fp8); None = the knob
 
     # ---- reference surface ------------------------------------------------------------------
     def get_input_embeddings(self):
@@ -180,7 +181,7 @@ class LlamaForCausalLM(nn.Module):
         lora = getattr(self, "_lora_scaling", None)
         p0 = self.lm_head.weight
         sig = (p0.data_ptr(), p0._version, p0.dtype, str(p0.device), tuple(img_ids), self.cache_cap, self.max_new,
-               self.max_prefill_rows)
+               self.max_prefill_rows, self.decode_weights)
         if self._engine is None or self._engine_sig != sig:
             if not p0.is_cuda:
                 raise RuntimeError("LlamaForCausalLM must be moved to the GPU first (no CPU path)")
@@ -191,7 +192,8 @@ class LlamaForCausalLM(nn.Module):
                                        rms_eps=c.rms_norm_eps, max_pos=c.max_position_embeddings,
                                        cache_cap=self.cache_cap, max_new=self.max_new,
                                        max_prefill_rows=self.max_prefill_rows, img_ids=img_ids,
-                                       eos_id=c.eos_token_id, lora_scaling=lora if lora is not None else 2.0)
+                                       eos_id=c.eos_token_id, lora_scaling=lora if lora is not None else 2.0,
+                                       decode_weights=self.decode_weights)
             self._engine_sig = sig
         return self._engine
 
