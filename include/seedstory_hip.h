@@ -344,6 +344,40 @@ int ss_gemv_w8_plan(int64_t N, int64_t K, int64_t nb, int dtype, int epilogue, i
 int ss_imgproc_argmax(void* logits, int64_t vocab, const int32_t* last_id_dev, const int32_t* img_ids,
                       int64_t n_img_ids, int32_t* token_out_dev, int dtype, void* stream);
 
+/* Sampling in the arg max's place: processor edit -> temperature -> top-k -> top-p -> one draw (Hugging Face's order; this
+ * definition, in fp32, is what is implemented — not the library's arithmetic in the model dtype).
+ *   z        the logits in the model dtype after the processor's in-place edit above.
+ *   successor  last id in img_ids[:-1]: the successor is the token, with certainty, and no draw is consumed.  DEVIATION: the
+ *            reference's processor only makes it overwhelmingly likely (max + 10); the engine's image-token block already
+ *            treats those 65 tokens as forced.
+ *   top-k    top_k > 0: keep i iff z_i >= the k-th largest z; ties are all kept (TopKLogitsWarper).  0 = off.
+ *   weights  w_i = exp((z_i - z_max) / temperature) over the top-k set, fp32; Z_k = sum w.
+ *   top-p    keep i iff A_i < top_p * Z_k, A_i = sum{ w_j : z_j > z_i }, the mass strictly above z_i: the arg max is always
+ *            kept, top_p = 1 keeps the whole top-k set.  DEVIATION: equal to TopPLogitsWarper except that tied values are
+ *            kept or dropped together, and in rounding when a cumulative mass meets top_p * Z_k to ~1e-5.
+ *   draw     u in [0, 1), t = u * Z_P (the kept mass); token = the first kept index, ascending, whose inclusive cumulative
+ *            weight exceeds t; fallback: the last kept index.
+ *   NaN and -inf entries are never kept; a row with nothing else gives token 0 (n_kept 0), like the greedy kernel's guard.
+ *   u        Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; Weyl 0x9E3779B9, 0xBB67AE85), key = the seed as (lo, hi),
+ *            counter = (draw, lane, 0, 0), u = (out0 >> 8) * 2^-24.
+ * Every mass is summed in one fixed order and there are no atomics: the same seed gives the same tokens on every run.
+ * temperature finite and > 0, 0 < top_p <= 1, top_k >= 0: SS_EINVAL otherwise, before any launch. */
+typedef struct ss_sampling {
+    float temperature;
+    float top_p;
+    int32_t top_k;
+    uint64_t seed;
+} ss_sampling;
+
+/* The sampler on rows of logits [rows][ld] (vocab <= 65535 entries each, model dtype), one token per row to
+ * token_out_dev[rows].  u_dev non-NULL: one u per row (clamped to [0, 1)); NULL: Philox with counter (draw0, row).
+ * last_ids_dev int32[rows] + img_ids (device, as in ss_imgproc_argmax), both optional: with both, the processor runs first
+ * and edits the row in place; otherwise the rows are only read.  n_kept_out_dev (optional) int32[rows]: the size of the final
+ * kept set, or 1 on the certain-successor path. */
+int ss_sample_logits(void* logits, int64_t rows, int64_t vocab, int64_t ld, const ss_sampling* p, const float* u_dev,
+                     uint32_t draw0, const int32_t* last_ids_dev, const int32_t* img_ids, int64_t n_img_ids,
+                     int32_t* token_out_dev, int32_t* n_kept_out_dev, int dtype, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * LLaMA decoder engine (native runtime: KV cache, prefill loop, hipGraph-captured decode)
  * ------------------------------------------------------------------------------------- */
@@ -415,6 +449,17 @@ int ss_llama_set_stop_id(ss_llama* h, int32_t token_id);
  * between engine calls, not while one is in flight (it updates the descriptor with a blocking copy). */
 int ss_llama_set_attn_capture(ss_llama* h, void* maps, int64_t n_rows, int64_t ld, int64_t row0, int32_t head,
                               int32_t row_calls);
+
+/* Sampling in the decode loop (definition: ss_sample_logits).  seq = a slot, or -1 for all; p = NULL = greedy (the default).
+ * The parameters, the seed and a per-slot draw counter live in device memory: ss_llama_generate / ss_llama_generate_batch
+ * (eager or captured) then open each token with the sampling kernel, which draws Philox (draw, slot) for a slot with sampling
+ * on and takes the arg max for one with it off (mixed batches work); changing temperature or seed does not re-capture.  A
+ * forced token and the certain image-token successor consume no draw; only a real draw advances the counter, which persists
+ * across generate calls (so the image-token block path and the token-by-token loop give the same sequence) and is reset to 0
+ * by this call.  The captured sampling graph is cached apart from the greedy one; with every addressed slot greedy the decode
+ * token launches exactly what it launched before.  Works with attention-map capture and fp8 decode weights.  Call it between
+ * engine calls (blocking copy).  SS_EINVAL: a parameter outside its range (ss_sampling), or a bad slot. */
+int ss_llama_set_sampling(ss_llama* h, int32_t seq, const ss_sampling* p);
 
 /* fp8 (OCP e4m3fn) weight-only decode.  Per layer: the four byte planes in the 16-bit weights' layouts (wqkv [3*hidden, hidden],
  * wo [hidden, hidden], wgu [2*inter, hidden] = [gate; up], wdown [hidden, inter]) and one fp32 scale per row of each

@@ -88,6 +88,59 @@ __global__ __launch_bounds__(1024) void sample_embed_kernel(T* logits, int vocab
         st16(x + (int64_t)p * V, ld16(embed + (int64_t)tok * hidden + (int64_t)p * V));
 }
 
+// sample_embed_kernel with the sampler in the arg max's place (chosen on the host when a slot of the launch has sampling on,
+// ss_llama_set_sampling).  Per slot, from its SampleParams: sampling off -> the arg max, exactly as above; on -> the certain
+// image-token successor, or one draw (Philox counter (draw, slot)); a forced token wins over either and takes no draw.
+template <typename T, int NS>
+__global__ __launch_bounds__(1024) void sample_embed_draw_kernel(T* logits, int vocab, int32_t* st, SampleParams* samp, int seq0,
+                                                                 const int32_t* __restrict__ img_ids, int n_img_ids,
+                                                                 const int32_t* __restrict__ forced, int32_t* gen_ids,
+                                                                 const T* __restrict__ embed, T* x, int hidden,
+                                                                 int max_new) {
+    __shared__ float sv[16];
+    __shared__ int si[16];
+    __shared__ SampleSmem sm;
+    {
+        const int b = blockIdx.x;
+        logits += (int64_t)b * vocab;
+        st += b * ST_WORDS;
+        samp += b;
+        forced += (int64_t)b * max_new;
+        gen_ids += (int64_t)b * max_new;
+        x += (int64_t)b * hidden;
+    }
+    if (st[ST_DONE]) return;
+    const SampleParams sp = *samp;
+    const int n = st[ST_NGEN];
+    const bool is_forced = n < st[ST_NFORCED];
+    int tok, drew = 0;
+    if (!sp.enabled || is_forced) {     // (uniform over the block) the greedy kernel's path; a forced token overrides its result
+        tok = imgproc_argmax_block<T>(logits, vocab, st[ST_LAST], img_ids, n_img_ids, sv, si);
+        if ((unsigned)tok >= (unsigned)vocab) tok = 0;
+        if (is_forced) tok = forced[n];
+    } else {
+        int nk;
+        const float u = philox_uniform(sp.seed_lo, sp.seed_hi, sp.draw, (uint32_t)(seq0 + blockIdx.x));
+        tok = imgproc_sample_block<T, NS>(logits, vocab, true, st[ST_LAST], img_ids, n_img_ids, sp.inv_temp, sp.top_p, sp.top_k,
+                                          u, sv, si, sm, &nk, &drew);
+    }
+    const int eos_word = st[ST_EOS];
+    const int eos_id = eos_word & 0xFFFF, stop2 = (eos_word >> 16) - 1;
+    const bool stop = (tok == eos_id) || (tok == stop2) || (n + 1 >= st[ST_LIMIT]);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        gen_ids[n] = tok;
+        st[ST_LAST] = tok;
+        st[ST_NGEN] = n + 1;
+        if (stop) st[ST_DONE] = 1;
+        if (drew) samp->draw = sp.draw + 1;
+    }
+    if (stop) return;
+    constexpr int V = Tr<T>::kVec;
+    for (int p = threadIdx.x; p < hidden / V; p += blockDim.x)
+        st16(x + (int64_t)p * V, ld16(embed + (int64_t)tok * hidden + (int64_t)p * V));
+}
+
 // final RMSNorm of the single decode row: writes the fixed lm_head input buffer AND the
 // hidden-state ring row (n_gen - 1), then advances kv_len / pos.  One block of 256 per sequence.
 template <typename T>
@@ -172,6 +225,7 @@ struct SeqGraph {
     int mode;                // arithmetic knobs the captured kernels were chosen under (gemm_f32_split): part of the cache key
     int capture;             // attention-map capture on: one more launch per layer (a different graph; the buffer is NOT part of the key)
     int w8;                  // fp8 decode weights on (ss_llama_set_decode_w8): other kernels, other weight pointers
+    int sampling;            // a slot of [seq0, seq0+nb) has sampling on (ss_llama_set_sampling): the sampling kernel opens the token
     hipGraph_t graph;
     hipGraphExec_t exec;
 };
@@ -211,6 +265,13 @@ struct ss_llama {
     std::vector<ss_llama_layer_w8> w8;
     const void* w8_lm_head = nullptr;
     const float* w8_lm_scale = nullptr;
+    // sampling (ss_llama_set_sampling): per-slot parameters + draw counter in device memory, which slots have it on here
+    SampleParams* samp = nullptr;       // [n_seq]
+    std::vector<char> samp_on;
+    bool sampling_in(int seq0, int nb) const {
+        for (int b = seq0; b < seq0 + nb; ++b) if (samp_on[b]) return true;
+        return false;
+    }
     size_t plane_bytes() const { return (size_t)cfg.n_heads * cfg.cache_cap * hd * esz; }       // one layer of one slot
     size_t seq_kv_bytes() const { return (size_t)cfg.n_layers * plane_bytes(); }
     int32_t* upload() const { return pinned + (size_t)n_seq * ST_WORDS; }                        // the state upload area
@@ -269,6 +330,7 @@ static void carve(ss_llama* h, Carver& c) {
     h->splitk_bytes = sk;
     h->splitk_ws = sk ? c.take(sk) : nullptr;
     h->cap_desc = (AttnCaptureDesc*)c.take(sizeof(AttnCaptureDesc));     // zeroed with the workspace: capture off
+    h->samp = (SampleParams*)c.take(S * sizeof(SampleParams));           // zeroed with the workspace: every slot greedy
 }
 
 static int cfg_n_seq(const ss_llama_config* cfg) { return cfg->n_seq > 0 ? cfg->n_seq : 1; }
@@ -296,6 +358,20 @@ static int sample_embed_launch(ss_llama* h, int seq0, int nb, hipStream_t s) {
                        h->forced + (size_t)seq0 * g.max_new, h->gen_ids + (size_t)seq0 * g.max_new, (const T*)h->w.embed,
                        (T*)h->x, g.hidden, g.max_new);
     SS_LAUNCH_CHECK("sample_embed");
+    return SS_OK;
+}
+
+template <typename T>
+static int sample_embed_draw_launch(ss_llama* h, int seq0, int nb, hipStream_t s) {
+    const ss_llama_config& g = h->cfg;
+#define SS_DRAW_ARGS dim3((unsigned)nb), dim3(1024), 0, s, (T*)h->logits + (size_t)seq0 * g.vocab, g.vocab,                        \
+                     h->state + (size_t)seq0 * ST_WORDS, h->samp + seq0, seq0, h->img_ids, g.n_img_ids,                            \
+                     h->forced + (size_t)seq0 * g.max_new, h->gen_ids + (size_t)seq0 * g.max_new, (const T*)h->w.embed, (T*)h->x,  \
+                     g.hidden, g.max_new
+    if (sample_ns_half_fits(g.vocab)) hipLaunchKernelGGL((sample_embed_draw_kernel<T, sample_ns_full<T>() / 2>), SS_DRAW_ARGS);
+    else hipLaunchKernelGGL((sample_embed_draw_kernel<T, sample_ns_full<T>()>), SS_DRAW_ARGS);
+#undef SS_DRAW_ARGS
+    SS_LAUNCH_CHECK("sample_embed_draw");
     return SS_OK;
 }
 
@@ -331,7 +407,10 @@ static int decode_token(ss_llama* h, hipStream_t s, ProfSink* prof, int seq0, in
     static const ss_llama_layer_w8 kNoW8 = {};
 #define MARK(c) do { if (prof) prof->mark(c); } while (0)
     MARK(-1);
-    if ((rc = SS_DISPATCH(dt, sample_embed_launch, h, seq0, nb, s))) return rc;
+    // greedy slots only (the default): the launch it has always been
+    if (h->sampling_in(seq0, nb)) rc = SS_DISPATCH(dt, sample_embed_draw_launch, h, seq0, nb, s);
+    else rc = SS_DISPATCH(dt, sample_embed_launch, h, seq0, nb, s);
+    if (rc) return rc;
     MARK(3);
     for (int l = 0; l < g.n_layers; ++l) {
         const ss_llama_layer_weights& L = h->layers[l];
@@ -387,10 +466,15 @@ static int graph_for(ss_llama* h, int seq0, int nb, hipGraphExec_t* out) {
     const int mode = knob(K_gemm_f32_split);
     const int capture = (h->cap.maps && nb == 1) ? 1 : 0;
     const int w8 = h->w8.empty() ? 0 : 1;
+    const int sampling = h->sampling_in(seq0, nb) ? 1 : 0;
     for (const SeqGraph& sg : h->graphs)
-        if (sg.seq0 == seq0 && sg.nb == nb && sg.mode == mode && sg.capture == capture && sg.w8 == w8) { *out = sg.exec; return SS_OK; }
+        if (sg.seq0 == seq0 && sg.nb == nb && sg.mode == mode && sg.capture == capture && sg.w8 == w8 && sg.sampling == sampling) {
+            *out = sg.exec;
+            return SS_OK;
+        }
     SeqGraph sg;
-    sg.seq0 = seq0; sg.nb = nb; sg.mode = mode; sg.capture = capture; sg.w8 = w8; sg.graph = nullptr; sg.exec = nullptr;
+    sg.seq0 = seq0; sg.nb = nb; sg.mode = mode; sg.capture = capture; sg.w8 = w8; sg.sampling = sampling;
+    sg.graph = nullptr; sg.exec = nullptr;
     SS_HIP(hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
     int rc = decode_token(h, h->cap_stream, nullptr, seq0, nb);
     hipError_t ce = hipStreamEndCapture(h->cap_stream, &sg.graph);
@@ -612,6 +696,7 @@ int ss_llama_create(const ss_llama_config* cfg, const ss_llama_weights* w, void*
     }
     h->kv_len.assign(h->n_seq, 0);
     h->pos.assign(h->n_seq, 0);
+    h->samp_on.assign(h->n_seq, 0);
     hipError_t e = hipStreamCreateWithFlags(&h->cap_stream, hipStreamNonBlocking);
     if (e == hipSuccess)
         e = hipHostMalloc((void**)&h->pinned, (size_t)h->n_seq * 2 * ST_WORDS * sizeof(int32_t) + 64, hipHostMallocDefault);
@@ -662,6 +747,21 @@ int ss_llama_set_attn_capture(ss_llama* h, void* maps, int64_t n_rows, int64_t l
     SS_HIP(hipMemcpy(h->cap_desc, &d, sizeof(d), hipMemcpyHostToDevice));
     h->cap = d;
     h->cap_row_calls = maps ? row_calls : 0;
+    return SS_OK;
+}
+
+int ss_llama_set_sampling(ss_llama* h, int32_t seq, const ss_sampling* p) {
+    SS_REQUIRE(h, "llama_set_sampling: null handle");
+    SS_REQUIRE(seq >= -1 && seq < h->n_seq, "llama_set_sampling: sequence slot %d out of range (-1 = all, < %d)", (int)seq, h->n_seq);
+    SampleParams sp = {1.0f, 1.0f, 0, 0u, 0u, 0u, 0, 0};       // greedy
+    if (p)
+        if (int rc = sampling_params(p, "llama_set_sampling", &sp)) return rc;
+    // every decode loop of this engine has synchronised before it returned: nothing in flight reads the block
+    const int b0 = seq < 0 ? 0 : seq, b1 = seq < 0 ? h->n_seq : seq + 1;
+    for (int b = b0; b < b1; ++b) {
+        SS_HIP(hipMemcpy(h->samp + b, &sp, sizeof(sp), hipMemcpyHostToDevice));
+        h->samp_on[b] = p ? 1 : 0;
+    }
     return SS_OK;
 }
 

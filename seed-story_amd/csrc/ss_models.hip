@@ -32,6 +32,42 @@ int imgproc_argmax_launch(void* logits, int64_t vocab, const int32_t* last_id, c
     return SS_OK;
 }
 
+// ss_sample_logits: one block per row
+template <typename T, int NS>
+__global__ __launch_bounds__(1024) void sample_logits_kernel(T* logits, int vocab, int64_t ld, SampleParams p,
+                                                             const float* __restrict__ u_dev, uint32_t draw0,
+                                                             const int32_t* __restrict__ last_ids, const int32_t* img_ids,
+                                                             int n_img_ids, int32_t* tok, int32_t* n_kept) {
+    __shared__ float sv[16];
+    __shared__ int si[16];
+    __shared__ SampleSmem sm;
+    const int r = blockIdx.x;
+    logits += (int64_t)r * ld;
+    float u = u_dev ? u_dev[r] : philox_uniform(p.seed_lo, p.seed_hi, draw0, (uint32_t)r);
+    u = fminf(fmaxf(u, 0.f), 0.99999994f);      // a caller's u outside [0, 1) (or NaN) is clamped
+    int nk = 0, drew = 0;
+    const int t = imgproc_sample_block<T, NS>(logits, vocab, last_ids != nullptr, last_ids ? last_ids[r] : -1, img_ids,
+                                              n_img_ids, p.inv_temp, p.top_p, p.top_k, u, sv, si, sm, &nk, &drew);
+    if (threadIdx.x == 0) {
+        tok[r] = t;
+        if (n_kept) n_kept[r] = nk;
+    }
+}
+
+template <typename T>
+int sample_logits_launch(void* logits, int64_t rows, int64_t vocab, int64_t ld, const SampleParams& p, const float* u_dev,
+                         uint32_t draw0, const int32_t* last_ids, const int32_t* img_ids, int64_t n, int32_t* tok,
+                         int32_t* n_kept, hipStream_t s) {
+    if (sample_ns_half_fits(vocab))
+        hipLaunchKernelGGL((sample_logits_kernel<T, sample_ns_full<T>() / 2>), dim3((unsigned)rows), dim3(1024), 0, s, (T*)logits,
+                           (int)vocab, ld, p, u_dev, draw0, last_ids, img_ids, (int)n, tok, n_kept);
+    else
+        hipLaunchKernelGGL((sample_logits_kernel<T, sample_ns_full<T>()>), dim3((unsigned)rows), dim3(1024), 0, s, (T*)logits,
+                           (int)vocab, ld, p, u_dev, draw0, last_ids, img_ids, (int)n, tok, n_kept);
+    SS_LAUNCH_CHECK("sample_logits");
+    return SS_OK;
+}
+
 struct Bump {
     char* p; size_t off, cap;
     void* take(size_t bytes) { void* r = p + off; off += (bytes + 255) / 256 * 256; return r; }
@@ -47,6 +83,21 @@ int ss_imgproc_argmax(void* logits, int64_t vocab, const int32_t* last_id_dev, c
     SS_REQUIRE(logits && last_id_dev && token_out_dev && vocab > 0, "imgproc_argmax: bad arguments");
     return SS_DISPATCH(dtype, imgproc_argmax_launch, logits, vocab, last_id_dev, img_ids, n_img_ids, token_out_dev,
                        (hipStream_t)stream);
+}
+
+int ss_sample_logits(void* logits, int64_t rows, int64_t vocab, int64_t ld, const ss_sampling* p, const float* u_dev,
+                     uint32_t draw0, const int32_t* last_ids_dev, const int32_t* img_ids, int64_t n_img_ids,
+                     int32_t* token_out_dev, int32_t* n_kept_out_dev, int dtype, void* stream) {
+    SS_REQUIRE(logits && token_out_dev && p, "sample_logits: null argument");
+    SS_REQUIRE(rows > 0 && rows <= 0x7FFFFFFF && vocab > 0 && vocab <= 65535 && ld >= vocab,
+               "sample_logits: bad shape (rows=%lld vocab=%lld ld=%lld; vocab <= 65535)", (long long)rows, (long long)vocab,
+               (long long)ld);
+    SS_REQUIRE(n_img_ids >= 0 && n_img_ids <= 1024, "sample_logits: n_img_ids=%lld out of range (0..1024)", (long long)n_img_ids);
+    SampleParams sp;
+    if (int rc = sampling_params(p, "sample_logits", &sp)) return rc;
+    const bool proc = last_ids_dev && img_ids;
+    return SS_DISPATCH(dtype, sample_logits_launch, logits, rows, vocab, ld, sp, u_dev, draw0, proc ? last_ids_dev : nullptr,
+                       proc ? img_ids : nullptr, proc ? n_img_ids : 0, token_out_dev, n_kept_out_dev, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -319,6 +319,27 @@ class LlamaEngine:
         self._w8 = None
         self.decode_weights = None
 
+    # ---- sampling ------------------------------------------------------------------------------------------------
+    def set_sampling(self, temperature=1.0, top_k=0, top_p=1.0, seed=0, slot=None):
+        """Sampling instead of the arg max in ``generate`` / ``generate_batch`` (and the image-block variants), for ``slot``
+        or, with None, every slot: image-token processor -> temperature -> top-k (0 = off) -> top-p -> one Philox4x32-10 draw
+        with key ``seed`` and counter (draw, slot) — slots given one seed still diverge.  The definition and its two
+        deviations from Hugging Face's warpers (the image-token successor is certain; top-p keeps tied values together) are
+        in include/seedstory_hip.h.  Runs on the device inside the decode token (eager or captured; a graph of its own, cached
+        apart from the greedy one); the parameters and the per-slot draw counter live in device memory, so another
+        temperature or seed does not re-capture.  Forced tokens and the certain successor take no draw.  The counter
+        persists across calls and is reset by this method and ``set_greedy``.  Bad parameters raise ``SSError``."""
+        sp = ops.sampling_struct(temperature, top_k, top_p, seed)
+        self._set_sampling(slot, C.byref(sp))
+
+    def set_greedy(self, slot=None):
+        """Back to the arg max (the default) for ``slot`` or, with None, every slot."""
+        self._set_sampling(slot, None)
+
+    def _set_sampling(self, slot, sp):
+        torch.cuda.current_stream(self.device).synchronize()
+        check(lib().ss_llama_set_sampling(self._h, -1 if slot is None else int(slot), sp), "ss_llama_set_sampling")
+
     # ---- forward paths ---------------------------------------------------------------------------------
     def _ensure_prefill_tiles(self, M):
         if M > 128:      # the four prefill projections of this row-count bucket (tile table: seedstory/tune.py)
@@ -369,7 +390,8 @@ class LlamaEngine:
         return out
 
     def generate(self, n_steps, last_prompt_id, forced=None):
-        """Greedy decode from the current logits; returns the number of generated tokens."""
+        """Decode from the current logits — greedy, or sampled after ``set_sampling``; ``forced`` tokens win over either.
+        Returns the number of generated tokens."""
         forced = [] if forced is None else [int(t) for t in forced]
         arr = (C.c_int32 * max(1, len(forced)))(*forced)
         n = C.c_int64()
@@ -378,8 +400,8 @@ class LlamaEngine:
         return n.value
 
     def generate_batch(self, n_steps, last_prompt_ids, forced=None, active=None):
-        """Greedy decode of all ``n_seq`` slots in lock-step (one sweep of the weights per token
-        for the whole batch).  ``last_prompt_ids[b]``, optional ``forced[b]`` token lists and
+        """Decode of all ``n_seq`` slots in lock-step (one sweep of the weights per token for the whole batch): greedy, or
+        per slot sampled after ``set_sampling`` (mixed batches work).  ``last_prompt_ids[b]``, optional ``forced[b]`` token lists and
         ``active[b]`` flags are per slot; returns the per-slot generated-token counts."""
         self._refuse_capture("generate_batch")
         S = self.n_seq

@@ -396,6 +396,48 @@ def imgproc_argmax(logits, last_id, img_ids):
     return tok
 
 
+def sampling_struct(temperature=1.0, top_k=0, top_p=1.0, seed=0):
+    """The C ABI's ``ss_sampling``.  Ranges are checked by the library (``SSError``); only what ctypes would mangle silently
+    is checked here."""
+    if int(top_k) != top_k or not -2 ** 31 <= int(top_k) < 2 ** 31:
+        raise _lib.SSError("top_k must be an integer, not %r" % (top_k,))
+    return _lib.Sampling(float(temperature), float(top_p), int(top_k), int(seed) & (2 ** 64 - 1))
+
+
+def sample_logits(logits, temperature=1.0, top_k=0, top_p=1.0, seed=0, u=None, draw0=0, last_ids=None, img_ids=None,
+                  return_n_kept=False):
+    """One token per row of ``logits`` [rows, vocab] (or [vocab]; rows may be strided, unit stride inside a row) by the
+    engine's sampler: processor edit (only with ``last_ids`` [rows] AND ``img_ids``; in place, like ``imgproc_argmax``) ->
+    temperature -> top-k (0 = off) -> top-p -> one draw.  ``u`` float32 [rows] supplies the uniforms; None draws Philox4x32-10
+    with key ``seed`` and counter (``draw0``, row).  Returns int32 [rows] tokens (and the kept-set sizes with
+    ``return_n_kept``).  The definition is in include/seedstory_hip.h (``ss_sample_logits``)."""
+    if not logits.is_cuda:
+        raise _lib.SSError("logits must live on the GPU (there is no CPU path)")
+    lg = logits if logits.dim() == 2 else logits.view(1, -1)
+    if lg.dim() != 2 or (lg.shape[1] > 1 and lg.stride(1) != 1) or (lg.shape[0] > 1 and lg.stride(0) < lg.shape[1]):
+        raise _lib.SSError("logits must be [rows, vocab] with unit stride inside a row")
+    rows, vocab = lg.shape
+    dev = lg.device
+    sp = sampling_struct(temperature, top_k, top_p, seed)
+    if u is not None:
+        u = _req(torch.as_tensor(u, dtype=torch.float32, device=dev).reshape(-1), "u")
+        if u.numel() != rows:
+            raise _lib.SSError("u must hold one value per row (%d), not %d" % (rows, u.numel()))
+    last = ids = None
+    if last_ids is not None and img_ids is not None:
+        last = torch.as_tensor(last_ids, dtype=torch.int32, device=dev).reshape(-1).contiguous()
+        if last.numel() != rows:
+            raise _lib.SSError("last_ids must hold one id per row (%d), not %d" % (rows, last.numel()))
+        ids = torch.as_tensor(list(img_ids), dtype=torch.int32, device=dev)
+    tok = torch.zeros(rows, dtype=torch.int32, device=dev)
+    kept = torch.zeros(rows, dtype=torch.int32, device=dev) if return_n_kept else None
+    import ctypes as C
+    check(lib().ss_sample_logits(p(lg), rows, vocab, lg.stride(0) if rows > 1 else vocab, C.byref(sp), p(u), int(draw0) & 0xFFFFFFFF,
+                                 p(last), p(ids), 0 if ids is None else ids.numel(), p(tok), p(kept), dt(lg), stream()),
+          "ss_sample_logits")
+    return (tok, kept) if return_n_kept else tok
+
+
 # ---- SDXL de-tokenizer ops (NHWC activations: [B, H*W, C]) ------------------------------------------
 def conv3x3(x, w, B, H, W, stride=1, upsample=False, bias=None, rowvec=None, residual=None, rowvec_stride=0, out=None):
     """x [B*H*W, Cin] (NHWC) -> [B*Ho*Wo, Cout]; w [Cout, 9*Cin] (tap-major, channel-minor)."""

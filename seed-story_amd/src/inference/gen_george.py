@@ -149,6 +149,17 @@ def build(args, device, dtype):
     return tokenizer, adapter.image_transform, vit, agent, adapter
 
 
+def sample_kwargs(args, j, step):
+    """``--sample``: what ``ContinuousLVLM.generate`` gets on top.  This driver runs its stories one after another on one
+    engine slot, one ``generate`` call per story step, so ``--seed`` is advanced per call (story j, step): a fixed seed would
+    replay one random stream at every step.  Without ``--seed`` the model's own call counter over ``torch.initial_seed()``
+    does the same."""
+    if not getattr(args, "sample", False):
+        return {}
+    seed = None if args.seed is None else int(args.seed) + 100003 * j + step
+    return dict(do_sample=True, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, seed=seed)
+
+
 def run_story(args, j, question, image, tokenizer, transform, vit, agent, adapter, device, dtype):
     save_folder = os.path.join(args.out, "val_%d" % j)
     os.makedirs(save_folder, exist_ok=True)
@@ -179,7 +190,7 @@ def run_story(args, j, question, image, tokenizer, transform, vit, agent, adapte
         ids_mask, emb_mask = ctx.masks(device)
         out = agent.generate(tokenizer=tokenizer, input_ids=ctx.input_ids(device), image_embeds=ctx.image_embeds,
                              embeds_cmp_mask=emb_mask, ids_cmp_mask=ids_mask, max_new_tokens=500, num_img_gen_tokens=64,
-                             forced_tokens=forced)
+                             forced_tokens=forced, **sample_kwargs(args, j, step))
         if args.save_attn:                                       # [layers, rows, width], head 0 (NaN beyond each row's keys)
             torch.save(torch.stack([a[0] for a in out['attn_weights']]).cpu(),
                        os.path.join(args.save_attn, "val_%d_step_%02d.pt" % (j, step)))
@@ -219,6 +230,12 @@ def main():
     ap.add_argument("--parity", action="store_true",
                     help="string-level prompt bookkeeping exactly as the reference driver (decode -> scrub -> re-tokenise, "
                          "'[INST]'-length skip on eviction) instead of the id-level context")
+    ap.add_argument("--sample", action="store_true",
+                    help="sample the free tokens on the device (temperature -> top-k -> top-p -> one draw) instead of the arg max")
+    ap.add_argument("--temperature", type=float, default=0.7)
+    ap.add_argument("--top-k", type=int, default=0, help="0 = off")
+    ap.add_argument("--top-p", type=float, default=0.5)
+    ap.add_argument("--seed", type=int, default=None, help="with --sample: reproducible stories (default: torch.initial_seed())")
     args = ap.parse_args()
     device = "cuda:0"
     dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float16

@@ -335,15 +335,24 @@ class LlamaForCausalLM(nn.Module):
     @torch.no_grad()
     def generate(self, input_ids=None, inputs_embeds=None, logits_processor=None, past_key_values=None,
                  max_new_tokens=120, output_hidden_states=True, return_dict_in_generate=True, forced_tokens=None,
-                 output_attentions=None, **unused):
-        """Greedy search as ``ContinuousLVLM.generate`` drives it (reference models.py:146-153):
-        ``inputs_embeds`` feed step 0, ``input_ids`` is the running sequence, ``do_sample=False``
-        (temperature / top_p are inert), the image-token logits processor is applied on device.
+                 output_attentions=None, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=None, num_beams=1,
+                 **unused):
+        """Greedy search as ``ContinuousLVLM.generate`` drives it (reference models.py:146-153): ``inputs_embeds`` feed
+        step 0, ``input_ids`` is the running sequence, the image-token logits processor is applied on device.
+        ``do_sample=False`` (the default): temperature / top_k / top_p / seed are inert, as in Hugging Face.
+        ``do_sample=True``: every free token is drawn on the device, inside the decode token — processor -> temperature ->
+        top-k -> top-p -> one Philox draw (``LlamaEngine.set_sampling``; the definition and where it departs from the
+        warpers: include/seedstory_hip.h).  ``top_k=0`` means off: Hugging Face's default of 50 is NOT adopted.
+        ``seed=None`` takes ``torch.initial_seed()`` plus a per-model call counter, so ``torch.manual_seed`` governs the run
+        and successive calls differ; an explicit seed reproduces a call exactly.  The engine is greedy again when the call
+        returns or raises.  ``num_beams > 1`` with ``do_sample`` raises ``NotImplementedError``.
         ``output_attentions`` (default ``config.output_attentions``, the reference's switch): ``attentions`` = tuple over steps
         of tuple over layers — step 0 ``[1, q0, kv0 + q0]``, step j ``[1, 1, kv0 + q0 + j]``, as many as ``hidden_states`` —
         all VIEWS of one capture buffer, which ``attention_maps`` [layers, rows, width] hands out whole (one row per fed token,
         NaN beyond each row's key count: what the reference's pad-and-concatenate merge builds, models.py:164-179)."""
         want_attn = bool(getattr(self.config, "output_attentions", False) if output_attentions is None else output_attentions)
+        if do_sample and num_beams is not None and int(num_beams) > 1:
+            raise NotImplementedError("beam-search sampling (do_sample=True with num_beams=%d) is not implemented" % int(num_beams))
         img_ids = ()
         for proc in (logits_processor or []):
             img_ids = tuple(getattr(proc, "img_ids_list", ()))
@@ -354,10 +363,17 @@ class LlamaForCausalLM(nn.Module):
         if inputs_embeds is None:
             inputs_embeds = self.model.embed_tokens(input_ids)
         rows = inputs_embeds[0]
+        if do_sample:
+            if seed is None:
+                self._sample_calls = getattr(self, "_sample_calls", 0) + 1
+                seed = (torch.initial_seed() + self._sample_calls - 1) & (2 ** 64 - 1)
+            eng.set_sampling(temperature=temperature, top_k=top_k, top_p=top_p, seed=seed)     # raises on a bad parameter
         try:
             return self._generate(eng, input_ids, rows, S, img_ids, past_key_values, max_new_tokens, output_hidden_states,
                                   forced_tokens, want_attn)
         finally:
+            if do_sample:
+                eng.set_greedy()
             if want_attn:
                 eng.attn_capture_off()
 

@@ -108,7 +108,10 @@ class ContinuousLVLM(nn.Module):
     def generate(self, tokenizer, prompt=None, input_ids=None, image_embeds=None, embeds_cmp_mask=None,
                  ids_cmp_mask=None, logits_processor=None, num_img_gen_tokens=64, temperature=0.7, num_beams=1,
                  max_new_tokens=120, top_p=0.5, past_key_values=None, dtype=torch.float16, device='cuda',
-                 forced_tokens=None):
+                 forced_tokens=None, do_sample=False, top_k=0, seed=None):
+        """``do_sample=False`` (the default, what the reference passes): greedy; ``temperature`` / ``top_p`` / ``top_k`` /
+        ``seed`` are inert.  ``do_sample=True`` hands them to ``LlamaForCausalLM.generate``: on-device sampling
+        (``top_k=0`` = off, ``seed=None`` = governed by ``torch.manual_seed``)."""
         if logits_processor is None:
             logits_processor = LogitsProcessorList()
             logits_processor.append(
@@ -134,8 +137,8 @@ class ContinuousLVLM(nn.Module):
         output = self.llm.generate(input_ids=input_ids, inputs_embeds=input_embeds, output_hidden_states=True,
                                    return_dict_in_generate=True, logits_processor=logits_processor,
                                    past_key_values=past_key_values, max_new_tokens=max_new_tokens,
-                                   temperature=temperature, num_beams=num_beams, top_p=top_p, do_sample=False,
-                                   forced_tokens=forced_tokens)
+                                   temperature=temperature, num_beams=num_beams, top_p=top_p, do_sample=do_sample,
+                                   forced_tokens=forced_tokens, **({"top_k": top_k, "seed": seed} if do_sample else {}))
         output_past_key_values = self.llm.past_key_values
         generate_ids = output.sequences[0][input_ids.shape[1]:]
         boi_token_id = tokenizer.encode(BOI_TOKEN, add_special_tokens=False)[0]
