@@ -38,7 +38,9 @@
 // W a power of two >= 8 (every ResBlock convolution of the SDXL UNet and VAE at 1024^2): K tile t is 64 channels of ONE filter tap,
 // the A piece of a wave (8 consecutive output pixels of one image row) reads the same pixels shifted by the tap — an
 // affine function of the row index, so the tap is a SCALAR offset on the DMA base and the only per-lane work is the border
-// test.  Padding: out-of-image lanes read a 16-byte zero page through a 64-bit per-lane address, so EVERY piece is issued
+// test.  What depends on the piece alone (its pixel offset, which taps need padding and of which kind) is formed once per
+// output tile, the tap's offset and mask bits once per tap; a K tile costs a piece one bit test, one scalar add and the DMA.
+// Padding: out-of-image lanes read a 16-byte zero page through a 64-bit per-lane address, so EVERY piece is issued
 // with a full EXEC mask and the counted vmcnt schedule holds (the one-barrier conv kernel masks the DMA and zero-fills by
 // ds_write — a fully masked piece is skipped by the hardware, its count is not constant, and that kernel drains to
 // vmcnt(0) every K tile).
@@ -73,6 +75,38 @@ __device__ __forceinline__ void dma16v(const char* gsrc, uint32_t lds_base) {
         :
         : "v"(gsrc), "s"(lds_base)
         : "memory");
+}
+
+// the two DMA forms with the LDS destination given as a wave base + a compile-time offset, added on the way into M0: no scalar
+// register per destination (the K loop of the conv tiles has 8 A and 8 - 10 B destinations; held in registers they spilled)
+__device__ __forceinline__ void dma16s_at(uint32_t voff, const void* sbase, uint32_t lds_wave, int off) {
+    asm volatile(
+        "s_add_u32 m0, %2, %3\n\t"
+        "s_nop 0\n\t"
+        "global_load_lds_dwordx4 %0, %1"
+        :
+        : "v"(voff), "s"(sbase), "s"(lds_wave), "i"(off)
+        : "memory", "scc");
+}
+__device__ __forceinline__ void dma16v_at(const char* gsrc, uint32_t lds_wave, int off) {
+    asm volatile(
+        "s_add_u32 m0, %1, %2\n\t"
+        "s_nop 0\n\t"
+        "global_load_lds_dwordx4 %0, off"
+        :
+        : "v"(gsrc), "s"(lds_wave), "i"(off)
+        : "memory", "scc");
+}
+
+// a per-lane select by a wave-uniform 64-bit LANE MASK held in an SGPR pair: lane l gets b where bit l of mask is set, else a
+__device__ __forceinline__ uint32_t sel_lanes(uint32_t a, uint32_t b, uint64_t mask) {
+    uint32_t r;
+    asm("v_cndmask_b32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "s"(mask));
+    return r;
+}
+__device__ __forceinline__ uint64_t uniform_u64(uint64_t v) {
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
+    return ((uint64_t)hi << 32) | lo;
 }
 
 template <typename T, int BN, int FLAGS, bool CONV>
@@ -126,6 +160,15 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmArgs g, const in
     uint32_t voffA[EXACT ? 1 : 2][EXACT ? 1 : 2], voffW[EXACT ? 1 : 2][EXACT ? 1 : 3];   // [half][piece]
     const char* sbaseA = nullptr;
     const char* sbaseW = nullptr;
+    // conv: what the A staging needs of this wave's four pieces (A-half h, piece i: output pixels m0 .. m0 + 7 of one image row,
+    // m0 = m_blk + i*128 + h*64 + wid*8), all of it fixed for the whole output tile and all of it scalar:
+    //   cpoff[h][i]  the byte offset m0 * Cin * 2 of the piece's first pixel
+    //   cpad / crow  bit tap * 4 + h*2 + i: the piece needs padding at this filter tap / all of it is padding (its image row
+    //                shifted by the tap lies above or below the image).  A padded piece that is not a whole-row case pads the
+    //                one pixel that leaves the image on the left (taps with dx < 0: lane row 0) or on the right (dx > 0: lane row
+    //                7); with W = 8 a piece is both borders and the tap's dx decides, as it always did.
+    uint32_t cpoff[CONV ? 2 : 1][CONV ? 2 : 1];
+    uint64_t cpad = 0, crow = 0;
     auto setup_tile = [&](int vid) {
         int mt_, nt_;
         xcd_tile_id(g.swz, MT, NT, vid, mt_, nt_);
@@ -133,6 +176,23 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmArgs g, const in
         if constexpr (CONV) {
             voffA[0][0] = (uint32_t)(srow * g.conv_Cin * 2 + schunk * 16);       // NHWC, stride 1: pixel m sits at m * Cin
             voffW[0][0] = (uint32_t)((int64_t)srow * g.ldw * 2 + schunk * 16);
+            uint64_t pad = 0, row = 0;
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+#pragma unroll
+                for (int i = 0; i < 2; ++i) {
+                    const int m0 = m_blk + i * 128 + h * 64 + wid * 8;
+                    const int y0 = (m0 >> lw) & (g.conv_H - 1), x0 = m0 & (g.conv_W - 1);
+                    // tap = (dy + 1) * 3 + (dx + 1): dy < 0 is taps 0 1 2, dy > 0 taps 6 7 8, dx < 0 taps 0 3 6, dx > 0 taps 2 5 8
+                    // (one bit every four: the masks of piece 0, shifted by the piece)
+                    const uint64_t r9 = (y0 == 0 ? 0x000000111ull : 0ull) | (y0 == g.conv_H - 1 ? 0x111000000ull : 0ull);
+                    const uint64_t p9 = r9 | (x0 == 0 ? 0x001001001ull : 0ull) | (x0 + 8 == g.conv_W ? 0x100100100ull : 0ull);
+                    row |= r9 << (h * 2 + i);
+                    pad |= p9 << (h * 2 + i);
+                    cpoff[h][i] = __builtin_amdgcn_readfirstlane((uint32_t)(m0 * g.conv_Cin * 2));
+                }
+            }
+            cpad = uniform_u64(pad); crow = uniform_u64(row);
         } else if constexpr (EXACT) {
             voffA[0][0] = (uint32_t)((int64_t)srow * g.lda * 2 + schunk * 16);
             voffW[0][0] = (uint32_t)((int64_t)srow * g.ldw * 2 + schunk * 16);
@@ -159,11 +219,13 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmArgs g, const in
     // one half-tile of K tile t into buffer b.  which: 0 A0 | 1 A1 | 2 B0 | 3 B1
     // conv: where K tile t of the A operand lives — 64 channels [64 c, 64 c + 64) of filter tap (dy, dx); src = the address of
     // pixel 0's channels shifted by the tap.  All scalar; the K loop advances two cursors (tiles t+1, t+2) incrementally.
-    struct Cur { const char* src; int dy, dx, c, tap; };
-    auto cur_set_tap = [&](Cur& k) {
+    // bits: this tap's four bits of cpad (bits 0..3), of crow (4..7), and dx < 0 (bit 8)
+    struct Cur { const char* src; int c, tap; uint32_t bits; };
+    auto cur_set_tap = [&](Cur& k) {                         // all that happens at a tap change: the tap's byte offset and mask bits
         const int t3 = (k.tap * 11) >> 5;                    // tap / 3 for tap < 9
-        k.dy = t3 - 1; k.dx = k.tap - 3 * t3 - 1;
-        k.src = (const char*)g.A + ((int64_t)(k.dy * g.conv_W + k.dx) * g.conv_Cin + k.c * 64) * 2;
+        const int dy = t3 - 1, dx = k.tap - 3 * t3 - 1;
+        k.src = (const char*)g.A + ((int64_t)(dy * g.conv_W + dx) * g.conv_Cin + k.c * 64) * 2;
+        k.bits = ((uint32_t)(cpad >> (k.tap * 4)) & 15u) | (((uint32_t)(crow >> (k.tap * 4)) & 15u) << 4) | (dx < 0 ? 256u : 0u);
     };
     auto cur_make = [&](int t) {
         Cur k;
@@ -177,26 +239,31 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmArgs g, const in
         if (k.c == tpt) { k.c = 0; k.tap += 1; cur_set_tap(k); }
     };
     // A-half h of the cursor's K tile into buffer b.  A piece = output pixels m0 .. m0 + 7 of one image row (W % 8 == 0), this
-    // lane's pixel m0 + srow.  The row test is wave-uniform; in x only the first / last lane row of a piece at the left / right
-    // image border can fall outside.  Interior pieces (nearly all) take the GEMM form of the DMA (scalar base + lane offset);
-    // a piece with padding selects between its source and the zero page per lane (64-bit addresses).
+    // lane's pixel m0 + srow.  Per piece and K tile: one bit test, one scalar 64-bit add of the cursor and the piece's offset, one
+    // DMA.  Interior pieces (nearly all) take the GEMM form of the DMA (scalar base + lane offset); a piece with padding selects
+    // between its source and the zero page per lane (64-bit addresses) by a constant lane mask: every lane (whole-row case), lane
+    // row 0 = lanes 0..7 (left border) or lane row 7 = lanes 56..63 (right border).  Every piece is issued with a full EXEC mask.
+    const uint32_t ldsw = lds0 + (uint32_t)(wid * 1024);     // this wave's slice of every half-tile
+    const uint64_t zaddr = (uint64_t)(size_t)g_pp_zero_page; // 4 KB aligned: the lane's 16 bytes are an OR into the low word
+    const uint32_t zlo = (uint32_t)zaddr | (uint32_t)((tid & 255) << 4);
+    uint32_t zhi = (uint32_t)(zaddr >> 32);
+    // 256-wide tiles have vector registers to spare and (the persistent one) no scalar ones: the high word, which the select needs
+    // in a vector register anyway, lives there for good instead of being spilled and re-read as a scalar by every padded piece
+    if constexpr (CONV && BN == 256) asm volatile("" : "+v"(zhi));
     auto stage_conv = [&](const Cur& k, int b, int h) {
         const uint32_t keep = m0_save();
-        const uint32_t dst = lds0 + (uint32_t)(b * BUF + (h ? OFF_A1 : OFF_A0) + wid * 1024);
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            const int m0 = m_blk + i * 128 + h * 64 + wid * 8;
-            const int y0 = (m0 >> lw) & (g.conv_H - 1), x0 = m0 & (g.conv_W - 1);
-            const bool yok = (unsigned)(y0 + k.dy) < (unsigned)g.conv_H;
-            const int bad = (k.dx < 0 && x0 == 0) ? 0 : ((k.dx > 0 && x0 + 8 == g.conv_W) ? 7 : -1);
-            const char* ps = uniform_ptr(k.src + (int64_t)(m0 * g.conv_Cin * 2));
-            const uint32_t d = __builtin_amdgcn_readfirstlane(dst + i * 8192u);
-            if (yok && bad < 0) {
-                dma16s(voffA[0][0], ps, d);
+            const int p = h * 2 + i;
+            const char* ps = k.src + cpoff[CONV ? h : 0][CONV ? i : 0];
+            const int d = b * BUF + (h ? OFF_A1 : OFF_A0) + i * 8192;   // a constant once inlined
+            if (__builtin_expect(((k.bits >> p) & 1u) == 0, 1)) {
+                dma16s_at(voffA[0][0], ps, ldsw, d);
             } else {
-                const bool ok = yok && (lane >> 3) != bad;
-                const char* pa = ok ? ps + voffA[0][0] : reinterpret_cast<const char*>(g_pp_zero_page) + ((tid & 255) << 4);
-                dma16v(pa, d);
+                const uint64_t zm = ((k.bits >> (4 + p)) & 1u) ? ~0ull : ((k.bits & 256u) ? 0xFFull : 0xFFull << 56);
+                const uint64_t a = (uint64_t)(size_t)ps + voffA[0][0];
+                const uint32_t lo = sel_lanes((uint32_t)a, zlo, zm), hi = sel_lanes((uint32_t)(a >> 32), zhi, zm);
+                dma16v_at((const char*)(size_t)(((uint64_t)hi << 32) | lo), ldsw, d);
             }
         }
         m0_restore(keep);
@@ -221,7 +288,11 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmArgs g, const in
             const char* src = sbaseW + (int64_t)t * 128;
 #pragma unroll
             for (int i = 0; i < (h ? NP1 : NP0); ++i) {
-                if constexpr (EXACT)
+                if constexpr (CONV)
+                    // (the row offset fits 32 bits: pp_launch checks BN * ldw * 2 < 2^31)
+                    dma16s_at(voffW[0][0], src + (uint32_t)__builtin_amdgcn_readfirstlane((b_col(h, i) - srow) * g.ldw * 2), ldsw,
+                              b * BUF + (h ? OFF_B1 : OFF_B0) + i * 8192);
+                else if constexpr (EXACT)
                     dma16s(voffW[0][0], uniform_ptr(src + (int64_t)(b_col(h, i) - srow) * g.ldw * 2), __builtin_amdgcn_readfirstlane(dst + i * 8192u));
                 else
                     dma16s(voffW[h][i], src, __builtin_amdgcn_readfirstlane(dst + i * 8192u));
@@ -513,7 +584,10 @@ template <typename T> int gemm_pp_dispatch(int cfg, const GemmArgs& g, hipStream
 #if !SS_PP_CONV
         case 58: return pp_launch<T, 320, 12>(g, s);     // 256x320, two super-phases — GEMM ONLY: the conv instantiation of this
         // combination spills 17 registers INSIDE the K loop (256 VGPRs) and returned wrong tiles on every run (spill moves next to
-        // asm MFMAs the hazard recognizer cannot see); the GEMM instantiation has no in-loop spill and is bit-equal in the race screen
+        // asm MFMAs the hazard recognizer cannot see); the GEMM instantiation has no in-loop spill and is bit-equal in the race screen.
+        // (That was the conv staging before the per-tile masks: with them the listing of <320, 12, true> shows no spill between its
+        // first and last MFMA — profiles/conv_stage_isa.txt — but it has not been run, so it stays out until it has passed the
+        // equality tests and an A/B against cfg 56.)
 #endif
         default: return 1;
     }
