@@ -378,6 +378,41 @@ int ss_sample_logits(void* logits, int64_t rows, int64_t vocab, int64_t ld, cons
                      uint32_t draw0, const int32_t* last_ids_dev, const int32_t* img_ids, int64_t n_img_ids,
                      int32_t* token_out_dev, int32_t* n_kept_out_dev, int dtype, void* stream);
 
+/* Hugging Face's three history rules, applied to a logits row IN FRONT of the image-token processor, in the order of HF's
+ * processor list: repetition penalty -> no-repeat n-gram -> min_new_tokens -> processor -> arg max or sampler.
+ *   hist     the slot's token history: the ids the caller handed over (the whole running input_ids) followed by every token
+ *            the decode loop has appended since; prompt_len = its length at hand-over.  z = the row in the model dtype T.
+ *   1. repetition_penalty p (finite, > 0; 1 = off): for every id that occurs in hist, ONCE however often it occurs,
+ *            z_i <- round_T(z_i < 0 ? z_i * p : z_i / p), computed in fp32 with p at its float32 value, a correctly rounded
+ *            IEEE division and one rounding to T (bit-equal to RepetitionPenaltyLogitsProcessor in bf16, fp16 and fp32).
+ *            NaN stays NaN (the entry is not rewritten); +-inf follow the formula.
+ *   2. no_repeat_ngram n (0 = off, 1 <= n <= SS_LOGITS_RULES_MAX_NGRAM): when len(hist) + 1 >= n, every id that has followed
+ *            an earlier occurrence of the last n - 1 ids of hist gets -inf; n = 1 bans every id of hist.
+ *   3. min_new_tokens m (0 = off): while len(hist) - prompt_len < m the EOS id gets -inf.  The second stop id of
+ *            ss_llama_set_stop_id is not EOS and is left alone.
+ *   spare_img_ids (DEVIATION from Hugging Face, off by default): non-zero exempts the ids of img_ids from rule 1 only — a
+ *            story prompt carries earlier images' <img> ... </img> tokens, and the literal penalty would talk the model out
+ *            of producing images.
+ * -inf entries are never the arg max unless nothing else is left, and the sampler never keeps them.  No atomics: membership
+ * for rule 1 is a bitmap of ceil(vocab / 32) words in which every word has one owner thread.
+ * SS_EINVAL before any launch: p <= 0 or not finite, n < 0 or above the cap, m < 0. */
+#define SS_LOGITS_RULES_MAX_NGRAM 8
+typedef struct ss_logits_rules {
+    float repetition_penalty;
+    int32_t no_repeat_ngram;
+    int32_t min_new_tokens;
+    int32_t spare_img_ids;
+} ss_logits_rules;
+
+/* The three rules on caller-owned rows logits [rows][ld] (vocab <= 65535 entries each, model dtype), edited in place; the
+ * processor does not run.  Row r's history is hist_dev[r * hist_ld .. + hist_len_dev[r]) (int32, device; the length is
+ * clamped to [0, hist_ld]); prompt_len_dev int32[rows] (NULL = 0 for every row).  The history is device memory, so an id
+ * outside [0, vocab) cannot be refused: it is skipped and never used as an index.  eos_id < 0 = none.  img_ids (device,
+ * n_img_ids <= 1024) is read only with spare_img_ids. */
+int ss_process_logits(void* logits, int64_t rows, int64_t vocab, int64_t ld, const ss_logits_rules* rules,
+                      const int32_t* hist_dev, int64_t hist_ld, const int32_t* hist_len_dev, const int32_t* prompt_len_dev,
+                      int32_t eos_id, const int32_t* img_ids, int64_t n_img_ids, int dtype, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * LLaMA decoder engine (native runtime: KV cache, prefill loop, hipGraph-captured decode)
  * ------------------------------------------------------------------------------------- */
@@ -460,6 +495,24 @@ int ss_llama_set_attn_capture(ss_llama* h, void* maps, int64_t n_rows, int64_t l
  * token launches exactly what it launched before.  Works with attention-map capture and fp8 decode weights.  Call it between
  * engine calls (blocking copy).  SS_EINVAL: a parameter outside its range (ss_sampling), or a bad slot. */
 int ss_llama_set_sampling(ss_llama* h, int32_t seq, const ss_sampling* p);
+
+/* The history rules in the decode loop (definition: ss_process_logits).  seq = a slot, or -1 for all; rules = NULL = off (the
+ * default).  While a slot has rules on, every decode token of ss_llama_generate / ss_llama_generate_batch (eager or captured)
+ * opens with one more kernel, which appends the slot's previous token to its history and edits its logits row before the
+ * opening kernel (greedy or sampling, unchanged) reads it; a slot with rules off is skipped by it (mixed batches work), and
+ * with every addressed slot off the decode token launches exactly what it launched before.  The rules, the history
+ * int32[cache_cap + max_new], its length, prompt_len and the rule-1 bitmap live in device memory: changing them does not
+ * re-capture, and the captured rules graph is cached apart from the others.  EOS is the engine's eos_id.  Works with
+ * sampling, attention-map capture and fp8 decode weights.  A generate call on a rules-on slot whose history could outgrow
+ * the buffer is refused (SS_EINVAL).  Call it between engine calls (blocking copy). */
+int ss_llama_set_logits_rules(ss_llama* h, int32_t seq, const ss_logits_rules* rules);
+
+/* Hands slot seq's history over (seq = -1: the selected slot).  append = 0: the history becomes host_ids[0 .. n) and
+ * prompt_len = n (n = 0 empties it); append = 1: host_ids are added behind it — tokens that were fed outside the decode loop
+ * (the batched image-token block) — and prompt_len stays.  The history advances by itself only while the slot has rules on.
+ * SS_EINVAL before anything is copied: an id outside [0, vocab), or more ids than the buffer holds.  Blocking; call it
+ * between engine calls. */
+int ss_llama_set_history(ss_llama* h, int32_t seq, const int32_t* host_ids, int64_t n, int32_t append);
 
 /* fp8 (OCP e4m3fn) weight-only decode.  Per layer: the four byte planes in the 16-bit weights' layouts (wqkv [3*hidden, hidden],
  * wo [hidden, hidden], wgu [2*inter, hidden] = [gate; up], wdown [hidden, inter]) and one fp32 scale per row of each

@@ -13,6 +13,7 @@
 //    per-token scalars (kv_len, rope position, last token id, EOS flag) live in device memory, so
 //    the graph replays without host round trips; the reference syncs the host every token
 //    (`.item()` in generation.py:22, EOS check in HF).
+#include <stddef.h>
 #include <string.h>
 
 #include <vector>
@@ -20,6 +21,7 @@
 #include "ss_common.h"
 #include "ss_gemv.h"
 #include "ss_sample.h"
+#include "ss_rules.h"
 
 namespace ss {
 
@@ -141,6 +143,56 @@ __global__ __launch_bounds__(1024) void sample_embed_draw_kernel(T* logits, int 
         st16(x + (int64_t)p * V, ld16(embed + (int64_t)tok * hidden + (int64_t)p * V));
 }
 
+// The history rules of a decode token (ss_llama_set_logits_rules), one block per slot IN FRONT of the opening kernel, which
+// stays as it is: launched only when a slot of the launch has rules on; a slot without them returns at once.  The opening
+// kernel of the previous token left its choice in gen_ids[ST_NGEN - 1]: it is appended to the history (and its bit set in the
+// slot's bitmap, an ordinary store by the one thread that appends) here, before the rules read the history, so the history
+// is hist_at_call_start + every token of this call.  flush = 1 (after the last token of a generate call): append only — the
+// token that ended the call has no next decode token to append it.
+template <typename T>
+__global__ __launch_bounds__(1024) void logits_rules_kernel(T* logits, int vocab, const int32_t* st, RulesState* rs, int32_t* hist,
+                                                            int hist_cap, uint32_t* bitmap, int bm_words,
+                                                            const int32_t* __restrict__ gen_ids, int max_new,
+                                                            const int32_t* __restrict__ img_ids, int n_img_ids, int flush) {
+    __shared__ int s_len;
+    {
+        const int b = blockIdx.x;
+        logits += (int64_t)b * vocab;
+        st += b * ST_WORDS;
+        rs += b;
+        hist += (int64_t)b * hist_cap;
+        bitmap += (int64_t)b * bm_words;
+        gen_ids += (int64_t)b * max_new;
+    }
+    if (!rs->enabled) return;
+    if (!flush && st[ST_DONE]) return;
+    const int n = st[ST_NGEN];
+    if (threadIdx.x == 0) {
+        int na = n == 0 ? 0 : rs->n_app, len = rs->hist_len;
+        for (; na < n && na < max_new; ++na) {
+            const int tok = gen_ids[na];
+            if (len >= hist_cap) continue;      // (the host refuses a call that could get here)
+            hist[len++] = tok;
+            if ((unsigned)tok < (unsigned)vocab) bitmap[tok >> 5] |= 1u << (tok & 31);
+        }
+        rs->n_app = na;
+        rs->hist_len = len;
+        s_len = len;
+    }
+    __threadfence_block();
+    __syncthreads();
+    if (flush) return;
+    const int eos = st[ST_EOS] & 0xFFFF;        // 0xFFFF = none: never below vocab (<= 65535)
+    logits_rules_block<T>(logits, vocab, rs->penalty, rs->ngram, rs->min_new, rs->spare_img != 0, bitmap, hist, s_len,
+                          rs->prompt_len, eos, img_ids, n_img_ids);
+}
+
+// the bitmap of a history handed over by the host: the words of ids[0 .. n) rebuilt (keep = 0) or extended, one thread per word
+__global__ __launch_bounds__(256) void rules_bitmap_kernel(uint32_t* bitmap, int bm_words, const int32_t* __restrict__ ids, int n,
+                                                           int keep) {
+    rules_bitmap_add(bitmap, bm_words, blockIdx.x * 256 + threadIdx.x, gridDim.x * 256, ids, n, keep != 0);
+}
+
 // final RMSNorm of the single decode row: writes the fixed lm_head input buffer AND the
 // hidden-state ring row (n_gen - 1), then advances kv_len / pos.  One block of 256 per sequence.
 template <typename T>
@@ -226,6 +278,7 @@ struct SeqGraph {
     int capture;             // attention-map capture on: one more launch per layer (a different graph; the buffer is NOT part of the key)
     int w8;                  // fp8 decode weights on (ss_llama_set_decode_w8): other kernels, other weight pointers
     int sampling;            // a slot of [seq0, seq0+nb) has sampling on (ss_llama_set_sampling): the sampling kernel opens the token
+    int rules;               // a slot of [seq0, seq0+nb) has history rules on (ss_llama_set_logits_rules): the rules kernel in front
     hipGraph_t graph;
     hipGraphExec_t exec;
 };
@@ -272,6 +325,18 @@ struct ss_llama {
         for (int b = seq0; b < seq0 + nb; ++b) if (samp_on[b]) return true;
         return false;
     }
+    // history rules (ss_llama_set_logits_rules / ss_llama_set_history): per-slot block, history and rule-1 bitmap in device memory
+    RulesState* rules = nullptr;        // [n_seq]
+    int32_t* hist = nullptr;            // [n_seq][hist_cap()]
+    uint32_t* hist_bm = nullptr;        // [n_seq][bm_words()]
+    std::vector<char> rules_on;
+    std::vector<int64_t> hist_len;      // host mirror of RulesState::hist_len
+    bool rules_in(int seq0, int nb) const {
+        for (int b = seq0; b < seq0 + nb; ++b) if (rules_on[b]) return true;
+        return false;
+    }
+    int64_t hist_cap() const { return (int64_t)cfg.cache_cap + cfg.max_new; }
+    int bm_words() const { return rules_bitmap_words(cfg.vocab); }
     size_t plane_bytes() const { return (size_t)cfg.n_heads * cfg.cache_cap * hd * esz; }       // one layer of one slot
     size_t seq_kv_bytes() const { return (size_t)cfg.n_layers * plane_bytes(); }
     int32_t* upload() const { return pinned + (size_t)n_seq * ST_WORDS; }                        // the state upload area
@@ -331,6 +396,9 @@ static void carve(ss_llama* h, Carver& c) {
     h->splitk_ws = sk ? c.take(sk) : nullptr;
     h->cap_desc = (AttnCaptureDesc*)c.take(sizeof(AttnCaptureDesc));     // zeroed with the workspace: capture off
     h->samp = (SampleParams*)c.take(S * sizeof(SampleParams));           // zeroed with the workspace: every slot greedy
+    h->rules = (RulesState*)c.take(S * sizeof(RulesState));              // zeroed with the workspace: rules off, empty histories
+    h->hist = (int32_t*)c.take(S * (size_t)h->hist_cap() * sizeof(int32_t));
+    h->hist_bm = (uint32_t*)c.take(S * (size_t)h->bm_words() * sizeof(uint32_t));
 }
 
 static int cfg_n_seq(const ss_llama_config* cfg) { return cfg->n_seq > 0 ? cfg->n_seq : 1; }
@@ -376,6 +444,17 @@ static int sample_embed_draw_launch(ss_llama* h, int seq0, int nb, hipStream_t s
 }
 
 template <typename T>
+static int logits_rules_launch(ss_llama* h, int seq0, int nb, int flush, hipStream_t s) {
+    const ss_llama_config& g = h->cfg;
+    hipLaunchKernelGGL(logits_rules_kernel<T>, dim3((unsigned)nb), dim3(1024), 0, s, (T*)h->logits + (size_t)seq0 * g.vocab, g.vocab,
+                       h->state + (size_t)seq0 * ST_WORDS, h->rules + seq0, h->hist + (size_t)seq0 * h->hist_cap(), (int)h->hist_cap(),
+                       h->hist_bm + (size_t)seq0 * h->bm_words(), h->bm_words(), h->gen_ids + (size_t)seq0 * g.max_new, g.max_new,
+                       h->img_ids, g.n_img_ids, flush);
+    SS_LAUNCH_CHECK("logits_rules");
+    return SS_OK;
+}
+
+template <typename T>
 static int final_norm_advance_launch(ss_llama* h, int seq0, int nb, hipStream_t s) {
     const ss_llama_config& g = h->cfg;
     hipLaunchKernelGGL(final_norm_advance_kernel<T>, dim3((unsigned)nb), dim3(256), 0, s, (const T*)h->x,
@@ -407,6 +486,8 @@ static int decode_token(ss_llama* h, hipStream_t s, ProfSink* prof, int seq0, in
     static const ss_llama_layer_w8 kNoW8 = {};
 #define MARK(c) do { if (prof) prof->mark(c); } while (0)
     MARK(-1);
+    // history rules on for a slot: its row is edited before the opening kernel reads it (off everywhere, the default: no launch)
+    if (h->rules_in(seq0, nb) && (rc = SS_DISPATCH(dt, logits_rules_launch, h, seq0, nb, 0, s))) return rc;
     // greedy slots only (the default): the launch it has always been
     if (h->sampling_in(seq0, nb)) rc = SS_DISPATCH(dt, sample_embed_draw_launch, h, seq0, nb, s);
     else rc = SS_DISPATCH(dt, sample_embed_launch, h, seq0, nb, s);
@@ -467,13 +548,15 @@ static int graph_for(ss_llama* h, int seq0, int nb, hipGraphExec_t* out) {
     const int capture = (h->cap.maps && nb == 1) ? 1 : 0;
     const int w8 = h->w8.empty() ? 0 : 1;
     const int sampling = h->sampling_in(seq0, nb) ? 1 : 0;
+    const int rules = h->rules_in(seq0, nb) ? 1 : 0;
     for (const SeqGraph& sg : h->graphs)
-        if (sg.seq0 == seq0 && sg.nb == nb && sg.mode == mode && sg.capture == capture && sg.w8 == w8 && sg.sampling == sampling) {
+        if (sg.seq0 == seq0 && sg.nb == nb && sg.mode == mode && sg.capture == capture && sg.w8 == w8 && sg.sampling == sampling &&
+            sg.rules == rules) {
             *out = sg.exec;
             return SS_OK;
         }
     SeqGraph sg;
-    sg.seq0 = seq0; sg.nb = nb; sg.mode = mode; sg.capture = capture; sg.w8 = w8; sg.sampling = sampling;
+    sg.seq0 = seq0; sg.nb = nb; sg.mode = mode; sg.capture = capture; sg.w8 = w8; sg.sampling = sampling; sg.rules = rules;
     sg.graph = nullptr; sg.exec = nullptr;
     SS_HIP(hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
     int rc = decode_token(h, h->cap_stream, nullptr, seq0, nb);
@@ -483,6 +566,19 @@ static int graph_for(ss_llama* h, int seq0, int nb, hipGraphExec_t* out) {
     SS_HIP(hipGraphInstantiate(&sg.exec, sg.graph, nullptr, nullptr, 0));
     h->graphs.push_back(sg);
     *out = sg.exec;
+    return SS_OK;
+}
+
+// after the last token of a call (h->pinned holds the final state words): the token that ended it joins the history of every
+// rules-on slot, and the host mirror of the history lengths follows the device
+static int rules_finish(ss_llama* h, int seq0, int nb, hipStream_t s) {
+    if (!h->rules_in(seq0, nb)) return SS_OK;
+    if (int rc = SS_DISPATCH(h->cfg.dtype, logits_rules_launch, h, seq0, nb, 1, s)) return rc;
+    for (int b = seq0; b < seq0 + nb; ++b)
+        if (h->rules_on[b]) {
+            const int64_t len = h->hist_len[b] + h->pinned[b * ST_WORDS + ST_NGEN];
+            h->hist_len[b] = len < h->hist_cap() ? len : h->hist_cap();
+        }
     return SS_OK;
 }
 
@@ -510,7 +606,16 @@ static int run_decode(ss_llama* h, int seq0, int nb, int64_t eff_limit, hipStrea
         for (int b = seq0; b < seq0 + nb; ++b) all = all && h->pinned[b * ST_WORDS + ST_DONE];
         if (all) break;
     }
-    return launched ? SS_OK : sync_lengths(h, seq0, nb, s);
+    if (!launched) { int rc = sync_lengths(h, seq0, nb, s); if (rc) return rc; }
+    return rules_finish(h, seq0, nb, s);
+}
+
+// a rules-on slot appends every token of the call to its history: refused when the buffer could not hold them
+static int history_fits(const ss_llama* h, int b, int64_t limit, const char* who) {
+    SS_REQUIRE(!h->rules_on[b] || h->hist_len[b] + limit <= h->hist_cap(),
+               "%s: the token history of slot %d would outgrow its buffer (%lld + %lld > cache_cap + max_new = %lld)", who, b,
+               (long long)h->hist_len[b], (long long)limit, (long long)h->hist_cap());
+    return SS_OK;
 }
 
 // kv_len / pos of one slot: the device state words and the host mirrors (the callers have checked the range)
@@ -697,6 +802,8 @@ int ss_llama_create(const ss_llama_config* cfg, const ss_llama_weights* w, void*
     h->kv_len.assign(h->n_seq, 0);
     h->pos.assign(h->n_seq, 0);
     h->samp_on.assign(h->n_seq, 0);
+    h->rules_on.assign(h->n_seq, 0);
+    h->hist_len.assign(h->n_seq, 0);
     hipError_t e = hipStreamCreateWithFlags(&h->cap_stream, hipStreamNonBlocking);
     if (e == hipSuccess)
         e = hipHostMalloc((void**)&h->pinned, (size_t)h->n_seq * 2 * ST_WORDS * sizeof(int32_t) + 64, hipHostMallocDefault);
@@ -762,6 +869,48 @@ int ss_llama_set_sampling(ss_llama* h, int32_t seq, const ss_sampling* p) {
         SS_HIP(hipMemcpy(h->samp + b, &sp, sizeof(sp), hipMemcpyHostToDevice));
         h->samp_on[b] = p ? 1 : 0;
     }
+    return SS_OK;
+}
+
+int ss_llama_set_logits_rules(ss_llama* h, int32_t seq, const ss_logits_rules* p) {
+    SS_REQUIRE(h, "llama_set_logits_rules: null handle");
+    SS_REQUIRE(seq >= -1 && seq < h->n_seq, "llama_set_logits_rules: sequence slot %d out of range (-1 = all, < %d)", (int)seq, h->n_seq);
+    RulesState rp = {1.0f, 0, 0, 0, 0, 0, 0, 0};        // off
+    if (p)
+        if (int rc = logits_rules_params(p, "llama_set_logits_rules", &rp)) return rc;
+    // every decode loop of this engine has synchronised before it returned: nothing in flight reads the block.  Only the rule
+    // words are written: the history bookkeeping behind them is ss_llama_set_history's and the kernel's
+    const int b0 = seq < 0 ? 0 : seq, b1 = seq < 0 ? h->n_seq : seq + 1;
+    for (int b = b0; b < b1; ++b) {
+        SS_HIP(hipMemcpy(h->rules + b, &rp, offsetof(RulesState, hist_len), hipMemcpyHostToDevice));
+        h->rules_on[b] = p ? 1 : 0;
+    }
+    return SS_OK;
+}
+
+int ss_llama_set_history(ss_llama* h, int32_t seq, const int32_t* host_ids, int64_t n, int32_t append) {
+    SS_REQUIRE(h, "llama_set_history: null handle");
+    SS_REQUIRE(seq >= -1 && seq < h->n_seq, "llama_set_history: sequence slot %d out of range (-1 = the selected slot, < %d)", (int)seq,
+               h->n_seq);
+    SS_REQUIRE(n >= 0 && (host_ids || n == 0), "llama_set_history: bad arguments (n=%lld)", (long long)n);
+    const int b = seq < 0 ? h->cur : seq;
+    const int64_t len0 = append ? h->hist_len[b] : 0;
+    SS_REQUIRE(len0 + n <= h->hist_cap(), "llama_set_history: %lld + %lld ids exceed the history buffer (cache_cap + max_new = %lld)",
+               (long long)len0, (long long)n, (long long)h->hist_cap());
+    for (int64_t i = 0; i < n; ++i)
+        SS_REQUIRE(host_ids[i] >= 0 && host_ids[i] < h->cfg.vocab, "llama_set_history: id %d at index %lld outside [0, %d)",
+                   (int)host_ids[i], (long long)i, h->cfg.vocab);
+    // every decode loop of this engine has synchronised before it returned: nothing in flight reads the history
+    int32_t* dst = h->hist + (size_t)b * h->hist_cap() + len0;
+    if (n) SS_HIP(hipMemcpy(dst, host_ids, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (n || !append) {
+        hipLaunchKernelGGL(rules_bitmap_kernel, dim3((unsigned)cdiv(h->bm_words(), 256)), dim3(256), 0, (hipStream_t)0,
+                           h->hist_bm + (size_t)b * h->bm_words(), h->bm_words(), dst, (int)n, append ? 1 : 0);
+        SS_LAUNCH_CHECK("rules_bitmap");
+    }
+    const int32_t lens[2] = {(int32_t)(len0 + n), (int32_t)(append ? 0 : n)};       // hist_len, prompt_len
+    SS_HIP(hipMemcpy(&h->rules[b].hist_len, lens, (append ? 1 : 2) * sizeof(int32_t), hipMemcpyHostToDevice));
+    h->hist_len[b] = len0 + n;
     return SS_OK;
 }
 
@@ -932,6 +1081,7 @@ int ss_llama_generate(ss_llama* h, int64_t n_steps, int32_t last_prompt_id, cons
     SS_REQUIRE(h->pos[q] + limit <= g.max_pos, "llama_generate: position overflow (%lld + %lld > %d)", (long long)h->pos[q],
                (long long)limit, g.max_pos);
     if (int crc = capture_fits(h, h->kv_len[q], limit, "llama_generate")) return crc;
+    if (int hrc = history_fits(h, q, limit, "llama_generate")) return hrc;
     if (n_forced > 0)
         SS_HIP(hipMemcpyAsync(h->forced + (size_t)q * g.max_new, host_forced, (size_t)n_forced * sizeof(int32_t),
                               hipMemcpyHostToDevice, s));
@@ -961,6 +1111,8 @@ int ss_llama_generate_batch(ss_llama* h, int64_t n_steps, const int32_t* last_pr
                    (long long)limit, g.cache_cap);
         SS_REQUIRE(!on || h->pos[b] + limit <= g.max_pos, "llama_generate_batch: position overflow in slot %d (%lld + %lld > %d)",
                    b, (long long)h->pos[b], (long long)limit, g.max_pos);
+        if (on)
+            if (int hrc = history_fits(h, b, limit, "llama_generate_batch")) return hrc;
         const int32_t* f = host_forced ? host_forced + (size_t)b * forced_ld : nullptr;
         if (on && nf > 0)
             SS_HIP(hipMemcpyAsync(h->forced + (size_t)b * g.max_new, f, (size_t)nf * sizeof(int32_t),
@@ -981,6 +1133,7 @@ int ss_llama_profile_decode(ss_llama* h, int64_t n_tokens, float out_ms[8], doub
     hipStream_t s = (hipStream_t)stream;
     for (int b = 0; b < h->n_seq; ++b) {
         SS_REQUIRE(h->kv_len[b] + n_tokens + 1 <= g.cache_cap, "llama_profile_decode: KV cache too full (slot %d)", b);
+        if (int hrc = history_fits(h, b, n_tokens, "llama_profile_decode")) return hrc;
         fill_state(h->upload() + (size_t)b * ST_WORDS, h->kv_len[b], h->pos[b], false, 0, 0, g.max_new, -1);
     }
     SS_HIP(hipMemcpyAsync(h->state, h->upload(), (size_t)h->n_seq * ST_WORDS * sizeof(int32_t), hipMemcpyHostToDevice, s));
@@ -1019,7 +1172,8 @@ int ss_llama_profile_decode(ss_llama* h, int64_t n_tokens, float out_ms[8], doub
         out_bytes[2] += 4.0 * (double)g.n_layers * H;
     }
     out_bytes[3] = cnt[2] / (double)n_tokens;
-    return sync_lengths(h, 0, h->n_seq, s);
+    if (int rc = sync_lengths(h, 0, h->n_seq, s)) return rc;
+    return rules_finish(h, 0, h->n_seq, s);
 }
 
 }  // extern "C"

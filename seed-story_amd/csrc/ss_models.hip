@@ -9,6 +9,7 @@
 // instead of hundreds of framework-level op dispatches.
 #include "ss_common.h"
 #include "ss_sample.h"
+#include "ss_rules.h"
 
 namespace ss {
 int gemm_dev(const void* A, const void* W, void* C, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldw,
@@ -68,6 +69,37 @@ int sample_logits_launch(void* logits, int64_t rows, int64_t vocab, int64_t ld, 
     return SS_OK;
 }
 
+// ss_process_logits: one block per row; the rule-1 bitmap of the row's history is built in LDS (one owner thread per word)
+template <typename T>
+__global__ __launch_bounds__(1024) void process_logits_kernel(T* logits, int vocab, int64_t ld, RulesState p,
+                                                              const int32_t* __restrict__ hist, int64_t hist_ld,
+                                                              const int32_t* __restrict__ hist_len,
+                                                              const int32_t* __restrict__ prompt_len, int eos,
+                                                              const int32_t* __restrict__ img_ids, int n_img_ids) {
+    __shared__ uint32_t bm[2048];       // vocab <= 65535
+    const int r = blockIdx.x;
+    logits += (int64_t)r * ld;
+    hist += (int64_t)r * hist_ld;
+    int len = hist_len[r];
+    len = len < 0 ? 0 : (len > hist_ld ? (int)hist_ld : len);
+    if (p.penalty != 1.0f) {
+        rules_bitmap_add(bm, rules_bitmap_words(vocab), threadIdx.x, 1024, hist, len, false);
+        __syncthreads();
+    }
+    logits_rules_block<T>(logits, vocab, p.penalty, p.ngram, p.min_new, p.spare_img != 0, bm, hist, len,
+                          prompt_len ? prompt_len[r] : 0, eos, img_ids, n_img_ids);
+}
+
+template <typename T>
+int process_logits_launch(void* logits, int64_t rows, int64_t vocab, int64_t ld, const RulesState& p, const int32_t* hist,
+                          int64_t hist_ld, const int32_t* hist_len, const int32_t* prompt_len, int eos, const int32_t* img_ids,
+                          int64_t n, hipStream_t s) {
+    hipLaunchKernelGGL(process_logits_kernel<T>, dim3((unsigned)rows), dim3(1024), 0, s, (T*)logits, (int)vocab, ld, p, hist,
+                       hist_ld, hist_len, prompt_len, eos, img_ids, (int)n);
+    SS_LAUNCH_CHECK("process_logits");
+    return SS_OK;
+}
+
 struct Bump {
     char* p; size_t off, cap;
     void* take(size_t bytes) { void* r = p + off; off += (bytes + 255) / 256 * 256; return r; }
@@ -98,6 +130,23 @@ int ss_sample_logits(void* logits, int64_t rows, int64_t vocab, int64_t ld, cons
     const bool proc = last_ids_dev && img_ids;
     return SS_DISPATCH(dtype, sample_logits_launch, logits, rows, vocab, ld, sp, u_dev, draw0, proc ? last_ids_dev : nullptr,
                        proc ? img_ids : nullptr, proc ? n_img_ids : 0, token_out_dev, n_kept_out_dev, (hipStream_t)stream);
+}
+
+int ss_process_logits(void* logits, int64_t rows, int64_t vocab, int64_t ld, const ss_logits_rules* rules,
+                      const int32_t* hist_dev, int64_t hist_ld, const int32_t* hist_len_dev, const int32_t* prompt_len_dev,
+                      int32_t eos_id, const int32_t* img_ids, int64_t n_img_ids, int dtype, void* stream) {
+    SS_REQUIRE(logits && rules && hist_len_dev, "process_logits: null argument");
+    SS_REQUIRE(rows > 0 && rows <= 0x7FFFFFFF && vocab > 0 && vocab <= 65535 && ld >= vocab,
+               "process_logits: bad shape (rows=%lld vocab=%lld ld=%lld; vocab <= 65535)", (long long)rows, (long long)vocab,
+               (long long)ld);
+    SS_REQUIRE(hist_ld >= 0 && hist_ld <= 0x7FFFFFFF && (hist_dev || hist_ld == 0), "process_logits: bad history (hist_ld=%lld)",
+               (long long)hist_ld);
+    SS_REQUIRE(n_img_ids >= 0 && n_img_ids <= 1024 && (img_ids || n_img_ids == 0), "process_logits: n_img_ids=%lld out of range (0..1024)",
+               (long long)n_img_ids);
+    RulesState rp = {1.0f, 0, 0, 0, 0, 0, 0, 0};
+    if (int rc = logits_rules_params(rules, "process_logits", &rp)) return rc;
+    return SS_DISPATCH(dtype, process_logits_launch, logits, rows, vocab, ld, rp, hist_dev, hist_ld, hist_len_dev, prompt_len_dev,
+                       (int)eos_id, img_ids, n_img_ids, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------

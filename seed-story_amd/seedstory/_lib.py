@@ -39,6 +39,10 @@ class Sampling(C.Structure):
     _fields_ = [("temperature", f32), ("top_p", f32), ("top_k", i32), ("seed", C.c_uint64)]
 
 
+class LogitsRules(C.Structure):
+    _fields_ = [("repetition_penalty", f32), ("no_repeat_ngram", i32), ("min_new_tokens", i32), ("spare_img_ids", i32)]
+
+
 class LlamaWeights(C.Structure):
     _fields_ = [("embed", vp), ("lm_head", vp), ("final_norm", vp), ("rope_cos", vp), ("rope_sin", vp),
                 ("layers", C.POINTER(LlamaLayerWeights))]
@@ -118,6 +122,7 @@ PROTOTYPES = {
     "ss_gemv_w8_plan": (C.c_int, [i64, i64, i64, C.c_int, C.c_int, C.c_int, i32p, i64]),
     "ss_imgproc_argmax": (C.c_int, [vp, i64, vp, vp, i64, vp, C.c_int, vp]),
     "ss_sample_logits": (C.c_int, [vp, i64, i64, i64, C.POINTER(Sampling), vp, C.c_uint32, vp, vp, i64, vp, vp, C.c_int, vp]),
+    "ss_process_logits": (C.c_int, [vp, i64, i64, i64, C.POINTER(LogitsRules), vp, i64, vp, vp, i32, vp, i64, C.c_int, vp]),
     "ss_llama_workspace_bytes": (sz, [C.POINTER(LlamaConfig), i64]),
     "ss_llama_create": (C.c_int, [C.POINTER(LlamaConfig), C.POINTER(LlamaWeights), vp, sz, i64, i32p,
                                   C.POINTER(vp)]),
@@ -127,6 +132,8 @@ PROTOTYPES = {
     "ss_llama_set_attn_capture": (C.c_int, [vp, vp, i64, i64, i64, i32, i32]),
     "ss_llama_set_decode_w8": (C.c_int, [vp, C.POINTER(LlamaLayerW8), vp, vp]),
     "ss_llama_set_sampling": (C.c_int, [vp, i32, C.POINTER(Sampling)]),
+    "ss_llama_set_logits_rules": (C.c_int, [vp, i32, C.POINTER(LogitsRules)]),
+    "ss_llama_set_history": (C.c_int, [vp, i32, i32p, i64, i32]),
     "ss_llama_buffer": (vp, [vp, C.c_int]),
     "ss_llama_set_lengths": (C.c_int, [vp, i64, i64, vp]),
     "ss_llama_get_lengths": (C.c_int, [vp, C.POINTER(i64), C.POINTER(i64)]),

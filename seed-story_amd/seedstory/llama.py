@@ -140,6 +140,7 @@ class LlamaEngine:
         self._capture = None       # (maps, row0, head) while attention-map capture is on
         self._w8 = None            # tensors of the fp8 decode planes while the option is on
         self.decode_weights = None
+        self._rules_slots = set()  # slots whose history rules are on (set_logits_rules)
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -340,6 +341,49 @@ class LlamaEngine:
         torch.cuda.current_stream(self.device).synchronize()
         check(lib().ss_llama_set_sampling(self._h, -1 if slot is None else int(slot), sp), "ss_llama_set_sampling")
 
+    # ---- history rules -------------------------------------------------------------------------------------------
+    def set_logits_rules(self, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, spare_img_ids=False, slot=None):
+        """Hugging Face's ``repetition_penalty`` -> ``no_repeat_ngram_size`` -> ``min_new_tokens`` on the logits of every decode
+        token of ``generate`` / ``generate_batch`` (and the image-block variants), in front of the image-token processor and
+        the arg max or sampler, for ``slot`` or, with None, every slot.  The definition is in include/seedstory_hip.h
+        (``ss_process_logits``): the penalty is bit-equal to ``RepetitionPenaltyLogitsProcessor``; ``spare_img_ids=True`` is
+        the one deviation (the ids of ``img_ids`` are exempt from the penalty).  The rules see the slot's token history: hand
+        the prompt ids over with ``set_history``; every token the loop produces, and every image-block token, is appended
+        by the engine while the slot's rules are on.  One more kernel per token, eager or captured (a graph of its own); the
+        rules, the history and its bitmap live in device memory, so other values do not re-capture.  EOS for
+        ``min_new_tokens`` is the engine's ``eos_id``.  Bad values raise ``SSError``."""
+        rp = ops.logits_rules_struct(repetition_penalty, no_repeat_ngram_size, min_new_tokens, spare_img_ids)
+        self._set_logits_rules(slot, C.byref(rp))
+        self._rules_slots |= set(range(self.n_seq)) if slot is None else {int(slot)}
+
+    def clear_logits_rules(self, slot=None):
+        """Rules off (the default) for ``slot`` or, with None, every slot: the decode token is what it was without them."""
+        self._set_logits_rules(slot, None)
+        self._rules_slots -= set(range(self.n_seq)) if slot is None else {int(slot)}
+
+    def _set_logits_rules(self, slot, rp):
+        torch.cuda.current_stream(self.device).synchronize()
+        check(lib().ss_llama_set_logits_rules(self._h, -1 if slot is None else int(slot), rp), "ss_llama_set_logits_rules")
+
+    def set_history(self, ids, slot=None, append=False):
+        """The token history the rules of ``slot`` (None: the selected slot) see: ``ids`` = the whole running ``input_ids``
+        as Hugging Face's processors would get them; its length becomes ``prompt_len`` for ``min_new_tokens``.
+        ``append=True`` adds ``ids`` behind the history instead (tokens fed outside the decode loop).  Ids outside
+        [0, vocab) raise ``SSError``."""
+        ids = [int(t) for t in (ids.reshape(-1).tolist() if isinstance(ids, torch.Tensor) else ids)]
+        for t in ids:
+            if not -2 ** 31 <= t < 2 ** 31:
+                raise _lib.SSError("set_history: id %d is no int32" % t)
+        arr = (C.c_int32 * max(1, len(ids)))(*ids)
+        torch.cuda.current_stream(self.device).synchronize()
+        check(lib().ss_llama_set_history(self._h, -1 if slot is None else int(slot), arr, len(ids), 1 if append else 0),
+              "ss_llama_set_history")
+
+    def _history_append(self, slot, toks):
+        """image-block tokens of ``slot`` join its history (they were fed as one batched forward, outside the decode loop)"""
+        if toks and slot in getattr(self, "_rules_slots", ()):     # getattr: tests bind the block methods onto stand-in engines
+            self.set_history(toks, slot=slot, append=True)
+
     # ---- forward paths ---------------------------------------------------------------------------------
     def _ensure_prefill_tiles(self, M):
         if M > 128:      # the four prefill projections of this row-count bucket (tile table: seedstory/tune.py)
@@ -485,6 +529,7 @@ class LlamaEngine:
                 if n == 0 or g[-1] != boi or rem == 0:
                     break                                           # EOS, the token limit, or the budget ended at <img>
                 toks, hb, last_fed = self._img_block(rem, forced)
+                LlamaEngine._history_append(self, getattr(self, "_cur", 0), toks)
                 ids += toks
                 hid.append(hb)
                 forced, rem = forced[len(toks):], rem - len(toks)
@@ -546,6 +591,7 @@ class LlamaEngine:
                             continue
                         m, rows = v
                         toks = blk[1:m + 1]
+                        LlamaEngine._history_append(self, b, toks)
                         ids[b] += toks
                         forced[b], rem[b] = forced[b][len(toks):], rem[b] - len(toks)
                         if rows == m + 1:

@@ -438,6 +438,52 @@ def sample_logits(logits, temperature=1.0, top_k=0, top_p=1.0, seed=0, u=None, d
     return (tok, kept) if return_n_kept else tok
 
 
+def logits_rules_struct(repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, spare_img_ids=False):
+    """The C ABI's ``ss_logits_rules``.  Ranges are checked by the library (``SSError``); only what ctypes would mangle
+    silently is checked here."""
+    for name, v in (("no_repeat_ngram_size", no_repeat_ngram_size), ("min_new_tokens", min_new_tokens)):
+        if int(v) != v or not -2 ** 31 <= int(v) < 2 ** 31:
+            raise _lib.SSError("%s must be an integer, not %r" % (name, v))
+    return _lib.LogitsRules(float(repetition_penalty), int(no_repeat_ngram_size), int(min_new_tokens), 1 if spare_img_ids else 0)
+
+
+def process_logits(logits, hist, hist_len=None, prompt_len=None, repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0,
+                   spare_img_ids=False, eos_id=-1, img_ids=None):
+    """Hugging Face's repetition penalty -> no-repeat n-gram -> min_new_tokens on the rows of ``logits`` [rows, vocab] (or
+    [vocab]; rows may be strided, unit stride inside a row), IN PLACE, by the engine's kernel routine; the image-token
+    processor does not run.  ``hist`` int32 [rows, hist_ld] (or [hist_ld]) holds each row's token history, ``hist_len`` [rows]
+    its length (default: all of ``hist``), ``prompt_len`` [rows] the length at hand-over (default 0); ids outside
+    [0, vocab) are skipped.  ``img_ids`` is used by ``spare_img_ids`` only.  Returns ``logits``.  The definition is in
+    include/seedstory_hip.h (``ss_process_logits``)."""
+    if not logits.is_cuda:
+        raise _lib.SSError("logits must live on the GPU (there is no CPU path)")
+    lg = logits if logits.dim() == 2 else logits.view(1, -1)
+    if lg.dim() != 2 or (lg.shape[1] > 1 and lg.stride(1) != 1) or (lg.shape[0] > 1 and lg.stride(0) < lg.shape[1]):
+        raise _lib.SSError("logits must be [rows, vocab] with unit stride inside a row")
+    rows, vocab = lg.shape
+    dev = lg.device
+    rp = logits_rules_struct(repetition_penalty, no_repeat_ngram_size, min_new_tokens, spare_img_ids)
+    hs = torch.as_tensor(hist, dtype=torch.int32, device=dev)
+    hs = _req(hs.reshape(1, -1) if hs.dim() < 2 else hs, "hist")
+    if hs.shape[0] != rows:
+        raise _lib.SSError("hist must hold one history per row (%d), not %d" % (rows, hs.shape[0]))
+
+    def per_row(v, default, what):
+        t = torch.full((rows,), default, dtype=torch.int32, device=dev) if v is None else \
+            torch.as_tensor(v, dtype=torch.int32, device=dev).reshape(-1).contiguous()
+        if t.numel() != rows:
+            raise _lib.SSError("%s must hold one value per row (%d), not %d" % (what, rows, t.numel()))
+        return t
+    hl = per_row(hist_len, hs.shape[1], "hist_len")
+    pl = per_row(prompt_len, 0, "prompt_len")
+    ids = None if img_ids is None else torch.as_tensor(list(img_ids), dtype=torch.int32, device=dev)
+    import ctypes as C
+    check(lib().ss_process_logits(p(lg), rows, vocab, lg.stride(0) if rows > 1 else vocab, C.byref(rp), p(hs) if hs.numel() else None,
+                                  hs.shape[1], p(hl), p(pl), int(eos_id), p(ids), 0 if ids is None else ids.numel(), dt(lg), stream()),
+          "ss_process_logits")
+    return logits
+
+
 # ---- SDXL de-tokenizer ops (NHWC activations: [B, H*W, C]) ------------------------------------------
 def conv3x3(x, w, B, H, W, stride=1, upsample=False, bias=None, rowvec=None, residual=None, rowvec_stride=0, out=None):
     """x [B*H*W, Cin] (NHWC) -> [B*Ho*Wo, Cout]; w [Cout, 9*Cin] (tap-major, channel-minor)."""

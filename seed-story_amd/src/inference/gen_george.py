@@ -160,6 +160,27 @@ def sample_kwargs(args, j, step):
     return dict(do_sample=True, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, seed=seed)
 
 
+def add_rules_arguments(ap):
+    """``--repetition-penalty`` / ``--no-repeat-ngram-size`` / ``--min-new-tokens`` (Hugging Face's meanings; shared with
+    vis_george_sink.py)"""
+    ap.add_argument("--repetition-penalty", type=float, default=1.0,
+                    help="> 1 lowers the logits of ids already in the context (1 = off); the image-token ids are spared")
+    ap.add_argument("--no-repeat-ngram-size", type=int, default=0, help="ban every n-gram the context already holds (0 = off, at most 8)")
+    ap.add_argument("--min-new-tokens", type=int, default=0, help="no EOS before this many new tokens (0 = off)")
+
+
+def rules_kwargs(args):
+    """What ``ContinuousLVLM.generate`` gets on top for the three history rules.  With the penalty on, ``spare_img_ids=True``:
+    a story prompt carries earlier images' ``<img>`` ... ``</img>`` tokens, and the literal penalty would lower ``<img>``
+    itself (the declared deviation)."""
+    p = getattr(args, "repetition_penalty", 1.0)
+    n = getattr(args, "no_repeat_ngram_size", 0)
+    m = getattr(args, "min_new_tokens", 0)
+    if p == 1.0 and not n and not m:
+        return {}
+    return dict(repetition_penalty=p, no_repeat_ngram_size=n, min_new_tokens=m, spare_img_ids=p != 1.0)
+
+
 def run_story(args, j, question, image, tokenizer, transform, vit, agent, adapter, device, dtype):
     save_folder = os.path.join(args.out, "val_%d" % j)
     os.makedirs(save_folder, exist_ok=True)
@@ -190,7 +211,7 @@ def run_story(args, j, question, image, tokenizer, transform, vit, agent, adapte
         ids_mask, emb_mask = ctx.masks(device)
         out = agent.generate(tokenizer=tokenizer, input_ids=ctx.input_ids(device), image_embeds=ctx.image_embeds,
                              embeds_cmp_mask=emb_mask, ids_cmp_mask=ids_mask, max_new_tokens=500, num_img_gen_tokens=64,
-                             forced_tokens=forced, **sample_kwargs(args, j, step))
+                             forced_tokens=forced, **sample_kwargs(args, j, step), **rules_kwargs(args))
         if args.save_attn:                                       # [layers, rows, width], head 0 (NaN beyond each row's keys)
             torch.save(torch.stack([a[0] for a in out['attn_weights']]).cpu(),
                        os.path.join(args.save_attn, "val_%d_step_%02d.pt" % (j, step)))
@@ -236,6 +257,7 @@ def main():
     ap.add_argument("--top-k", type=int, default=0, help="0 = off")
     ap.add_argument("--top-p", type=float, default=0.5)
     ap.add_argument("--seed", type=int, default=None, help="with --sample: reproducible stories (default: torch.initial_seed())")
+    add_rules_arguments(ap)
     args = ap.parse_args()
     device = "cuda:0"
     dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float16

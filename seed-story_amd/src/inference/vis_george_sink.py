@@ -20,7 +20,7 @@ import os
 import torch
 
 from seedstory.story import StoryContext
-from src.inference.gen_george import BOI_TOKEN, EOI_TOKEN, IMG_TOKEN, build
+from src.inference.gen_george import BOI_TOKEN, EOI_TOKEN, IMG_TOKEN, add_rules_arguments, build, rules_kwargs
 
 
 def run_story(args, j, start_text, captions, image, tokenizer, transform, vit, agent, adapter, device, dtype):
@@ -51,7 +51,7 @@ def run_story(args, j, start_text, captions, image, tokenizer, transform, vit, a
             llama.kv_cache_head = cached
         out = agent.generate(tokenizer=tokenizer, input_ids=ctx.input_ids(device), image_embeds=ctx.image_embeds,
                              embeds_cmp_mask=emb_mask, ids_cmp_mask=ids_mask, max_new_tokens=500, num_img_gen_tokens=64,
-                             past_key_values=past, forced_tokens=forced)
+                             past_key_values=past, forced_tokens=forced, **rules_kwargs(args))
         with open(os.path.join(save_folder, "token.txt"), "a+") as f:
             f.write("context token: {} cached: {} sink: {}\n".format((1, len(ctx.ids)), cached, ctx.sink_len))
         if args.save_attn:                                       # [layers, rows, width], head 0 (NaN beyond each row's keys)
@@ -101,6 +101,7 @@ def main():
     ap.add_argument("--tiny", action="store_true")
     ap.add_argument("--caption-tokens", type=int, default=48)
     ap.add_argument("--stories", type=int, default=1)
+    add_rules_arguments(ap)
     ap.add_argument("--save-attn", default=None, metavar="DIR",
                     help="run the LLM with config.output_attentions and torch.save each step's attn_weights (head 0's "
                          "pre-softmax maps, the evidence behind the attention sink) into DIR")

@@ -336,7 +336,7 @@ class LlamaForCausalLM(nn.Module):
     def generate(self, input_ids=None, inputs_embeds=None, logits_processor=None, past_key_values=None,
                  max_new_tokens=120, output_hidden_states=True, return_dict_in_generate=True, forced_tokens=None,
                  output_attentions=None, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=None, num_beams=1,
-                 **unused):
+                 repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, spare_img_ids=False, **unused):
         """Greedy search as ``ContinuousLVLM.generate`` drives it (reference models.py:146-153): ``inputs_embeds`` feed
         step 0, ``input_ids`` is the running sequence, the image-token logits processor is applied on device.
         ``do_sample=False`` (the default): temperature / top_k / top_p / seed are inert, as in Hugging Face.
@@ -346,6 +346,11 @@ class LlamaForCausalLM(nn.Module):
         ``seed=None`` takes ``torch.initial_seed()`` plus a per-model call counter, so ``torch.manual_seed`` governs the run
         and successive calls differ; an explicit seed reproduces a call exactly.  The engine is greedy again when the call
         returns or raises.  ``num_beams > 1`` with ``do_sample`` raises ``NotImplementedError``.
+        ``repetition_penalty`` / ``no_repeat_ngram_size`` / ``min_new_tokens`` (Hugging Face's defaults 1.0 / 0 / 0: inert) act on
+        greedy search and on sampling alike, on the device, in HF's order in front of the image-token processor
+        (``LlamaEngine.set_logits_rules``; include/seedstory_hip.h): when one of them is active ``input_ids[0]`` is handed over as
+        the token history and the rules are cleared when the call returns or raises.  ``spare_img_ids=True`` (a declared
+        deviation, off by default) exempts the image-token ids from the penalty.
         ``output_attentions`` (default ``config.output_attentions``, the reference's switch): ``attentions`` = tuple over steps
         of tuple over layers — step 0 ``[1, q0, kv0 + q0]``, step j ``[1, 1, kv0 + q0 + j]``, as many as ``hidden_states`` —
         all VIEWS of one capture buffer, which ``attention_maps`` [layers, rows, width] hands out whole (one row per fed token,
@@ -368,10 +373,19 @@ class LlamaForCausalLM(nn.Module):
                 self._sample_calls = getattr(self, "_sample_calls", 0) + 1
                 seed = (torch.initial_seed() + self._sample_calls - 1) & (2 ** 64 - 1)
             eng.set_sampling(temperature=temperature, top_k=top_k, top_p=top_p, seed=seed)     # raises on a bad parameter
+        # (Hugging Face also takes None for "off")
+        rules = (repetition_penalty not in (None, 1.0) or no_repeat_ngram_size not in (None, 0) or min_new_tokens not in (None, 0))
         try:
+            if rules:
+                eng.set_logits_rules(repetition_penalty=1.0 if repetition_penalty is None else repetition_penalty,
+                                     no_repeat_ngram_size=no_repeat_ngram_size or 0, min_new_tokens=min_new_tokens or 0,
+                                     spare_img_ids=bool(spare_img_ids))               # raises on a bad value
+                eng.set_history(input_ids[0].tolist())
             return self._generate(eng, input_ids, rows, S, img_ids, past_key_values, max_new_tokens, output_hidden_states,
                                   forced_tokens, want_attn)
         finally:
+            if rules:
+                eng.clear_logits_rules()
             if do_sample:
                 eng.set_greedy()
             if want_attn:

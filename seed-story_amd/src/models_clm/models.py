@@ -108,10 +108,13 @@ class ContinuousLVLM(nn.Module):
     def generate(self, tokenizer, prompt=None, input_ids=None, image_embeds=None, embeds_cmp_mask=None,
                  ids_cmp_mask=None, logits_processor=None, num_img_gen_tokens=64, temperature=0.7, num_beams=1,
                  max_new_tokens=120, top_p=0.5, past_key_values=None, dtype=torch.float16, device='cuda',
-                 forced_tokens=None, do_sample=False, top_k=0, seed=None):
+                 forced_tokens=None, do_sample=False, top_k=0, seed=None, repetition_penalty=1.0, no_repeat_ngram_size=0,
+                 min_new_tokens=0, spare_img_ids=False):
         """``do_sample=False`` (the default, what the reference passes): greedy; ``temperature`` / ``top_p`` / ``top_k`` /
         ``seed`` are inert.  ``do_sample=True`` hands them to ``LlamaForCausalLM.generate``: on-device sampling
-        (``top_k=0`` = off, ``seed=None`` = governed by ``torch.manual_seed``)."""
+        (``top_k=0`` = off, ``seed=None`` = governed by ``torch.manual_seed``).  ``repetition_penalty`` /
+        ``no_repeat_ngram_size`` / ``min_new_tokens`` (Hugging Face's defaults: inert) and ``spare_img_ids`` are handed on only
+        when one of the three is active: they act on greedy search and on sampling (``LlamaForCausalLM.generate``)."""
         if logits_processor is None:
             logits_processor = LogitsProcessorList()
             logits_processor.append(
@@ -134,11 +137,15 @@ class ContinuousLVLM(nn.Module):
             assert idx.numel() == sel.shape[0], "ids_cmp_mask / embeds_cmp_mask disagree"
             ops.scatter_rows_(input_embeds.view(-1, dim), idx, sel)       # (:135)
 
+        rules = {}
+        if repetition_penalty not in (None, 1.0) or no_repeat_ngram_size not in (None, 0) or min_new_tokens not in (None, 0):
+            rules = dict(repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
+                         min_new_tokens=min_new_tokens, spare_img_ids=spare_img_ids)
         output = self.llm.generate(input_ids=input_ids, inputs_embeds=input_embeds, output_hidden_states=True,
                                    return_dict_in_generate=True, logits_processor=logits_processor,
                                    past_key_values=past_key_values, max_new_tokens=max_new_tokens,
                                    temperature=temperature, num_beams=num_beams, top_p=top_p, do_sample=do_sample,
-                                   forced_tokens=forced_tokens, **({"top_k": top_k, "seed": seed} if do_sample else {}))
+                                   forced_tokens=forced_tokens, **({"top_k": top_k, "seed": seed} if do_sample else {}), **rules)
         output_past_key_values = self.llm.past_key_values
         generate_ids = output.sequences[0][input_ids.shape[1]:]
         boi_token_id = tokenizer.encode(BOI_TOKEN, add_special_tokens=False)[0]
