@@ -239,6 +239,25 @@ int ss_attn_decode(const void* q, const void* kcache, const void* vcache, void* 
                    const int32_t* kv_len_dev, int64_t n_heads, int64_t hd, int64_t cache_cap, int dtype,
                    void* stream);
 
+/* fp8 (OCP e4m3fn) shadow of a KV cache, for the q_len = 1 decode token (the engine option: ss_llama_set_kv8).
+ * The quantisation, per (head, position), of the hd values x of a key (post-RoPE, as stored) or a value in the model dtype:
+ *   amax = max |x_j|;  amax == 0: scale = 1, every code 0;  otherwise scale = 2^e with the smallest integer e such that
+ *   amax <= 448 * 2^e  (amax = m * 2^t, m in [0.5, 1): e = t - 9 if m <= 0.875, else t - 8), e >= -126;
+ *   code_j = e4m3fn(x_j * 2^-e), round to nearest even (the product is exact in fp32 and at most 448: nothing saturates).
+ * A power-of-two scale costs no relative precision in e4m3's normal range, and code * scale is exactly representable in bf16
+ * and fp16.  Rows with non-finite entries are outside the definition (no fault, any result).
+ * ss_kv_quantize_fp8: rows [lo, hi) of the planes k, v [n_heads, cache_cap, hd] of ONE layer -> k_codes, v_codes (same shape,
+ * bytes) and k_scale, v_scale fp32 [n_heads, cache_cap]; nothing outside those rows is written.
+ * ss_attn_decode_kv8: ss_attn_decode over such planes, fp32 throughout: s = (q . codes) * k_scale[key] / sqrt(hd),
+ * out = sum softmax(s) * v_scale[key] * codes.  Positions >= *kv_len_dev are never read, codes or scales.  Same workspace.
+ * bf16 / fp16 only; hd a multiple of 16, at most 256, hd / 16 a power of two (64 and 128 are).  SS_EINVAL before anything is
+ * launched: fp32, another hd, a NULL plane, a code plane that is not 16-byte aligned. */
+int ss_kv_quantize_fp8(const void* k, const void* v, void* k_codes, void* v_codes, float* k_scale, float* v_scale,
+                       int64_t n_heads, int64_t cache_cap, int64_t hd, int64_t lo, int64_t hi, int dtype, void* stream);
+int ss_attn_decode_kv8(const void* q, const void* k_codes, const void* v_codes, const float* k_scale, const float* v_scale,
+                       void* out, void* workspace, const int32_t* kv_len_dev, int64_t n_heads, int64_t hd, int64_t cache_cap,
+                       int dtype, void* stream);
+
 /* Attention MAP of one head, as the reference returns it under `output_attentions`
  * (modeling_llama_xformer.py:246-276, 299-301): PRE-softmax scores with the mask added, every rounding in the model dtype:
  *   s = rnd_T(rnd_T(q . k) / sqrt(head_dim)), q / k post-RoPE.
@@ -530,6 +549,29 @@ typedef struct ss_llama_layer_w8 {
     const float *s_qkv, *s_o, *s_gu, *s_down;
 } ss_llama_layer_w8;
 int ss_llama_set_decode_w8(ss_llama* h, const ss_llama_layer_w8* layers, const void* lm_head_q, const float* lm_head_scale);
+
+/* fp8 (e4m3) KV shadow cache for decode attention (the quantisation: ss_kv_quantize_fp8).  k_codes, v_codes
+ * [n_seq][n_layers][n_heads][cache_cap][hd] bytes and k_scale, v_scale [n_seq][n_layers][n_heads][cache_cap] fp32: device
+ * memory owned by the caller and kept alive while the option is on (sizes: ss_llama_kv8_bytes; ss_llama_workspace_bytes does
+ * not change).  All four NULL = off (the default): the decode token then launches exactly what it launched before.
+ * While it is on, the attention of every decode token of ss_llama_generate / ss_llama_generate_batch / ss_llama_profile_decode
+ * (eager or captured; the captured graph is cached apart and dropped when the planes change) reads keys and values from the
+ * shadow — half the KV bytes per token — and its fused append writes the new row to the 16-bit cache, as before, AND to the
+ * shadow.  The new token's own k / v are used unquantised.
+ * The 16-bit cache stays the truth and everything else keeps using it unchanged: ss_llama_prefill*, the image-token block,
+ * ss_llama_buffer's views, ss_llama_kv_gather, attention-map capture.  The option therefore COSTS memory: hd + 4 bytes per
+ * (slot, layer, head, position) on top (LLaMA-7B: 0.27 MB per position per slot, 0.31 GB per slot at cache_cap 1152).
+ * Attention-map capture keeps computing its decode rows from the 16-bit keys: with the option on, the maps show the 16-bit
+ * scores, not the ones the token used.
+ * Each slot has a host-side watermark: shadow rows below it equal the quantiser applied to the 16-bit rows.  The three
+ * decode entry points start with one launch that quantises the rows [watermark, kv_len) of their slots, whoever wrote them.
+ * ss_llama_set_lengths lowers the watermark to min(watermark, kv_len), ss_llama_kv_gather to 0; a caller that writes cache
+ * rows through ss_llama_buffer's views calls ss_llama_kv8_invalidate(h, first row written) for the selected slot.
+ * Works with fp8 decode weights, sampling and the history rules.  Call these between engine calls.
+ * SS_EINVAL: an fp32 engine, a head dim ss_attn_decode_kv8 does not take, some but not all planes NULL, a misaligned plane. */
+int ss_llama_kv8_bytes(const ss_llama_config* cfg, size_t* codes_bytes, size_t* scales_bytes);    /* per plane, all slots */
+int ss_llama_set_kv8(ss_llama* h, void* k_codes, void* v_codes, float* k_scale, float* v_scale);
+int ss_llama_kv8_invalidate(ss_llama* h, int64_t from_row);
 
 /* Device pointers into the engine's workspace (views for the Python side), for the selected slot:
  * which: 0 = K cache [n_layers, n_heads, cache_cap, hd], 1 = V cache (same shape),

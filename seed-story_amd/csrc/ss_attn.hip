@@ -1532,10 +1532,33 @@ __global__ void attn_combine_kernel(const float* __restrict__ part, T* __restric
 
 // KV splits per (head, slot): 16 at one slot (512 blocks of ~25 keys at S = 400 — enough to fill the chip, measured
 // optimum), fewer when several story slots already multiply the block count (4 slots: 4 splits, -6 % token time)
-static inline int decode_nsplit(int nb) {
+int decode_nsplit(int nb) {
     int n = knob(K_attn_decode_nsplit);
     if (n <= 0) n = 16 / (nb < 1 ? 1 : nb);
     return n <= 4 ? 4 : n <= 8 ? 8 : n <= 16 ? 16 : 32;
+}
+
+// the merge of one decode launch's partial records: nsplit is one of decode_nsplit's values
+template <typename T>
+int attn_combine_launch(const float* part, void* out, const int32_t* done_flag, int64_t n_heads, int64_t hd, int nb, int nsplit,
+                        int state_stride, int64_t part_stride, int64_t out_stride, hipStream_t s) {
+#define SS_COMBINE(NS)                                                                                                  \
+    hipLaunchKernelGGL((attn_combine_kernel<T, NS>), dim3((unsigned)n_heads, (unsigned)nb), dim3((unsigned)hd), 0, s, part, \
+                       (T*)out, done_flag, (int)hd, state_stride, part_stride, out_stride)
+    switch (nsplit) {
+        case 4: SS_COMBINE(4); break;
+        case 8: SS_COMBINE(8); break;
+        case 16: SS_COMBINE(16); break;
+        default: SS_COMBINE(32); break;
+    }
+#undef SS_COMBINE
+    SS_LAUNCH_CHECK("attn_combine");
+    return SS_OK;
+}
+// (for the fp8-shadow decode kernel of ss_attn_kv8.hip, which writes the same partial records)
+int attn_combine_dev(const float* part, void* out, const int32_t* done_flag, int64_t n_heads, int64_t hd, int nb, int nsplit,
+                     int state_stride, int64_t part_stride, int64_t out_stride, int dtype, hipStream_t s) {
+    return SS_DISPATCH(dtype, attn_combine_launch, part, out, done_flag, n_heads, hd, nb, nsplit, state_stride, part_stride, out_stride, s);
 }
 
 template <typename T>
@@ -1552,19 +1575,7 @@ int attn_decode_launch(const DecodeArgs& a0, void* out, int64_t n_heads, int64_t
     hipLaunchKernelGGL(attn_decode_kernel<T>, dim3((unsigned)n_heads, (unsigned)a.nsplit, (unsigned)a.nb), dim3(256),
                        lds, s, a);
     SS_LAUNCH_CHECK("attn_decode");
-#define SS_COMBINE(NS)                                                                                          \
-    hipLaunchKernelGGL((attn_combine_kernel<T, NS>), dim3((unsigned)n_heads, (unsigned)a.nb), dim3((unsigned)hd), 0, \
-                       s, (const float*)a.part, (T*)out, a.done_flag, (int)hd, a.state_stride, a.part_stride,       \
-                       a.out_stride)
-    switch (a.nsplit) {
-        case 4: SS_COMBINE(4); break;
-        case 8: SS_COMBINE(8); break;
-        case 16: SS_COMBINE(16); break;
-        default: SS_COMBINE(32); break;
-    }
-#undef SS_COMBINE
-    SS_LAUNCH_CHECK("attn_combine");
-    return SS_OK;
+    return attn_combine_launch<T>(a.part, out, a.done_flag, n_heads, hd, a.nb, a.nsplit, a.state_stride, a.part_stride, a.out_stride, s);
 }
 
 // (positional: mind the order at the call sites, the nullptr arguments carry no type protection)

@@ -13,6 +13,9 @@
 //    per-token scalars (kv_len, rope position, last token id, EOS flag) live in device memory, so
 //    the graph replays without host round trips; the reference syncs the host every token
 //    (`.item()` in generation.py:22, EOS check in HF).
+//  * option (ss_llama_set_kv8, off by default): the attention of the decode token reads an fp8 (e4m3) SHADOW of the slab (caller-owned
+//    code + scale planes, ss_attn_kv8.hip) and appends to both; the slab stays the truth for everything else.  A host-side
+//    watermark per slot says how many shadow rows are valid; the decode entry points quantise the rest in one launch up front.
 #include <stddef.h>
 #include <string.h>
 
@@ -22,6 +25,7 @@
 #include "ss_gemv.h"
 #include "ss_sample.h"
 #include "ss_rules.h"
+#include "ss_kv8.h"
 
 namespace ss {
 
@@ -279,6 +283,7 @@ struct SeqGraph {
     int w8;                  // fp8 decode weights on (ss_llama_set_decode_w8): other kernels, other weight pointers
     int sampling;            // a slot of [seq0, seq0+nb) has sampling on (ss_llama_set_sampling): the sampling kernel opens the token
     int rules;               // a slot of [seq0, seq0+nb) has history rules on (ss_llama_set_logits_rules): the rules kernel in front
+    int kv8;                 // fp8 KV shadow on (ss_llama_set_kv8): another attention kernel, the planes' pointers
     hipGraph_t graph;
     hipGraphExec_t exec;
 };
@@ -318,6 +323,12 @@ struct ss_llama {
     std::vector<ss_llama_layer_w8> w8;
     const void* w8_lm_head = nullptr;
     const float* w8_lm_scale = nullptr;
+    // fp8 shadow of the KV cache (ss_llama_set_kv8): caller-owned planes, kq == NULL = off.  Invariant: shadow rows
+    // [0, kv8_rows[b]) of slot b equal the quantiser applied to its 16-bit rows (host-side watermark, <= kv_len[b] wherever
+    // it matters: everything that rewrites 16-bit rows below it lowers it)
+    uint8_t *kq = nullptr, *vq = nullptr;      // [n_seq][L][H][cap][hd]
+    float *kscale = nullptr, *vscale = nullptr;  // [n_seq][L][H][cap]
+    std::vector<int64_t> kv8_rows;
     // sampling (ss_llama_set_sampling): per-slot parameters + draw counter in device memory, which slots have it on here
     SampleParams* samp = nullptr;       // [n_seq]
     std::vector<char> samp_on;
@@ -502,9 +513,17 @@ static int decode_token(ss_llama* h, hipStream_t s, ProfSink* prof, int seq0, in
         rc = proj(L.wqkv, Q.wqkv, Q.s_qkv, h->x, h->qkv, 3 * H, H, L.ln1, nullptr, SS_EPI_NONE, 3 * H, 0);
         if (rc) return rc;
         MARK(0);
-        // RoPE(q,k) + KV append + split-KV attention in one kernel (+ the split merge)
-        rc = attn_decode_fused_dev(h->qkv, kc, vc, h->w.rope_cos, h->w.rope_sin, h->attn, attn_ws, st + ST_KV_LEN,
-                                   st + ST_POS, done, g.n_heads, hd, g.cache_cap, nb, ST_WORDS, cache_stride, dt, s);
+        // RoPE(q,k) + KV append + split-KV attention in one kernel (+ the split merge); with the fp8 shadow on, its sibling
+        // that reads the shadow and appends to both
+        if (h->kq) {
+            const size_t so = ((size_t)seq0 * g.n_layers + l) * g.n_heads * g.cache_cap;        // rows in front of this plane
+            rc = attn_decode_kv8_fused_dev(h->qkv, kc, vc, h->kq + so * hd, h->vq + so * hd, h->kscale + so, h->vscale + so,
+                                           h->w.rope_cos, h->w.rope_sin, h->attn, attn_ws, st + ST_KV_LEN, st + ST_POS, done,
+                                           g.n_heads, hd, g.cache_cap, nb, ST_WORDS, cache_stride, dt, s);
+        } else {
+            rc = attn_decode_fused_dev(h->qkv, kc, vc, h->w.rope_cos, h->w.rope_sin, h->attn, attn_ws, st + ST_KV_LEN,
+                                       st + ST_POS, done, g.n_heads, hd, g.cache_cap, nb, ST_WORDS, cache_stride, dt, s);
+        }
         if (rc) return rc;
         if (h->cap.maps && nb == 1) {   // attention-map capture: this layer's row of head cap.head (capture off: no launch)
             rc = attn_scores_decode_dev(h->qkv, kc, h->w.rope_cos, h->w.rope_sin, st + ST_KV_LEN, st + ST_POS, done, h->cap_desc,
@@ -549,14 +568,15 @@ static int graph_for(ss_llama* h, int seq0, int nb, hipGraphExec_t* out) {
     const int w8 = h->w8.empty() ? 0 : 1;
     const int sampling = h->sampling_in(seq0, nb) ? 1 : 0;
     const int rules = h->rules_in(seq0, nb) ? 1 : 0;
+    const int kv8 = h->kq ? 1 : 0;
     for (const SeqGraph& sg : h->graphs)
         if (sg.seq0 == seq0 && sg.nb == nb && sg.mode == mode && sg.capture == capture && sg.w8 == w8 && sg.sampling == sampling &&
-            sg.rules == rules) {
+            sg.rules == rules && sg.kv8 == kv8) {
             *out = sg.exec;
             return SS_OK;
         }
     SeqGraph sg;
-    sg.seq0 = seq0; sg.nb = nb; sg.mode = mode; sg.capture = capture; sg.w8 = w8; sg.sampling = sampling; sg.rules = rules;
+    sg.seq0 = seq0; sg.nb = nb; sg.mode = mode; sg.capture = capture; sg.w8 = w8; sg.sampling = sampling; sg.rules = rules; sg.kv8 = kv8;
     sg.graph = nullptr; sg.exec = nullptr;
     SS_HIP(hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
     int rc = decode_token(h, h->cap_stream, nullptr, seq0, nb);
@@ -582,10 +602,39 @@ static int rules_finish(ss_llama* h, int seq0, int nb, hipStream_t s) {
     return SS_OK;
 }
 
+// fp8 KV shadow, lazy sync: ONE eager launch in front of a decode loop quantises the 16-bit rows [kv8_rows, kv_len) of slots
+// [seq0, seq0+nb) — whatever wrote them (prefill, the image-token block, a loaded or gathered cache).  Inside the loop only the
+// fused decode kernel's own append writes the shadow.
+static int kv8_sync(ss_llama* h, int seq0, int nb, hipStream_t s) {
+    if (!h->kq) return SS_OK;
+    const ss_llama_config& g = h->cfg;
+    const size_t so = (size_t)seq0 * g.n_layers * g.n_heads * g.cache_cap;       // rows in front of slot seq0
+    Kv8QuantArgs a = {h->kc + so * h->hd * h->esz, h->vc + so * h->hd * h->esz, h->kq + so * h->hd, h->vq + so * h->hd,
+                      h->kscale + so, h->vscale + so, g.n_heads, g.cache_cap, h->hd, g.n_layers, nb,
+                      (int64_t)(h->seq_kv_bytes() / h->esz), {0, 0, 0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0, 0, 0}};
+    bool any = false;
+    for (int b = 0; b < nb; ++b) {
+        const int64_t len = h->kv_len[seq0 + b], have = h->kv8_rows[seq0 + b];
+        a.lo[b] = (int)(have < len ? have : len);
+        a.hi[b] = (int)len;
+        any = any || a.lo[b] < a.hi[b];
+    }
+    if (any)
+        if (int rc = kv8_quantize_dev(a, g.dtype, s)) return rc;
+    for (int b = seq0; b < seq0 + nb; ++b) h->kv8_rows[b] = h->kv_len[b];
+    return SS_OK;
+}
+// after a decode loop (the host mirrors hold the final lengths): every row it appended has its shadow row
+static void kv8_advance(ss_llama* h, int seq0, int nb) {
+    if (h->kq)
+        for (int b = seq0; b < seq0 + nb; ++b) h->kv8_rows[b] = h->kv_len[b];
+}
+
 // shared driver of ss_llama_generate / ss_llama_generate_batch: the state words of slots
 // [seq0, seq0+nb) have been staged in h->pinned[upload area]; replays the decode graph until every
 // slot reports done or `eff_limit` tokens were launched.
 static int run_decode(ss_llama* h, int seq0, int nb, int64_t eff_limit, hipStream_t s) {
+    if (int rc = kv8_sync(h, seq0, nb, s)) return rc;
     SS_HIP(hipMemcpyAsync(h->state + (size_t)seq0 * ST_WORDS, h->upload() + (size_t)seq0 * ST_WORDS,
                           (size_t)nb * ST_WORDS * sizeof(int32_t), hipMemcpyHostToDevice, s));
     const bool use_graph = knob(K_llama_graph) != 0;
@@ -607,6 +656,7 @@ static int run_decode(ss_llama* h, int seq0, int nb, int64_t eff_limit, hipStrea
         if (all) break;
     }
     if (!launched) { int rc = sync_lengths(h, seq0, nb, s); if (rc) return rc; }
+    kv8_advance(h, seq0, nb);
     return rules_finish(h, seq0, nb, s);
 }
 
@@ -625,6 +675,7 @@ static int set_lengths_slot(ss_llama* h, int slot, int64_t kv_len, int64_t pos, 
     SS_LAUNCH_CHECK("set_state");
     h->kv_len[slot] = kv_len;
     h->pos[slot] = pos;
+    if (h->kv8_rows[slot] > kv_len) h->kv8_rows[slot] = kv_len;       // a truncated cache: the rows beyond will be rewritten
     return SS_OK;
 }
 
@@ -804,6 +855,7 @@ int ss_llama_create(const ss_llama_config* cfg, const ss_llama_weights* w, void*
     h->samp_on.assign(h->n_seq, 0);
     h->rules_on.assign(h->n_seq, 0);
     h->hist_len.assign(h->n_seq, 0);
+    h->kv8_rows.assign(h->n_seq, 0);
     hipError_t e = hipStreamCreateWithFlags(&h->cap_stream, hipStreamNonBlocking);
     if (e == hipSuccess)
         e = hipHostMalloc((void**)&h->pinned, (size_t)h->n_seq * 2 * ST_WORDS * sizeof(int32_t) + 64, hipHostMallocDefault);
@@ -914,11 +966,12 @@ int ss_llama_set_history(ss_llama* h, int32_t seq, const int32_t* host_ids, int6
     return SS_OK;
 }
 
-// the captured fp8 graphs hold the weight pointers of the planes they were captured over: dropped when the planes change
-static void drop_w8_graphs(ss_llama* h) {
+// the captured fp8 graphs hold the pointers of the planes they were captured over (weights: flag = &SeqGraph::w8, KV shadow:
+// &SeqGraph::kv8): dropped when those planes change
+static void drop_graphs(ss_llama* h, int SeqGraph::*flag) {
     size_t keep = 0;
     for (SeqGraph& sg : h->graphs) {
-        if (!sg.w8) { h->graphs[keep++] = sg; continue; }
+        if (!(sg.*flag)) { h->graphs[keep++] = sg; continue; }
         if (sg.exec) hipGraphExecDestroy(sg.exec);
         if (sg.graph) hipGraphDestroy(sg.graph);
     }
@@ -928,7 +981,7 @@ static void drop_w8_graphs(ss_llama* h) {
 int ss_llama_set_decode_w8(ss_llama* h, const ss_llama_layer_w8* layers, const void* lm_head_q, const float* lm_head_scale) {
     SS_REQUIRE(h, "llama_set_decode_w8: null handle");
     if (!layers) {      // off: the 16-bit graphs are still cached; the fp8 ones go with their planes
-        drop_w8_graphs(h);
+        drop_graphs(h, &SeqGraph::w8);
         h->w8.clear();
         h->w8_lm_head = nullptr;
         h->w8_lm_scale = nullptr;
@@ -954,10 +1007,42 @@ int ss_llama_set_decode_w8(ss_llama* h, const ss_llama_layer_w8* layers, const v
                    "llama_set_decode_w8: layer %d: the byte planes must be 16-byte aligned", l);
     }
     SS_REQUIRE(((size_t)lm_head_q & 15) == 0, "llama_set_decode_w8: the lm_head plane must be 16-byte aligned");
-    drop_w8_graphs(h);
+    drop_graphs(h, &SeqGraph::w8);
     h->w8.assign(layers, layers + g.n_layers);
     h->w8_lm_head = lm_head_q;
     h->w8_lm_scale = lm_head_scale;
+    return SS_OK;
+}
+
+int ss_llama_kv8_bytes(const ss_llama_config* cfg, size_t* codes_bytes, size_t* scales_bytes) {
+    SS_REQUIRE(cfg && codes_bytes && scales_bytes, "llama_kv8_bytes: null argument");
+    SS_REQUIRE(cfg->n_heads > 0 && cfg->hidden % cfg->n_heads == 0 && cfg->n_layers > 0 && cfg->cache_cap > 0, "llama_kv8_bytes: bad config");
+    if (int rc = kv8_check(cfg->hidden / cfg->n_heads, cfg->dtype, "llama_kv8_bytes")) return rc;
+    const size_t rows = (size_t)cfg_n_seq(cfg) * cfg->n_layers * cfg->n_heads * cfg->cache_cap;
+    *codes_bytes = rows * (size_t)(cfg->hidden / cfg->n_heads);
+    *scales_bytes = rows * sizeof(float);
+    return SS_OK;
+}
+
+int ss_llama_set_kv8(ss_llama* h, void* k_codes, void* v_codes, float* k_scale, float* v_scale) {
+    SS_REQUIRE(h, "llama_set_kv8: null handle");
+    const bool off = !k_codes && !v_codes && !k_scale && !v_scale;
+    if (!off) {
+        if (int rc = kv8_check(h->hd, h->cfg.dtype, "llama_set_kv8")) return rc;
+        SS_REQUIRE(k_codes && v_codes && k_scale && v_scale, "llama_set_kv8: NULL plane (all four, or none to switch the option off)");
+        SS_REQUIRE((((size_t)k_codes | (size_t)v_codes) & 15) == 0 && (((size_t)k_scale | (size_t)v_scale) & 3) == 0,
+                   "llama_set_kv8: the code planes must be 16-byte aligned (scales: 4)");
+    }
+    // every decode loop of this engine has synchronised before it returned: nothing in flight reads the planes
+    drop_graphs(h, &SeqGraph::kv8);
+    h->kq = (uint8_t*)k_codes; h->vq = (uint8_t*)v_codes; h->kscale = k_scale; h->vscale = v_scale;
+    h->kv8_rows.assign(h->n_seq, 0);        // new planes hold nothing yet
+    return SS_OK;
+}
+
+int ss_llama_kv8_invalidate(ss_llama* h, int64_t from_row) {
+    SS_REQUIRE(h && from_row >= 0, "llama_kv8_invalidate: bad arguments (from_row=%lld)", (long long)from_row);
+    if (h->kv8_rows[h->cur] > from_row) h->kv8_rows[h->cur] = from_row;
     return SS_OK;
 }
 
@@ -1005,6 +1090,7 @@ int ss_llama_kv_gather(ss_llama* h, const int32_t* keep_idx_dev, int64_t n_keep,
         for (char* plane : {slot_k(h, h->cur, l), slot_v(h, h->cur, l)})
             if (int rc = SS_DISPATCH(g.dtype, kv_repack_launch, h, plane, keep_idx_dev, (int)n_keep, (hipStream_t)stream))
                 return rc;
+    h->kv8_rows[h->cur] = 0;     // rows moved: the shadow of this slot is rebuilt by the next decode loop
     return ss_llama_set_lengths(h, n_keep, h->pos[h->cur], stream);
 }
 
@@ -1137,6 +1223,7 @@ int ss_llama_profile_decode(ss_llama* h, int64_t n_tokens, float out_ms[8], doub
         fill_state(h->upload() + (size_t)b * ST_WORDS, h->kv_len[b], h->pos[b], false, 0, 0, g.max_new, -1);
     }
     SS_HIP(hipMemcpyAsync(h->state, h->upload(), (size_t)h->n_seq * ST_WORDS * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    if (int rc = kv8_sync(h, 0, h->n_seq, s)) return rc;
     for (int i = 0; i < 8; ++i) out_ms[i] = 0.f;
     double cnt[4] = {0, 0, 0, 0};
     for (int64_t t = 0; t < n_tokens && t < g.max_new - 1; ++t) {
@@ -1173,6 +1260,7 @@ int ss_llama_profile_decode(ss_llama* h, int64_t n_tokens, float out_ms[8], doub
     }
     out_bytes[3] = cnt[2] / (double)n_tokens;
     if (int rc = sync_lengths(h, 0, h->n_seq, s)) return rc;
+    kv8_advance(h, 0, h->n_seq);
     return rules_finish(h, 0, h->n_seq, s);
 }
 

@@ -105,6 +105,8 @@ PROTOTYPES = {
     "ss_attention_ragged": (C.c_int, [vp, vp, vp, vp] + [i64] * 3 + [vp] + [i64] * 13 + [f32, C.c_int, C.c_int, vp]),
     "ss_attn_decode_workspace_bytes": (sz, [i64, i64]),
     "ss_attn_decode": (C.c_int, [vp, vp, vp, vp, vp, vp, i64, i64, i64, C.c_int, vp]),
+    "ss_kv_quantize_fp8": (C.c_int, [vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, C.c_int, vp]),
+    "ss_attn_decode_kv8": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, C.c_int, vp]),
     "ss_attn_scores": (C.c_int, [vp, i64, vp, i64, vp, i64, i64, i64, i64, C.c_int, C.c_int, vp]),
     "ss_gemm": (C.c_int, [vp, vp, vp, i64, i64, i64, i64, i64, i64, vp, vp, i64, C.c_int, C.c_int, vp]),
     "ss_gemm_tune_workspace_bytes": (sz, [i64, i64, i64, C.c_int]),
@@ -131,6 +133,9 @@ PROTOTYPES = {
     "ss_llama_set_stop_id": (C.c_int, [vp, i32]),
     "ss_llama_set_attn_capture": (C.c_int, [vp, vp, i64, i64, i64, i32, i32]),
     "ss_llama_set_decode_w8": (C.c_int, [vp, C.POINTER(LlamaLayerW8), vp, vp]),
+    "ss_llama_kv8_bytes": (C.c_int, [C.POINTER(LlamaConfig), C.POINTER(sz), C.POINTER(sz)]),
+    "ss_llama_set_kv8": (C.c_int, [vp, vp, vp, vp, vp]),
+    "ss_llama_kv8_invalidate": (C.c_int, [vp, i64]),
     "ss_llama_set_sampling": (C.c_int, [vp, i32, C.POINTER(Sampling)]),
     "ss_llama_set_logits_rules": (C.c_int, [vp, i32, C.POINTER(LogitsRules)]),
     "ss_llama_set_history": (C.c_int, [vp, i32, i32p, i64, i32]),

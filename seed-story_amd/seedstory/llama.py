@@ -47,9 +47,11 @@ def _prefill_chunked(eng, emb, want_hidden):
 class LlamaEngine:
     def __init__(self, state_dict, *, hidden, n_heads, n_layers, inter, vocab, dtype=torch.bfloat16, device="cuda:0",
                  rms_eps=1e-5, max_pos=4096, cache_cap=2048, max_new=512, max_prefill_rows=1024, img_ids=(),
-                 eos_id=2, lora_scaling=2.0, n_seq=1, decode_weights=None):
+                 eos_id=2, lora_scaling=2.0, n_seq=1, decode_weights=None, kv_cache=None):
         """``decode_weights``: None = the ``llama_decode_w8`` tuning knob decides (default off), "fp8" = decode tokens
-        stream e4m3 copies of the five projections (``enable_decode_fp8``), "16bit" = off whatever the knob says."""
+        stream e4m3 copies of the five projections (``enable_decode_fp8``), "16bit" = off whatever the knob says.
+        ``kv_cache``: the same three values for the e4m3 shadow of the KV cache that decode attention reads
+        (``enable_kv_fp8``; knob ``llama_kv8``, default off)."""
         self.n_seq = int(n_seq)
         self.device = torch.device(device)
         self.dtype = dtype
@@ -90,11 +92,12 @@ class LlamaEngine:
         self._layers = layers
         self._init_engine(max_pos, rms_eps)
         self._init_decode_weights(decode_weights)
+        self._init_kv_cache(kv_cache)
 
     @classmethod
     def from_prebuilt(cls, *, embed, lm_head, final_norm, layers, hidden, n_heads, n_layers, inter, vocab,
                       dtype=torch.bfloat16, device="cuda:0", rms_eps=1e-5, max_pos=4096, cache_cap=2048, max_new=512,
-                      max_prefill_rows=1024, img_ids=(), eos_id=2, n_seq=1, decode_weights=None):
+                      max_prefill_rows=1024, img_ids=(), eos_id=2, n_seq=1, decode_weights=None, kv_cache=None):
         """Engine over already merged/concatenated device tensors: ``layers`` is a list of
         ``(wqkv, wo, wgu, wdown, ln1, ln2)`` (used by the synthetic-weight benchmark, which
         creates the 13.5 GB of weights directly on the GPU)."""
@@ -118,6 +121,7 @@ class LlamaEngine:
         self._layers = arr
         self._init_engine(max_pos, rms_eps)
         self._init_decode_weights(decode_weights)
+        self._init_kv_cache(kv_cache)
         return self
 
     def _init_engine(self, max_pos, rms_eps):
@@ -140,6 +144,8 @@ class LlamaEngine:
         self._capture = None       # (maps, row0, head) while attention-map capture is on
         self._w8 = None            # tensors of the fp8 decode planes while the option is on
         self.decode_weights = None
+        self._kv8 = None           # the four shadow planes (k_codes, v_codes, k_scale, v_scale) while kv_cache="fp8" is on
+        self.kv_cache = None
         self._rules_slots = set()  # slots whose history rules are on (set_logits_rules)
 
     def __del__(self):
@@ -214,12 +220,17 @@ class LlamaEngine:
     def load_past_key_values(self, past, pos=None):
         """Copy an external reference-layout cache into the slab (no-op for our own views)."""
         n = past[0][0].shape[2]
+        wrote = False
         for l, (k, v) in enumerate(past):
             dk, dv = self.k_cache[l, :, :n], self.v_cache[l, :, :n]
             if k.data_ptr() != dk.data_ptr():
                 dk.copy_(k[0])
+                wrote = True
             if v.data_ptr() != dv.data_ptr():
                 dv.copy_(v[0])
+                wrote = True
+        if wrote:       # rows written through the views: their fp8 shadow rows (kv_cache="fp8") are stale
+            self.kv_invalidate(0)
         self.set_lengths(n, n if pos is None else pos)
 
     def kv_gather(self, keep_idx):
@@ -319,6 +330,71 @@ class LlamaEngine:
         check(lib().ss_llama_set_decode_w8(self._h, None, None, None), "ss_llama_set_decode_w8")
         self._w8 = None
         self.decode_weights = None
+
+    # ---- fp8 (e4m3) shadow of the KV cache for decode attention --------------------------------------------------
+    def _init_kv_cache(self, kv_cache):
+        if kv_cache is None:            # the knob, like llama_decode_w8, is ignored by fp32 (gate mode) engines
+            on = _lib.get_tuning("llama_kv8", 0) and self.dtype in (torch.bfloat16, torch.float16)
+            kv_cache = "fp8" if on else None
+        if kv_cache not in (None, "16bit", "fp8"):
+            raise ValueError("kv_cache must be None, '16bit' or 'fp8', not %r" % (kv_cache,))
+        if kv_cache == "fp8":
+            self.enable_kv_fp8()
+
+    def enable_kv_fp8(self):
+        """Allocate the e4m3 shadow of the KV cache (codes + one fp32 power-of-two scale per slot, layer, head and position;
+        the definition is in include/seedstory_hip.h) and switch decode attention to it: ``generate`` / ``generate_batch`` /
+        ``profile_decode`` then read half the key / value bytes per token.  The 16-bit cache stays the truth — prefill, the
+        image-token block, ``past_key_values``, ``kv_gather`` and attention-map capture keep using it — so the option COSTS
+        memory: ``hd + 4`` bytes per cached row on top (0.27 MB per position per slot for LLaMA-7B).  The engine quantises
+        rows it has not seen at the start of each decode call; write cache rows through ``k_cache`` / ``v_cache`` yourself and
+        you owe it a ``kv_invalidate``.  Off by default: what an e4m3 cache does to stories on a real checkpoint has not been
+        measured.  Raises ``SSError`` on an fp32 engine or a head dim the kernel does not take."""
+        nc, ns = C.c_size_t(), C.c_size_t()
+        check(lib().ss_llama_kv8_bytes(C.byref(self._cfg), C.byref(nc), C.byref(ns)), "ss_llama_kv8_bytes")
+        shape = (self.n_seq, self.n_layers, self.n_heads, self.cache_cap)
+        planes = [torch.zeros(shape + (self.hd,), dtype=torch.uint8, device=self.device) for _ in range(2)]
+        planes += [torch.ones(shape, dtype=torch.float32, device=self.device) for _ in range(2)]
+        assert planes[0].numel() == nc.value and planes[2].numel() * 4 == ns.value
+        torch.cuda.current_stream(self.device).synchronize()
+        check(lib().ss_llama_set_kv8(self._h, *[t.data_ptr() for t in planes]), "ss_llama_set_kv8")
+        self._kv8 = planes
+        self.kv_cache = "fp8"
+
+    def disable_kv_fp8(self):
+        torch.cuda.current_stream(self.device).synchronize()
+        check(lib().ss_llama_set_kv8(self._h, None, None, None, None), "ss_llama_set_kv8")
+        self._kv8 = None
+        self.kv_cache = None
+
+    def kv_invalidate(self, from_row=0):
+        """Tell the engine that 16-bit cache rows of the selected slot from ``from_row`` on were written behind its back
+        (through the ``k_cache`` / ``v_cache`` views): their shadow rows are rebuilt by the next decode call.  A no-op while
+        ``kv_cache`` is off."""
+        check(lib().ss_llama_kv8_invalidate(self._h, int(from_row)), "ss_llama_kv8_invalidate")
+
+    def _kv8_plane(self, i):
+        if self._kv8 is None:
+            raise _lib.SSError("the fp8 KV shadow is off (kv_cache='fp8' / enable_kv_fp8)")
+        return self._kv8[i][self._cur]
+
+    @property
+    def k_codes(self):
+        """uint8 ``[n_layers, n_heads, cache_cap, hd]`` view of the selected slot's key codes (``v_codes``, and the fp32
+        ``k_scale`` / ``v_scale`` ``[n_layers, n_heads, cache_cap]``, likewise); rows the engine has not synced yet are stale."""
+        return self._kv8_plane(0)
+
+    @property
+    def v_codes(self):
+        return self._kv8_plane(1)
+
+    @property
+    def k_scale(self):
+        return self._kv8_plane(2)
+
+    @property
+    def v_scale(self):
+        return self._kv8_plane(3)
 
     # ---- sampling ------------------------------------------------------------------------------------------------
     def set_sampling(self, temperature=1.0, top_k=0, top_p=1.0, seed=0, slot=None):

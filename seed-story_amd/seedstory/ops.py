@@ -177,6 +177,34 @@ def attn_decode(q, kcache, vcache, kv_len_dev, out=None):
     return out
 
 
+def kv_quantize_fp8(k, v, lo=0, hi=None, out=None):
+    """e4m3 codes + power-of-two fp32 scales of rows [lo, hi) of one layer's cache planes k, v [n_heads, cap, hd]
+    (ss_kv_quantize_fp8; the definition is in include/seedstory_hip.h).  Returns ``(k_codes, v_codes, k_scale, v_scale)``:
+    uint8 [n_heads, cap, hd] and fp32 [n_heads, cap]; ``out`` = such a tuple to write into (rows outside [lo, hi) are left)."""
+    _req(k); _req(v)
+    n_heads, cap, hd = k.shape
+    hi = cap if hi is None else hi
+    if out is None:
+        out = tuple(torch.zeros(k.shape, dtype=torch.uint8, device=k.device) for _ in range(2)) + \
+              tuple(torch.ones(n_heads, cap, dtype=torch.float32, device=k.device) for _ in range(2))
+    for t in out:
+        _req(t)
+    check(lib().ss_kv_quantize_fp8(p(k), p(v), p(out[0]), p(out[1]), p(out[2]), p(out[3]), n_heads, cap, hd, int(lo), int(hi), dt(k),
+                                   stream()), "ss_kv_quantize_fp8")
+    return out
+
+
+def attn_decode_kv8(q, k_codes, v_codes, k_scale, v_scale, kv_len_dev, out=None):
+    """``attn_decode`` over an e4m3 shadow: codes uint8 [n_heads, cap, hd], scales fp32 [n_heads, cap] (ss_attn_decode_kv8)."""
+    _req(q); _req(k_codes); _req(v_codes); _req(k_scale); _req(v_scale)
+    n_heads, cap, hd = k_codes.shape
+    ws = torch.empty(lib().ss_attn_decode_workspace_bytes(n_heads, hd), dtype=torch.uint8, device=q.device)
+    out = _out(out, q.shape, q, "attn_decode_kv8")
+    check(lib().ss_attn_decode_kv8(p(q), p(k_codes), p(v_codes), p(k_scale), p(v_scale), p(out), p(ws), p(kv_len_dev), n_heads, hd, cap,
+                                   dt(q), stream()), "ss_attn_decode_kv8")
+    return out
+
+
 def attn_scores(q, k, out, row_calls=False):
     """Attention map of one head, the reference's ``output_attentions`` values (ss_attn_scores): q [M, hd] rows of one head
     (post-RoPE), k [kv, hd] one head's plane of the KV cache, out [M, >= kv] in the same dtype — any of them may be a strided

@@ -116,6 +116,7 @@ class LlamaForCausalLM(nn.Module):
         self.max_new = 512
         self.max_prefill_rows = 1280
         self.decode_weights = None      # "fp8": e4m3 weight-only decode projections (LlamaEngine.enable_decode_fp8); None = the knob
+        self.kv_cache = None            # "fp8": decode attention reads an e4m3 shadow of the KV cache (LlamaEngine.enable_kv_fp8); None = the knob
 
     # ---- reference surface ------------------------------------------------------------------
     def get_input_embeddings(self):
@@ -181,7 +182,7 @@ class LlamaForCausalLM(nn.Module):
         lora = getattr(self, "_lora_scaling", None)
         p0 = self.lm_head.weight
         sig = (p0.data_ptr(), p0._version, p0.dtype, str(p0.device), tuple(img_ids), self.cache_cap, self.max_new,
-               self.max_prefill_rows, self.decode_weights)
+               self.max_prefill_rows, self.decode_weights, self.kv_cache)
         if self._engine is None or self._engine_sig != sig:
             if not p0.is_cuda:
                 raise RuntimeError("LlamaForCausalLM must be moved to the GPU first (no CPU path)")
@@ -193,7 +194,7 @@ class LlamaForCausalLM(nn.Module):
                                        cache_cap=self.cache_cap, max_new=self.max_new,
                                        max_prefill_rows=self.max_prefill_rows, img_ids=img_ids,
                                        eos_id=c.eos_token_id, lora_scaling=lora if lora is not None else 2.0,
-                                       decode_weights=self.decode_weights)
+                                       decode_weights=self.decode_weights, kv_cache=self.kv_cache)
             self._engine_sig = sig
         return self._engine
 
