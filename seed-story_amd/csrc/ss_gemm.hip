@@ -460,6 +460,7 @@ template <> int gemm_sp_dispatch<float>(int, const GemmArgs&, hipStream_t) { ret
 template <> int gemm_sp_dispatch_conv<float>(int, const GemmArgs&, hipStream_t) { return 1; }
 template <> int gemm_pp_dispatch<float>(int, const GemmArgs&, hipStream_t) { return 1; }
 template <> int gemm_pp_dispatch_conv<float>(int, const GemmArgs&, hipStream_t) { return 1; }
+template <> int gemm_pp_dispatch_convup<float>(int, const GemmArgs&, hipStream_t) { return 1; }
 template <> int gemm_w4_dispatch<float>(int, const GemmArgs&, hipStream_t) { return 1; }
 template <> int gemm_w4_dispatch_conv<float>(int, const GemmArgs&, hipStream_t) { return 1; }
 

@@ -848,6 +848,7 @@ template <typename T> int gemm_sp_dispatch_conv(int cfg, const GemmArgs& g, hipS
 // ping-pong 8-phase 256x256 / 256x320 tiles (ss_gemm_pp.inc): cfg 50-59
 template <typename T> int gemm_pp_dispatch(int cfg, const GemmArgs& g, hipStream_t s);
 template <typename T> int gemm_pp_dispatch_conv(int cfg, const GemmArgs& g, hipStream_t s);
+template <typename T> int gemm_pp_dispatch_convup(int cfg, const GemmArgs& g, hipStream_t s);   // nearest-2x upsampled input
 // one-stream-per-SIMD 4-wave kernels (ss_gemm_w4.inc, EXPERIMENTAL builds; ss_gemm_w4_stub.hip otherwise): cfg 90-99
 template <typename T> int gemm_w4_dispatch(int cfg, const GemmArgs& g, hipStream_t s);
 template <typename T> int gemm_w4_dispatch_conv(int cfg, const GemmArgs& g, hipStream_t s);
@@ -859,7 +860,8 @@ template <typename T> static int gemm_sp_run(int cfg, const GemmArgs& g, hipStre
     return g.conv_Cin > 0 ? gemm_sp_dispatch_conv<T>(cfg, g, s) : gemm_sp_dispatch<T>(cfg, g, s);
 }
 template <typename T> static int gemm_pp_run(int cfg, const GemmArgs& g, hipStream_t s) {
-    return g.conv_Cin > 0 ? gemm_pp_dispatch_conv<T>(cfg, g, s) : gemm_pp_dispatch<T>(cfg, g, s);
+    if (g.conv_Cin > 0) return g.conv_up ? gemm_pp_dispatch_convup<T>(cfg, g, s) : gemm_pp_dispatch_conv<T>(cfg, g, s);
+    return gemm_pp_dispatch<T>(cfg, g, s);
 }
 template <typename T> static int gemm_w4_run(int cfg, const GemmArgs& g, hipStream_t s) {
     return g.conv_Cin > 0 ? gemm_w4_dispatch_conv<T>(cfg, g, s) : gemm_w4_dispatch<T>(cfg, g, s);

@@ -1,6 +1,6 @@
 // "Ping-pong" 256x256 / 256x320 GEMM and implicit-GEMM 3x3 convolution for 16-bit dtypes: the 8-phase schedule of
 // cdna_hip_programming.md ("The 256^2 8-phase template"), re-derived on this library's LDS tile image, DMA helpers and
-// epilogues (K % 64 == 0).  Included by ss_gemm_pp_{bf16,f16}[_conv].hip with SS_PP_T (element type) and SS_PP_CONV (0 | 1).
+// epilogues (K % 64 == 0).  Included by ss_gemm_pp_{bf16,f16}[_conv|_convup].hip with SS_PP_T (element type) and SS_PP_CONV (0 | 1 | 2: upsampled input).
 // (The description below is written for the 256-wide tile; the 320-wide one and the two-super-phase variant are described at
 // the template parameters / at tile2 inside the kernel.)
 //
@@ -44,11 +44,18 @@
 // with a full EXEC mask and the counted vmcnt schedule holds (the one-barrier conv kernel masks the DMA and zero-fills by
 // ds_write — a fully masked piece is skipped by the hardware, its count is not constant, and that kernel drains to
 // vmcnt(0) every K tile).
+// UP (ss_gemm_pp_*_convup.hip; SS_PP_CONV = 2): the same with the input read through a nearest-2x upsampling (output 2H x 2W, both
+// powers of two, output W >= 8): a piece is 8 output pixels of one OUTPUT row, its source row (oy + dy) >> 1 is a scalar that moves
+// with dy by the parity of oy (re-formed per piece at the tap change), its lanes' source columns are ox0 / 2 + ((r + dx) >> 1): one
+// of two loop-invariant lane offsets, picked by the tap.  Padding, masks, K order and the vmcnt schedule are those of CONV.  The
+// arithmetic is ss_conv_up.h, shared with a host program that walks every address (tests/conv_up_addr_check.cpp).
 //
 // FLAGS: 1 s_setprio around the MFMA stretch | 2 persistent (the next output tile's first 7 half-tiles fly under the
 // epilogue; 256-wide only) | 4 two super-phases per K tile (tile2) | 8 LDS-staged epilogue (256-wide: strips behind the ring,
 // 128 KB + 18 KB; 320-wide: inside ring buffer 0) | 16 folded-LayerNorm epilogue | 32 row statistics (16 / 32: template support
 // only, no instantiation selects them).
+
+#include "ss_conv_up.h"
 
 namespace ss {
 
@@ -109,7 +116,7 @@ __device__ __forceinline__ uint64_t uniform_u64(uint64_t v) {
     return ((uint64_t)hi << 32) | lo;
 }
 
-template <typename T, int BN, int FLAGS, bool CONV>
+template <typename T, int BN, int FLAGS, bool CONV, bool UP = false>
 __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmArgs g, const int total_tiles) {
     // BN = 256: wave tile 128x64 (4 column fragments, halves 2 + 2).  BN = 320: wave tile 128x80 (5 column fragments, halves
     // 3 + 2; phases of 24 / 16 / 16 / 24 MFMAs) — [16384, 1280] outputs are exactly 256 tiles = one per CU, [65536, 640] two
@@ -119,6 +126,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmArgs g, const in
     using Lds = PpLds<BN, FLAGS>;
     constexpr int BM = 256, FN = Lds::FN, FN0 = Lds::FN0, FN1 = Lds::FN1, TM = 128, TN = Lds::TN, FM = 8;
     static_assert(BN == 256 || BN == 320, "tile widths");
+    static_assert(CONV || !UP, "upsampling is a conv input");
     constexpr bool EXACT = BN == 320 || CONV;
     constexpr bool PRIO = (FLAGS & 1) != 0, PERSIST = (FLAGS & 2) != 0, TWO = (FLAGS & 4) != 0, STAGED = (FLAGS & 8) != 0, RSTAT = (FLAGS & 32) != 0;
     constexpr int EM = ((FLAGS & 16) != 0) ? 2 : 0;
@@ -143,7 +151,9 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmArgs g, const in
     // conv: K tiles per filter tap and its reciprocal (tap = t / tpt as a multiply: t < 9 * 40, exact for tpt <= 64)
     const int tpt = CONV ? g.conv_Cin / 64 : 1;
     const uint32_t tpt_inv = CONV ? (65536u + (uint32_t)tpt - 1u) / (uint32_t)tpt : 0u;
-    const int lw = CONV ? __builtin_ctz((unsigned)g.conv_W) : 0;
+    // conv: the OUTPUT grid (UP: twice the source's), both sides powers of two
+    const int cWo = UP ? 2 * g.conv_W : g.conv_W, cHo = UP ? 2 * g.conv_H : g.conv_H;
+    const int lw = CONV ? __builtin_ctz((unsigned)cWo) : 0;
     const uint32_t lds0 = __builtin_amdgcn_readfirstlane((uint32_t)(size_t)(lds_void_t*)smem_raw);
 
     // ---- staging coordinates of this wave --------------------------------------------------------------------------
@@ -167,13 +177,36 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmArgs g, const in
     //                shifted by the tap lies above or below the image).  A padded piece that is not a whole-row case pads the
     //                one pixel that leaves the image on the left (taps with dx < 0: lane row 0) or on the right (dx > 0: lane row
     //                7); with W = 8 a piece is both borders and the tap's dx decides, as it always did.
+    // UP (ss_conv_up.h): cpoff is the offset of the piece's SOURCE pixel (b, oy >> 1, ox0 / 2); the source row moves with the tap's
+    // dy by the parity of oy (cshift: bit (dy + 1) * 4 + h*2 + i), so the offset in use is re-formed per tap (Cur::po); the source
+    // column of a lane moves with dx: lane row r reads column r >> 1 (dx = 0, voffA) or (r + 1) >> 1 (dx != 0, voffA_odd)
     uint32_t cpoff[CONV ? 2 : 1][CONV ? 2 : 1];
     uint64_t cpad = 0, crow = 0;
+    uint32_t cshift = 0, voffA_odd = 0;
     auto setup_tile = [&](int vid) {
         int mt_, nt_;
         xcd_tile_id(g.swz, MT, NT, vid, mt_, nt_);
         m_blk = mt_ * BM; n_blk = nt_ * BN;
-        if constexpr (CONV) {
+        if constexpr (UP) {
+            voffA[0][0] = up_lane_off(srow, schunk, g.conv_Cin, false);
+            voffA_odd = up_lane_off(srow, schunk, g.conv_Cin, true);
+            voffW[0][0] = (uint32_t)((int64_t)srow * g.ldw * 2 + schunk * 16);
+            uint64_t pad = 0, row = 0;
+            uint32_t shift = 0;
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+#pragma unroll
+                for (int i = 0; i < 2; ++i) {
+                    const UpPiece q = up_piece(m_blk + i * 128 + h * 64 + wid * 8, lw, cHo, cWo, g.conv_Cin);
+                    row |= q.row9 << (h * 2 + i);
+                    pad |= q.pad9 << (h * 2 + i);
+                    shift |= up_shift_bits(q.odd, h * 2 + i);
+                    cpoff[h][i] = __builtin_amdgcn_readfirstlane(q.off);
+                }
+            }
+            cpad = uniform_u64(pad); crow = uniform_u64(row);
+            cshift = __builtin_amdgcn_readfirstlane(shift);
+        } else if constexpr (CONV) {
             voffA[0][0] = (uint32_t)(srow * g.conv_Cin * 2 + schunk * 16);       // NHWC, stride 1: pixel m sits at m * Cin
             voffW[0][0] = (uint32_t)((int64_t)srow * g.ldw * 2 + schunk * 16);
             uint64_t pad = 0, row = 0;
@@ -219,16 +252,25 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmArgs g, const in
     // one half-tile of K tile t into buffer b.  which: 0 A0 | 1 A1 | 2 B0 | 3 B1
     // conv: where K tile t of the A operand lives — 64 channels [64 c, 64 c + 64) of filter tap (dy, dx); src = the address of
     // pixel 0's channels shifted by the tap.  All scalar; the K loop advances two cursors (tiles t+1, t+2) incrementally.
-    // bits: this tap's four bits of cpad (bits 0..3), of crow (4..7), and dx < 0 (bit 8)
-    struct Cur { const char* src; int c, tap; uint32_t bits; };
+    // bits: this tap's four bits of cpad (bits 0..3), of crow (4..7), and dx < 0 (bit 8); UP: dx != 0 (bit 9)
+    // po (UP): the four pieces' source offsets at this tap's dy
+    struct Cur { const char* src; int c, tap; uint32_t bits; uint32_t po[2][2]; };
     auto cur_set_tap = [&](Cur& k) {                         // all that happens at a tap change: the tap's byte offset and mask bits
         const int t3 = (k.tap * 11) >> 5;                    // tap / 3 for tap < 9
         const int dy = t3 - 1, dx = k.tap - 3 * t3 - 1;
-        k.src = (const char*)g.A + ((int64_t)(dy * g.conv_W + dx) * g.conv_Cin + k.c * 64) * 2;
-        k.bits = ((uint32_t)(cpad >> (k.tap * 4)) & 15u) | (((uint32_t)(crow >> (k.tap * 4)) & 15u) << 4) | (dx < 0 ? 256u : 0u);
+        if constexpr (UP) {
+            k.src = (const char*)g.A + up_tap_off(dx, k.c, g.conv_Cin);
+            const uint32_t row_bytes = (uint32_t)(g.conv_W * g.conv_Cin * 2);
+#pragma unroll
+            for (int p = 0; p < 4; ++p) k.po[p >> 1][p & 1] = up_piece_off(cpoff[CONV ? p >> 1 : 0][CONV ? p & 1 : 0], cshift, p, t3, row_bytes);
+        } else {
+            k.src = (const char*)g.A + ((int64_t)(dy * g.conv_W + dx) * g.conv_Cin + k.c * 64) * 2;
+        }
+        k.bits = ((uint32_t)(cpad >> (k.tap * 4)) & 15u) | (((uint32_t)(crow >> (k.tap * 4)) & 15u) << 4) | (dx < 0 ? 256u : 0u) |
+                 (UP && dx != 0 ? 512u : 0u);
     };
     auto cur_make = [&](int t) {
-        Cur k;
+        Cur k{};
         k.tap = (int)(((uint32_t)t * tpt_inv) >> 16);
         k.c = t - k.tap * tpt;
         cur_set_tap(k);
@@ -252,16 +294,18 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmArgs g, const in
     if constexpr (CONV && BN == 256) asm volatile("" : "+v"(zhi));
     auto stage_conv = [&](const Cur& k, int b, int h) {
         const uint32_t keep = m0_save();
+        // UP: this tap's lane offset, one select for the two pieces
+        const uint32_t vo = UP && (k.bits & 512u) ? voffA_odd : voffA[0][0];
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int p = h * 2 + i;
-            const char* ps = k.src + cpoff[CONV ? h : 0][CONV ? i : 0];
+            const char* ps = k.src + (UP ? k.po[h][i] : cpoff[CONV ? h : 0][CONV ? i : 0]);
             const int d = b * BUF + (h ? OFF_A1 : OFF_A0) + i * 8192;   // a constant once inlined
             if (__builtin_expect(((k.bits >> p) & 1u) == 0, 1)) {
-                dma16s_at(voffA[0][0], ps, ldsw, d);
+                dma16s_at(vo, ps, ldsw, d);
             } else {
-                const uint64_t zm = ((k.bits >> (4 + p)) & 1u) ? ~0ull : ((k.bits & 256u) ? 0xFFull : 0xFFull << 56);
-                const uint64_t a = (uint64_t)(size_t)ps + voffA[0][0];
+                const uint64_t zm = up_pad_lanes(((k.bits >> (4 + p)) & 1u) != 0, (k.bits & 256u) != 0);
+                const uint64_t a = (uint64_t)(size_t)ps + vo;
                 const uint32_t lo = sel_lanes((uint32_t)a, zlo, zm), hi = sel_lanes((uint32_t)(a >> 32), zhi, zm);
                 dma16v_at((const char*)(size_t)(((uint64_t)hi << 32) | lo), ldsw, d);
             }
@@ -546,30 +590,35 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmArgs g, const in
 
 template <typename T, int BN, int FLAGS>
 static int pp_launch(const GemmArgs& g, hipStream_t s) {
-    constexpr bool CONV = SS_PP_CONV != 0;
+    constexpr bool CONV = SS_PP_CONV != 0, UP = SS_PP_CONV == 2;
     const bool conv = g.conv_Cin > 0;
-    if (conv != CONV || g.ksplit > 1) return 1;
+    if (conv != CONV || (conv && (g.conv_up != 0) != UP) || g.ksplit > 1) return 1;
     // (tests/kernel_check.py pp320_eligible / conv_pp320_eligible copy the rule below to make sure their shapes reach the 320-wide
-    // tiles and not the fallback: change both together)
+    // tiles and not the fallback: change both together; the copy there knows no upsampling, tests/test_conv_pp_upsample_gpu.py
+    // up_pp_eligible is the copy of the conv_up form)
     bool ok = (g.K % 64 == 0) && g.K >= 64 && (int64_t)BN * g.ldw * 2 < (1ll << 31);
     if (conv) {
-        // whole tiles, stride 1, no upsampling, W a power of two >= 8 (an 8-pixel DMA piece stays inside one image row), H a
-        // power of two (the row index is split by shifts), <= 64 K tiles per tap (the reciprocal in the kernel)
-        ok = ok && g.conv_stride == 1 && !g.conv_up && g.conv_Cin % 64 == 0 && g.conv_Cin <= 4096 && g.conv_W >= 8 &&
-             (g.conv_W & (g.conv_W - 1)) == 0 && (g.conv_H & (g.conv_H - 1)) == 0 && g.M % 256 == 0 && g.N % BN == 0 &&
-             (int64_t)g.M * g.conv_Cin * 2 < (1ll << 31);      // pixel offsets (m * Cin * 2) are formed in 32 bits
+        // whole tiles, stride 1, OUTPUT W a power of two >= 8 (an 8-pixel DMA piece stays inside one image row), output H a
+        // power of two (the row index is split by shifts), <= 64 K tiles per tap (the reciprocal in the kernel).  With the nearest-2x
+        // upsampled input (conv_up; the *_convup.hip instantiations) the output grid is 2H x 2W and the source has M / 4 pixels.
+        const int Wo = g.conv_up ? 2 * g.conv_W : g.conv_W, Ho = g.conv_up ? 2 * g.conv_H : g.conv_H;
+        ok = ok && g.conv_stride == 1 && g.conv_Cin % 64 == 0 && g.conv_Cin <= 4096 && g.conv_W > 0 && g.conv_H > 0 && Wo >= 8 &&
+             (Wo & (Wo - 1)) == 0 && (Ho & (Ho - 1)) == 0 && g.M % 256 == 0 && g.N % BN == 0 &&
+             (int64_t)(g.conv_up ? g.M / 4 : g.M) * g.conv_Cin * 2 < (1ll << 31);   // source pixel offsets (pixel * Cin * 2) are formed in 32 bits
     } else {
         ok = ok && (int64_t)256 * g.lda * 2 < (1ll << 31);
         if (BN == 320 && (g.M % 256 != 0 || g.N % 320 != 0)) ok = false;       // whole tiles only (see the kernel)
     }
     if (!ok) return 1;
     if ((g.rowstat_out || g.rowpart) && !(FLAGS & 32)) return 1;
-    return launch_tiles<gemm_pp_kernel<T, BN, FLAGS, CONV>>("gemm_pp", g, cdiv(g.M, 256) * cdiv(g.N, BN), (FLAGS & 2) ? num_cus() : 0, 512,
+    return launch_tiles<gemm_pp_kernel<T, BN, FLAGS, CONV, UP>>("gemm_pp", g, cdiv(g.M, 256) * cdiv(g.N, BN), (FLAGS & 2) ? num_cus() : 0, 512,
                                                             PpLds<BN, FLAGS>::BYTES, s);
 }
 
 // cfg 50 .. 59: the ping-pong tiles
-#if SS_PP_CONV
+#if SS_PP_CONV == 2
+template <typename T> int gemm_pp_dispatch_convup(int cfg, const GemmArgs& g, hipStream_t s) {
+#elif SS_PP_CONV
 template <typename T> int gemm_pp_dispatch_conv(int cfg, const GemmArgs& g, hipStream_t s) {
 #else
 template <typename T> int gemm_pp_dispatch(int cfg, const GemmArgs& g, hipStream_t s) {
@@ -578,21 +627,26 @@ template <typename T> int gemm_pp_dispatch(int cfg, const GemmArgs& g, hipStream
         // (measured, profiles/round6_pp_ubench.txt: s_setprio around the MFMA stretch — FLAGS 1 — changes nothing here, the two
         // groups never compete for the matrix pipe; direct epilogue 772 vs staged 716 us at 8192^3)
         case 54: return pp_launch<T, 256, 8>(g, s);      // 256x256, LDS-staged epilogue
+#if SS_PP_CONV != 2
         case 55: return pp_launch<T, 256, 10>(g, s);     // + persistent
+#endif
         case 56: return pp_launch<T, 320, 8>(g, s);      // 256x320 (whole tiles only), staged epilogue (strips in the ring)
         case 57: return pp_launch<T, 256, 12>(g, s);     // 256x256, two super-phases per K tile (4 barriers)
-#if !SS_PP_CONV
-        case 58: return pp_launch<T, 320, 12>(g, s);     // 256x320, two super-phases — GEMM ONLY: the conv instantiation of this
-        // combination spills 17 registers INSIDE the K loop (256 VGPRs) and returned wrong tiles on every run (spill moves next to
-        // asm MFMAs the hazard recognizer cannot see); the GEMM instantiation has no in-loop spill and is bit-equal in the race screen.
-        // (That was the conv staging before the per-tile masks: with them the listing of <320, 12, true> shows no spill between its
-        // first and last MFMA — profiles/conv_stage_isa.txt — but it has not been run, so it stays out until it has passed the
-        // equality tests and an A/B against cfg 56.)
+#if SS_PP_CONV != 2
+        case 58: return pp_launch<T, 320, 12>(g, s);     // 256x320, two super-phases.  (Its conv instantiation once spilled 17 registers
+        // INSIDE the K loop and returned wrong tiles on every run: spill moves next to asm MFMAs the hazard recognizer cannot see.
+        // Since the per-tile masks of the conv staging the listing of <320, 12, true> has no scratch access between its first and last
+        // MFMA, bf16 and f16 — profiles/conv_up_isa.txt.)
 #endif
+        // Upsampled input (SS_PP_CONV == 2) has no cfg 55 and no cfg 58, which then fall back to the one-barrier tile: <320, 12, true, true>
+        // DOES spill inside the K loop (43 - 49 scratch accesses in the listing), and the persistent <256, 10> keeps the scratch loads on
+        // its padded-piece paths that the stride-1 one has in f16, with no table entry that would select it for a convolution.
         default: return 1;
     }
 }
-#if SS_PP_CONV
+#if SS_PP_CONV == 2
+template int gemm_pp_dispatch_convup<SS_PP_T>(int, const GemmArgs&, hipStream_t);
+#elif SS_PP_CONV
 template int gemm_pp_dispatch_conv<SS_PP_T>(int, const GemmArgs&, hipStream_t);
 #else
 template int gemm_pp_dispatch<SS_PP_T>(int, const GemmArgs&, hipStream_t);
