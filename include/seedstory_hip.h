@@ -432,6 +432,41 @@ int ss_process_logits(void* logits, int64_t rows, int64_t vocab, int64_t ld, con
                       const int32_t* hist_dev, int64_t hist_ld, const int32_t* hist_len_dev, const int32_t* prompt_len_dev,
                       int32_t eos_id, const int32_t* img_ids, int64_t n_img_ids, int dtype, void* stream);
 
+/* Token log-probabilities: how likely was the token that was chosen, and what would the model have said instead.
+ * For the decode token that produces gen_ids[n] of a slot, raw = the lm_head row in the model dtype before anything edits it,
+ * z = the row after the slot's history rules (if on) and the image-token processor's in-place edit.  All arithmetic is fp32;
+ * every sum is taken in one fixed order (per thread in index order, xor butterfly over the wave, xor butterfly over the 16
+ * wave sums) and there are no atomics: a row gives the same bits on every run.
+ *   lsm(x)[t]      = (x_t - x_max) - log sum_i exp(x_i - x_max), the log-softmax at temperature 1 over the whole vocabulary.
+ *                  NaN and -inf entries carry no mass, as in the sampler; x_max is taken over the others.  x_t = -inf gives
+ *                  -inf and x_t = NaN gives NaN (by the entry alone, never a NaN made by the arithmetic: a row without any
+ *                  mass gives -inf / NaN as well).  A row whose maximum is +inf is outside the definition.
+ *   model_logprob[n] = lsm(raw)[tok]: the model's own score of the token.
+ *   logprob[n]     the log of the probability with which the engine's policy picked tok:
+ *                  greedy slot    lsm(z)[tok] (for a free token: Hugging Face's compute_transition_scores(...,
+ *                                 normalize_logits=True) of a greedy run);
+ *                  sampling slot  log(w_tok / Z_P) = (z_tok - z_max) / temperature - log Z_P, with w, the kept set and Z_P
+ *                                 exactly as ss_sample_logits defines them; in the decode loop it is computed by the sampling
+ *                                 kernel from the kept set and the Z_P of the draw itself; -inf for a token outside the set;
+ *                  0.0            for a token the policy did not choose: an entry of forced_tokens (even one that z bans), and
+ *                                 the certain image-token successor.  DEVIATION: the successor rule is the one ss_sample_logits
+ *                                 declares for sampling, extended to greedy slots (the reference's processor only makes the
+ *                                 successor overwhelmingly likely).
+ *   top_ids[n][0 .. top_n), top_logprobs[n][0 .. top_n)   the top_n largest entries of raw with their model_logprob values, in
+ *                  descending order, equal values by ascending id; 0 <= top_n <= 8; when fewer than top_n entries carry mass
+ *                  the remaining places hold id -1 and -inf.
+ * Recording changes nothing else: the tokens, the hidden rows, the final logits row and the Philox draw counter are
+ * bit-equal to a run without it.
+ *
+ * ss_token_logprobs: the operator on caller-owned rows logits [rows][ld] (vocab <= 65535 entries each, model dtype), which it
+ * only reads; one block per row, one pass over the row.  p = NULL: lp_out[r] = lsm(row r)[ids_dev[r]].  p non-NULL:
+ * lp_out[r] = the sampler's log(w / Z_P) of ids_dev[r] on row r (the processor does not run: hand it z).  top_n > 0:
+ * top_ids_out / top_lp_out [rows][top_n] as defined above, from lsm(row r) in either form.  An id outside [0, vocab) is never
+ * used as an index: NaN (p = NULL) or -inf.  SS_EINVAL before any launch: a bad shape, top_n outside [0, 8], top_n > 0
+ * without both top-n buffers, a sampling parameter outside its range. */
+int ss_token_logprobs(const void* logits, int64_t rows, int64_t vocab, int64_t ld, const int32_t* ids_dev, const ss_sampling* p,
+                      int32_t top_n, float* lp_out, int32_t* top_ids_out, float* top_lp_out, int dtype, void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * LLaMA decoder engine (native runtime: KV cache, prefill loop, hipGraph-captured decode)
  * ------------------------------------------------------------------------------------- */
@@ -525,6 +560,22 @@ int ss_llama_set_sampling(ss_llama* h, int32_t seq, const ss_sampling* p);
  * sampling, attention-map capture and fp8 decode weights.  A generate call on a rules-on slot whose history could outgrow
  * the buffer is refused (SS_EINVAL).  Call it between engine calls (blocking copy). */
 int ss_llama_set_logits_rules(ss_llama* h, int32_t seq, const ss_logits_rules* rules);
+
+/* Token log-probabilities in the decode loop (definition: ss_token_logprobs).  seq = a slot, or -1 for all; every buffer NULL =
+ * off (the default).  The buffers are device memory owned by the caller and kept alive while the option is on, per slot
+ * model_lp, policy_lp float[max_new] and, for top_n > 0, top_ids int32 / top_lp float [max_new][top_n]; with seq = -1 they
+ * hold n_seq such blocks, slot-major.  While a slot records, every decode token of ss_llama_generate /
+ * ss_llama_generate_batch (eager or captured) runs two more small kernels: one in front of the rules kernel, which reads raw
+ * (statistics, the top-n, a scratch copy of the row), and one behind the opening kernel, which writes entry n = the index of
+ * the token in gen_ids; with sampling on, the sampling kernel's sibling also hands over log(w_tok / Z_P) of its draw.  A done
+ * slot writes nothing, a slot with the option off writes nothing (mixed batches work), and with every addressed slot off the
+ * decode token launches exactly what it launched before.  The buffers are reached through a descriptor in device memory:
+ * other buffers or another top_n do not re-capture, and the captured graph is cached apart from the others.  Works with
+ * sampling, the history rules, attention-map capture, fp8 decode weights and the fp8 KV shadow.  Call it between engine
+ * calls (blocking copy).  SS_EINVAL before anything is written: top_n outside [0, 8], a bad slot, or some but not all of the
+ * buffers NULL (model_lp and policy_lp always; top_ids and top_lp exactly when top_n > 0). */
+int ss_llama_set_logprobs(ss_llama* h, int32_t seq, float* model_lp, float* policy_lp, int32_t* top_ids, float* top_lp,
+                          int32_t top_n);
 
 /* Hands slot seq's history over (seq = -1: the selected slot).  append = 0: the history becomes host_ids[0 .. n) and
  * prompt_len = n (n = 0 empties it); append = 1: host_ids are added behind it — tokens that were fed outside the decode loop

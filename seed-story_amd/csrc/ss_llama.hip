@@ -26,6 +26,7 @@
 #include "ss_sample.h"
 #include "ss_rules.h"
 #include "ss_kv8.h"
+#include "ss_logprob.h"
 
 namespace ss {
 
@@ -97,12 +98,14 @@ __global__ __launch_bounds__(1024) void sample_embed_kernel(T* logits, int vocab
 // sample_embed_kernel with the sampler in the arg max's place (chosen on the host when a slot of the launch has sampling on,
 // ss_llama_set_sampling).  Per slot, from its SampleParams: sampling off -> the arg max, exactly as above; on -> the certain
 // image-token successor, or one draw (Philox counter (draw, slot)); a forced token wins over either and takes no draw.
-template <typename T, int NS>
+// LP (chosen on the host when a slot of the launch records log-probabilities, ss_llama_set_logprobs): the same kernel, which
+// also leaves log(w_tok / Z_P) of a drawn token, from the draw's own kept set, in the slot's LogprobScratch.
+template <typename T, int NS, bool LP>
 __global__ __launch_bounds__(1024) void sample_embed_draw_kernel(T* logits, int vocab, int32_t* st, SampleParams* samp, int seq0,
                                                                  const int32_t* __restrict__ img_ids, int n_img_ids,
                                                                  const int32_t* __restrict__ forced, int32_t* gen_ids,
                                                                  const T* __restrict__ embed, T* x, int hidden,
-                                                                 int max_new) {
+                                                                 int max_new, LogprobScratch* lps) {
     __shared__ float sv[16];
     __shared__ int si[16];
     __shared__ SampleSmem sm;
@@ -120,6 +123,7 @@ __global__ __launch_bounds__(1024) void sample_embed_draw_kernel(T* logits, int 
     const int n = st[ST_NGEN];
     const bool is_forced = n < st[ST_NFORCED];
     int tok, drew = 0;
+    float lp = 0.f;
     if (!sp.enabled || is_forced) {     // (uniform over the block) the greedy kernel's path; a forced token overrides its result
         tok = imgproc_argmax_block<T>(logits, vocab, st[ST_LAST], img_ids, n_img_ids, sv, si);
         if ((unsigned)tok >= (unsigned)vocab) tok = 0;
@@ -127,8 +131,8 @@ __global__ __launch_bounds__(1024) void sample_embed_draw_kernel(T* logits, int 
     } else {
         int nk;
         const float u = philox_uniform(sp.seed_lo, sp.seed_hi, sp.draw, (uint32_t)(seq0 + blockIdx.x));
-        tok = imgproc_sample_block<T, NS>(logits, vocab, true, st[ST_LAST], img_ids, n_img_ids, sp.inv_temp, sp.top_p, sp.top_k,
-                                          u, sv, si, sm, &nk, &drew);
+        tok = imgproc_sample_block<T, NS, LP>(logits, vocab, true, st[ST_LAST], img_ids, n_img_ids, sp.inv_temp, sp.top_p, sp.top_k,
+                                              u, sv, si, sm, &nk, &drew, &lp);
     }
     const int eos_word = st[ST_EOS];
     const int eos_id = eos_word & 0xFFFF, stop2 = (eos_word >> 16) - 1;
@@ -140,11 +144,96 @@ __global__ __launch_bounds__(1024) void sample_embed_draw_kernel(T* logits, int 
         st[ST_NGEN] = n + 1;
         if (stop) st[ST_DONE] = 1;
         if (drew) samp->draw = sp.draw + 1;
+        if (LP && drew) lps[blockIdx.x].samp_lp = lp;
     }
     if (stop) return;
     constexpr int V = Tr<T>::kVec;
     for (int p = threadIdx.x; p < hidden / V; p += blockDim.x)
         st16(x + (int64_t)p * V, ld16(embed + (int64_t)tok * hidden + (int64_t)p * V));
+}
+
+// Token log-probabilities in the decode loop (ss_llama_set_logprobs): two small kernels, one block per slot, launched only when
+// a slot of the launch records; a slot that does not (or is done) returns at once and writes nothing.
+//   logprob_raw_kernel   IN FRONT of the rules kernel: the lm_head row is still `raw`.  Its stats and the top-n go out here
+//                        (entry n = ST_NGEN, the entry the opening kernel is about to fill); the row itself is copied to the
+//                        slot's scratch row, because raw[tok] is wanted once tok is known and the rules and the processor
+//                        edit the row in place before that.
+//   logprob_tok_kernel   BEHIND the opening kernel: tok = gen_ids[n], the row holds z.  model_logprob from the copy; logprob =
+//                        0 for a forced token and for the certain image-token successor, the sampling kernel's own value
+//                        for a drawn token, the log-softmax of z for a greedy one.
+template <typename T, int EPT>
+__global__ __launch_bounds__(1024) void logprob_raw_kernel(const T* logits, int vocab, const int32_t* st, const LogprobDesc* desc,
+                                                           LogprobScratch* lps, T* raw_copy, int max_new) {
+    __shared__ LogprobSmem sm;
+    {
+        const int b = blockIdx.x;
+        logits += (int64_t)b * vocab;
+        st += b * ST_WORDS;
+        desc += b;
+        lps += b;
+        raw_copy += (int64_t)b * vocab;
+    }
+    const LogprobDesc d = *desc;
+    if (!d.on) return;
+    const int n = st[ST_NGEN];
+    if (st[ST_DONE] || n >= max_new) {
+        if (threadIdx.x == 0) lps->live = 0;
+        return;
+    }
+    float v[EPT];
+    int flip = 0;
+    const LogprobStats s = logprob_load_block<T, EPT>(logits, vocab, v, sm, flip);
+    for (int i = threadIdx.x; i < vocab; i += 1024) raw_copy[i] = logits[i];
+    if (threadIdx.x == 0) {
+        lps->zmax = s.zmax; lps->logz = s.logz; lps->any = s.any;
+        lps->n = n; lps->last = st[ST_LAST]; lps->live = 1;
+    }
+    if (d.top_n > 0)
+        logprob_top_block(v, vocab, s, d.top_n, d.top_ids + (int64_t)n * d.top_n, d.top_lp + (int64_t)n * d.top_n, sm);
+}
+
+template <typename T, int EPT>
+__global__ __launch_bounds__(1024) void logprob_tok_kernel(const T* logits, int vocab, const int32_t* st, const LogprobDesc* desc,
+                                                           const LogprobScratch* lps, const T* raw_copy,
+                                                           const SampleParams* __restrict__ samp,
+                                                           const int32_t* __restrict__ img_ids, int n_img_ids,
+                                                           const int32_t* __restrict__ gen_ids, int max_new) {
+    __shared__ LogprobSmem sm;
+    {
+        const int b = blockIdx.x;
+        logits += (int64_t)b * vocab;
+        st += b * ST_WORDS;
+        desc += b;
+        lps += b;
+        raw_copy += (int64_t)b * vocab;
+        samp += b;
+        gen_ids += (int64_t)b * max_new;
+    }
+    const LogprobDesc d = *desc;
+    if (!d.on) return;
+    const LogprobScratch sc = *lps;
+    if (!sc.live) return;
+    const int n = sc.n, tok = gen_ids[n];
+    const bool in_row = (unsigned)tok < (unsigned)vocab;
+    const float nan = __uint_as_float(0x7FC00000u);
+    // the policy's part (every condition is uniform over the block)
+    int succ = -1;
+    for (int j = 0; j + 1 < n_img_ids; ++j)
+        if (img_ids[j] == sc.last) { succ = img_ids[j + 1]; break; }
+    float plp;
+    if (n < st[ST_NFORCED] || (succ >= 0 && succ < vocab)) plp = 0.f;
+    else if (samp->enabled) plp = sc.samp_lp;
+    else {
+        float v[EPT];
+        int flip = 0;
+        const LogprobStats s = logprob_load_block<T, EPT>(logits, vocab, v, sm, flip);
+        plp = in_row ? logprob_value(Tr<T>::ld(logits + tok), s) : nan;
+    }
+    if (threadIdx.x == 0) {
+        const LogprobStats rs{sc.zmax, sc.logz, sc.any};
+        d.model_lp[n] = in_row ? logprob_value(Tr<T>::ld(raw_copy + tok), rs) : nan;
+        d.policy_lp[n] = plp;
+    }
 }
 
 // The history rules of a decode token (ss_llama_set_logits_rules), one block per slot IN FRONT of the opening kernel, which
@@ -284,6 +373,7 @@ struct SeqGraph {
     int sampling;            // a slot of [seq0, seq0+nb) has sampling on (ss_llama_set_sampling): the sampling kernel opens the token
     int rules;               // a slot of [seq0, seq0+nb) has history rules on (ss_llama_set_logits_rules): the rules kernel in front
     int kv8;                 // fp8 KV shadow on (ss_llama_set_kv8): another attention kernel, the planes' pointers
+    int logprobs;            // a slot of [seq0, seq0+nb) records log-probabilities (ss_llama_set_logprobs): two more kernels; the buffers are NOT part of the key
     hipGraph_t graph;
     hipGraphExec_t exec;
 };
@@ -344,6 +434,15 @@ struct ss_llama {
     std::vector<int64_t> hist_len;      // host mirror of RulesState::hist_len
     bool rules_in(int seq0, int nb) const {
         for (int b = seq0; b < seq0 + nb; ++b) if (rules_on[b]) return true;
+        return false;
+    }
+    // token log-probabilities (ss_llama_set_logprobs): per-slot descriptor of the caller's buffers, scratch words and raw-row copy
+    LogprobDesc* lp_desc = nullptr;     // [n_seq]
+    LogprobScratch* lp_scratch = nullptr;  // [n_seq]
+    char* lp_raw = nullptr;             // [n_seq][vocab]
+    std::vector<char> lp_on;
+    bool logprobs_in(int seq0, int nb) const {
+        for (int b = seq0; b < seq0 + nb; ++b) if (lp_on[b]) return true;
         return false;
     }
     int64_t hist_cap() const { return (int64_t)cfg.cache_cap + cfg.max_new; }
@@ -410,6 +509,9 @@ static void carve(ss_llama* h, Carver& c) {
     h->rules = (RulesState*)c.take(S * sizeof(RulesState));              // zeroed with the workspace: rules off, empty histories
     h->hist = (int32_t*)c.take(S * (size_t)h->hist_cap() * sizeof(int32_t));
     h->hist_bm = (uint32_t*)c.take(S * (size_t)h->bm_words() * sizeof(uint32_t));
+    h->lp_desc = (LogprobDesc*)c.take(S * sizeof(LogprobDesc));          // zeroed with the workspace: no slot records
+    h->lp_scratch = (LogprobScratch*)c.take(S * sizeof(LogprobScratch));
+    h->lp_raw = c.take(S * (size_t)g.vocab * e);
 }
 
 static int cfg_n_seq(const ss_llama_config* cfg) { return cfg->n_seq > 0 ? cfg->n_seq : 1; }
@@ -441,16 +543,46 @@ static int sample_embed_launch(ss_llama* h, int seq0, int nb, hipStream_t s) {
 }
 
 template <typename T>
-static int sample_embed_draw_launch(ss_llama* h, int seq0, int nb, hipStream_t s) {
+static int sample_embed_draw_launch(ss_llama* h, int seq0, int nb, bool lp, hipStream_t s) {
     const ss_llama_config& g = h->cfg;
 #define SS_DRAW_ARGS dim3((unsigned)nb), dim3(1024), 0, s, (T*)h->logits + (size_t)seq0 * g.vocab, g.vocab,                        \
                      h->state + (size_t)seq0 * ST_WORDS, h->samp + seq0, seq0, h->img_ids, g.n_img_ids,                            \
                      h->forced + (size_t)seq0 * g.max_new, h->gen_ids + (size_t)seq0 * g.max_new, (const T*)h->w.embed, (T*)h->x,  \
-                     g.hidden, g.max_new
-    if (sample_ns_half_fits(g.vocab)) hipLaunchKernelGGL((sample_embed_draw_kernel<T, sample_ns_full<T>() / 2>), SS_DRAW_ARGS);
-    else hipLaunchKernelGGL((sample_embed_draw_kernel<T, sample_ns_full<T>()>), SS_DRAW_ARGS);
+                     g.hidden, g.max_new, h->lp_scratch + seq0
+    const bool half = sample_ns_half_fits(g.vocab);
+    if (half && lp) hipLaunchKernelGGL((sample_embed_draw_kernel<T, sample_ns_full<T>() / 2, true>), SS_DRAW_ARGS);
+    else if (half) hipLaunchKernelGGL((sample_embed_draw_kernel<T, sample_ns_full<T>() / 2, false>), SS_DRAW_ARGS);
+    else if (lp) hipLaunchKernelGGL((sample_embed_draw_kernel<T, sample_ns_full<T>(), true>), SS_DRAW_ARGS);
+    else hipLaunchKernelGGL((sample_embed_draw_kernel<T, sample_ns_full<T>(), false>), SS_DRAW_ARGS);
 #undef SS_DRAW_ARGS
     SS_LAUNCH_CHECK("sample_embed_draw");
+    return SS_OK;
+}
+
+template <typename T>
+static int logprob_raw_launch(ss_llama* h, int seq0, int nb, hipStream_t s) {
+    const ss_llama_config& g = h->cfg;
+#define SS_LP_RAW_ARGS dim3((unsigned)nb), dim3(1024), 0, s, (const T*)h->logits + (size_t)seq0 * g.vocab, g.vocab,                   \
+                       h->state + (size_t)seq0 * ST_WORDS, h->lp_desc + seq0, h->lp_scratch + seq0,                               \
+                       (T*)h->lp_raw + (size_t)seq0 * g.vocab, g.max_new
+    if (logprob_ept_half_fits(g.vocab)) hipLaunchKernelGGL((logprob_raw_kernel<T, kLpEptFull / 2>), SS_LP_RAW_ARGS);
+    else hipLaunchKernelGGL((logprob_raw_kernel<T, kLpEptFull>), SS_LP_RAW_ARGS);
+#undef SS_LP_RAW_ARGS
+    SS_LAUNCH_CHECK("logprob_raw");
+    return SS_OK;
+}
+
+template <typename T>
+static int logprob_tok_launch(ss_llama* h, int seq0, int nb, hipStream_t s) {
+    const ss_llama_config& g = h->cfg;
+#define SS_LP_TOK_ARGS dim3((unsigned)nb), dim3(1024), 0, s, (const T*)h->logits + (size_t)seq0 * g.vocab, g.vocab,                   \
+                       h->state + (size_t)seq0 * ST_WORDS, h->lp_desc + seq0, h->lp_scratch + seq0,                               \
+                       (const T*)h->lp_raw + (size_t)seq0 * g.vocab, h->samp + seq0, h->img_ids, g.n_img_ids,                    \
+                       h->gen_ids + (size_t)seq0 * g.max_new, g.max_new
+    if (logprob_ept_half_fits(g.vocab)) hipLaunchKernelGGL((logprob_tok_kernel<T, kLpEptFull / 2>), SS_LP_TOK_ARGS);
+    else hipLaunchKernelGGL((logprob_tok_kernel<T, kLpEptFull>), SS_LP_TOK_ARGS);
+#undef SS_LP_TOK_ARGS
+    SS_LAUNCH_CHECK("logprob_tok");
     return SS_OK;
 }
 
@@ -497,12 +629,16 @@ static int decode_token(ss_llama* h, hipStream_t s, ProfSink* prof, int seq0, in
     static const ss_llama_layer_w8 kNoW8 = {};
 #define MARK(c) do { if (prof) prof->mark(c); } while (0)
     MARK(-1);
+    // a slot records log-probabilities: the raw row is read before anything edits it (off everywhere, the default: no launch)
+    const bool lp = h->logprobs_in(seq0, nb);
+    if (lp && (rc = SS_DISPATCH(dt, logprob_raw_launch, h, seq0, nb, s))) return rc;
     // history rules on for a slot: its row is edited before the opening kernel reads it (off everywhere, the default: no launch)
     if (h->rules_in(seq0, nb) && (rc = SS_DISPATCH(dt, logits_rules_launch, h, seq0, nb, 0, s))) return rc;
     // greedy slots only (the default): the launch it has always been
-    if (h->sampling_in(seq0, nb)) rc = SS_DISPATCH(dt, sample_embed_draw_launch, h, seq0, nb, s);
+    if (h->sampling_in(seq0, nb)) rc = SS_DISPATCH(dt, sample_embed_draw_launch, h, seq0, nb, lp, s);
     else rc = SS_DISPATCH(dt, sample_embed_launch, h, seq0, nb, s);
     if (rc) return rc;
+    if (lp && (rc = SS_DISPATCH(dt, logprob_tok_launch, h, seq0, nb, s))) return rc;
     MARK(3);
     for (int l = 0; l < g.n_layers; ++l) {
         const ss_llama_layer_weights& L = h->layers[l];
@@ -569,14 +705,16 @@ static int graph_for(ss_llama* h, int seq0, int nb, hipGraphExec_t* out) {
     const int sampling = h->sampling_in(seq0, nb) ? 1 : 0;
     const int rules = h->rules_in(seq0, nb) ? 1 : 0;
     const int kv8 = h->kq ? 1 : 0;
+    const int logprobs = h->logprobs_in(seq0, nb) ? 1 : 0;
     for (const SeqGraph& sg : h->graphs)
         if (sg.seq0 == seq0 && sg.nb == nb && sg.mode == mode && sg.capture == capture && sg.w8 == w8 && sg.sampling == sampling &&
-            sg.rules == rules && sg.kv8 == kv8) {
+            sg.rules == rules && sg.kv8 == kv8 && sg.logprobs == logprobs) {
             *out = sg.exec;
             return SS_OK;
         }
     SeqGraph sg;
     sg.seq0 = seq0; sg.nb = nb; sg.mode = mode; sg.capture = capture; sg.w8 = w8; sg.sampling = sampling; sg.rules = rules; sg.kv8 = kv8;
+    sg.logprobs = logprobs;
     sg.graph = nullptr; sg.exec = nullptr;
     SS_HIP(hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
     int rc = decode_token(h, h->cap_stream, nullptr, seq0, nb);
@@ -854,6 +992,7 @@ int ss_llama_create(const ss_llama_config* cfg, const ss_llama_weights* w, void*
     h->pos.assign(h->n_seq, 0);
     h->samp_on.assign(h->n_seq, 0);
     h->rules_on.assign(h->n_seq, 0);
+    h->lp_on.assign(h->n_seq, 0);
     h->hist_len.assign(h->n_seq, 0);
     h->kv8_rows.assign(h->n_seq, 0);
     hipError_t e = hipStreamCreateWithFlags(&h->cap_stream, hipStreamNonBlocking);
@@ -936,6 +1075,34 @@ int ss_llama_set_logits_rules(ss_llama* h, int32_t seq, const ss_logits_rules* p
     for (int b = b0; b < b1; ++b) {
         SS_HIP(hipMemcpy(h->rules + b, &rp, offsetof(RulesState, hist_len), hipMemcpyHostToDevice));
         h->rules_on[b] = p ? 1 : 0;
+    }
+    return SS_OK;
+}
+
+int ss_llama_set_logprobs(ss_llama* h, int32_t seq, float* model_lp, float* policy_lp, int32_t* top_ids, float* top_lp,
+                          int32_t top_n) {
+    SS_REQUIRE(top_n >= 0 && top_n <= SS_LOGPROB_MAX_TOP, "llama_set_logprobs: top_n %d outside [0, %d]", (int)top_n, SS_LOGPROB_MAX_TOP);
+    const bool off = !model_lp && !policy_lp && !top_ids && !top_lp;
+    if (!off) {
+        SS_REQUIRE(model_lp && policy_lp, "llama_set_logprobs: NULL log-probability buffer (both, or every buffer NULL to switch the option off)");
+        SS_REQUIRE(top_n > 0 ? (top_ids && top_lp) : (!top_ids && !top_lp),
+                   "llama_set_logprobs: top_n %d %s", (int)top_n, top_n > 0 ? "needs both top-n buffers" : "takes no top-n buffers");
+    }
+    SS_REQUIRE(h, "llama_set_logprobs: null handle");
+    SS_REQUIRE(seq >= -1 && seq < h->n_seq, "llama_set_logprobs: sequence slot %d out of range (-1 = all, < %d)", (int)seq, h->n_seq);
+    // every decode loop of this engine has synchronised before it returned: nothing in flight reads the block
+    const int b0 = seq < 0 ? 0 : seq, b1 = seq < 0 ? h->n_seq : seq + 1;
+    const size_t n = (size_t)h->cfg.max_new;
+    for (int b = b0; b < b1; ++b) {
+        const size_t i = (size_t)(b - b0);      // seq = -1: the buffers hold [n_seq] slots, slot-major
+        LogprobDesc d = {nullptr, nullptr, nullptr, nullptr, 0, 0};
+        if (!off) {
+            d.model_lp = model_lp + i * n; d.policy_lp = policy_lp + i * n;
+            if (top_n > 0) { d.top_ids = top_ids + i * n * top_n; d.top_lp = top_lp + i * n * top_n; }
+            d.top_n = top_n; d.on = 1;
+        }
+        SS_HIP(hipMemcpy(h->lp_desc + b, &d, sizeof(d), hipMemcpyHostToDevice));
+        h->lp_on[b] = off ? 0 : 1;
     }
     return SS_OK;
 }

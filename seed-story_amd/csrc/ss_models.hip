@@ -10,6 +10,7 @@
 #include "ss_common.h"
 #include "ss_sample.h"
 #include "ss_rules.h"
+#include "ss_logprob.h"
 
 namespace ss {
 int gemm_dev(const void* A, const void* W, void* C, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldw,
@@ -100,6 +101,61 @@ int process_logits_launch(void* logits, int64_t rows, int64_t vocab, int64_t ld,
     return SS_OK;
 }
 
+// ss_token_logprobs, plain form: one block per row, the row only read
+template <typename T, int EPT>
+__global__ __launch_bounds__(1024) void token_logprobs_kernel(const T* logits, int vocab, int64_t ld, const int32_t* __restrict__ ids,
+                                                              int top_n, float* lp_out, int32_t* top_ids, float* top_lp) {
+    __shared__ LogprobSmem sm;
+    const int r = blockIdx.x;
+    logits += (int64_t)r * ld;
+    float v[EPT];
+    int flip = 0;
+    const LogprobStats s = logprob_load_block<T, EPT>(logits, vocab, v, sm, flip);
+    if (lp_out && threadIdx.x == 0) {
+        const int tok = ids[r];         // device memory cannot be refused: an id outside the row is never used as an index
+        lp_out[r] = (unsigned)tok < (unsigned)vocab ? logprob_value(Tr<T>::ld(logits + tok), s) : __uint_as_float(0x7FC00000u);
+    }
+    if (top_n > 0) logprob_top_block(v, vocab, s, top_n, top_ids + (int64_t)r * top_n, top_lp + (int64_t)r * top_n, sm);
+}
+
+// ss_token_logprobs, sampling form: the sampler's own kept set and Z_P, scored at ids[r]; nothing is drawn
+template <typename T, int NS>
+__global__ __launch_bounds__(1024) void token_logprobs_sampling_kernel(const T* logits, int vocab, int64_t ld, SampleParams p,
+                                                                       const int32_t* __restrict__ ids, float* lp_out) {
+    __shared__ SampleSmem sm;
+    const int r = blockIdx.x;
+    int nk = 0;
+    float lp = -INFINITY;
+    const int tok = ids[r];
+    sample_block<T, NS, true>(logits + (int64_t)r * ld, vocab, p.inv_temp, p.top_p, p.top_k, 0.f, sm, &nk,
+                              (unsigned)tok < (unsigned)vocab ? tok : 0x7ffffffe, &lp);
+    if (threadIdx.x == 0) lp_out[r] = lp;
+}
+
+template <typename T>
+int token_logprobs_launch(const void* logits, int64_t rows, int64_t vocab, int64_t ld, const int32_t* ids, const SampleParams* p,
+                          int top_n, float* lp_out, int32_t* top_ids, float* top_lp, hipStream_t s) {
+    if (!p || top_n > 0) {
+        if (logprob_ept_half_fits(vocab))
+            hipLaunchKernelGGL((token_logprobs_kernel<T, kLpEptFull / 2>), dim3((unsigned)rows), dim3(1024), 0, s, (const T*)logits,
+                               (int)vocab, ld, ids, top_n, p ? nullptr : lp_out, top_ids, top_lp);
+        else
+            hipLaunchKernelGGL((token_logprobs_kernel<T, kLpEptFull>), dim3((unsigned)rows), dim3(1024), 0, s, (const T*)logits,
+                               (int)vocab, ld, ids, top_n, p ? nullptr : lp_out, top_ids, top_lp);
+        SS_LAUNCH_CHECK("token_logprobs");
+    }
+    if (p) {
+        if (sample_ns_half_fits(vocab))
+            hipLaunchKernelGGL((token_logprobs_sampling_kernel<T, sample_ns_full<T>() / 2>), dim3((unsigned)rows), dim3(1024), 0, s,
+                               (const T*)logits, (int)vocab, ld, *p, ids, lp_out);
+        else
+            hipLaunchKernelGGL((token_logprobs_sampling_kernel<T, sample_ns_full<T>()>), dim3((unsigned)rows), dim3(1024), 0, s,
+                               (const T*)logits, (int)vocab, ld, *p, ids, lp_out);
+        SS_LAUNCH_CHECK("token_logprobs_sampling");
+    }
+    return SS_OK;
+}
+
 struct Bump {
     char* p; size_t off, cap;
     void* take(size_t bytes) { void* r = p + off; off += (bytes + 255) / 256 * 256; return r; }
@@ -147,6 +203,21 @@ int ss_process_logits(void* logits, int64_t rows, int64_t vocab, int64_t ld, con
     if (int rc = logits_rules_params(rules, "process_logits", &rp)) return rc;
     return SS_DISPATCH(dtype, process_logits_launch, logits, rows, vocab, ld, rp, hist_dev, hist_ld, hist_len_dev, prompt_len_dev,
                        (int)eos_id, img_ids, n_img_ids, (hipStream_t)stream);
+}
+
+int ss_token_logprobs(const void* logits, int64_t rows, int64_t vocab, int64_t ld, const int32_t* ids_dev, const ss_sampling* p,
+                      int32_t top_n, float* lp_out, int32_t* top_ids_out, float* top_lp_out, int dtype, void* stream) {
+    SS_REQUIRE(logits && ids_dev && lp_out, "token_logprobs: null argument");
+    SS_REQUIRE(rows > 0 && rows <= 0x7FFFFFFF && vocab > 0 && vocab <= 65535 && ld >= vocab,
+               "token_logprobs: bad shape (rows=%lld vocab=%lld ld=%lld; vocab <= 65535)", (long long)rows, (long long)vocab,
+               (long long)ld);
+    SS_REQUIRE(top_n >= 0 && top_n <= SS_LOGPROB_MAX_TOP, "token_logprobs: top_n %d outside [0, %d]", (int)top_n, SS_LOGPROB_MAX_TOP);
+    SS_REQUIRE(top_n == 0 || (top_ids_out && top_lp_out), "token_logprobs: top_n %d needs both top-n buffers", (int)top_n);
+    SampleParams sp;
+    if (p)
+        if (int rc = sampling_params(p, "token_logprobs", &sp)) return rc;
+    return SS_DISPATCH(dtype, token_logprobs_launch, logits, rows, vocab, ld, ids_dev, p ? &sp : nullptr, (int)top_n, lp_out,
+                       top_ids_out, top_lp_out, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------

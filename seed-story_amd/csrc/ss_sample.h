@@ -186,15 +186,18 @@ struct SampleSmem {
     float tot[256];         // scan: sum of every (step, wave), step-major = index order
     float base[256];        // its exclusive prefix
     float total;
+    float lp_arg;           // LP: (z_tok - z_max) / temperature of the scored token, -inf when it is not kept
 };
 
 // One row, 1024 threads, vocab <= 65535.  NS = 16-byte steps per thread: NS * 1024 * kVec >= vocab + kVec - 1.  The row is
 // held in registers: thread t owns the runs (s * 1024 + t), s < NS, of kVec consecutive elements, so (step, thread, element)
 // is index order; the runs are the 16-byte aligned ones of the row's memory (first and last partial), or, where shifting by
 // the misalignment would not fit, element loads.  Returns the token (same value in every thread); *n_kept_out likewise.
-template <typename T, int NS>
+// LP (token log-probabilities, ss_logprob.h): *lp_out = log(w_t / Z_P) of t = `want`, or of the drawn token when want < 0,
+// as (z_t - z_max) / temperature - log Z_P with the kept set and the Z_P (sm.total) of this very draw; -inf when t is not kept.
+template <typename T, int NS, bool LP = false>
 __device__ __forceinline__ int sample_block(const T* row, int vocab, float inv_temp, float top_p, int top_k, float u,
-                                            SampleSmem& sm, int* n_kept_out) {
+                                            SampleSmem& sm, int* n_kept_out, int want = -1, float* lp_out = nullptr) {
     constexpr int V = Tr<T>::kVec, NE = NS * V, KB = SKey<T>::kBits, PW = 32 / KB, NW = NE / PW;
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     int flip = 0;
@@ -230,7 +233,11 @@ __device__ __forceinline__ int sample_block(const T* row, int vocab, float inv_t
 #pragma unroll
     for (int e = 0; e < NE; ++e) kmax = max(kmax, key_at(e));
     kmax = sample_block_reduce<SRedMax>(kmax, sm.red, flip);
-    if (kmax == 0u) { *n_kept_out = 0; return 0; }      // nothing but NaN / -inf (uniform branch)
+    if (kmax == 0u) {       // nothing but NaN / -inf (uniform branch)
+        *n_kept_out = 0;
+        if constexpr (LP) *lp_out = -INFINITY;
+        return 0;
+    }
     const float zmax = skey_value<T>(kmax);
 
     // top-k: th = the largest key with count(key >= th) >= k
@@ -330,23 +337,38 @@ __device__ __forceinline__ int sample_block(const T* row, int vocab, float inv_t
     }
     pick = sample_block_reduce<SRedMin>(pick, sm.red, flip);
     *n_kept_out = cnt;
-    return pick != 0x7fffffff ? pick : last;
+    const int res = pick != 0x7fffffff ? pick : last;
+    if constexpr (LP) {     // the owner of the scored entry publishes its exponent; an id outside the row is not kept
+        const int tgt = want >= 0 ? want : res;
+        if (tid == 0) sm.lp_arg = -INFINITY;
+        __syncthreads();
+#pragma unroll
+        for (int e = 0; e < NE; ++e) {
+            const uint32_t k = key_at(e);
+            if (((e / V) * 1024 + tid) * V + (e % V) - off == tgt && k >= th)
+                sm.lp_arg = k == kmax ? 0.f : (skey_value<T>(k) - zmax) * inv_temp;
+        }
+        __syncthreads();
+        *lp_out = sm.lp_arg - logf(sm.total);
+    }
+    return res;
 }
 
 // NS of sample_block for a vocabulary: half the registers (and unrolled work) up to 32K entries
 template <typename T> constexpr int sample_ns_full() { return 65536 / (1024 * Tr<T>::kVec); }
 inline bool sample_ns_half_fits(int64_t vocab) { return vocab + 8 <= 32768; }
 
-// processor edit -> certain successor | sample.  Returns the token; *drew = 1 iff a draw was consumed.
-template <typename T, int NS>
+// processor edit -> certain successor | sample.  Returns the token; *drew = 1 iff a draw was consumed (LP: *lp_out is set then).
+template <typename T, int NS, bool LP = false>
 __device__ __forceinline__ int imgproc_sample_block(T* logits, int vocab, bool has_last, int last_id, const int32_t* img_ids,
                                                     int n_img_ids, float inv_temp, float top_p, int top_k, float u,
-                                                    float* sv, int* si, SampleSmem& sm, int* n_kept_out, int* drew) {
+                                                    float* sv, int* si, SampleSmem& sm, int* n_kept_out, int* drew,
+                                                    float* lp_out = nullptr) {
     const int succ = has_last ? imgproc_edit_block<T>(logits, vocab, last_id, img_ids, n_img_ids, sv, si) : -1;
     *drew = 0;
     if (succ >= 0 && succ < vocab) { *n_kept_out = 1; return succ; }
     *drew = 1;
-    return sample_block<T, NS>(logits, vocab, inv_temp, top_p, top_k, u, sm, n_kept_out);
+    return sample_block<T, NS, LP>(logits, vocab, inv_temp, top_p, top_k, u, sm, n_kept_out, -1, lp_out);
 }
 
 }  // namespace ss

@@ -125,6 +125,7 @@ PROTOTYPES = {
     "ss_imgproc_argmax": (C.c_int, [vp, i64, vp, vp, i64, vp, C.c_int, vp]),
     "ss_sample_logits": (C.c_int, [vp, i64, i64, i64, C.POINTER(Sampling), vp, C.c_uint32, vp, vp, i64, vp, vp, C.c_int, vp]),
     "ss_process_logits": (C.c_int, [vp, i64, i64, i64, C.POINTER(LogitsRules), vp, i64, vp, vp, i32, vp, i64, C.c_int, vp]),
+    "ss_token_logprobs": (C.c_int, [vp, i64, i64, i64, vp, C.POINTER(Sampling), i32, vp, vp, vp, C.c_int, vp]),
     "ss_llama_workspace_bytes": (sz, [C.POINTER(LlamaConfig), i64]),
     "ss_llama_create": (C.c_int, [C.POINTER(LlamaConfig), C.POINTER(LlamaWeights), vp, sz, i64, i32p,
                                   C.POINTER(vp)]),
@@ -138,6 +139,7 @@ PROTOTYPES = {
     "ss_llama_kv8_invalidate": (C.c_int, [vp, i64]),
     "ss_llama_set_sampling": (C.c_int, [vp, i32, C.POINTER(Sampling)]),
     "ss_llama_set_logits_rules": (C.c_int, [vp, i32, C.POINTER(LogitsRules)]),
+    "ss_llama_set_logprobs": (C.c_int, [vp, i32, vp, vp, vp, vp, i32]),
     "ss_llama_set_history": (C.c_int, [vp, i32, i32p, i64, i32]),
     "ss_llama_buffer": (vp, [vp, C.c_int]),
     "ss_llama_set_lengths": (C.c_int, [vp, i64, i64, vp]),

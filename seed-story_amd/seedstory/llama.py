@@ -147,6 +147,9 @@ class LlamaEngine:
         self._kv8 = None           # the four shadow planes (k_codes, v_codes, k_scale, v_scale) while kv_cache="fp8" is on
         self.kv_cache = None
         self._rules_slots = set()  # slots whose history rules are on (set_logits_rules)
+        self._lp = None            # the result tensors of set_logprobs (model, policy, top ids, top values) while any slot records
+        self._lp_slots = {}        # slot -> top_n of the slots that record
+        self.last_logprobs = None  # what the image-block generate methods assembled for their last call
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -460,6 +463,75 @@ class LlamaEngine:
         if toks and slot in getattr(self, "_rules_slots", ()):     # getattr: tests bind the block methods onto stand-in engines
             self.set_history(toks, slot=slot, append=True)
 
+    # ---- token log-probabilities -----------------------------------------------------------------------------------
+    def set_logprobs(self, on=True, top_n=0, slot=None):
+        """Record, for every token the decode loop produces on ``slot`` (None: every slot), how likely it was: ``model_logprob``
+        (the model's log-softmax of the untouched lm_head row), ``logprob`` (the log of the probability with which the policy
+        picked it: greedy = log-softmax of the edited row, sampling = the sampler's own ``log(w / Z_P)``, 0.0 for a forced
+        token and for the certain image-token successor) and the ``top_n`` (at most 8) most likely tokens of the model with
+        their log-probabilities.  The definition is in include/seedstory_hip.h (``ss_token_logprobs``).  Runs on the device
+        inside the decode token (eager or captured; a graph of its own, cached apart from the others): two more small
+        kernels, nothing goes back to the host, and tokens, hidden rows and the draw counter stay bit-equal.  The engine owns
+        the result tensors (``logprobs(n)``); entry i lines up with ``gen_ids[i]`` of the last ``generate`` call.
+        ``on=False`` switches it off (the default).  Bad values raise ``SSError``."""
+        slots = list(range(self.n_seq)) if slot is None else [int(slot)]
+        if not 0 <= slots[0] < self.n_seq:
+            raise _lib.SSError("set_logprobs: sequence slot %d out of range (< %d)" % (slots[0], self.n_seq))
+        if on and (int(top_n) != top_n or not -2 ** 31 <= int(top_n) < 2 ** 31):
+            raise _lib.SSError("top_n must be an integer, not %r" % (top_n,))
+        top_n = int(top_n) if on else 0
+        torch.cuda.current_stream(self.device).synchronize()
+        if not on:
+            check(lib().ss_llama_set_logprobs(self._h, -1 if slot is None else int(slot), None, None, None, None, 0),
+                  "ss_llama_set_logprobs")
+            for b in slots:
+                self._lp_slots.pop(b, None)
+            if not self._lp_slots:
+                self._lp = None
+            return
+        if self._lp is None:
+            S, N = self.n_seq, self.max_new
+            self._lp = (torch.zeros(S, N, dtype=torch.float32, device=self.device), torch.zeros(S, N, dtype=torch.float32, device=self.device),
+                        torch.full((S, N, 8), -1, dtype=torch.int32, device=self.device),
+                        torch.full((S, N, 8), float("-inf"), dtype=torch.float32, device=self.device))
+            torch.cuda.current_stream(self.device).synchronize()
+        m, q, ti, tl = self._lp
+        for b in slots:     # (each slot's [max_new][top_n] block starts at its own [max_new][8] block of the tensors)
+            check(lib().ss_llama_set_logprobs(self._h, b, m[b].data_ptr(), q[b].data_ptr(), ti[b].data_ptr() if top_n > 0 else None,
+                                              tl[b].data_ptr() if top_n > 0 else None, top_n), "ss_llama_set_logprobs")
+            self._lp_slots[b] = top_n
+
+    def logprobs(self, n, slot=None):
+        """Views of the first ``n`` recorded entries of ``slot`` (None: the selected slot): ``{"logprob", "model_logprob"``
+        float32 [n], ``"top_ids"`` int32 [n, top_n], ``"top_logprobs"`` float32 [n, top_n]``}``.  The next ``generate`` call on
+        the slot overwrites them."""
+        b = self._cur if slot is None else int(slot)
+        if b not in self._lp_slots:
+            raise _lib.SSError("slot %d records no log-probabilities (set_logprobs)" % b)
+        k, n = self._lp_slots[b], int(n)
+        m, q, ti, tl = self._lp
+        return {"logprob": q[b, :n], "model_logprob": m[b, :n],
+                "top_ids": ti[b].view(-1)[:n * k].view(n, k), "top_logprobs": tl[b].view(-1)[:n * k].view(n, k)}
+
+    def _lp_segment(self, slot, n):
+        """a copy of the loop's first ``n`` entries of ``slot``, or None when the slot records nothing"""
+        if slot not in getattr(self, "_lp_slots", {}):      # getattr: tests bind the block methods onto stand-in engines
+            return None
+        return {k: v.clone() for k, v in self.logprobs(n, slot).items()}
+
+    def _lp_block(self, slot, logits, toks):
+        """the entries of image-block tokens ``toks``: row i of ``logits`` (lm_head of the block's hidden rows) scores
+        ``toks[i]``; the policy did not choose them, so their ``logprob`` is 0.0"""
+        k = self._lp_slots[slot]
+        r = ops.token_logprobs(logits, toks, top_n=k)
+        lp, ti, tl = r if k > 0 else (r, torch.zeros(len(toks), 0, dtype=torch.int32, device=logits.device),
+                                      torch.zeros(len(toks), 0, dtype=torch.float32, device=logits.device))
+        return {"logprob": torch.zeros_like(lp), "model_logprob": lp, "top_ids": ti, "top_logprobs": tl}
+
+    @staticmethod
+    def _lp_join(parts):
+        return {k: torch.cat([p[k] for p in parts]) for k in parts[0]} if parts else None
+
     # ---- forward paths ---------------------------------------------------------------------------------
     def _ensure_prefill_tiles(self, M):
         if M > 128:      # the four prefill projections of this row-count bucket (tile table: seedstory/tune.py)
@@ -581,7 +653,9 @@ class LlamaEngine:
         finally:
             if capture is not None:
                 self._set_capture(*capture, 0)
-        if _lib.get_tuning("img_block_logits", 1):
+        if getattr(self, "_cur", 0) in getattr(self, "_lp_slots", {}):      # kept, whatever the knob says: row i scores blk[i + 1]
+            self._blk_lp = LlamaEngine._lp_block(self, getattr(self, "_cur", 0), ops.gemm(hb, self.lm_head)[:m], blk[1:m + 1])
+        elif _lib.get_tuning("img_block_logits", 1):
             ops.gemm(hb, self.lm_head)                             # the reference's per-position logits (unused: forced)
         return blk[1:m + 1], hb, (blk[rows - 1] if rows == m + 1 else None)
 
@@ -590,10 +664,14 @@ class LlamaEngine:
         hidden rows [n - 1, hidden]) — the same tokens / rows the token-by-token loop yields."""
         if len(self.img_ids) < 3:
             n = self.generate(n_steps, last_prompt_id, forced)
+            self.last_logprobs = LlamaEngine._lp_segment(self, getattr(self, "_cur", 0), n)
             return self.gen_ids[:n].tolist(), self.hidden_rows[:max(n - 1, 0)]
         boi = self.img_ids[0]
         forced = [] if forced is None else [int(t) for t in forced]
         ids, hid, rem, last = [], [], min(int(n_steps), 1 << 30), int(last_prompt_id)
+        cur = getattr(self, "_cur", 0)
+        lps = [] if cur in getattr(self, "_lp_slots", {}) else None        # per-token values of the whole call, segment by segment
+        self.last_logprobs = None
         self.set_stop_id(boi)
         try:
             while rem > 0:
@@ -601,11 +679,15 @@ class LlamaEngine:
                 g = self.gen_ids[:n].tolist()
                 ids += g
                 hid.append(self.hidden_rows[:max(n - 1, 0)].clone())
+                if lps is not None:
+                    lps.append(LlamaEngine._lp_segment(self, cur, n))
                 forced, rem = forced[n:], rem - n
                 if n == 0 or g[-1] != boi or rem == 0:
                     break                                           # EOS, the token limit, or the budget ended at <img>
                 toks, hb, last_fed = self._img_block(rem, forced)
                 LlamaEngine._history_append(self, getattr(self, "_cur", 0), toks)
+                if lps is not None:
+                    lps.append(self._blk_lp)
                 ids += toks
                 hid.append(hb)
                 forced, rem = forced[len(toks):], rem - len(toks)
@@ -614,6 +696,8 @@ class LlamaEngine:
                 last = last_fed
         finally:
             self.set_stop_id(-1)
+        if lps is not None:
+            self.last_logprobs = LlamaEngine._lp_join(lps)
         return ids, torch.cat(hid)[:max(len(ids) - 1, 0)]
 
     def generate_batch_img_block(self, n_steps, last_prompt_ids, forced=None):
@@ -622,12 +706,16 @@ class LlamaEngine:
         S = self.n_seq
         if len(self.img_ids) < 3:
             ns = self.generate_batch(n_steps, last_prompt_ids, forced)
+            self.last_logprobs = [LlamaEngine._lp_segment(self, b, ns[b]) for b in range(S)] if getattr(self, "_lp_slots", {}) else None
             return ([self.select(b).gen_ids[:ns[b]].tolist() for b in range(S)],
                     [self.select(b).hidden_rows[:max(ns[b] - 1, 0)] for b in range(S)])
         boi = self.img_ids[0]
         forced = [[] for _ in range(S)] if forced is None else [[int(t) for t in (f or [])] for f in forced]
         ids, hid = [[] for _ in range(S)], [[] for _ in range(S)]
         rem, last, active = [int(n_steps)] * S, [int(t) for t in last_prompt_ids], [True] * S
+        lp_slots = getattr(self, "_lp_slots", {})
+        lps = [[] if b in lp_slots else None for b in range(S)]
+        self.last_logprobs = None
         self.set_stop_id(boi)
         try:
             blk = self.img_ids
@@ -644,6 +732,8 @@ class LlamaEngine:
                     g = self.gen_ids[:n].tolist()
                     ids[b] += g
                     hid[b].append(self.hidden_rows[:max(n - 1, 0)].clone())
+                    if lps[b] is not None:
+                        lps[b].append(LlamaEngine._lp_segment(self, b, n))
                     forced[b], rem[b] = forced[b][n:], rem[b] - n
                     if n == 0 or rem[b] == 0 or g[-1] == self.eos_id:
                         active[b] = False
@@ -657,9 +747,16 @@ class LlamaEngine:
                 if plan:
                     hbs = self.prefill_batch([None if f is None else ops.gather_rows(self.embed, f) for f in feed],
                                              want_hidden=True)
-                    if _lib.get_tuning("img_block_logits", 1) and any(v is not None for v in plan.values()):
-                        # the reference's per-position logits of the block rows (unused: those tokens are forced)
-                        ops.gemm(torch.cat([hbs[b] for b, v in plan.items() if v is not None]).contiguous(), self.lm_head)
+                    blocks = [b for b, v in plan.items() if v is not None]
+                    if blocks and (_lib.get_tuning("img_block_logits", 1) or any(lps[b] is not None for b in blocks)):
+                        # the reference's per-position logits of the block rows (those tokens are forced): unused, or kept for
+                        # the slots that record log-probabilities (row i of a slot's rows scores blk[i + 1])
+                        lg = ops.gemm(torch.cat([hbs[b] for b in blocks]).contiguous(), self.lm_head)
+                        r0 = 0
+                        for b in blocks:
+                            if lps[b] is not None:
+                                lps[b].append(LlamaEngine._lp_block(self, b, lg[r0:r0 + plan[b][0]], blk[1:plan[b][0] + 1]))
+                            r0 += hbs[b].shape[0]
                     for b, v in plan.items():
                         hid[b].append(hbs[b].clone())
                         if v is None:
@@ -676,6 +773,8 @@ class LlamaEngine:
                             active[b] = False
         finally:
             self.set_stop_id(-1)
+        if lp_slots:
+            self.last_logprobs = [None if l is None else LlamaEngine._lp_join(l) for l in lps]
         return ids, [torch.cat(h)[:max(len(i) - 1, 0)] for h, i in zip(hid, ids)]
 
     def profile_decode(self, n_tokens=4):

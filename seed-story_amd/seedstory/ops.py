@@ -466,6 +466,38 @@ def sample_logits(logits, temperature=1.0, top_k=0, top_p=1.0, seed=0, u=None, d
     return (tok, kept) if return_n_kept else tok
 
 
+def token_logprobs(logits, ids, sampling=None, top_n=0):
+    """Log-probability of ``ids`` [rows] on the rows of ``logits`` [rows, vocab] (or [vocab]; rows may be strided, unit stride
+    inside a row), which are only read.  ``sampling=None``: the log-softmax at temperature 1 over the whole vocabulary
+    (``model_logprob``); ``sampling`` = a dict of ``temperature`` / ``top_k`` / ``top_p``: the sampler's renormalised
+    ``log(w / Z_P)``, -inf outside its kept set.  Returns float32 [rows]; with ``top_n`` > 0 (at most 8) the tuple
+    (logprobs, top_ids int32 [rows, top_n], top_logprobs float32 [rows, top_n]) — the largest entries with their log-softmax
+    values, descending, ties by ascending id, -1 / -inf where fewer carry mass.  The definition is in
+    include/seedstory_hip.h (``ss_token_logprobs``)."""
+    if not logits.is_cuda:
+        raise _lib.SSError("logits must live on the GPU (there is no CPU path)")
+    lg = logits if logits.dim() == 2 else logits.view(1, -1)
+    if lg.dim() != 2 or (lg.shape[1] > 1 and lg.stride(1) != 1) or (lg.shape[0] > 1 and lg.stride(0) < lg.shape[1]):
+        raise _lib.SSError("logits must be [rows, vocab] with unit stride inside a row")
+    rows, vocab = lg.shape
+    dev = lg.device
+    if int(top_n) != top_n or not -2 ** 31 <= int(top_n) < 2 ** 31:
+        raise _lib.SSError("top_n must be an integer, not %r" % (top_n,))
+    top_n = int(top_n)
+    tok = torch.as_tensor(ids, dtype=torch.int32, device=dev).reshape(-1).contiguous()
+    if tok.numel() != rows:
+        raise _lib.SSError("ids must hold one id per row (%d), not %d" % (rows, tok.numel()))
+    import ctypes as C
+    sps = None if sampling is None else sampling_struct(**dict(sampling))
+    sp = None if sps is None else C.byref(sps)
+    lp = torch.zeros(rows, dtype=torch.float32, device=dev)
+    tid = torch.zeros(rows, max(top_n, 0), dtype=torch.int32, device=dev) if top_n > 0 else None
+    tlp = torch.zeros(rows, max(top_n, 0), dtype=torch.float32, device=dev) if top_n > 0 else None
+    check(lib().ss_token_logprobs(p(lg), rows, vocab, lg.stride(0) if rows > 1 else vocab, p(tok), sp, top_n, p(lp), p(tid), p(tlp),
+                                  dt(lg), stream()), "ss_token_logprobs")
+    return (lp, tid, tlp) if top_n > 0 else lp
+
+
 def logits_rules_struct(repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, spare_img_ids=False):
     """The C ABI's ``ss_logits_rules``.  Ranges are checked by the library (``SSError``); only what ctypes would mangle
     silently is checked here."""

@@ -19,6 +19,7 @@ Differences from the reference script:
 """
 import argparse
 import json
+import math
 import os
 import re
 import zlib
@@ -181,6 +182,30 @@ def rules_kwargs(args):
     return dict(repetition_penalty=p, no_repeat_ngram_size=n, min_new_tokens=m, spare_img_ids=p != 1.0)
 
 
+def add_logprobs_argument(ap):
+    """``--logprobs`` (shared with vis_george_sink.py)"""
+    ap.add_argument("--logprobs", action="store_true",
+                    help="record token log-probabilities on the device; prints each step's mean caption model_logprob and perplexity")
+
+
+def logprobs_kwargs(args):
+    return dict(output_logprobs=True) if getattr(args, "logprobs", False) else {}
+
+
+def report_caption_logprobs(args, j, step, out, boi):
+    """``--logprobs``: the caption = the generated ids in front of ``<img>``; its mean ``model_logprob`` (the model's own
+    log-softmax of the untouched logits, whatever policy picked the tokens) and perplexity exp(-mean)."""
+    if not getattr(args, "logprobs", False):
+        return
+    ids = out['generate_ids'].tolist()
+    n = ids.index(boi) if boi in ids else len(ids)
+    if n == 0:
+        print("story %d step %d: empty caption" % (j, step))
+        return
+    mean = float(out['model_logprobs'][:n].double().mean())
+    print("story %d step %d: caption of %d tokens, mean model_logprob %.4f, perplexity %.3f" % (j, step, n, mean, math.exp(-mean)))
+
+
 def run_story(args, j, question, image, tokenizer, transform, vit, agent, adapter, device, dtype):
     save_folder = os.path.join(args.out, "val_%d" % j)
     os.makedirs(save_folder, exist_ok=True)
@@ -211,7 +236,8 @@ def run_story(args, j, question, image, tokenizer, transform, vit, agent, adapte
         ids_mask, emb_mask = ctx.masks(device)
         out = agent.generate(tokenizer=tokenizer, input_ids=ctx.input_ids(device), image_embeds=ctx.image_embeds,
                              embeds_cmp_mask=emb_mask, ids_cmp_mask=ids_mask, max_new_tokens=500, num_img_gen_tokens=64,
-                             forced_tokens=forced, **sample_kwargs(args, j, step), **rules_kwargs(args))
+                             forced_tokens=forced, **sample_kwargs(args, j, step), **rules_kwargs(args), **logprobs_kwargs(args))
+        report_caption_logprobs(args, j, step, out, boi)
         if args.save_attn:                                       # [layers, rows, width], head 0 (NaN beyond each row's keys)
             torch.save(torch.stack([a[0] for a in out['attn_weights']]).cpu(),
                        os.path.join(args.save_attn, "val_%d_step_%02d.pt" % (j, step)))
@@ -257,6 +283,7 @@ def main():
     ap.add_argument("--top-k", type=int, default=0, help="0 = off")
     ap.add_argument("--top-p", type=float, default=0.5)
     ap.add_argument("--seed", type=int, default=None, help="with --sample: reproducible stories (default: torch.initial_seed())")
+    add_logprobs_argument(ap)
     add_rules_arguments(ap)
     args = ap.parse_args()
     device = "cuda:0"

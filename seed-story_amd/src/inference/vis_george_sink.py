@@ -20,7 +20,8 @@ import os
 import torch
 
 from seedstory.story import StoryContext
-from src.inference.gen_george import BOI_TOKEN, EOI_TOKEN, IMG_TOKEN, add_rules_arguments, build, rules_kwargs
+from src.inference.gen_george import (BOI_TOKEN, EOI_TOKEN, IMG_TOKEN, add_logprobs_argument, add_rules_arguments, build, logprobs_kwargs,
+                                      report_caption_logprobs, rules_kwargs)
 
 
 def run_story(args, j, start_text, captions, image, tokenizer, transform, vit, agent, adapter, device, dtype):
@@ -51,7 +52,8 @@ def run_story(args, j, start_text, captions, image, tokenizer, transform, vit, a
             llama.kv_cache_head = cached
         out = agent.generate(tokenizer=tokenizer, input_ids=ctx.input_ids(device), image_embeds=ctx.image_embeds,
                              embeds_cmp_mask=emb_mask, ids_cmp_mask=ids_mask, max_new_tokens=500, num_img_gen_tokens=64,
-                             past_key_values=past, forced_tokens=forced, **rules_kwargs(args))
+                             past_key_values=past, forced_tokens=forced, **rules_kwargs(args), **logprobs_kwargs(args))
+        report_caption_logprobs(args, j, step, out, boi)
         with open(os.path.join(save_folder, "token.txt"), "a+") as f:
             f.write("context token: {} cached: {} sink: {}\n".format((1, len(ctx.ids)), cached, ctx.sink_len))
         if args.save_attn:                                       # [layers, rows, width], head 0 (NaN beyond each row's keys)
@@ -102,6 +104,7 @@ def main():
     ap.add_argument("--caption-tokens", type=int, default=48)
     ap.add_argument("--stories", type=int, default=1)
     add_rules_arguments(ap)
+    add_logprobs_argument(ap)
     ap.add_argument("--save-attn", default=None, metavar="DIR",
                     help="run the LLM with config.output_attentions and torch.save each step's attn_weights (head 0's "
                          "pre-softmax maps, the evidence behind the attention sink) into DIR")

@@ -337,7 +337,8 @@ class LlamaForCausalLM(nn.Module):
     def generate(self, input_ids=None, inputs_embeds=None, logits_processor=None, past_key_values=None,
                  max_new_tokens=120, output_hidden_states=True, return_dict_in_generate=True, forced_tokens=None,
                  output_attentions=None, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=None, num_beams=1,
-                 repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, spare_img_ids=False, **unused):
+                 repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, spare_img_ids=False, output_logprobs=False,
+                 top_logprobs=0, **unused):
         """Greedy search as ``ContinuousLVLM.generate`` drives it (reference models.py:146-153): ``inputs_embeds`` feed
         step 0, ``input_ids`` is the running sequence, the image-token logits processor is applied on device.
         ``do_sample=False`` (the default): temperature / top_k / top_p / seed are inert, as in Hugging Face.
@@ -355,7 +356,14 @@ class LlamaForCausalLM(nn.Module):
         ``output_attentions`` (default ``config.output_attentions``, the reference's switch): ``attentions`` = tuple over steps
         of tuple over layers — step 0 ``[1, q0, kv0 + q0]``, step j ``[1, 1, kv0 + q0 + j]``, as many as ``hidden_states`` —
         all VIEWS of one capture buffer, which ``attention_maps`` [layers, rows, width] hands out whole (one row per fed token,
-        NaN beyond each row's key count: what the reference's pad-and-concatenate merge builds, models.py:164-179)."""
+        NaN beyond each row's key count: what the reference's pad-and-concatenate merge builds, models.py:164-179).
+        ``output_logprobs=True``: the output's ``logprobs`` (the log of the probability with which the policy — greedy or
+        sampling, after the rules and the processor — picked each token; 0.0 for a forced token and a processor-forced image
+        token), ``model_logprobs`` (the model's own log-softmax of the untouched logits) and, with ``top_logprobs`` = 1 .. 8,
+        ``top_logprob_ids`` / ``top_logprob_values`` [n, top_logprobs] hold one float32 entry per generated token, computed
+        on the device inside the decode token (``LlamaEngine.set_logprobs``; include/seedstory_hip.h); the engine records
+        nothing any more when the call returns or raises.  ``output_scores`` / ``output_logits`` (full [vocab] rows per
+        step) are not part of this and stay ignored."""
         want_attn = bool(getattr(self.config, "output_attentions", False) if output_attentions is None else output_attentions)
         if do_sample and num_beams is not None and int(num_beams) > 1:
             raise NotImplementedError("beam-search sampling (do_sample=True with num_beams=%d) is not implemented" % int(num_beams))
@@ -377,14 +385,18 @@ class LlamaForCausalLM(nn.Module):
         # (Hugging Face also takes None for "off")
         rules = (repetition_penalty not in (None, 1.0) or no_repeat_ngram_size not in (None, 0) or min_new_tokens not in (None, 0))
         try:
+            if output_logprobs:
+                eng.set_logprobs(True, top_n=top_logprobs)                            # raises on a bad value
             if rules:
                 eng.set_logits_rules(repetition_penalty=1.0 if repetition_penalty is None else repetition_penalty,
                                      no_repeat_ngram_size=no_repeat_ngram_size or 0, min_new_tokens=min_new_tokens or 0,
                                      spare_img_ids=bool(spare_img_ids))               # raises on a bad value
                 eng.set_history(input_ids[0].tolist())
             return self._generate(eng, input_ids, rows, S, img_ids, past_key_values, max_new_tokens, output_hidden_states,
-                                  forced_tokens, want_attn)
+                                  forced_tokens, want_attn, **({"want_logprobs": True} if output_logprobs else {}))
         finally:
+            if output_logprobs:
+                eng.set_logprobs(False)
             if rules:
                 eng.clear_logits_rules()
             if do_sample:
@@ -393,7 +405,7 @@ class LlamaForCausalLM(nn.Module):
                 eng.attn_capture_off()
 
     def _generate(self, eng, input_ids, rows, S, img_ids, past_key_values, max_new_tokens, output_hidden_states,
-                  forced_tokens, want_attn):
+                  forced_tokens, want_attn, want_logprobs=False):
         dev = eng.device
         maps, kv0 = None, 0
         if past_key_values is None:
@@ -420,10 +432,12 @@ class LlamaForCausalLM(nn.Module):
             gen_list, hr = eng.generate_img_block(max_new_tokens, int(input_ids[0, -1]), forced_tokens)
             n = len(gen_list)
             gen = torch.tensor(gen_list, dtype=torch.long, device=dev)
+            lp = eng.last_logprobs if want_logprobs else None
         else:
             n = eng.generate(max_new_tokens, int(input_ids[0, -1]), forced_tokens)
             gen = eng.gen_ids[:n].to(torch.long)
             hr = eng.hidden_rows[:max(n - 1, 0)]
+            lp = {k: v.clone() for k, v in eng.logprobs(n).items()} if want_logprobs else None
         sequences = torch.cat([input_ids[0], gen]).unsqueeze(0)
         hidden_states = None
         if output_hidden_states:
@@ -439,8 +453,12 @@ class LlamaForCausalLM(nn.Module):
             fed = fed0 + max(n - 1, 0)
             attentions = attention_step_views(maps, kv0, fed0, fed)
             attention_maps = maps[:, :fed, :kv0 + fed]
+        scores = {}
+        if lp is not None:
+            scores = dict(logprobs=lp["logprob"], model_logprobs=lp["model_logprob"], top_logprob_ids=lp["top_ids"],
+                          top_logprob_values=lp["top_logprobs"])
         return GenerateOutput(sequences=sequences, hidden_states=hidden_states, attentions=attentions,
-                              attention_maps=attention_maps)
+                              attention_maps=attention_maps, **scores)
 
 
 def attention_step_views(maps, kv0, fed0, fed):
@@ -466,8 +484,12 @@ class CausalLMOutputWithPast:
 
 
 class GenerateOutput:
-    def __init__(self, sequences, hidden_states, attentions, attention_maps=None):
+    def __init__(self, sequences, hidden_states, attentions, attention_maps=None, logprobs=None, model_logprobs=None,
+                 top_logprob_ids=None, top_logprob_values=None):
         self.sequences = sequences
         self.hidden_states = hidden_states
         self.attentions = attentions
         self.attention_maps = attention_maps      # [layers, rows, width]: the buffer every entry of `attentions` is a view of
+        # float32, one entry per generated token (generate(output_logprobs=True)); None when not asked for
+        self.logprobs, self.model_logprobs = logprobs, model_logprobs
+        self.top_logprob_ids, self.top_logprob_values = top_logprob_ids, top_logprob_values

@@ -109,12 +109,14 @@ class ContinuousLVLM(nn.Module):
                  ids_cmp_mask=None, logits_processor=None, num_img_gen_tokens=64, temperature=0.7, num_beams=1,
                  max_new_tokens=120, top_p=0.5, past_key_values=None, dtype=torch.float16, device='cuda',
                  forced_tokens=None, do_sample=False, top_k=0, seed=None, repetition_penalty=1.0, no_repeat_ngram_size=0,
-                 min_new_tokens=0, spare_img_ids=False):
+                 min_new_tokens=0, spare_img_ids=False, output_logprobs=False, top_logprobs=0):
         """``do_sample=False`` (the default, what the reference passes): greedy; ``temperature`` / ``top_p`` / ``top_k`` /
         ``seed`` are inert.  ``do_sample=True`` hands them to ``LlamaForCausalLM.generate``: on-device sampling
         (``top_k=0`` = off, ``seed=None`` = governed by ``torch.manual_seed``).  ``repetition_penalty`` /
         ``no_repeat_ngram_size`` / ``min_new_tokens`` (Hugging Face's defaults: inert) and ``spare_img_ids`` are handed on only
-        when one of the three is active: they act on greedy search and on sampling (``LlamaForCausalLM.generate``)."""
+        when one of the three is active: they act on greedy search and on sampling (``LlamaForCausalLM.generate``).
+        ``output_logprobs=True`` adds ``'logprobs'``, ``'model_logprobs'`` (float32, one entry per generated id) and
+        ``'top_logprobs'`` = (ids, values) [n, top_logprobs] to the returned dict (``LlamaForCausalLM.generate``)."""
         if logits_processor is None:
             logits_processor = LogitsProcessorList()
             logits_processor.append(
@@ -145,7 +147,8 @@ class ContinuousLVLM(nn.Module):
                                    return_dict_in_generate=True, logits_processor=logits_processor,
                                    past_key_values=past_key_values, max_new_tokens=max_new_tokens,
                                    temperature=temperature, num_beams=num_beams, top_p=top_p, do_sample=do_sample,
-                                   forced_tokens=forced_tokens, **({"top_k": top_k, "seed": seed} if do_sample else {}), **rules)
+                                   forced_tokens=forced_tokens, **({"top_k": top_k, "seed": seed} if do_sample else {}), **rules,
+                                   **({"output_logprobs": True, "top_logprobs": top_logprobs} if output_logprobs else {}))
         output_past_key_values = self.llm.past_key_values
         generate_ids = output.sequences[0][input_ids.shape[1]:]
         boi_token_id = tokenizer.encode(BOI_TOKEN, add_special_tokens=False)[0]
@@ -175,7 +178,12 @@ class ContinuousLVLM(nn.Module):
         attn_weights = ()
         if output.attentions is not None:
             attn_weights = tuple(output.attention_maps[l].unsqueeze(0) for l in range(output.attention_maps.shape[0]))
+        scores = {}
+        if output_logprobs:
+            scores = {'logprobs': output.logprobs, 'model_logprobs': output.model_logprobs,
+                      'top_logprobs': (output.top_logprob_ids, output.top_logprob_values)}
         return {
+            **scores,
             'text': generate_text,
             'generate_ids': generate_ids,
             'has_img_output': has_img_output,
