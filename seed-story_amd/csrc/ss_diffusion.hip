@@ -207,6 +207,8 @@ __global__ __launch_bounds__(256) void groupnorm_apply_kernel(const T* __restric
 
 static int groupnorm_rows_per_block(int64_t B, int64_t HW, int64_t C, size_t elem) {
     // ~128 KiB of activations per block, at least enough blocks to fill the chip several times
+    // (tests/kernel_check.py GN_ROWS_MAX_BYTES / groupnorm_rows_per_block is a hand copy of this rule: its GroupNorm bound takes
+    // the longest fp32 chain from it.  Change both together.)
     int rows_per_block = (int)((128 * 1024) / (C * elem));
     if (rows_per_block < 16) rows_per_block = 16;
     while (rows_per_block > 16 && B * cdiv(HW, rows_per_block) < 2048) rows_per_block /= 2;

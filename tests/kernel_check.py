@@ -47,7 +47,62 @@ Attention (per query row; P = fp64 softmax of the fp64 scores, masked keys have 
   output        one final round: u_T |ref|.
   bound         |out - ref| <= u_T |ref| + (2 u_T + 2 max_j delta_s) (P @ |V|).
 The fp32 accumulation of P V (kv_len terms of one sign pattern, rescaled per tile) is not budgeted on its own; it rides in the
-factor 2 of delta_s.  The constants are derived, not tuned: the GPU file records the worst error / bound ratio per family."""
+factor 2 of delta_s.  The constants are derived, not tuned: the GPU file records the worst error / bound ratio per family.
+
+Norms, softmax, point-wise kernels and loss heads (tests/test_pointwise_edges_gpu.py).  Two more steps:
+
+  sum32        an fp32 sum of n terms in ANY order (thread chains, shuffle trees, LDS folds): |x - v| <= gamma_n sum |term|,
+               gamma_n = n u32 / (1 - n u32).  Additions of an exact 0 (idle lanes, a chain's first term) round nothing, so a tree
+               over n terms has at most n - 1 rounding additions whatever its shape.  No factor 2: no MFMA is involved.
+  sqrt, 1 / x  |sqrt(x) - sqrt(v)| = |x - v| / (sqrt(x) + sqrt(v)) <= t / (sqrt(max(v - t, 0)) + sqrt(v));
+               |1 / x - 1 / v| <= t / (v (v - t));  each followed by its own fp32 rounding (an fp32 op).
+
+  RMSNorm      ss = sum x^2 (sum32 over cols; the fma rounds once per term); ss / cols, + eps, sqrt, 1 / : four fp32 ops -> rstd.
+               h = rnd_T(x rstd): one fp32 op, mid round.  y = rnd_T(w h): w h is exact in fp32 for 16-bit T (for fp32 the
+               product's own rounding IS the final round): final round.  An all-zero row gives h = 0 exactly, bound eta_T.
+  LayerNorm    two-pass, block and wave kernels alike.  mean: sum32 over cols, one division: t_mean = gamma_cols mean|x| +
+               u32 |mean|.  d = x - mean is one fp32 op on an operand known to t_mean; d^2 moves by 2 |d| t_d + t_d^2 and the
+               squares are summed by sum32; / cols, + eps, sqrt, 1 / -> rstd.  y = rnd_T(((x - mean) rstd) w + b): the
+               subtraction, two products, one addition (four fp32 ops), final round.  A constant row has variance 0 in the
+               reference and rstd = 1 / sqrt(eps); the kernel's mean may be off by t_mean, which the bound carries through d
+               (it is loose there, gamma_cols |c| / sqrt(eps), and valid).  |mean| >> std costs gamma_cols mean|x| in every
+               d: the price of an fp32 mean, charged as such.
+  GroupNorm    per (image, group), n = HW cg elements.  Pass 1 sums x and x^2 per channel and block in fp32: a thread chain
+               over the block's rows followed by one fold over the row lanes, together an any-order sum of at most
+               rows_per_block terms: sum32 with k = min(HW, max(16, 128 KiB / row bytes)), the largest rows_per_block the launch
+               rule can return (GN_ROWS_MAX_BYTES below: a hand copy).  Everything after that is fp64 (channels of a group,
+               blocks, E[x^2] - mean^2) except 1 / n, which the kernel forms in fp32 (two roundings) before widening it:
+               t_S1 = (gamma_k + 2 u32) sum|x|, t_S2 = (gamma_k + 2 u32) sum x^2, t_mean = t_S1 / n, and var = E[x^2] - mean^2
+               carries t_S2 / n + 2 |mean| t_mean + t_mean^2: the error of the fp32 chains scaled by E[x^2], NOT by the
+               variance; a group with mean 8 and spread 1 pays 65 gamma_k, the design's price.  mean and var are narrowed
+               to fp32 (one rounding each); + eps, sqrt, 1 / ; sc = rstd gamma, sh = beta - mean sc (two fp32 ops);
+               out = fma(x, sc, sh): one rounding.  Since x sc + (beta - mean sc) = (x - mean) sc + beta, the error of sc
+               multiplies x - mean, not x: t = |x - mean| t_sc + |sc| t_mean + u32 (|mean sc| + |sh| + |out|).  Then the final round.  With SiLU: mid round, the fast SiLU on hardware rcp /
+               exp2 (evaluation term 2^-21 max(|v|, |f(v)|) in every dtype, as for the 16-bit GELU), final round.
+  softmax_rows s = x scale: one fp32 op.  The kernel's own maximum m' enters every term of the row alike and cancels in e / sum
+               e, so m' is a parameter, not an error: d = s - m is one more fp32 op, |d' - d| <= u32 (|s| + |s - m|).
+               e = expf(d): e (exp(t_d) - 1) + 4 u32 e (libm: 2 ulp).  sum: the terms' errors plus sum32 over cols of positive
+               terms; 1 / ; e inv: product; final round.
+  silu_mul     rnd_T(rnd_T(silu(g)) u): silu of an exact gate (evaluation term only), mid round, product with the exact u,
+               final round.  geglu: rnd_T(a rnd_T(gelu(g))) the same way.  unary: f(x), final round.
+  l2normalize  s = sum of L squares (sum32), sqrt (fp32 op), mid round of the norm, clamp at 1e-12, x / norm (1 / x step times
+               |x|, one fp32 op), final round.  An all-zero column divides 0 by the clamp: exactly 0.
+  cross-entropy row  m is the exact maximum of exact inputs.  d = x - m: one fp32 op; e = expf(d) as above; s: sum32 over vocab
+               of positive terms (s >= 1: the maximum contributes e^0); logf(s): t_s / (s - t_s) + 4 u32 |log s|;
+               (x_lab - m) - logf(s): two fp32 ops; rnd_T: final round.  The loss is stored in fp32 without another rounding.
+  cosine row   na = rnd_T(sqrt(sum32 a^2)), nb alike: mid rounds.  rnd_T(a / na), rnd_T(b / nb): 1 / x step, fp32 op, mid round.
+               p = rnd_T(product): mid round.  s = rnd_T(sum32 over dim of p): the terms' errors add up (each mid round may flip:
+               2 u_T |p| per term; this dominates and grows with sum |p| <= 1), mid round.  1 - s: fp32 op, final round.
+  mse          d = fl(a - b), fl(d d): relative 3 u32 per term (+ eta32); the terms are summed in fp64 (n 2^-53, below), divided
+               and narrowed once: (4 u32 + n 2^-52) sum|term| / n.  masked_mean: fl(val mask), fp64 sums, one narrowing:
+               (2 u32 + n 2^-52) sum|term| / count; the count is an exact integer; an all-zero mask gives (0, 0) exactly.
+  euler_scale_dup  inv = 1 / sqrtf(sigma^2 + 1) formed on the host in fp32: four fp32 ops.  x inv: one fp32 op, final round.
+
+Exact expectations (no bound; mirrored in fp32 on the CPU with the kernel's rnd points, so double rounding cannot differ): every
+data mover; add_bcast (one correctly rounded fp32 add, stored); RoPE q / k (rnd(rnd(a c) + rnd(-b s)) in T); euler_cfg_step
+(rnd(eu + rnd(g rnd(ec - eu))), x + rnd(e dsigma), stored); image_to_u8 (rnd_T(0.5 x + 0.5), clamp, rintf(255 v): 255 v is exact
+in fp32 for a 16-bit v, one fp32 rounding otherwise; ties to even).  The library is built with -ffp-contract=off, so the fp32
+mirrors see the same operations."""
 import numpy as np
 import torch
 
@@ -252,8 +307,27 @@ def check(y, ref, tol, what="", family=None, dtype=None):
     return worst
 
 
-def worst_table():
-    return "\n".join("  %-22s %-5s worst error / bound = %.3f" % (f, d, r) for (f, d), r in sorted(WORST.items()))
+def worst_table(families=None):
+    """families: only these (a test file prints the ones it recorded itself)"""
+    return "\n".join("  %-22s %-5s worst error / bound = %.3f" % (f, d, r) for (f, d), r in sorted(WORST.items())
+                     if families is None or f in families)
+
+
+def check_exact(y, expected, what="", family=None, dtype=None, alt=None):
+    """bit-for-bit (compared as integers: -0 and NaN payloads count); recorded under (family, dtype) as ratio 0.  alt: a second
+    admissible mirror (see euler_cfg_step_exact): an element must equal one of the two."""
+    y, expected = y.cpu().contiguous(), expected.contiguous()
+    if alt is not None:
+        expected = torch.where(y.view(_INT[y.dtype]) == alt.contiguous().view(_INT[y.dtype]), alt.contiguous(), expected)
+    assert y.shape == expected.shape and y.dtype == expected.dtype, "%s: %s %s, expected %s %s" % (what, tuple(y.shape), y.dtype, tuple(expected.shape), expected.dtype)
+    it = _INT.get(y.dtype)
+    a, b = (y.view(it), expected.view(it)) if it is not None else (y, expected)
+    bad = (a != b).nonzero()
+    if family is not None:
+        key = (family, NAME.get(dtype, str(dtype)))
+        WORST[key] = max(WORST.get(key, 0.0), float("inf") if bad.numel() else 0.0)
+    assert not bad.numel(), "%s: %d of %d elements differ from the exact expectation, first at %s: got %r, expected %r" % (
+        what, bad.shape[0], y.numel(), tuple(bad[0].tolist()), y[tuple(bad[0].tolist())].item(), expected[tuple(bad[0].tolist())].item())
 
 
 # ---- guarded outputs ----------------------------------------------------------------------------------------------------------
@@ -293,9 +367,9 @@ class GuardedOut:
     def data_ptr(self):
         return self.out.data_ptr()
 
-    def problems(self, cpu=True):
+    def problems(self, cpu=True, payload=True):
         """-> (messages, payload).  The comparisons run where the buffer lives (integers); the payload comes back on the CPU
-        unless cpu=False."""
+        unless cpu=False.  payload=False checks guards, offset and gaps only (buffers a kernel fills in part, byte outputs)."""
         if self.flat.is_cuda:
             torch.cuda.synchronize()
         f = self.flat.cpu() if cpu else self.flat
@@ -319,17 +393,37 @@ class GuardedOut:
             pay = grid[:, :self.width]
         else:
             pay = body.view(self.rows, self.width)
-        left = (pay == s).nonzero()
+        left = (pay == s).nonzero() if payload else pay[:0]
         if left.numel():
             r, c = int(left[0, 0]), int(left[0, 1])
             msgs.append("%d payload elements never written (first at (%d, %d): mod 16 = (%d, %d), mod 64 = (%d, %d), mod 256 = (%d, %d))"
                         % (left.shape[0], r, c, r % 16, c % 16, r % 64, c % 64, r % 256, c % 256))
         return msgs, pay.contiguous().view(self.dtype)
 
-    def check(self, what="", cpu=True):
-        msgs, pay = self.problems(cpu)
+    def untouched(self, pay):
+        """bool mask over a payload that check() returned: elements that still hold the sentinel bits"""
+        return pay.view(_INT[self.dtype]) == _sentinel_int(self.dtype)
+
+    def check(self, what="", cpu=True, payload=True):
+        msgs, pay = self.problems(cpu, payload)
         assert not msgs, "%s: %s" % (what, "; ".join(msgs))
         return pay
+
+
+class GuardedBytes(GuardedOut):
+    """nbytes of raw output (a uint8 image, an opaque workspace) carved from a guarded fp32 allocation: 16-byte aligned, the
+    bytes between nbytes and the next multiple of 4 belong to the guard."""
+
+    def __init__(self, nbytes, device="cpu"):
+        self.nbytes = int(nbytes)
+        super().__init__(1, max((self.nbytes + 3) // 4, 1), torch.float32, device=device)
+
+    def bytes(self, what=""):
+        """asserts the guards (and the tail bytes of the last word) and returns the nbytes as uint8 on the CPU"""
+        pay = self.check(what, payload=False).view(torch.uint8).flatten()
+        fresh = torch.full((self.width,), _sentinel_int(self.dtype), dtype=torch.int32).view(torch.uint8)
+        assert torch.equal(pay[self.nbytes:], fresh[self.nbytes:]), "%s: bytes written past the %d-byte output" % (what, self.nbytes)
+        return pay[:self.nbytes].clone()
 
 
 # ---- exact probes -------------------------------------------------------------------------------------------------------------
@@ -555,3 +649,404 @@ def unheads(x):
     """[B, H, L, hd] -> [B, L, H * hd]"""
     B, H, L, hd = x.shape
     return x.transpose(1, 2).reshape(B, L, H * hd)
+
+
+# ==== norms, softmax, point-wise kernels, loss heads (tests/test_pointwise_edges_gpu.py) ======================================
+def vec(dtype):
+    """elements per 16-byte pack"""
+    return 4 if dtype == torch.float32 else 8
+
+
+def esize(dtype):
+    return 4 if dtype == torch.float32 else 2
+
+
+def gamma(n):
+    return n * U32 / (1.0 - n * U32)
+
+
+def sqrt32(v, t):
+    lo = (v - t).clamp_min(0.0)
+    den = lo.sqrt() + v.sqrt()
+    return op32(v.sqrt(), torch.where(t > 0, t / den.clamp_min(1e-300), torch.zeros_like(t)))
+
+
+def recip32(v, t):
+    return op32(1.0 / v, t / (v.abs() * (v.abs() - t).clamp_min(1e-300)))
+
+
+def exp32(v, t):
+    e = torch.exp(v)
+    return e, e * torch.expm1(t) + 4.0 * U32 * e
+
+
+def rmsnorm_bound(x, w, eps, dtype):
+    """x [rows, cols], w [cols] -> (reference, bound) of ss_rmsnorm"""
+    xd, wd = x.double(), w.double()
+    cols = x.shape[1]
+    ss = (xd * xd).sum(1, keepdim=True)
+    v, t = op32(ss / cols, gamma(cols) * ss / cols)
+    v, t = op32(v + float(np.float32(eps)), t)
+    v, t = recip32(*sqrt32(v, t))
+    h, th = op32(xd * v, xd.abs() * t)
+    h, th = mid_round(h, th, dtype)
+    return final_round(wd * h, wd.abs() * th, dtype)
+
+
+def layernorm_bound(x, w, b, eps, dtype):
+    """x [rows, cols], w / b [cols] -> (reference, bound) of ss_layernorm (block and wave kernels)"""
+    xd, wd, bd = x.double(), w.double(), b.double()
+    cols = x.shape[1]
+    mean, tm = op32(xd.mean(1, keepdim=True), gamma(cols) * xd.abs().mean(1, keepdim=True))
+    d, td = op32(xd - mean, tm.expand_as(xd))
+    s2 = (d * d).sum(1, keepdim=True)
+    ts2 = (2.0 * d.abs() * td + td * td).sum(1, keepdim=True) + gamma(cols) * ((d.abs() + td) ** 2).sum(1, keepdim=True)
+    v, t = op32(s2 / cols, ts2 / cols)
+    v, t = op32(v + float(np.float32(eps)), t)
+    rv, rt = recip32(*sqrt32(v, t))
+    v, t = product(d, td, rv.expand_as(d), rt.expand_as(d))
+    v, t = op32(v * wd, t * wd.abs())
+    v, t = op32(v + bd, t)
+    return final_round(v, t, dtype)
+
+
+# ss_diffusion.hip groupnorm_rows_per_block: "~128 KiB of activations per block", at least 16 rows.  A hand copy (the library
+# does not report its launch geometry); groupnorm_rows_per_block carries a comment that points here, change both together.
+GN_ROWS_MAX_BYTES = 128 * 1024
+
+
+def groupnorm_rows_per_block(B, HW, C, dtype):
+    """the whole launch rule (the CPU simulation needs the block boundaries; the bound only the maximum)"""
+    rpb = max(16, GN_ROWS_MAX_BYTES // (C * esize(dtype)))
+    while rpb > 16 and B * (-(-HW // rpb)) < 2048:
+        rpb //= 2
+    return min(rpb, HW)
+
+
+def groupnorm_bound(x, gw, gb, G, eps, silu_, dtype):
+    """x [B, HW, C], gw / gb [C] -> (reference, bound) [B, HW, C] of ss_groupnorm"""
+    B, HW, C = x.shape
+    cg = C // G
+    n = HW * cg
+    k = min(HW, max(16, GN_ROWS_MAX_BYTES // (C * esize(dtype))))
+    xd = x.double().view(B, HW, G, cg)
+    ga, be = gw.double().view(1, 1, G, cg), gb.double().view(1, 1, G, cg)
+    c = gamma(k) + 2.0 * U32
+    S1, S2 = xd.sum((1, 3), keepdim=True), (xd * xd).sum((1, 3), keepdim=True)
+    md, tmd = S1 / n, c * xd.abs().sum((1, 3), keepdim=True) / n
+    var = (S2 / n - md * md).clamp_min(0.0)
+    tvar = c * S2 / n + 2.0 * md.abs() * tmd + tmd * tmd
+    mean, tmean = op32(md, tmd)
+    v, t = op32(var, tvar)
+    v, t = op32(v + float(np.float32(eps)), t)
+    rv, rt = recip32(*sqrt32(v, t))
+    sc, tsc = op32(rv * ga, rt * ga.abs())
+    # x sc' + sh' = (x - mean') sc' + beta up to the roundings of mean' sc', of sh' and of the fma: the error of sc meets x - mean
+    sh = be - mean * sc
+    v = xd * sc + sh
+    t = (xd - mean).abs() * tsc + sc.abs() * tmean + tmean * tsc
+    t = t + U32 * ((mean * sc).abs() + sh.abs() + v.abs() + 3.0 * t)
+    if silu_:
+        v, t = mid_round(v, t, dtype)
+        v, t = _apply(_silu, _silu_d, 1.1, 0.5, v, t, 2.0 ** -21)
+    v, t = final_round(v, t, dtype)
+    return v.reshape(B, HW, C), t.reshape(B, HW, C)
+
+
+def softmax_rows_bound(x, scale, dtype):
+    """x [rows, cols] -> (reference, bound) of ss_softmax_rows (in place on x)"""
+    sc = float(np.float32(scale))
+    s, ts = op32(x.double() * sc, torch.zeros_like(x, dtype=torch.float64))
+    m = s.amax(1, keepdim=True)
+    e, te = exp32(*op32(s - m, ts))
+    tot, ttot = op32(e.sum(1, keepdim=True), te.sum(1, keepdim=True) + gamma(x.shape[1]) * e.sum(1, keepdim=True))
+    iv, it = recip32(tot, ttot)
+    v, t = product(e, te, iv.expand_as(e), it.expand_as(e))
+    return final_round(v, t, dtype)
+
+
+def silu_mul_ew_bound(gu, dtype):
+    """gu [rows, 2 I] = [gate | up] -> (reference, bound) of ss_silu_mul"""
+    I = gu.shape[1] // 2
+    g, u = gu[:, :I].double(), gu[:, I:].double()
+    v, t = silu(g, torch.zeros_like(g), dtype)
+    v, t = mid_round(v, t, dtype)
+    return final_round(v * u, t * u.abs(), dtype)
+
+
+def geglu_ew_bound(x, dtype):
+    """x [rows, 2 D] = [val | gate] -> (reference, bound) of ss_geglu"""
+    D = x.shape[1] // 2
+    a, g = x[:, :D].double(), x[:, D:].double()
+    v, t = gelu(g, torch.zeros_like(g), dtype)
+    v, t = mid_round(v, t, dtype)
+    return final_round(v * a, t * a.abs(), dtype)
+
+
+def unary_bound(x, op, dtype):
+    """op 0: silu, 1: gelu"""
+    xd = x.double()
+    v, t = (silu if op == 0 else gelu)(xd, torch.zeros_like(xd), dtype)
+    return final_round(v, t, dtype)
+
+
+def l2normalize_bound(x, dtype):
+    """x [B, L, C], normalised over dim 1"""
+    xd = x.double()
+    L = x.shape[1]
+    s = (xd * xd).sum(1, keepdim=True)
+    v, t = sqrt32(s, gamma(L) * s)
+    v, t = mid_round(v, t, dtype)
+    floor = float(np.float32(1e-12))
+    v = v.clamp_min(floor)
+    q, tq = op32(xd / v, xd.abs() * t / (v * (v - t).clamp_min(floor)))
+    return final_round(q, tq, dtype)
+
+
+def cross_entropy_rows_bound(logits, labels, dtype, ignore_index=-100):
+    """logits [rows, vocab] (the valid columns only), labels [rows] -> (loss reference, bound, valid flags) per row"""
+    x = logits.double()
+    rows, vocab = x.shape
+    valid = (labels != ignore_index) & (labels >= 0) & (labels < vocab)
+    lab = labels.clamp(0, vocab - 1)
+    m = x.amax(1, keepdim=True)
+    e, te = exp32(*op32(x - m, torch.zeros_like(x)))
+    s, ts = e.sum(1), te.sum(1) + gamma(vocab) * e.sum(1)
+    lg = torch.log(s)
+    tlg = ts / (s - ts).clamp_min(0.5) + 4.0 * U32 * lg.abs()
+    a, ta = op32(x.gather(1, lab[:, None])[:, 0] - m[:, 0], torch.zeros(rows, dtype=torch.float64))
+    v, t = op32(a - lg, ta + tlg)
+    v, t = final_round(v, t, dtype)
+    z = torch.zeros_like(v)
+    return torch.where(valid, -v, z), torch.where(valid, t, z), valid.double()
+
+
+def cosine_rows_bound(rec, tgt, dtype):
+    """rec / tgt [rows, dim] -> (reference, bound) [rows] of ss_cosine_rows"""
+    dim = rec.shape[1]
+
+    def unit(a):
+        ad = a.double()
+        s = (ad * ad).sum(1, keepdim=True)
+        n, tn = mid_round(*sqrt32(s, gamma(dim) * s), dtype)
+        q, tq = op32(ad / n, ad.abs() * tn / (n * (n - tn).clamp_min(1e-300)))
+        return mid_round(q, tq, dtype)
+    (x, tx), (y, ty) = unit(rec), unit(tgt)
+    p, tp = mid_round(*product(y, ty, x, tx), dtype)
+    s, ts = mid_round(p.sum(1), tp.sum(1) + gamma(dim) * (p.abs() + tp).sum(1), dtype)
+    v, t = op32(1.0 - s, ts)
+    return final_round(v, t, dtype)
+
+
+def mse_bound(a, b):
+    """-> (reference, bound) scalars of ss_mse: fl(fl(a - b)^2) summed in fp64, one division, one narrowing"""
+    d = (a.double() - b.double()).flatten()
+    n = d.numel()
+    terms = d * d
+    return terms.sum() / n, ((4.0 * U32 + n * 2.0 ** -52) * terms.sum() + n * 2.0 ** -149) / n
+
+
+def masked_mean_bound(vals, mask):
+    """-> (mean reference, bound, count) of ss_masked_mean (fp32 inputs)"""
+    v = vals.double().flatten()
+    m = torch.ones_like(v) if mask is None else mask.double().flatten()
+    cnt = float(m.sum())
+    if cnt <= 0:
+        return torch.zeros((), dtype=torch.float64), torch.zeros((), dtype=torch.float64), 0.0
+    terms = v * m
+    n = v.numel()
+    return terms.sum() / cnt, ((2.0 * U32 + n * 2.0 ** -52) * terms.abs().sum() + n * 2.0 ** -149) / cnt, cnt
+
+
+def euler_scale_dup_bound(x, sigma, dtype):
+    """-> (reference, bound) [2, n] of ss_euler_scale_dup"""
+    sg = torch.tensor(float(np.float32(sigma)), dtype=torch.float64)
+    v, t = op32(sg * sg, torch.zeros((), dtype=torch.float64))
+    v, t = op32(v + 1.0, t)
+    iv, it = recip32(*sqrt32(v, t))
+    xd = x.double().flatten()
+    v, t = final_round(*op32(xd * iv, xd.abs() * it), dtype)
+    return torch.stack([v, v]), torch.stack([t, t])
+
+
+# ---- exact mirrors (fp32 on the CPU, the kernel's rnd points) ---------------------------------------------------------------
+def r32(x, dtype):
+    """fp32 -> T -> fp32"""
+    return x.to(dtype).float()
+
+
+def add_bcast_exact(x, pos):
+    return (x.float() + pos.float()[None]).to(x.dtype)
+
+
+def rope_tables(hd, max_pos, dtype, base=10000.0):
+    """cat(freqs, freqs) cos / sin tables [max_pos, hd] cast to T (the LLaMA rotary embedding)"""
+    inv_freq = 1.0 / (base ** (torch.arange(0, hd, 2).float() / hd))
+    fr = torch.arange(max_pos, dtype=torch.float32)[:, None] * inv_freq[None]
+    emb = torch.cat([fr, fr], -1)
+    return emb.cos().to(dtype), emb.sin().to(dtype)
+
+
+def rope_exact(x, cos, sin, pos):
+    """x [M, H, hd] T, cos / sin [P, hd] T, pos [M] -> rnd(rnd(x c) + rnd(rot(x) s)) [M, H, hd] T"""
+    dtype = x.dtype
+    half = x.shape[-1] // 2
+    xf = x.float()
+    c, s = cos[pos].float()[:, None], sin[pos].float()[:, None]
+    rot = torch.cat([-xf[..., half:], xf[..., :half]], -1)
+    return (r32(xf * c, dtype) + r32(rot * s, dtype)).to(dtype)
+
+
+def euler_cfg_step_exact(x, eps, guidance, sigma, sigma_next, fused_f16=False):
+    """x [n] T, eps [2, n] T -> x after ss_euler_cfg_step.
+    fused_f16 (fp16 only): rnd_T(s v), an fp32 scalar s times a value v of T, written as an fp32 product followed by a conversion,
+    is compiled for gfx950 to one v_fma_mixlo_f16, which converts the EXACT product to fp16: one rounding where the source (and
+    torch's fp16 multiply) has two.  The two differ when the fp32 product lands on an fp16 midpoint the exact product is not on:
+    about 2^-11 of the elements for a 24-bit dsigma, none for a guidance of a few bits.  Both are roundings of the same product
+    and which one comes out is the compiler's choice, so the fp16 check admits either, element by element (found on the MI355X:
+    96 of 1,048,579 elements at sigma 0.0413 -> 0, exactly the elements this flag changes)."""
+    dtype = x.dtype
+    g = torch.tensor(guidance, dtype=torch.float32)
+    ds = torch.tensor(sigma_next, dtype=torch.float32) - torch.tensor(sigma, dtype=torch.float32)
+
+    def mul(s, v):
+        if fused_f16:           # numpy converts float64 -> float16 in one step (torch goes through fp32)
+            assert dtype == torch.float16
+            return torch.from_numpy((v.double().numpy() * float(s)).astype(np.float16)).float()
+        return r32(s * v, dtype)
+    eu, ec = eps[0].float(), eps[1].float()
+    e = r32(eu + mul(g, r32(ec - eu, dtype)), dtype)
+    return (x.float() + mul(ds, e)).to(dtype)
+
+
+def image_to_u8_exact(x, pixels, half_up=False):
+    """x [pixels, cpad] T -> uint8 [pixels, 3].  half_up: the mutant (floor(v + 0.5))"""
+    v = r32(x[:pixels, :3].float() * 0.5 + 0.5, x.dtype).clamp(0.0, 1.0) * 255.0
+    return (torch.floor(v + 0.5) if half_up else torch.round(v)).to(torch.uint8)
+
+
+def im2col_exact(img, P, kpad):
+    """img [B, 3, S, S] -> [B G G, kpad], column (c P + dy) P + dx, zero beyond 3 P P"""
+    B, _, S, _ = img.shape
+    G = S // P
+    t = img.view(B, 3, G, P, G, P).permute(0, 2, 4, 1, 3, 5).reshape(B * G * G, 3 * P * P)
+    out = torch.zeros(B * G * G, kpad, dtype=img.dtype)
+    out[:, :3 * P * P] = t
+    return out
+
+
+# ---- cases and inputs --------------------------------------------------------------------------------------------------------
+NORM_BLOCK_ROWS, NORM_BLOCK_PACKS = [1, 3], [1, 255, 256, 257, 2048]
+LN_WAVE_ROWS, LN_WAVE_PACKS = [256, 257, 259], [1, 63, 64, 65, 255, 256]
+LN_KNOB_ROWS, LN_KNOB_PACKS, LN_KNOBS = [8192, 8193, 8195, 8199], [1, 65], [1, 2, 4]
+NORM_EPS = 1e-5
+
+
+def norm_inputs(rows, cols, dtype, seed, zero_row=False):
+    """N(0.3, 2^2) rows; the last row of three or more (and the only row of one-row cases with an odd seed) is replaced:
+    rows >= 3 carry an offset row (mean 50, std 0.5: |mean| / std = 100) and a constant row, RMSNorm also an all-zero row."""
+    g = torch.Generator().manual_seed(11000 + seed)
+    x = torch.randn(rows, cols, generator=g) * 2.0 + 0.3
+    if rows >= 3:
+        x[1] = torch.randn(cols, generator=g) * 0.5 + 50.0
+        x[2] = 1.75
+        if zero_row:
+            x[0] = 0.0
+    elif seed % 2:
+        x[0] = torch.randn(cols, generator=g) * 0.5 + 50.0
+    w = torch.randn(cols, generator=g) * 0.1 + 1.0
+    b = torch.randn(cols, generator=g) * 0.1
+    return x.to(dtype), w.to(dtype), b.to(dtype)
+
+
+def gn_cases(dtype):
+    V = vec(dtype)
+    return [(2, 35, 64, 32), (1, 17, 320, 32), (1, 1, 128, 32), (2, 145, 256, 256), (1, 33, 66 * V, 264), (1, 16, 257 * V, 1)]
+
+
+def gn_inputs(B, HW, C, dtype, seed, offset=False):
+    """N(0.5, 2^2), or mean 8 / std 1 in every group (offset)"""
+    g = torch.Generator().manual_seed(12000 + seed)
+    x = torch.randn(B, HW, C, generator=g) + 8.0 if offset else torch.randn(B, HW, C, generator=g) * 2.0 + 0.5
+    return x.to(dtype), (torch.randn(C, generator=g) * 0.1 + 1.0).to(dtype), (torch.randn(C, generator=g) * 0.1).to(dtype)
+
+
+SOFTMAX_ROWS, SOFTMAX_PACKS, SOFTMAX_SCALES = [1, 3], [1, 255, 256, 257, 1000], [0.3, -0.3]
+
+
+def softmax_inputs(rows, cols, dtype, seed):
+    """N(0, 3^2); with three rows: row 1 has one entry 80 above the rest, row 2 is constant"""
+    g = torch.Generator().manual_seed(13000 + seed)
+    x = torch.randn(rows, cols, generator=g) * 3.0
+    if rows >= 3:
+        x[1] = x[1].clamp(-9.0, 9.0)
+        x[1, (7 * seed + cols // 2) % cols] = x[1].max() + 80.0
+        x[2] = -2.5
+    return x.to(dtype)
+
+
+def gated_shapes(dtype):
+    V = vec(dtype)
+    return [(1, V), (3, 33 * V), (1025, 1025 * V)]
+
+
+def gated_inputs(rows, inter, dtype, seed):
+    """[rows, 2 inter]: both halves span -20 .. 20 and hold exact zeros (silu_mul gates on the left, geglu gates on the right)"""
+    g = torch.Generator().manual_seed(14000 + seed)
+    x = (torch.rand(rows, 2 * inter, generator=g) * 40.0 - 20.0)
+    x[:, ::7] *= 0.05
+    x[0, 0], x[0, inter], x[-1, -1], x[-1, inter - 1] = 0.0, 0.0, -20.0, 20.0
+    return x.to(dtype)
+
+
+def add_bcast_shapes(dtype):
+    V = vec(dtype)
+    return [(1, 1, V), (3, 5, 7 * V), (5, 1031, 204 * V)]
+
+
+EW_N = [1, 257, 1048579]
+EULER_SIGMAS = [(11.476846458, 9.543582567), (0.041314412, 0.0)]      # both ends of the 30-step table (tests/test_sdxl_oracle.py)
+EULER_GUIDANCE = [0.0, 1.0, 7.5]
+U8_CASES = [(px, cpad) for px in (1, 85, 349527) for cpad in (4, 8)]
+
+
+def u8_inputs(pixels, cpad, dtype, seed):
+    """[pixels, cpad]: N(0, 0.8^2), then (as far as they fit) every level 2 (k / 255) - 1, the 127.5 tie 0, +-1, +-1.5 and the
+    neighbours of each tie (k + 0.5) / 127.5 - 1 in T"""
+    g = torch.Generator().manual_seed(15000 + seed)
+    x = torch.randn(pixels, cpad, generator=g) * 0.8
+    k = torch.arange(256, dtype=torch.float64)
+    special = torch.cat([2.0 * k / 255.0 - 1.0, torch.tensor([0.0, 1.0, -1.0, 1.5, -1.5], dtype=torch.float64), (k + 0.5) / 127.5 - 1.0]).float()
+    flat = x[:, :3].reshape(-1).clone()
+    m = min(flat.numel(), special.numel())
+    flat[:m] = special[:m] if pixels > 1 else torch.tensor([0.0, 1.5, -1.0])[:m]
+    x[:, :3] = flat.view(pixels, 3)
+    return x.to(dtype)
+
+
+def gather_cases(dtype):
+    V = vec(dtype)
+    return [(5, 9, V), (37, 50, 33 * V), (4100, 300, 257 * V)]       # n, table rows, cols
+
+
+TRANSPOSE_SHAPES = [(1, 1), (31, 33), (32, 32), (33, 31), (45, 70), (65, 129), (1, 1000), (1000, 1)]
+
+
+def concat_cases(dtype):
+    V = vec(dtype)
+    return [(1, V, V), (11, 8 * V, 3 * V), (7, V, 40 * V), (4099, 200 * V, 56 * V)]      # the last: 1,049,344 packs
+
+
+LAYOUT_CASES = [(1, 4, 1, 8), (2, 4, 30, 8), (2, 3, 35, 4), (1, 8, 9, 8), (1, 4, 300000, 8)]
+IM2COL_CASES = [(1, 14, 14, 588), (2, 56, 14, 640), (1, 28, 7, 152)]
+IM2COL_LARGE = (6, 224, 14, 688)          # 6 * 256 * 688 = 1,056,768 elements: the grid-stride loop
+ROPE_HD, ROPE_M, ROPE_MAXPOS = [2, 64, 104, 128, 256], [1, 6], 512
+L2_CASES = [(1, 1, 1), (2, 16, 256), (3, 7, 257)]
+CE_VOCABS, CE_PAD = [1, 255, 256, 257, 32066], 24
+COSINE_DIMS, COSINE_ROWS = [1, 63, 64, 65, 4096], [1, 4, 5]
+MEAN_N = [1, 255, 65536, 65537, 200001]
+
+
+def randn_t(shape, dtype, seed, std=1.0, mean=0.0):
+    g = torch.Generator().manual_seed(16000 + seed)
+    return (torch.randn(*shape, generator=g) * std + mean).to(dtype)

@@ -1,6 +1,7 @@
 """The checker (tests/kernel_check.py) is tested before it judges a kernel: a correct kernel SIMULATED on the CPU (fp32 math,
 chunked and reversed summation, the kernels' rounding points; attention: a tile-64 online softmax with P rounded to T) must
-produce zero violations on every case tests/test_kernel_edges_gpu.py runs, and every seeded mutant must be flagged."""
+produce zero violations on every case tests/test_kernel_edges_gpu.py and tests/test_pointwise_edges_gpu.py run (the grid-stride
+shapes of the latter reduced to a small shape of the same family), and every seeded mutant must be flagged."""
 import math
 
 import pytest
@@ -387,3 +388,407 @@ def test_frobenius_norm_misses_what_the_bound_flags(mutant_case):
     z[100, 100:108] = 0
     rel = float((z.double() - ref).norm() / ref.norm())
     assert rel < 4e-3 and count(z, ref, tol) >= 7
+
+
+# ==== norms, softmax, point-wise kernels, loss heads: simulated kernels ========================================================
+def fsum(t, chunk=64):
+    """fp32 sum over the last dim in chunks of `chunk`, last chunk first"""
+    acc = torch.zeros(t.shape[:-1], dtype=torch.float32)
+    for k0 in reversed(range(0, t.shape[-1], chunk)):
+        acc = acc + t[..., k0:k0 + chunk].sum(-1)
+    return acc
+
+
+def f32(v):
+    return torch.tensor(v, dtype=torch.float32)
+
+
+def bump(y, idx, n=4):
+    """y with element idx moved n ulps of T away from zero"""
+    z = y.clone()
+    v = z[idx].reshape(1)
+    for _ in range(n):
+        v = torch.nextafter(v, torch.full_like(v, float("inf")) * torch.sign(v.float()).to(v.dtype))
+    z[idx] = v[0]
+    return z
+
+
+def sim_rmsnorm(x, w, eps, dtype, drop_last=False, trunc=False):
+    x32, V = x.float(), KC.vec(dtype)
+    sq = x32 * x32
+    ss = fsum(sq[:, :-V] if drop_last else sq)
+    rstd = 1.0 / torch.sqrt(ss / f32(x.shape[1]) + f32(eps))
+    return r(w.float() * r(x32 * rstd[:, None], dtype), dtype, trunc).to(dtype)
+
+
+def sim_layernorm(x, w, b, eps, dtype, drop_last=False, unbiased=False, onepass=False, trunc=False):
+    x32, V = x.float(), KC.vec(dtype)
+    cols = x.shape[1]
+    xs = x32[:, :-V] if drop_last else x32
+    mean = (fsum(xs) / f32(cols))[:, None]
+    if onepass:
+        var = fsum(xs * xs) / f32(cols) - mean[:, 0] * mean[:, 0]
+    else:
+        d = xs - mean
+        var = fsum(d * d) / f32(cols - 1 if unbiased else cols)
+    rstd = (1.0 / torch.sqrt(var + f32(eps)))[:, None]
+    return r((x32 - mean) * rstd * w.float() + b.float(), dtype, trunc).to(dtype)
+
+
+def prev_row_last_pack(y, dtype):
+    z, V = y.clone(), KC.vec(dtype)
+    z[1:, -V:] = y[:-1, -V:]
+    return z
+
+
+def sim_groupnorm(x, gw, gb, G, eps, silu_, dtype, group_of_pack=False, fp32_var=False):
+    """the three passes: per-thread fp32 chains over a block's rows (stride rows-in-flight), the fold over the row lanes, fp64
+    over channels and blocks, the fp32 apply.  group_of_pack: mutant, every channel of a pack takes the group of the pack's first
+    channel.  fp32_var: mutant, E[x^2] - mean^2 in fp32."""
+    B, HW, C = x.shape
+    V, cg = KC.vec(dtype), C // G
+    rpb = KC.groupnorm_rows_per_block(B, HW, C, dtype)
+    x32 = x.float()
+    S = torch.zeros(B, C, 2, dtype=torch.float64)
+    for r0 in range(0, HW, rpb):
+        r1 = min(HW, r0 + rpb)
+        chs = torch.zeros(B, C, 2, dtype=torch.float32)
+        for pc in range(0, C // V, 256):
+            cw = min(256, C // V - pc)
+            rip = 256 // cw
+            c0, c1 = pc * V, (pc + cw) * V
+            tot1 = tot2 = None
+            for ry in range(rip):
+                s1 = torch.zeros(B, c1 - c0)
+                s2 = torch.zeros(B, c1 - c0)
+                for rr in range(r0 + ry, r1, rip):
+                    f = x32[:, rr, c0:c1]
+                    s1 = s1 + f
+                    s2 = s2 + f * f
+                tot1 = s1 if tot1 is None else tot1 + s1
+                tot2 = s2 if tot2 is None else tot2 + s2
+            chs[:, c0:c1, 0], chs[:, c0:c1, 1] = tot1, tot2
+        S += chs.double()
+    Sg = S.view(B, G, cg, 2).sum(2)                                  # [B, G, 2] fp64
+    inv_n = (f32(1.0) / (f32(HW) * f32(cg))).double()
+    md = Sg[..., 0] * inv_n
+    mean = md.float()
+    if fp32_var:
+        var = ((Sg[..., 1] * inv_n).float() - mean * mean).clamp_min(0.0)
+    else:
+        var = (Sg[..., 1] * inv_n - md * md).clamp_min(0.0).float()
+    rstd = 1.0 / torch.sqrt(var + f32(eps))
+    ch = torch.arange(C)
+    gi = ((ch // V) * V // cg) if group_of_pack else ch // cg
+    sc = rstd[:, gi] * gw.float()[None]
+    sh = gb.float()[None] - mean[:, gi] * sc
+    v = (x32.double() * sc.double()[:, None] + sh.double()[:, None]).float()          # fma: one rounding
+    if silu_:
+        v = r(v, dtype)
+        v = v * (1.0 / (1.0 + torch.exp2(-1.4426950408889634 * v)))
+    return v.to(dtype)
+
+
+def sim_softmax(x, scale, dtype, skip_wave=None):
+    V = KC.vec(dtype)
+    s = x.float() * f32(scale)
+    m = s.amax(1, keepdim=True)
+    e = torch.exp(s - m)
+    es = e
+    if skip_wave is not None:            # mutant: the partial of one wave (threads 64 w .. 64 w + 63 own packs p with p % 256 in that range) is lost
+        p = torch.arange(x.shape[1]) // V % 256
+        es = e[:, (p // 64) != skip_wave]
+    inv = 1.0 / fsum(es)
+    return (e * inv[:, None]).to(dtype)
+
+
+def silu32(g):
+    return g / (1.0 + torch.exp(-g))
+
+
+def sim_silu_mul(gu, dtype):
+    I = gu.shape[1] // 2
+    return (r(silu32(gu[:, :I].float()), dtype) * gu[:, I:].float()).to(dtype)
+
+
+def sim_geglu(x, dtype):
+    D = x.shape[1] // 2
+    return (x[:, :D].float() * r(gelu32(x[:, D:].float()), dtype)).to(dtype)
+
+
+def sim_l2norm(x, dtype):
+    x32 = x.float()
+    s = torch.zeros(x.shape[0], x.shape[2])
+    for l in reversed(range(x.shape[1])):
+        s = s + x32[:, l] * x32[:, l]
+    nrm = torch.maximum(r(torch.sqrt(s), dtype), f32(1e-12))
+    return (x32 / nrm[:, None]).to(dtype)
+
+
+def sim_cross_entropy(logits, labels, vocab, dtype, ignore_index=-100):
+    """logits [rows, ld]: only the first `vocab` columns are read"""
+    x = logits[:, :vocab].float()
+    m = x.amax(1)
+    s = fsum(torch.exp(x - m[:, None]), chunk=256)
+    lab = labels.clamp(0, vocab - 1)
+    lsm = r(x.gather(1, lab[:, None])[:, 0] - m - torch.log(s), dtype)
+    ok = labels != ignore_index
+    return torch.where(ok, -lsm, torch.zeros_like(lsm)), ok.float()
+
+
+def sim_cosine(rec, tgt, dtype):
+    a, b = rec.float(), tgt.float()
+    na, nb = r(torch.sqrt(fsum(a * a)), dtype), r(torch.sqrt(fsum(b * b)), dtype)
+    p = r(r(b / nb[:, None], dtype) * r(a / na[:, None], dtype), dtype)
+    return r(1.0 - r(fsum(p), dtype), dtype)
+
+
+def sim_mse(a, b):
+    d = a.float() - b.float()
+    return ((d * d).double().sum() / a.numel()).float()
+
+
+def sim_masked_mean(vals, mask):
+    m = torch.ones_like(vals) if mask is None else mask
+    c = m.double().sum()
+    return ((vals * m).double().sum() / c).float() if c > 0 else f32(0.0)
+
+
+def sim_euler_scale_dup(x, sigma, dtype):
+    sg = f32(sigma)
+    inv = 1.0 / torch.sqrt(sg * sg + 1.0)
+    v = (x.float().flatten() * inv).to(dtype)
+    return torch.stack([v, v])
+
+
+# ---- zero violations on every listed case (the grid-stride shapes reduced to a small shape of the same family) -----------------
+dt_ids = lambda d: KC.NAME[d]
+
+
+@pytest.mark.parametrize("dtype", ALL, ids=dt_ids)
+def test_simulated_norms_stay_inside_the_bound(dtype):
+    V = KC.vec(dtype)
+    worst_r = worst_l = 0.0
+    cases = [(rows, p) for rows in KC.NORM_BLOCK_ROWS for p in KC.NORM_BLOCK_PACKS] + [(3, 63), (3, 65), (7, 64)]
+    for i, (rows, packs) in enumerate(cases):
+        x, w, b = KC.norm_inputs(rows, packs * V, dtype, i, zero_row=True)
+        worst_r = max(worst_r, KC.check(sim_rmsnorm(x, w, KC.NORM_EPS, dtype), *KC.rmsnorm_bound(x, w, KC.NORM_EPS, dtype), "sim rmsnorm %s" % ((rows, packs),)))
+        x, w, b = KC.norm_inputs(rows, packs * V, dtype, i)
+        worst_l = max(worst_l, KC.check(sim_layernorm(x, w, b, KC.NORM_EPS, dtype), *KC.layernorm_bound(x, w, b, KC.NORM_EPS, dtype), "sim layernorm %s" % ((rows, packs),)))
+    print("simulated rmsnorm / layernorm %s: worst error / bound %.3f / %.3f" % (KC.NAME[dtype], worst_r, worst_l))
+    assert worst_r > 0.05 and worst_l > 0.05
+
+
+@pytest.mark.parametrize("dtype", ALL, ids=dt_ids)
+@pytest.mark.parametrize("silu_", [False, True], ids=["plain", "silu"])
+def test_simulated_groupnorm_stays_inside_the_bound(silu_, dtype):
+    worst = 0.0
+    for i, (B, HW, C, G) in enumerate(KC.gn_cases(dtype)):
+        for offset in ([False, True] if i == 1 else [False]):
+            x, gw, gb = KC.gn_inputs(B, HW, C, dtype, i, offset)
+            y = sim_groupnorm(x, gw, gb, G, KC.NORM_EPS, silu_, dtype)
+            worst = max(worst, KC.check(y, *KC.groupnorm_bound(x, gw, gb, G, KC.NORM_EPS, silu_, dtype), "sim groupnorm %s offset %s" % ((B, HW, C, G), offset)))
+    assert worst > 0.05
+
+
+@pytest.mark.parametrize("dtype", ALL, ids=dt_ids)
+def test_simulated_softmax_stays_inside_the_bound(dtype):
+    V, worst = KC.vec(dtype), 0.0
+    for i, (rows, packs) in enumerate((rows, p) for rows in KC.SOFTMAX_ROWS for p in KC.SOFTMAX_PACKS):
+        for scale in KC.SOFTMAX_SCALES:
+            x = KC.softmax_inputs(rows, packs * V, dtype, i)
+            worst = max(worst, KC.check(sim_softmax(x, scale, dtype), *KC.softmax_rows_bound(x, scale, dtype), "sim softmax %s %s" % ((rows, packs), scale)))
+    assert worst > 0.05
+
+
+@pytest.mark.parametrize("dtype", ALL, ids=dt_ids)
+def test_simulated_pointwise_stay_inside_the_bound(dtype):
+    V = KC.vec(dtype)
+    for i, (rows, inter) in enumerate(KC.gated_shapes(dtype)[:2] + [(5, 65 * V)]):
+        x = KC.gated_inputs(rows, inter, dtype, i)
+        KC.check(sim_silu_mul(x, dtype), *KC.silu_mul_ew_bound(x, dtype), "sim silu_mul")
+        KC.check(sim_geglu(x, dtype), *KC.geglu_ew_bound(x, dtype), "sim geglu")
+    for i, n in enumerate(KC.EW_N[:2] + [4099]):
+        x = KC.gated_inputs(1, n, dtype, 10 + i)[0, :n]
+        KC.check(silu32(x.float()).to(dtype), *KC.unary_bound(x, 0, dtype), "sim unary silu")
+        KC.check(gelu32(x.float()).to(dtype), *KC.unary_bound(x, 1, dtype), "sim unary gelu")
+        lat = KC.randn_t((n,), dtype, 20 + i)
+        for sg, _ in KC.EULER_SIGMAS:
+            KC.check(sim_euler_scale_dup(lat, sg, dtype), *KC.euler_scale_dup_bound(lat, sg, dtype), "sim euler_scale_dup")
+    for i, (B, L, C) in enumerate(KC.L2_CASES):
+        x = KC.randn_t((B, L, C), dtype, 30 + i)
+        if C > 1:
+            x[:, :, 1] = 0
+        KC.check(sim_l2norm(x, dtype), *KC.l2normalize_bound(x, dtype), "sim l2normalize")
+
+
+def ce_case(vocab, dtype, seed):
+    rows = 5
+    x = KC.randn_t((rows, vocab + KC.CE_PAD), dtype, 40 + seed, std=3.0)
+    KC.poison_(x[:, vocab:])
+    labels = torch.tensor([0, vocab - 1, -100, (vocab * 3) // 7, int(x[4, :vocab].float().argmax())])
+    return x, labels
+
+
+@pytest.mark.parametrize("dtype", ALL, ids=dt_ids)
+def test_simulated_losses_stay_inside_the_bound(dtype):
+    for i, vocab in enumerate(KC.CE_VOCABS):
+        x, labels = ce_case(vocab, dtype, i)
+        loss, valid = sim_cross_entropy(x, labels, vocab, dtype)
+        ref, tol, vref = KC.cross_entropy_rows_bound(x[:, :vocab], labels, dtype)
+        KC.check(loss, ref, tol, "sim cross-entropy vocab %d" % vocab)
+        assert torch.equal(valid.double(), vref)
+        # mutant: one column of the ld pad read
+        assert count(sim_cross_entropy(x, labels, vocab + 1, dtype)[0], ref, tol) >= 4
+    for i, (dim, rows) in enumerate((d, n) for d in KC.COSINE_DIMS for n in KC.COSINE_ROWS):
+        a, b = KC.randn_t((rows, dim), dtype, 50 + i), KC.randn_t((rows, dim), dtype, 80 + i)
+        KC.check(sim_cosine(a, b, dtype), *KC.cosine_rows_bound(a, b, dtype), "sim cosine %s" % ((rows, dim),))
+    for i, n in enumerate(KC.MEAN_N):
+        a, b = KC.randn_t((n,), dtype, 110 + i), KC.randn_t((n,), dtype, 120 + i)
+        KC.check(sim_mse(a, b).reshape(1), *(t.reshape(1) for t in KC.mse_bound(a, b)), "sim mse %d" % n)
+        if dtype == torch.float32:
+            for mask in (None, (torch.arange(n) % 3 != 0).float(), torch.zeros(n)):
+                ref, tol, cnt = KC.masked_mean_bound(a, mask)
+                KC.check(sim_masked_mean(a, mask).reshape(1), ref.reshape(1), tol.reshape(1), "sim masked_mean %d" % n)
+                assert cnt == (n if mask is None else float(mask.sum()))
+
+
+# ---- seeded mutants -------------------------------------------------------------------------------------------------------------
+def test_mutants_norm_statistics():
+    eps = KC.NORM_EPS
+    dtype = torch.float32
+    V = KC.vec(dtype)
+    # the last pack of a row left out of the statistic (3 x 255 packs, fp32; 16-bit rounding hides 4 of 1020 terms)
+    x, w, b = KC.norm_inputs(3, 255 * V, dtype, 1, zero_row=True)
+    ref, tol = KC.rmsnorm_bound(x, w, eps, dtype)
+    assert count(sim_rmsnorm(x, w, eps, dtype), ref, tol) == 0
+    assert count(sim_rmsnorm(x, w, eps, dtype, drop_last=True), ref, tol) > 0.3 * x.shape[1]
+    x, w, b = KC.norm_inputs(3, 255 * V, dtype, 1)
+    ref, tol = KC.layernorm_bound(x, w, b, eps, dtype)
+    good = sim_layernorm(x, w, b, eps, dtype)
+    assert count(good, ref, tol) == 0
+    assert count(sim_layernorm(x, w, b, eps, dtype, drop_last=True), ref, tol) > 0.3 * x.shape[1]
+    # fp32 E[x^2] - mean^2 on the offset row (|mean| / std = 100): the one-pass variance is off by u32 mean^2 / var = 6e-4
+    # whatever the width, the bound's gamma_cols mean|x| grows with it: one pack per row is where the mutant stands out
+    hits = 0
+    for seed in (1, 2, 3, 4):
+        x, w, b = KC.norm_inputs(3, V, dtype, seed)
+        ref, tol = KC.layernorm_bound(x, w, b, eps, dtype)
+        assert count(sim_layernorm(x, w, b, eps, dtype), ref, tol) == 0
+        n, _, coords = KC.violations(sim_layernorm(x, w, b, eps, dtype, onepass=True), ref, tol)
+        assert all(c[0] == 1 for c, _ in coords)
+        hits += n
+    assert hits >= 4
+    # unbiased variance on a <= 256-column case, every dtype
+    for dt_ in ALL:
+        x, w, b = KC.norm_inputs(3, 256 if dt_ != torch.float32 else 252, dt_, 2)
+        ref, tol = KC.layernorm_bound(x, w, b, eps, dt_)
+        assert count(sim_layernorm(x, w, b, eps, dt_), ref, tol) == 0
+        assert count(sim_layernorm(x, w, b, eps, dt_, unbiased=True), ref, tol) > (0.05 if dt_ == torch.bfloat16 else 0.2) * x.shape[1]
+        # the last pack stored from the previous row
+        n, _, coords = KC.violations(prev_row_last_pack(sim_layernorm(x, w, b, eps, dt_), dt_), ref, tol)
+        assert n >= KC.vec(dt_) and all(c[1] >= x.shape[1] - KC.vec(dt_) for c, _ in coords)
+        # a truncating store (16-bit) and a 4-ulp offset on one element
+        x, w, b = KC.norm_inputs(3, 256 * KC.vec(dt_), dt_, 3, zero_row=True)
+        ref, tol = KC.rmsnorm_bound(x, w, eps, dt_)
+        y = sim_rmsnorm(x, w, eps, dt_)
+        assert count(y, ref, tol) == 0
+        if dt_ != torch.float32:        # one final round is all the LayerNorm bound grants (RMSNorm's mid round hides a truncation)
+            xl, wl, bl = KC.norm_inputs(3, 256, dt_, 2)
+            assert count(sim_layernorm(xl, wl, bl, eps, dt_, trunc=True), *KC.layernorm_bound(xl, wl, bl, eps, dt_)) > 0.1 * xl.shape[1]
+        if dt_ != torch.float32:        # (4 fp32 ulps vanish under gamma_1024 of the statistic; test_mutants_softmax_and_pointwise bumps an fp32 element)
+            n, _, coords = KC.violations(bump(y, (1, 77)), ref, tol)
+            assert n == 1 and coords[0][0] == (1, 77)
+
+
+def test_mutants_groupnorm():
+    for dtype in ALL:
+        B, HW, C, G = KC.gn_cases(dtype)[1]                 # cg = 10: group edges inside a pack
+        x, gw, gb = KC.gn_inputs(B, HW, C, dtype, 1)
+        ref, tol = KC.groupnorm_bound(x, gw, gb, G, KC.NORM_EPS, False, dtype)
+        assert count(sim_groupnorm(x, gw, gb, G, KC.NORM_EPS, False, dtype), ref, tol) == 0
+        assert count(sim_groupnorm(x, gw, gb, G, KC.NORM_EPS, False, dtype, group_of_pack=True), ref, tol) > 0.05 * ref.numel()
+    # E[x^2] - mean^2 narrowed to fp32 before the subtraction errs by 2 u32 E[x^2]; the GroupNorm bound grants the fp32 chains
+    # (gamma_k + 2 u32) E[x^2] on the same quantity, so THIS bound cannot tell the two apart (the two-pass LayerNorm bound does:
+    # test_mutants_norm_statistics).  What it must do is stay valid on the offset data:
+    dtype = torch.float32
+    x, gw, gb = KC.gn_inputs(B, HW, C, dtype, 1, offset=True)
+    ref, tol = KC.groupnorm_bound(x, gw, gb, G, KC.NORM_EPS, False, dtype)
+    assert count(sim_groupnorm(x, gw, gb, G, KC.NORM_EPS, False, dtype), ref, tol) == 0
+
+
+def test_mutants_softmax_and_pointwise():
+    for dtype in ALL:
+        V = KC.vec(dtype)
+        x = KC.softmax_inputs(3, 257 * V, dtype, 7)
+        ref, tol = KC.softmax_rows_bound(x, 0.3, dtype)
+        y = sim_softmax(x, 0.3, dtype)
+        assert count(y, ref, tol) == 0
+        # one wave's partial missing from the normaliser: every entry of the random and the constant row grows by a quarter
+        n, _, coords = KC.violations(sim_softmax(x, 0.3, dtype, skip_wave=1), ref, tol)
+        assert n > 0.5 * x.shape[1]
+        x = KC.gated_inputs(3, 33 * V, dtype, 1)
+        ref, tol = KC.silu_mul_ew_bound(x, dtype)
+        y = sim_silu_mul(x, dtype)
+        assert count(y, ref, tol) == 0
+        I = x.shape[1] // 2          # a positive gate: silu of a large negative one is a cancellation, and the evaluation term says so
+        idx = (2, int(((x[2, :I].float() > 1) & (x[2, I:].float().abs() > 1)).nonzero()[0]))
+        n, _, coords = KC.violations(bump(y, idx), ref, tol)
+        assert n == 1 and coords[0][0] == idx
+        if dtype != torch.float32:
+            # a truncating store, where one final round is all the bound grants (the mid round of silu_mul hides it)
+            ref, tol = KC.unary_bound(x, 0, dtype)
+            assert count(silu32(x.float()).to(dtype), ref, tol) == 0
+            assert count(trunc_to(silu32(x.float()), dtype).to(dtype), ref, tol) > 0.1 * ref.numel()
+
+
+def test_mutants_exact_expectations():
+    # a transpose that drops the ragged tile column
+    x = KC.randn_t((45, 70), torch.bfloat16, 1)
+    good = x.t().contiguous()
+    z = torch.zeros_like(good)
+    z[:64] = good[:64]
+    assert not torch.equal(z, good) and torch.equal(x.t().contiguous(), good)
+    # image_to_u8 rounding half up: 255 v is exact for a 16-bit v and then 127.5 is its only tie (-> 128 either way); an fp32 v
+    # times 255 rounds onto other ties, and the listed inputs (the neighbours of every tie) reach them
+    for dtype in ALL:
+        x = KC.u8_inputs(349527, 8, dtype, 0)
+        even, up = KC.image_to_u8_exact(x, 349527), KC.image_to_u8_exact(x, 349527, half_up=True)
+        assert even[0, 0] == 0 and int(even.max()) == 255
+        assert (dtype == torch.float32) == (not torch.equal(even, up))
+    # the mirrors round where the kernel rounds: an fp64 evaluation rounded once differs on random data
+    x, e = KC.randn_t((4099,), torch.bfloat16, 2), KC.randn_t((2, 4099), torch.bfloat16, 3)
+    exact = KC.euler_cfg_step_exact(x, e, 7.5, *KC.EULER_SIGMAS[0])
+    once = (x.double() + (e[0].double() + 7.5 * (e[1].double() - e[0].double())) * (KC.EULER_SIGMAS[0][1] - KC.EULER_SIGMAS[0][0])).to(torch.bfloat16)
+    assert not torch.equal(exact, once)
+
+
+def test_euler_fp16_fused_product_is_a_second_admissible_mirror():
+    """the two fp16 mirrors of euler_cfg_step differ on a few elements in ten thousand at a 24-bit dsigma, check_exact admits either
+    per element and still flags a third value"""
+    n = 1048579
+    x, e = KC.randn_t((n,), torch.float16, 2, std=3.0), KC.randn_t((2, n), torch.float16, 3)
+    sg, sn = KC.EULER_SIGMAS[1]
+    a, b = KC.euler_cfg_step_exact(x, e, 7.5, sg, sn), KC.euler_cfg_step_exact(x, e, 7.5, sg, sn, fused_f16=True)
+    d = (a != b).nonzero().flatten()
+    assert 0 < d.numel() < n // 2000
+    mixed = a.clone()
+    mixed[d[::2]] = b[d[::2]]
+    KC.check_exact(mixed, a, "either", alt=b)
+    with pytest.raises(AssertionError):
+        KC.check_exact(mixed, a, "one mirror only")
+    with pytest.raises(AssertionError):
+        KC.check_exact(bump(mixed, int(d[0]), 1), a, "a third value", alt=b)
+    with pytest.raises(AssertionError):
+        KC.check_exact(bump(mixed, 5, 1), a, "elsewhere", alt=b)
+
+
+def test_guarded_out_guards_only_mode():
+    g = KC.GuardedOut(6, 16, torch.float16)
+    g.out[2] = 1.0
+    assert any("never written" in m for m in g.problems()[0])
+    pay = g.check("rows in part", payload=False)
+    assert g.untouched(pay)[[0, 1, 3, 4, 5]].all() and not g.untouched(pay)[2].any()
+    g.flat[g.start - 1] = 0
+    with pytest.raises(AssertionError):
+        g.check("before", payload=False)
