@@ -639,6 +639,24 @@ int ss_llama_get_lengths(ss_llama* h, int64_t* kv_len, int64_t* pos);
  * old cache gathered at keep_idx[0..n_keep) (device int32, ascending), kv_len = n_keep. */
 int ss_llama_kv_gather(ss_llama* h, const int32_t* keep_idx_dev, int64_t n_keep, void* stream);
 
+/* Slot fork: after it each of the n_dst slots of host_dst (host array, at most n_seq - 1 = 7 entries) is in the state slot
+ * src is in, so that ss_llama_generate / ss_llama_generate_batch / ss_llama_prefill* on a destination behave as on src —
+ * n sampled continuations of one prompt cost one prefill, not n.
+ * Copied: K and V rows [0, kv_len[src]) of every layer and head (rows at and above kv_len of a destination are not touched),
+ * the last-token logits row, the state words kv_len / pos / last_id, the token history with its length, prompt_len and the
+ * rule-1 bitmap (rules on or off: they are small) and, with the fp8 KV shadow on, its codes and scales below
+ * min(watermark[src], kv_len[src]); the destinations' watermarks are set to that.  The host views of kv_len, pos and the
+ * history length follow.
+ * Not copied, because they belong to the slot: the sampling parameters and the draw counter (slots given one seed diverge
+ * because the slot is part of the Philox counter), the rule parameters and on/off flags, the log-probability descriptor,
+ * attention capture, the generated-id and hidden-row rings, the forced-token buffer.
+ * One kernel per plane kind, over (K|V plane, layer, head, row chunk): each 16-byte packet of the source is loaded once and
+ * stored to every destination (the list travels by value); one more small launch moves the per-slot pieces.  Asynchronous on
+ * `stream`: no host synchronisation, no allocation.  kv_len[src] == 0 is legal (the state alone is copied).
+ * SS_EINVAL before anything is launched or any host view changes: h or host_dst NULL, src outside [0, n_seq), n_dst < 1, a
+ * destination out of range, equal to src, or listed twice. */
+int ss_llama_fork(ss_llama* h, int32_t src, const int32_t* host_dst, int32_t n_dst, void* stream);
+
 /* LlamaModel.forward on M new rows against the cached prefix (prefill when the cache is
  * empty, bottom-right-causal continuation otherwise) — modeling_llama_xformer.py:532-666.
  * embeds [M, hidden]; pos_ids device int32[M] or NULL (pos, pos+1, …).  Writes the

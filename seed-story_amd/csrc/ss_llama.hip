@@ -16,6 +16,8 @@
 //  * option (ss_llama_set_kv8, off by default): the attention of the decode token reads an fp8 (e4m3) SHADOW of the slab (caller-owned
 //    code + scale planes, ss_attn_kv8.hip) and appends to both; the slab stays the truth for everything else.  A host-side
 //    watermark per slot says how many shadow rows are valid; the decode entry points quantise the rest in one launch up front.
+//  * slot fork (ss_llama_fork): one slot's cache rows, last logits, lengths and history copied to up to 7 others on the device,
+//    each packet read once and written to all of them — n sampled continuations of one prompt cost one prefill.
 #include <stddef.h>
 #include <string.h>
 
@@ -343,6 +345,86 @@ __global__ __launch_bounds__(256) void kv_gather_kernel(const T* __restrict__ sr
         const int r = (int)(i / ppr), p = (int)(i % ppr);
         const int srow = keep ? keep[r] : r;
         st16(dst + ((int64_t)h * dst_cap + r) * hd + p * V, ld16(src + ((int64_t)h * cap + srow) * hd + p * V));
+    }
+}
+
+// ---- slot fork (ss_llama_fork) -------------------------------------------------------------------
+// The destination list travels by value: at most n_seq - 1 = 7 slots.
+constexpr int kForkMaxDst = 7;
+constexpr int kForkPackets = 4;         // packets per thread: all loaded before the first store
+struct ForkDst {
+    int32_t n;
+    int32_t slot[kForkMaxDst];
+};
+
+// One plane kind of every slot, [n_seq][units][unit_stride] packets P, twice (K | V: blockIdx.z picks the slab).  Unit
+// blockIdx.y (layer, head) of slot `src`, packets [0, span): each is loaded ONCE and stored to every destination — read once,
+// write n.  The valid rows of a (layer, head) are one contiguous run, so lanes walk consecutive packets: 16 B per lane, 1 KiB per
+// wave and instruction for P = uint4.  256 x kForkPackets packets per block; the loads are independent and issued together.
+template <typename P>
+__global__ __launch_bounds__(256) void fork_planes_kernel(P* plane0, P* plane1, int64_t slot_stride, int64_t unit_stride,
+                                                          int64_t span, int src, ForkDst d) {
+    P* base = blockIdx.z ? plane1 : plane0;
+    const int64_t unit = (int64_t)blockIdx.y * unit_stride;
+    const P* __restrict__ s = base + (int64_t)src * slot_stride + unit;
+    const int64_t i0 = (int64_t)blockIdx.x * (256 * kForkPackets) + threadIdx.x;
+    P v[kForkPackets];
+#pragma unroll
+    for (int u = 0; u < kForkPackets; ++u) {
+        const int64_t i = i0 + u * 256;
+        if (i < span) v[u] = s[i];
+    }
+#pragma unroll
+    for (int j = 0; j < kForkMaxDst; ++j) {
+        if (j >= d.n) break;
+        P* o = base + (int64_t)d.slot[j] * slot_stride + unit;
+#pragma unroll
+        for (int u = 0; u < kForkPackets; ++u) {
+            const int64_t i = i0 + u * 256;
+            if (i < span) o[i] = v[u];
+        }
+    }
+}
+
+// The small per-slot pieces of a fork, one launch: the last-token logits row, the history (its device-side length), the rule-1
+// bitmap, and the words a later call reads (kv_len, pos, last id; hist_len, prompt_len, n_app).  Each element is read once and
+// stored to every destination.  What belongs to the slot (rule parameters, `enabled`, the other state words) stays.
+template <typename T>
+__global__ __launch_bounds__(256) void fork_state_kernel(T* logits, int vocab, int32_t* st, RulesState* rules, int32_t* hist,
+                                                         int64_t hist_cap, uint32_t* bitmap, int bm_words, int src, ForkDst d) {
+    const int tid = blockIdx.x * 256 + threadIdx.x, nth = gridDim.x * 256;
+    int hl = rules[src].hist_len;
+    hl = hl < 0 ? 0 : (hl > hist_cap ? (int)hist_cap : hl);
+    for (int i = tid; i < vocab; i += nth) {
+        const T v = logits[(int64_t)src * vocab + i];
+#pragma unroll
+        for (int j = 0; j < kForkMaxDst; ++j)
+            if (j < d.n) logits[(int64_t)d.slot[j] * vocab + i] = v;
+    }
+    for (int i = tid; i < hl; i += nth) {
+        const int32_t v = hist[(int64_t)src * hist_cap + i];
+#pragma unroll
+        for (int j = 0; j < kForkMaxDst; ++j)
+            if (j < d.n) hist[(int64_t)d.slot[j] * hist_cap + i] = v;
+    }
+    for (int i = tid; i < bm_words; i += nth) {
+        const uint32_t v = bitmap[(int64_t)src * bm_words + i];
+#pragma unroll
+        for (int j = 0; j < kForkMaxDst; ++j)
+            if (j < d.n) bitmap[(int64_t)d.slot[j] * bm_words + i] = v;
+    }
+    if (tid == 0) {
+        const int32_t* ss = st + src * ST_WORDS;
+        const int32_t kv = ss[ST_KV_LEN], pos = ss[ST_POS], last = ss[ST_LAST];
+        const int32_t pl = rules[src].prompt_len, na = rules[src].n_app;
+#pragma unroll
+        for (int j = 0; j < kForkMaxDst; ++j)
+            if (j < d.n) {
+                int32_t* sd = st + d.slot[j] * ST_WORDS;
+                sd[ST_KV_LEN] = kv; sd[ST_POS] = pos; sd[ST_LAST] = last;
+                RulesState* rd = rules + d.slot[j];
+                rd->hist_len = hl; rd->prompt_len = pl; rd->n_app = na;
+            }
     }
 }
 
@@ -940,6 +1022,28 @@ static int prefill_forward(ss_llama* h, const PrefillSeg* segs, int nseg, const 
     return SS_OK;
 }
 
+// one plane kind of a fork: `span` packets of every (layer, head) unit of both slabs, source to every destination
+template <typename P>
+static int fork_planes_launch(const ss_llama* h, void* plane0, void* plane1, int64_t unit_stride, int64_t span, int src,
+                              const ForkDst& d, hipStream_t s) {
+    if (span <= 0) return SS_OK;
+    const int64_t units = (int64_t)h->cfg.n_layers * h->cfg.n_heads;
+    const dim3 grid((unsigned)cdiv(span, 256 * kForkPackets), (unsigned)units, 2);
+    hipLaunchKernelGGL(fork_planes_kernel<P>, grid, dim3(256), 0, s, (P*)plane0, (P*)plane1, units * unit_stride, unit_stride, span,
+                       src, d);
+    SS_LAUNCH_CHECK("fork_planes");
+    return SS_OK;
+}
+
+template <typename T>
+static int fork_state_launch(ss_llama* h, int src, const ForkDst& d, hipStream_t s) {
+    const ss_llama_config& g = h->cfg;
+    hipLaunchKernelGGL(fork_state_kernel<T>, dim3(16), dim3(256), 0, s, (T*)h->logits, g.vocab, h->state, h->rules, h->hist,
+                       h->hist_cap(), h->hist_bm, h->bm_words(), src, d);
+    SS_LAUNCH_CHECK("fork_state");
+    return SS_OK;
+}
+
 extern "C" {
 
 size_t ss_llama_workspace_bytes(const ss_llama_config* cfg, int64_t max_prefill_rows) {
@@ -1259,6 +1363,43 @@ int ss_llama_kv_gather(ss_llama* h, const int32_t* keep_idx_dev, int64_t n_keep,
                 return rc;
     h->kv8_rows[h->cur] = 0;     // rows moved: the shadow of this slot is rebuilt by the next decode loop
     return ss_llama_set_lengths(h, n_keep, h->pos[h->cur], stream);
+}
+
+int ss_llama_fork(ss_llama* h, int32_t src, const int32_t* host_dst, int32_t n_dst, void* stream) {
+    SS_REQUIRE(h && host_dst, "llama_fork: null argument");
+    SS_REQUIRE(src >= 0 && src < h->n_seq, "llama_fork: source slot %d out of range (< %d)", (int)src, h->n_seq);
+    SS_REQUIRE(n_dst >= 1, "llama_fork: n_dst=%d (at least one destination)", (int)n_dst);
+    ForkDst d = {0, {0, 0, 0, 0, 0, 0, 0}};
+    for (int j = 0; j < n_dst; ++j) {
+        const int32_t b = host_dst[j];
+        SS_REQUIRE(b >= 0 && b < h->n_seq, "llama_fork: destination slot %d out of range (< %d)", (int)b, h->n_seq);
+        SS_REQUIRE(b != src, "llama_fork: destination slot %d is the source", (int)b);
+        for (int i = 0; i < d.n; ++i) SS_REQUIRE(d.slot[i] != b, "llama_fork: destination slot %d listed twice", (int)b);
+        d.slot[d.n++] = b;      // (distinct, in range and not src: never more than n_seq - 1 <= kForkMaxDst)
+    }
+    const ss_llama_config& g = h->cfg;
+    const int64_t row_bytes = (int64_t)h->hd * (int64_t)h->esz;
+    SS_REQUIRE(row_bytes % 16 == 0, "llama_fork: a cache row of %lld bytes is no multiple of the 16-byte packet", (long long)row_bytes);
+    SS_REQUIRE(!h->kq || h->hd % 16 == 0, "llama_fork: head dim %d of the fp8 shadow is no multiple of 16", h->hd);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t kv = h->kv_len[src];
+    int rc;
+    if ((rc = fork_planes_launch<uint4>(h, h->kc, h->vc, g.cache_cap * row_bytes / 16, kv * row_bytes / 16, src, d, s))) return rc;
+    int64_t rows8 = 0;
+    if (h->kq) {        // the shadow below the source's watermark goes the same way: codes in 16-byte packets, scales one word each
+        rows8 = h->kv8_rows[src] < kv ? h->kv8_rows[src] : kv;
+        if ((rc = fork_planes_launch<uint4>(h, h->kq, h->vq, (int64_t)g.cache_cap * h->hd / 16, rows8 * h->hd / 16, src, d, s))) return rc;
+        if ((rc = fork_planes_launch<uint32_t>(h, h->kscale, h->vscale, g.cache_cap, rows8, src, d, s))) return rc;
+    }
+    if ((rc = SS_DISPATCH(g.dtype, fork_state_launch, h, (int)src, d, s))) return rc;
+    for (int j = 0; j < d.n; ++j) {
+        const int b = d.slot[j];
+        h->kv_len[b] = kv;
+        h->pos[b] = h->pos[src];
+        h->hist_len[b] = h->hist_len[src];
+        h->kv8_rows[b] = rows8;
+    }
+    return SS_OK;
 }
 
 int ss_llama_prefill(ss_llama* h, const void* embeds, int64_t M, const int32_t* pos_ids, void* hidden_out,

@@ -145,6 +145,7 @@ PROTOTYPES = {
     "ss_llama_set_lengths": (C.c_int, [vp, i64, i64, vp]),
     "ss_llama_get_lengths": (C.c_int, [vp, C.POINTER(i64), C.POINTER(i64)]),
     "ss_llama_kv_gather": (C.c_int, [vp, vp, i64, vp]),
+    "ss_llama_fork": (C.c_int, [vp, i32, i32p, i32, vp]),
     "ss_llama_prefill": (C.c_int, [vp, vp, i64, vp, vp, vp]),
     "ss_llama_prefill_batch": (C.c_int, [vp, vp, C.POINTER(i64), vp, vp]),
     "ss_llama_generate": (C.c_int, [vp, i64, i32, i32p, i64, C.POINTER(i64), vp]),

@@ -240,6 +240,22 @@ class LlamaEngine:
         idx = torch.as_tensor(keep_idx, dtype=torch.int32, device=self.device).contiguous()
         check(lib().ss_llama_kv_gather(self._h, idx.data_ptr(), idx.numel(), ops.stream()), "ss_llama_kv_gather")
 
+    def fork(self, src=None, dsts=None):
+        """Put every slot of ``dsts`` (None: every other slot) in the state slot ``src`` (None: the selected slot) is in, on
+        the device (ss_llama_fork; include/seedstory_hip.h): its cache rows below the cache length, last logits, lengths, token
+        history and, with ``kv_cache="fp8"``, the shadow below its watermark — each packet read once and written to all
+        destinations, asynchronously on the current stream.  ``generate`` / ``generate_batch`` / ``prefill`` on a destination
+        then behave as on ``src``; sampling and rule parameters, recording and the result rings stay the slot's own.  The
+        selected slot is unchanged.  Returns the destination list.  A bad slot list raises ``SSError`` and changes nothing."""
+        src = self._cur if src is None else int(src)
+        dsts = [b for b in range(self.n_seq) if b != src] if dsts is None else [int(b) for b in dsts]
+        for b in [src] + dsts:
+            if not -2 ** 31 <= b < 2 ** 31:
+                raise _lib.SSError("fork: slot %d is no int32" % b)
+        arr = (C.c_int32 * max(1, len(dsts)))(*dsts)
+        check(lib().ss_llama_fork(self._h, src, arr, len(dsts), ops.stream()), "ss_llama_fork")
+        return dsts
+
     # ---- attention maps (the reference's config.output_attentions) --------------------------------------
     def attn_capture_on(self, rows, cols, head=0, row0=None):
         """Start recording head ``head``'s attention map of every layer (pre-softmax scores + mask in the model dtype, as the
@@ -700,21 +716,27 @@ class LlamaEngine:
             self.last_logprobs = LlamaEngine._lp_join(lps)
         return ids, torch.cat(hid)[:max(len(ids) - 1, 0)]
 
-    def generate_batch_img_block(self, n_steps, last_prompt_ids, forced=None):
+    def generate_batch_img_block(self, n_steps, last_prompt_ids, forced=None, active=None):
         """``generate_batch`` with the forced image-token runs batched, per slot.  Returns (ids per slot, hidden rows per
-        slot).  Slots are independent: one may be inside its block while another still writes its caption."""
+        slot).  Slots are independent: one may be inside its block while another still writes its caption.
+        ``active[b]`` false (None: every slot takes part): slot b is never read, fed or written; its entries of the results
+        are ``[]`` and ``None``."""
         S = self.n_seq
+        on = [True] * S if active is None else [bool(a) for a in active]
+        assert len(on) == S
         if len(self.img_ids) < 3:
-            ns = self.generate_batch(n_steps, last_prompt_ids, forced)
-            self.last_logprobs = [LlamaEngine._lp_segment(self, b, ns[b]) for b in range(S)] if getattr(self, "_lp_slots", {}) else None
-            return ([self.select(b).gen_ids[:ns[b]].tolist() for b in range(S)],
-                    [self.select(b).hidden_rows[:max(ns[b] - 1, 0)] for b in range(S)])
+            ns = self.generate_batch(n_steps, last_prompt_ids, forced) if active is None else \
+                self.generate_batch(n_steps, last_prompt_ids, forced, on)
+            self.last_logprobs = ([LlamaEngine._lp_segment(self, b, ns[b]) if on[b] else None for b in range(S)]
+                                  if getattr(self, "_lp_slots", {}) else None)
+            return ([self.select(b).gen_ids[:ns[b]].tolist() if on[b] else [] for b in range(S)],
+                    [self.select(b).hidden_rows[:max(ns[b] - 1, 0)] if on[b] else None for b in range(S)])
         boi = self.img_ids[0]
         forced = [[] for _ in range(S)] if forced is None else [[int(t) for t in (f or [])] for f in forced]
         ids, hid = [[] for _ in range(S)], [[] for _ in range(S)]
-        rem, last, active = [int(n_steps)] * S, [int(t) for t in last_prompt_ids], [True] * S
+        rem, last, active = [int(n_steps)] * S, [int(t) for t in last_prompt_ids], list(on)
         lp_slots = getattr(self, "_lp_slots", {})
-        lps = [[] if b in lp_slots else None for b in range(S)]
+        lps = [[] if b in lp_slots and on[b] else None for b in range(S)]
         self.last_logprobs = None
         self.set_stop_id(boi)
         try:
@@ -775,7 +797,7 @@ class LlamaEngine:
             self.set_stop_id(-1)
         if lp_slots:
             self.last_logprobs = [None if l is None else LlamaEngine._lp_join(l) for l in lps]
-        return ids, [torch.cat(h)[:max(len(i) - 1, 0)] for h, i in zip(hid, ids)]
+        return ids, [torch.cat(h)[:max(len(i) - 1, 0)] if h else None for h, i in zip(hid, ids)]
 
     def profile_decode(self, n_tokens=4):
         ms = (C.c_float * 8)()

@@ -155,10 +155,36 @@ def sample_kwargs(args, j, step):
     engine slot, one ``generate`` call per story step, so ``--seed`` is advanced per call (story j, step): a fixed seed would
     replay one random stream at every step.  Without ``--seed`` the model's own call counter over ``torch.initial_seed()``
     does the same."""
-    if not getattr(args, "sample", False):
+    n = int(getattr(args, "best_of", 1) or 1)
+    if not getattr(args, "sample", False) and n <= 1:
         return {}
     seed = None if args.seed is None else int(args.seed) + 100003 * j + step
-    return dict(do_sample=True, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, seed=seed)
+    kw = dict(do_sample=True, temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, seed=seed)
+    if n > 1:           # --best-of implies --sample: n candidates of every step, the best one goes on
+        kw["num_return_sequences"] = n
+    return kw
+
+
+def add_best_of_argument(ap):
+    """``--best-of N`` (shared with vis_george_sink.py)"""
+    ap.add_argument("--best-of", type=int, default=1, metavar="N",
+                    help="sample N (at most 8) continuations of every step from one prefill and keep the one with the highest mean "
+                         "model log-probability; implies --sample; prints each step's candidate scores")
+
+
+def apply_best_of(args, llama):
+    """``--best-of N``: the engine gets N sequence slots (before the first generate builds it)"""
+    n = int(getattr(args, "best_of", 1) or 1)
+    if not 1 <= n <= 8:
+        raise SystemExit("--best-of must be 1 .. 8")
+    if n > 1:
+        llama.n_seq = n
+
+
+def report_candidates(args, j, step, out):
+    if 'candidates' in out:
+        print("story %d step %d: best of %d = candidate %d, scores %s" % (
+            j, step, len(out['candidates']), out['best'], " ".join("%.4f" % c['score'] for c in out['candidates'])))
 
 
 def add_rules_arguments(ap):
@@ -224,6 +250,7 @@ def run_story(args, j, question, image, tokenizer, transform, vit, agent, adapte
             ctx.start(tokenizer.encode(question, add_special_tokens=False), vit(image_tensor))   # gen_george.py:168-188
     llama = agent.llm.base_model.model if hasattr(agent.llm, "base_model") else agent.llm
     llama.use_kv_cache_head = False                                                         # :165
+    apply_best_of(args, llama)
     if args.save_attn:                                           # the reference's switch: one merged attention map per layer
         llama.config.output_attentions = True
         os.makedirs(args.save_attn, exist_ok=True)
@@ -238,6 +265,7 @@ def run_story(args, j, question, image, tokenizer, transform, vit, agent, adapte
                              embeds_cmp_mask=emb_mask, ids_cmp_mask=ids_mask, max_new_tokens=500, num_img_gen_tokens=64,
                              forced_tokens=forced, **sample_kwargs(args, j, step), **rules_kwargs(args), **logprobs_kwargs(args))
         report_caption_logprobs(args, j, step, out, boi)
+        report_candidates(args, j, step, out)
         if args.save_attn:                                       # [layers, rows, width], head 0 (NaN beyond each row's keys)
             torch.save(torch.stack([a[0] for a in out['attn_weights']]).cpu(),
                        os.path.join(args.save_attn, "val_%d_step_%02d.pt" % (j, step)))
@@ -283,6 +311,7 @@ def main():
     ap.add_argument("--top-k", type=int, default=0, help="0 = off")
     ap.add_argument("--top-p", type=float, default=0.5)
     ap.add_argument("--seed", type=int, default=None, help="with --sample: reproducible stories (default: torch.initial_seed())")
+    add_best_of_argument(ap)
     add_logprobs_argument(ap)
     add_rules_arguments(ap)
     args = ap.parse_args()

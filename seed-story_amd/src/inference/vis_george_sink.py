@@ -20,8 +20,9 @@ import os
 import torch
 
 from seedstory.story import StoryContext
-from src.inference.gen_george import (BOI_TOKEN, EOI_TOKEN, IMG_TOKEN, add_logprobs_argument, add_rules_arguments, build, logprobs_kwargs,
-                                      report_caption_logprobs, rules_kwargs)
+from src.inference.gen_george import (BOI_TOKEN, EOI_TOKEN, IMG_TOKEN, add_best_of_argument, add_logprobs_argument, add_rules_arguments,
+                                      apply_best_of, build, logprobs_kwargs, report_candidates, report_caption_logprobs, rules_kwargs,
+                                      sample_kwargs)
 
 
 def run_story(args, j, start_text, captions, image, tokenizer, transform, vit, agent, adapter, device, dtype):
@@ -36,6 +37,7 @@ def run_story(args, j, start_text, captions, image, tokenizer, transform, vit, a
     llama.past_key_values = None
     sink = args.cache_mode == "img_head_tail"
     llama.use_kv_cache_head = sink
+    apply_best_of(args, llama)          # --best-of N: the winner's slot is the one the next step's cache continues from
     if args.save_attn:                                           # the reference's switch: one merged attention map per layer
         llama.config.output_attentions = True
         os.makedirs(args.save_attn, exist_ok=True)
@@ -52,8 +54,10 @@ def run_story(args, j, start_text, captions, image, tokenizer, transform, vit, a
             llama.kv_cache_head = cached
         out = agent.generate(tokenizer=tokenizer, input_ids=ctx.input_ids(device), image_embeds=ctx.image_embeds,
                              embeds_cmp_mask=emb_mask, ids_cmp_mask=ids_mask, max_new_tokens=500, num_img_gen_tokens=64,
-                             past_key_values=past, forced_tokens=forced, **rules_kwargs(args), **logprobs_kwargs(args))
+                             past_key_values=past, forced_tokens=forced, **sample_kwargs(args, j, step), **rules_kwargs(args),
+                             **logprobs_kwargs(args))
         report_caption_logprobs(args, j, step, out, boi)
+        report_candidates(args, j, step, out)
         with open(os.path.join(save_folder, "token.txt"), "a+") as f:
             f.write("context token: {} cached: {} sink: {}\n".format((1, len(ctx.ids)), cached, ctx.sink_len))
         if args.save_attn:                                       # [layers, rows, width], head 0 (NaN beyond each row's keys)
@@ -105,6 +109,11 @@ def main():
     ap.add_argument("--stories", type=int, default=1)
     add_rules_arguments(ap)
     add_logprobs_argument(ap)
+    add_best_of_argument(ap)
+    ap.add_argument("--temperature", type=float, default=0.7, help="with --best-of")
+    ap.add_argument("--top-k", type=int, default=0, help="with --best-of; 0 = off")
+    ap.add_argument("--top-p", type=float, default=0.5, help="with --best-of")
+    ap.add_argument("--seed", type=int, default=None, help="with --best-of: reproducible candidates (default: torch.initial_seed())")
     ap.add_argument("--save-attn", default=None, metavar="DIR",
                     help="run the LLM with config.output_attentions and torch.save each step's attn_weights (head 0's "
                          "pre-softmax maps, the evidence behind the attention sink) into DIR")

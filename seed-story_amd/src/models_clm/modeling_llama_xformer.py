@@ -117,6 +117,8 @@ class LlamaForCausalLM(nn.Module):
         self.max_prefill_rows = 1280
         self.decode_weights = None      # "fp8": e4m3 weight-only decode projections (LlamaEngine.enable_decode_fp8); None = the knob
         self.kv_cache = None            # "fp8": decode attention reads an e4m3 shadow of the KV cache (LlamaEngine.enable_kv_fp8); None = the knob
+        self.n_seq = 1                  # sequence slots of the engine: generate(num_return_sequences=n) needs n_seq >= n
+        self._candidates = None         # (slots, kv_cache_head per candidate) of the last generate(num_return_sequences > 1)
 
     # ---- reference surface ------------------------------------------------------------------
     def get_input_embeddings(self):
@@ -182,7 +184,7 @@ class LlamaForCausalLM(nn.Module):
         lora = getattr(self, "_lora_scaling", None)
         p0 = self.lm_head.weight
         sig = (p0.data_ptr(), p0._version, p0.dtype, str(p0.device), tuple(img_ids), self.cache_cap, self.max_new,
-               self.max_prefill_rows, self.decode_weights, self.kv_cache)
+               self.max_prefill_rows, self.decode_weights, self.kv_cache) + (int(self.n_seq),)
         if self._engine is None or self._engine_sig != sig:
             if not p0.is_cuda:
                 raise RuntimeError("LlamaForCausalLM must be moved to the GPU first (no CPU path)")
@@ -194,7 +196,8 @@ class LlamaForCausalLM(nn.Module):
                                        cache_cap=self.cache_cap, max_new=self.max_new,
                                        max_prefill_rows=self.max_prefill_rows, img_ids=img_ids,
                                        eos_id=c.eos_token_id, lora_scaling=lora if lora is not None else 2.0,
-                                       decode_weights=self.decode_weights, kv_cache=self.kv_cache)
+                                       decode_weights=self.decode_weights, kv_cache=self.kv_cache,
+                                       **({"n_seq": int(self.n_seq)} if int(self.n_seq) > 1 else {}))
             self._engine_sig = sig
         return self._engine
 
@@ -338,7 +341,7 @@ class LlamaForCausalLM(nn.Module):
                  max_new_tokens=120, output_hidden_states=True, return_dict_in_generate=True, forced_tokens=None,
                  output_attentions=None, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=None, num_beams=1,
                  repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, spare_img_ids=False, output_logprobs=False,
-                 top_logprobs=0, **unused):
+                 top_logprobs=0, num_return_sequences=1, **unused):
         """Greedy search as ``ContinuousLVLM.generate`` drives it (reference models.py:146-153): ``inputs_embeds`` feed
         step 0, ``input_ids`` is the running sequence, the image-token logits processor is applied on device.
         ``do_sample=False`` (the default): temperature / top_k / top_p / seed are inert, as in Hugging Face.
@@ -363,10 +366,28 @@ class LlamaForCausalLM(nn.Module):
         ``top_logprob_ids`` / ``top_logprob_values`` [n, top_logprobs] hold one float32 entry per generated token, computed
         on the device inside the decode token (``LlamaEngine.set_logprobs``; include/seedstory_hip.h); the engine records
         nothing any more when the call returns or raises.  ``output_scores`` / ``output_logits`` (full [vocab] rows per
-        step) are not part of this and stay ignored."""
+        step) are not part of this and stay ignored.
+        ``num_return_sequences=n`` (> 1; needs ``do_sample=True`` and ``n <= self.n_seq``, the engine's slot count, set before
+        the first ``generate``): n sampled continuations of the one prompt.  The prompt is prefilled once, on slot 0 (with
+        ``past_key_values``: on the selected slot), the slot is forked on the device to the n - 1 lowest other slots
+        (``LlamaEngine.fork``), and all candidates decode in lock-step, one sweep of the weights per token; they share the
+        seed and diverge because the slot is part of the Philox counter.  ``sequences`` is ``[n, S + longest]``, right-padded
+        with ``config.pad_token_id`` (EOS when that is None); ``candidates`` holds n outputs in the batch-1 layout (candidate 0
+        = the source slot, then ascending slots); the top-level ``hidden_states`` / log-probability fields are candidate 0's,
+        ``self.past_key_values`` and the ``kv_cache_head`` advance refer to it, and ``select_candidate(i)`` switches to
+        another.  ``num_beams`` stays inert without ``do_sample``."""
         want_attn = bool(getattr(self.config, "output_attentions", False) if output_attentions is None else output_attentions)
         if do_sample and num_beams is not None and int(num_beams) > 1:
             raise NotImplementedError("beam-search sampling (do_sample=True with num_beams=%d) is not implemented" % int(num_beams))
+        n_ret = 1 if num_return_sequences is None else int(num_return_sequences)
+        if n_ret > 1:
+            if not do_sample:
+                raise ValueError("num_return_sequences=%d needs do_sample=True: greedy search has one continuation" % n_ret)
+            if n_ret > int(self.n_seq):
+                raise ValueError("num_return_sequences=%d exceeds the engine's sequence slots: set LlamaForCausalLM.n_seq "
+                                 "(now %d, at most 8) before the first generate()" % (n_ret, int(self.n_seq)))
+            if want_attn:
+                raise NotImplementedError("attention maps are a single-sequence tool (output_attentions with num_return_sequences=%d)" % n_ret)
         img_ids = ()
         for proc in (logits_processor or []):
             img_ids = tuple(getattr(proc, "img_ids_list", ()))
@@ -377,6 +398,8 @@ class LlamaForCausalLM(nn.Module):
         if inputs_embeds is None:
             inputs_embeds = self.model.embed_tokens(input_ids)
         rows = inputs_embeds[0]
+        if n_ret > 1 and past_key_values is None:
+            eng.select(0)
         if do_sample:
             if seed is None:
                 self._sample_calls = getattr(self, "_sample_calls", 0) + 1
@@ -392,6 +415,9 @@ class LlamaForCausalLM(nn.Module):
                                      no_repeat_ngram_size=no_repeat_ngram_size or 0, min_new_tokens=min_new_tokens or 0,
                                      spare_img_ids=bool(spare_img_ids))               # raises on a bad value
                 eng.set_history(input_ids[0].tolist())
+            if n_ret > 1:
+                return self._generate_candidates(eng, n_ret, input_ids, rows, S, img_ids, past_key_values, max_new_tokens,
+                                                 output_hidden_states, forced_tokens, bool(output_logprobs))
             return self._generate(eng, input_ids, rows, S, img_ids, past_key_values, max_new_tokens, output_hidden_states,
                                   forced_tokens, want_attn, **({"want_logprobs": True} if output_logprobs else {}))
         finally:
@@ -406,6 +432,50 @@ class LlamaForCausalLM(nn.Module):
 
     def _generate(self, eng, input_ids, rows, S, img_ids, past_key_values, max_new_tokens, output_hidden_states,
                   forced_tokens, want_attn, want_logprobs=False):
+        dev = eng.device
+        maps, kv0, fed0, hid0 = self._feed_prompt(eng, rows, S, past_key_values, max_new_tokens, output_hidden_states, want_attn)
+        self._candidates = None
+        if img_ids and eng.img_block_enabled():
+            # the 65 processor-forced tokens behind <img> run as one batched continuation (seedstory/llama.py)
+            gen_list, hr = eng.generate_img_block(max_new_tokens, int(input_ids[0, -1]), forced_tokens)
+            n = len(gen_list)
+            gen = torch.tensor(gen_list, dtype=torch.long, device=dev)
+            lp = eng.last_logprobs if want_logprobs else None
+        else:
+            n = eng.generate(max_new_tokens, int(input_ids[0, -1]), forced_tokens)
+            gen = eng.gen_ids[:n].to(torch.long)
+            hr = eng.hidden_rows[:max(n - 1, 0)]
+            lp = {k: v.clone() for k, v in eng.logprobs(n).items()} if want_logprobs else None
+        self.past_key_values = eng.past_key_values()
+        if self.use_kv_cache_head:
+            adv = fed0 + max(n - 1, 0)
+            self.kv_cache_head = adv if self.kv_cache_head is None else self.kv_cache_head + adv
+        attentions = attention_maps = None
+        if want_attn:
+            fed = fed0 + max(n - 1, 0)
+            attentions = attention_step_views(maps, kv0, fed0, fed)
+            attention_maps = maps[:, :fed, :kv0 + fed]
+        return self._output(input_ids, gen, hid0, hr, lp, output_hidden_states, attentions, attention_maps)
+
+    @staticmethod
+    def _output(input_ids, gen, hid0, hr, lp, output_hidden_states, attentions=None, attention_maps=None):
+        """one sequence's ``GenerateOutput`` in the batch-1 layout"""
+        sequences = torch.cat([input_ids[0], gen]).unsqueeze(0)
+        hidden_states = None
+        if output_hidden_states:
+            steps = [(hid0.unsqueeze(0),)]
+            steps += [(hr[j].view(1, 1, -1),) for j in range(hr.shape[0])]
+            hidden_states = tuple(steps)
+        scores = {}
+        if lp is not None:
+            scores = dict(logprobs=lp["logprob"], model_logprobs=lp["model_logprob"], top_logprob_ids=lp["top_ids"],
+                          top_logprob_values=lp["top_logprobs"])
+        return GenerateOutput(sequences=sequences, hidden_states=hidden_states, attentions=attentions,
+                              attention_maps=attention_maps, **scores)
+
+    def _feed_prompt(self, eng, rows, S, past_key_values, max_new_tokens, output_hidden_states, want_attn):
+        """The prompt rows (all of them, or those behind ``past_key_values``) on the selected slot; returns (capture buffer,
+        cache length before, rows fed, their hidden rows)."""
         dev = eng.device
         maps, kv0 = None, 0
         if past_key_values is None:
@@ -427,38 +497,70 @@ class LlamaForCausalLM(nn.Module):
         if max_new_tokens > eng.max_new:
             raise ValueError("max_new_tokens=%d exceeds the engine's generated-token ring (max_new=%d): raise "
                              "LlamaForCausalLM.max_new before the first generate()" % (max_new_tokens, eng.max_new))
+        return maps, kv0, fed0, hid0
+
+    def _generate_candidates(self, eng, n_ret, input_ids, rows, S, img_ids, past_key_values, max_new_tokens,
+                             output_hidden_states, forced_tokens, want_logprobs):
+        """``generate(num_return_sequences=n_ret)``: one prefill on the selected (source) slot, a device fork to the n_ret - 1
+        lowest other slots, one lock-step decode of the n_ret candidates.  The caller has set sampling, rules, the source's
+        history and recording (each for every slot; the fork hands the history on) and restores them."""
+        dev = eng.device
+        NS = int(eng.n_seq)
+        src = int(getattr(eng, "_cur", 0))
+        _, _, fed0, hid0 = self._feed_prompt(eng, rows, S, past_key_values, max_new_tokens, output_hidden_states, False)
+        others = [b for b in range(NS) if b != src][:n_ret - 1]
+        eng.fork(src, others)
+        slots = [src] + others
+        on = [b in slots for b in range(NS)]
+        last = int(input_ids[0, -1])
+        forced = [list(forced_tokens or []) if on[b] else [] for b in range(NS)]
         if img_ids and eng.img_block_enabled():
-            # the 65 processor-forced tokens behind <img> run as one batched continuation (seedstory/llama.py)
-            gen_list, hr = eng.generate_img_block(max_new_tokens, int(input_ids[0, -1]), forced_tokens)
-            n = len(gen_list)
-            gen = torch.tensor(gen_list, dtype=torch.long, device=dev)
-            lp = eng.last_logprobs if want_logprobs else None
+            ids, hrs = eng.generate_batch_img_block(max_new_tokens, [last] * NS, forced, active=on)
+            lps = eng.last_logprobs if want_logprobs else None
         else:
-            n = eng.generate(max_new_tokens, int(input_ids[0, -1]), forced_tokens)
-            gen = eng.gen_ids[:n].to(torch.long)
-            hr = eng.hidden_rows[:max(n - 1, 0)]
-            lp = {k: v.clone() for k, v in eng.logprobs(n).items()} if want_logprobs else None
-        sequences = torch.cat([input_ids[0], gen]).unsqueeze(0)
-        hidden_states = None
-        if output_hidden_states:
-            steps = [(hid0.unsqueeze(0),)]
-            steps += [(hr[j].view(1, 1, -1),) for j in range(hr.shape[0])]
-            hidden_states = tuple(steps)
+            ns = eng.generate_batch(max_new_tokens, [last] * NS, forced, on)
+            ids, hrs, lps = [[] for _ in range(NS)], [None] * NS, [None] * NS
+            for b in slots:
+                eng.select(b)
+                ids[b] = eng.gen_ids[:ns[b]].tolist()
+                hrs[b] = eng.hidden_rows[:max(ns[b] - 1, 0)]
+                if want_logprobs:
+                    lps[b] = {k: v.clone() for k, v in eng.logprobs(ns[b], b).items()}
+        eng.select(src)
+        cands = [self._output(input_ids, torch.tensor(ids[b], dtype=torch.long, device=dev), hid0, hrs[b],
+                              lps[b] if want_logprobs else None, output_hidden_states) for b in slots]
+        self.past_key_values = eng.past_key_values()
+        base = self.kv_cache_head
+        heads = [None] * n_ret
+        if self.use_kv_cache_head:
+            heads = [(0 if base is None else base) + fed0 + max(len(ids[b]) - 1, 0) for b in slots]
+            self.kv_cache_head = heads[0]
+        self._candidates = (slots, heads)
+        pad = getattr(self.config, "pad_token_id", None)
+        pad = self.config.eos_token_id if pad is None else pad
+        width = max(c.sequences.shape[1] for c in cands)
+        sequences = torch.full((n_ret, width), int(pad), dtype=cands[0].sequences.dtype, device=dev)
+        for i, c in enumerate(cands):
+            sequences[i, :c.sequences.shape[1]] = c.sequences[0]
+        c0 = cands[0]
+        return GenerateOutput(sequences=sequences, hidden_states=c0.hidden_states, attentions=None, logprobs=c0.logprobs,
+                              model_logprobs=c0.model_logprobs, top_logprob_ids=c0.top_logprob_ids,
+                              top_logprob_values=c0.top_logprob_values, candidates=cands)
+
+    def select_candidate(self, i):
+        """After ``generate(num_return_sequences=n)``: continue from candidate ``i`` — its slot becomes the selected one,
+        ``past_key_values`` and ``kv_cache_head`` refer to it.  Returns the slot."""
+        if self._candidates is None:
+            raise ValueError("select_candidate: the last generate() returned one sequence")
+        slots, heads = self._candidates
+        if not 0 <= int(i) < len(slots):
+            raise ValueError("select_candidate: candidate %d outside [0, %d)" % (int(i), len(slots)))
+        eng = self._engine if self._engine is not None else self.engine_for_generation(tuple(getattr(self, "_img_ids", ())))
+        eng.select(slots[int(i)])
         self.past_key_values = eng.past_key_values()
         if self.use_kv_cache_head:
-            adv = fed0 + max(n - 1, 0)
-            self.kv_cache_head = adv if self.kv_cache_head is None else self.kv_cache_head + adv
-        attentions = attention_maps = None
-        if want_attn:
-            fed = fed0 + max(n - 1, 0)
-            attentions = attention_step_views(maps, kv0, fed0, fed)
-            attention_maps = maps[:, :fed, :kv0 + fed]
-        scores = {}
-        if lp is not None:
-            scores = dict(logprobs=lp["logprob"], model_logprobs=lp["model_logprob"], top_logprob_ids=lp["top_ids"],
-                          top_logprob_values=lp["top_logprobs"])
-        return GenerateOutput(sequences=sequences, hidden_states=hidden_states, attentions=attentions,
-                              attention_maps=attention_maps, **scores)
+            self.kv_cache_head = heads[int(i)]
+        return slots[int(i)]
 
 
 def attention_step_views(maps, kv0, fed0, fed):
@@ -485,7 +587,7 @@ class CausalLMOutputWithPast:
 
 class GenerateOutput:
     def __init__(self, sequences, hidden_states, attentions, attention_maps=None, logprobs=None, model_logprobs=None,
-                 top_logprob_ids=None, top_logprob_values=None):
+                 top_logprob_ids=None, top_logprob_values=None, candidates=None):
         self.sequences = sequences
         self.hidden_states = hidden_states
         self.attentions = attentions
@@ -493,3 +595,5 @@ class GenerateOutput:
         # float32, one entry per generated token (generate(output_logprobs=True)); None when not asked for
         self.logprobs, self.model_logprobs = logprobs, model_logprobs
         self.top_logprob_ids, self.top_logprob_values = top_logprob_ids, top_logprob_values
+        # generate(num_return_sequences=n > 1): the n outputs in the batch-1 layout (`sequences` above is then [n, S + longest])
+        self.candidates = candidates

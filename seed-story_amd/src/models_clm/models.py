@@ -21,6 +21,27 @@ EOI_TOKEN = '</img>'
 IMG_TOKEN = '<img_{:05d}>'
 
 
+def candidate_score(ids, model_logprobs, img_ids):
+    """Score of one sampled candidate for best-of-n: the mean of ``model_logprobs`` (the model's own log-probability of
+    each generated token, ``generate(output_logprobs=True)``) over the generated positions whose id is not in ``img_ids``
+    — the 65 ids the image-token processor forces behind ``<img>``, which the model did not choose.  ``-inf`` when no such
+    position exists.  Pure host arithmetic on lists or tensors."""
+    skip = set(int(t) for t in img_ids)
+    ids = ids.tolist() if isinstance(ids, torch.Tensor) else list(ids)
+    lps = model_logprobs.tolist() if isinstance(model_logprobs, torch.Tensor) else list(model_logprobs)
+    vals = [float(v) for t, v in zip(ids, lps) if int(t) not in skip]
+    return sum(vals) / len(vals) if vals else float("-inf")
+
+
+def best_candidate(scores):
+    """index of the highest score; ties (and all ``-inf``) go to the lowest index"""
+    best = 0
+    for i, v in enumerate(scores):
+        if v > scores[best]:
+            best = i
+    return best
+
+
 class ContinuousLVLM(nn.Module):
 
     def __init__(self, llm, input_resampler, output_resampler, lm_loss_scale=1.0, rec_loss_scale=1.0) -> None:
@@ -109,14 +130,21 @@ class ContinuousLVLM(nn.Module):
                  ids_cmp_mask=None, logits_processor=None, num_img_gen_tokens=64, temperature=0.7, num_beams=1,
                  max_new_tokens=120, top_p=0.5, past_key_values=None, dtype=torch.float16, device='cuda',
                  forced_tokens=None, do_sample=False, top_k=0, seed=None, repetition_penalty=1.0, no_repeat_ngram_size=0,
-                 min_new_tokens=0, spare_img_ids=False, output_logprobs=False, top_logprobs=0):
+                 min_new_tokens=0, spare_img_ids=False, output_logprobs=False, top_logprobs=0, num_return_sequences=1):
         """``do_sample=False`` (the default, what the reference passes): greedy; ``temperature`` / ``top_p`` / ``top_k`` /
         ``seed`` are inert.  ``do_sample=True`` hands them to ``LlamaForCausalLM.generate``: on-device sampling
         (``top_k=0`` = off, ``seed=None`` = governed by ``torch.manual_seed``).  ``repetition_penalty`` /
         ``no_repeat_ngram_size`` / ``min_new_tokens`` (Hugging Face's defaults: inert) and ``spare_img_ids`` are handed on only
         when one of the three is active: they act on greedy search and on sampling (``LlamaForCausalLM.generate``).
         ``output_logprobs=True`` adds ``'logprobs'``, ``'model_logprobs'`` (float32, one entry per generated id) and
-        ``'top_logprobs'`` = (ids, values) [n, top_logprobs] to the returned dict (``LlamaForCausalLM.generate``)."""
+        ``'top_logprobs'`` = (ids, values) [n, top_logprobs] to the returned dict (``LlamaForCausalLM.generate``).
+        ``num_return_sequences=n`` (> 1, with ``do_sample=True`` and ``llm.n_seq >= n``): best-of-n.  n candidates are sampled
+        from the one prompt (``LlamaForCausalLM.generate``), each is scored with ``candidate_score`` (mean model
+        log-probability of its free tokens; recording is switched on internally), the highest wins (ties: the lowest index),
+        ``llm.select_candidate(best)`` makes its cache the one ``'past_key_values'`` returns, and the dict is the winner's,
+        plus ``'candidates'`` (the n dicts with ``'score'``, ``'text'``, ``'generate_ids'``, ``'has_img_output'``,
+        ``'img_gen_feat'``) and ``'best'``.  The output resampler runs once, on the stacked rows of every candidate that
+        produced an image."""
         if logits_processor is None:
             logits_processor = LogitsProcessorList()
             logits_processor.append(
@@ -143,34 +171,26 @@ class ContinuousLVLM(nn.Module):
         if repetition_penalty not in (None, 1.0) or no_repeat_ngram_size not in (None, 0) or min_new_tokens not in (None, 0):
             rules = dict(repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
                          min_new_tokens=min_new_tokens, spare_img_ids=spare_img_ids)
+        n_ret = 1 if num_return_sequences is None else int(num_return_sequences)
+        want_lp = bool(output_logprobs) or n_ret > 1
         output = self.llm.generate(input_ids=input_ids, inputs_embeds=input_embeds, output_hidden_states=True,
                                    return_dict_in_generate=True, logits_processor=logits_processor,
                                    past_key_values=past_key_values, max_new_tokens=max_new_tokens,
                                    temperature=temperature, num_beams=num_beams, top_p=top_p, do_sample=do_sample,
                                    forced_tokens=forced_tokens, **({"top_k": top_k, "seed": seed} if do_sample else {}), **rules,
-                                   **({"output_logprobs": True, "top_logprobs": top_logprobs} if output_logprobs else {}))
-        output_past_key_values = self.llm.past_key_values
-        generate_ids = output.sequences[0][input_ids.shape[1]:]
+                                   **({"output_logprobs": True, "top_logprobs": top_logprobs} if want_lp else {}),
+                                   **({"num_return_sequences": n_ret} if n_ret > 1 else {}))
         boi_token_id = tokenizer.encode(BOI_TOKEN, add_special_tokens=False)[0]
         eoi_token_id = tokenizer.encode(EOI_TOKEN, add_special_tokens=False)[0]
-
-        last_hidden_states = torch.cat([hs[-1] for hs in output.hidden_states], dim=1)   # (:182)
-        if past_key_values is None:
-            last_hidden_states = last_hidden_states[0, input_ids.shape[1]:, :]
-            eoi_indices = torch.where(generate_ids == eoi_token_id)[0].tolist()
-        else:
-            last_hidden_states = last_hidden_states[0, :, :]
-            hidden_len = last_hidden_states.shape[0]
-            eoi_indices = torch.where(output.sequences[0][-hidden_len:] == eoi_token_id)[0].tolist()
-
-        num_gen_imgs = 1 if len(eoi_indices) > 0 else 0
+        if n_ret > 1:
+            return self._best_of(tokenizer, output, input_ids, past_key_values, logits_processor, eoi_token_id,
+                                 num_img_gen_tokens, bool(output_logprobs))
+        output_past_key_values = self.llm.past_key_values
+        generate_ids = output.sequences[0][input_ids.shape[1]:]
+        img_gen_feats = self._img_rows(output, input_ids, past_key_values, eoi_token_id, num_img_gen_tokens)
+        num_gen_imgs = 1 if img_gen_feats is not None else 0
         has_img_output = num_gen_imgs > 0
-        if has_img_output:
-            e = eoi_indices[-1]
-            img_gen_feats = last_hidden_states[e - num_img_gen_tokens:e].unsqueeze(0).contiguous()  # (:197)
-            img_gen_feat = self._regress(img_gen_feats)                                             # (:205)
-        else:
-            img_gen_feat = None
+        img_gen_feat = self._regress(img_gen_feats) if has_img_output else None                     # (:205)
         generate_text = tokenizer.decode(generate_ids, skip_special_tokens=False)
         # one merged attention map per decoder layer when the LLM ran with config.output_attentions (:162-179): the reference
         # pads the running map with a NaN column per step and concatenates; here every step wrote its row into one NaN-filled
@@ -192,6 +212,54 @@ class ContinuousLVLM(nn.Module):
             'attn_weights': attn_weights,
             'past_key_values': output_past_key_values
         }
+
+    @staticmethod
+    def _img_rows(output, input_ids, past_key_values, eoi_token_id, num_img_gen_tokens):
+        """the ``num_img_gen_tokens`` last-layer rows in front of the last ``</img>`` of a batch-1 output ``[1, n, H]``
+        (:182-197), or None when it produced no image"""
+        generate_ids = output.sequences[0][input_ids.shape[1]:]
+        last_hidden_states = torch.cat([hs[-1] for hs in output.hidden_states], dim=1)   # (:182)
+        if past_key_values is None:
+            last_hidden_states = last_hidden_states[0, input_ids.shape[1]:, :]
+            eoi_indices = torch.where(generate_ids == eoi_token_id)[0].tolist()
+        else:
+            last_hidden_states = last_hidden_states[0, :, :]
+            hidden_len = last_hidden_states.shape[0]
+            eoi_indices = torch.where(output.sequences[0][-hidden_len:] == eoi_token_id)[0].tolist()
+
+        if not eoi_indices:
+            return None
+        e = eoi_indices[-1]
+        return last_hidden_states[e - num_img_gen_tokens:e].unsqueeze(0).contiguous()               # (:197)
+
+    def _best_of(self, tokenizer, output, input_ids, past_key_values, logits_processor, eoi_token_id, num_img_gen_tokens,
+                 output_logprobs):
+        """the dict of ``generate(num_return_sequences=n)``: the winner's, plus ``'candidates'`` and ``'best'``"""
+        img_ids = ()
+        for proc in (logits_processor or []):
+            img_ids = tuple(getattr(proc, "img_ids_list", ()))
+        S = input_ids.shape[1]
+        cands, rows = [], []
+        for c in output.candidates:
+            gen = c.sequences[0][S:]
+            r = self._img_rows(c, input_ids, past_key_values, eoi_token_id, num_img_gen_tokens)
+            rows.append(r)
+            d = {'score': candidate_score(gen, c.model_logprobs, img_ids[1:]),
+                 'text': tokenizer.decode(gen, skip_special_tokens=False), 'generate_ids': gen,
+                 'has_img_output': r is not None, 'img_gen_feat': None, 'num_gen_imgs': 1 if r is not None else 0}
+            if output_logprobs:
+                d.update({'logprobs': c.logprobs, 'model_logprobs': c.model_logprobs,
+                          'top_logprobs': (c.top_logprob_ids, c.top_logprob_values)})
+            cands.append(d)
+        with_img = [i for i, r in enumerate(rows) if r is not None]
+        if with_img:        # ONE pass of the output resampler over every candidate's image rows
+            feats = self._regress(torch.cat([rows[i] for i in with_img], dim=0).contiguous())
+            for j, i in enumerate(with_img):
+                cands[i]['img_gen_feat'] = feats[j:j + 1]
+        best = best_candidate([d['score'] for d in cands])
+        self.llm.select_candidate(best)
+        win = {k: v for k, v in cands[best].items() if k != 'score'}
+        return {**win, 'attn_weights': (), 'past_key_values': self.llm.past_key_values, 'candidates': cands, 'best': best}
 
     @classmethod
     def from_pretrained(cls, llm, input_resampler, output_resampler, pretrained_model_path=None, **kwargs):
