@@ -467,6 +467,22 @@ int ss_process_logits(void* logits, int64_t rows, int64_t vocab, int64_t ld, con
 int ss_token_logprobs(const void* logits, int64_t rows, int64_t vocab, int64_t ld, const int32_t* ids_dev, const ss_sampling* p,
                       int32_t top_n, float* lp_out, int32_t* top_ids_out, float* top_lp_out, int dtype, void* stream);
 
+/* Beam search, one step of the selection (the search itself: ss_llama_beam_search below).
+ * Row b of logits [rows][ld] (vocab <= 65535 entries each, model dtype; only read) is the edited row z of running hypothesis b,
+ * beam_scores[b] (device, fp32) its accumulated score; a score of -inf marks a dead row, which offers nothing (step 0 of a
+ * search is the vector [0, -inf, ...]).  The candidates are  beam_scores[b] + lsm(z_b)[t]  over every live row b and every
+ * token t that carries mass (lsm, NaN and -inf as ss_token_logprobs defines them; fp32, fixed summation order, no atomics).
+ * Written (device): the K = max(2, 1 + n_stop) * rows best, descending, equal scores by ascending b * vocab + t — Hugging Face
+ * leaves ties to torch.topk, this operator does not: cand_score / cand_beam / cand_token [K]; where fewer than K candidates
+ * exist the remaining places hold -inf / -1 / -1.  stop_ids (host, n_stop <= 2 ids inside [0, vocab)) only set K here: which
+ * candidates are finished is the caller's bookkeeping.  rows <= SS_BEAM_MAX.  One block: the rows one after the other, their
+ * lists in LDS, then the merge.  SS_EINVAL before any launch: a NULL pointer, a bad shape, n_stop outside [0, 2], a stop id
+ * outside the row. */
+#define SS_BEAM_MAX 8
+int ss_beam_step(const void* logits, int64_t rows, int64_t vocab, int64_t ld, const float* beam_scores_dev, int32_t n_stop,
+                 const int32_t* stop_ids, float* cand_score_out, int32_t* cand_beam_out, int32_t* cand_token_out, int dtype,
+                 void* stream);
+
 /* ---------------------------------------------------------------------------------------
  * LLaMA decoder engine (native runtime: KV cache, prefill loop, hipGraph-captured decode)
  * ------------------------------------------------------------------------------------- */
@@ -628,7 +644,8 @@ int ss_llama_kv8_invalidate(ss_llama* h, int64_t from_row);
  * which: 0 = K cache [n_layers, n_heads, cache_cap, hd], 1 = V cache (same shape),
  * 2 = generated ids int32[max_new], 3 = hidden rows [max_new, hidden] (post final norm,
  * row j = state whose input token was generated id j; models.py:182-184),
- * 4 = last-token logits [vocab], 5 = state int32[8] {kv_len,pos,n_gen,done,last_id,…}. */
+ * 4 = last-token logits [vocab], 5 = state int32[8] {kv_len,pos,n_gen,done,last_id,…},
+ * 6 = token history int32[cache_cap + max_new] (ss_llama_set_history), 7 = its rule-1 bitmap uint32[ceil(vocab / 32)]. */
 void* ss_llama_buffer(ss_llama* h, int which);
 
 /* Set / get the live KV length and next rope position (host view).  Truncating the cache
@@ -656,6 +673,64 @@ int ss_llama_kv_gather(ss_llama* h, const int32_t* keep_idx_dev, int64_t n_keep,
  * SS_EINVAL before anything is launched or any host view changes: h or host_dst NULL, src outside [0, n_seq), n_dst < 1, a
  * destination out of range, equal to src, or listed twice. */
 int ss_llama_fork(ss_llama* h, int32_t src, const int32_t* host_dst, int32_t n_dst, void* stream);
+
+/* Beam search over forked slots, on the device inside the captured decode token.
+ * The prompt is on slot 0 (prefilled, its last-token logits in place).  The call forks slot 0 to slots 1 .. n-1
+ * (ss_llama_fork), then runs the decode loop on slots [0, n) with the token opened by three kernels instead of the arg max:
+ *   [logits_rules]  each slot's history rules, when on (they must be on for all n slots or for none)
+ *   beam_topk       one block per slot: image-token processor edit, then the K best of  running score + lsm(z)  (ss_beam_step)
+ *   beam_advance    one block: merge to the K best overall, the update below, parent[n] / token[n], the slots' generated ids,
+ *                   last-id / n-generated words and embedding rows; the done word of every slot once the search is over
+ *   beam_permute    K and V rows [kv0, kv_len) of every layer and head follow parent[] (kv0 = the cache length at the start:
+ *                   the shared prompt below it never moves); one thread per 16-byte packet position across the n slots loads
+ *                   from every parent, then stores to every slot whose parent is another slot, so cycles and fan-out are safe
+ *                   in one launch; an all-identity parent[] stores nothing.  With rules on, the history suffix and the rule-1
+ *                   bitmap follow in one more small launch.
+ * then the layers and lm_head, unchanged.  One graph per (n, n_steps, workspace).
+ * Definition (Hugging Face transformers 5.x GenerationMixin._beam_search and its helpers, one batch item): the running
+ * scores start as [0, dead ...]; per step t = 0, 1, ... the K = max(2, 1 + stop ids) * n best candidates are taken (stop ids:
+ * the engine's eos_id and the id of ss_llama_set_stop_id); a candidate whose token is a stop id, or with t + 1 >= n_steps, is
+ * finished; the n best unfinished ones run on; the finished ones among the first n enter the finished table with score
+ * sum / (t + 1) ** length_penalty, which keeps its n best, sorted (equal scores: the older entry first); once the table is
+ * full the sticky heuristic  best running sum / hyp ** length_penalty > worst table score  (hyp = t + 1, or n_steps for
+ * early_stopping "never" with length_penalty > 0) must hold for the search to go on; it also ends when the table is full and
+ * early_stopping is True, when every candidate of the step was finished, or when no hypothesis is left running.
+ * DEVIATION from Hugging Face: the row scores are the log-softmax of the row AFTER the history rules and the image-token
+ * processor; HF hands its processors the log-softmax row, on which the image-token processor's `scores[ids] = 0.0` would
+ * turn 65 ids into probability 1 — the reference's own num_beams > 1 cannot work, so there is nothing to be compatible with.
+ * NaN and -inf entries offer no candidate.
+ * ss_beam_state is the head of the caller-owned workspace of ss_llama_beam_bytes() bytes (device memory, 16-byte aligned, owned
+ * as the planes of ss_llama_set_kv8 are); it is readable after the call: fin_* sorted best first, the sequences behind it as
+ * int32 [2][n][max_new] running | [2][n][max_new] finished at byte offset ss_llama_beam_seq_offset(), buffer (step & 1) current.
+ * Afterwards slots [0, n) hold the running hypotheses' caches; the caller puts the slot it goes on with back in shape
+ * (ss_llama_set_lengths + ss_llama_prefill of the winner).
+ * SS_EINVAL before any launch or state change: num_beams outside [1, min(n_seq, 8)], a selected slot other than 0, the fp8 KV
+ * shadow on (permuting the shadow is not built), attention capture on, log-probability recording or sampling on for a slot
+ * of the group, rules on for only some of them, n_steps outside [1, max_new], a non-finite length_penalty, early_stopping
+ * outside 0..2, a cache, position or history overflow. */
+typedef struct ss_beam_params {
+    int32_t num_beams;
+    float length_penalty;
+    int32_t early_stopping;     /* 0 False, 1 True, 2 "never" */
+} ss_beam_params;
+typedef struct ss_beam_state {
+    int32_t n, K, n_stop, stop_ids[2], limit, max_new, early_stopping;
+    float length_penalty;
+    int32_t kv0, hist0, step, unsat, ended, pad[2];
+    float run_score[SS_BEAM_MAX];       /* running hypotheses: accumulated score, live flag */
+    int32_t run_live[SS_BEAM_MAX];
+    float fin_score[SS_BEAM_MAX];       /* finished table, best first: score, length, valid flag */
+    int32_t fin_len[SS_BEAM_MAX], fin_flag[SS_BEAM_MAX];
+    int32_t parent[SS_BEAM_MAX], token[SS_BEAM_MAX];    /* of the last step */
+} ss_beam_state;
+size_t ss_llama_beam_bytes(const ss_llama_config* cfg, int32_t num_beams);
+size_t ss_llama_beam_seq_offset(void);
+int ss_llama_beam_search(ss_llama* h, const ss_beam_params* p, void* beam_ws, int64_t n_steps, int32_t last_prompt_id,
+                         void* stream);
+/* test hook: one beam_permute (+ the history launch when rules are on for slot 0) of slots [0, n) with parent[] (host) over the
+ * cache rows [kv0, kv_len of slot 0) and history entries [hist0, history length of slot 0), through `beam_ws`.  Same refusals. */
+int ss_llama_beam_permute(ss_llama* h, void* beam_ws, const int32_t* host_parent, int32_t n, int64_t kv0, int64_t hist0,
+                          void* stream);
 
 /* LlamaModel.forward on M new rows against the cached prefix (prefill when the cache is
  * empty, bottom-right-causal continuation otherwise) — modeling_llama_xformer.py:532-666.

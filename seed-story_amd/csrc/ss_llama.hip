@@ -18,6 +18,8 @@
 //    watermark per slot says how many shadow rows are valid; the decode entry points quantise the rest in one launch up front.
 //  * slot fork (ss_llama_fork): one slot's cache rows, last logits, lengths and history copied to up to 7 others on the device,
 //    each packet read once and written to all of them — n sampled continuations of one prompt cost one prefill.
+//  * beam search (ss_llama_beam_search, ss_beam.h): slots [0, n) carry the running hypotheses; the token is opened by top-K,
+//    advance and a cycle-safe permutation of the slots' cache suffixes instead of the arg max, inside the same captured graph.
 #include <stddef.h>
 #include <string.h>
 
@@ -29,6 +31,7 @@
 #include "ss_rules.h"
 #include "ss_kv8.h"
 #include "ss_logprob.h"
+#include "ss_beam.h"
 
 namespace ss {
 
@@ -456,6 +459,8 @@ struct SeqGraph {
     int rules;               // a slot of [seq0, seq0+nb) has history rules on (ss_llama_set_logits_rules): the rules kernel in front
     int kv8;                 // fp8 KV shadow on (ss_llama_set_kv8): another attention kernel, the planes' pointers
     int logprobs;            // a slot of [seq0, seq0+nb) records log-probabilities (ss_llama_set_logprobs): two more kernels; the buffers are NOT part of the key
+    int beam;                // beam search (ss_llama_beam_search): other opening kernels; 0 = none, else n_steps * 16 + n (the permute's grid)
+    void* beam_ws;           // ... over this workspace (its pointers are kernel arguments)
     hipGraph_t graph;
     hipGraphExec_t exec;
 };
@@ -527,6 +532,9 @@ struct ss_llama {
         for (int b = seq0; b < seq0 + nb; ++b) if (lp_on[b]) return true;
         return false;
     }
+    // beam search (ss_llama_beam_search): the caller's workspace while a search runs, hdr == NULL otherwise
+    BeamPtrs beam = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    int beam_rows = 0;                  // its n_steps: the suffix rows the permute's grid covers
     int64_t hist_cap() const { return (int64_t)cfg.cache_cap + cfg.max_new; }
     int bm_words() const { return rules_bitmap_words(cfg.vocab); }
     size_t plane_bytes() const { return (size_t)cfg.n_heads * cfg.cache_cap * hd * esz; }       // one layer of one slot
@@ -689,6 +697,41 @@ static int final_norm_advance_launch(ss_llama* h, int seq0, int nb, hipStream_t 
     return SS_OK;
 }
 
+static const BeamSt kBeamSt = {ST_KV_LEN, ST_NGEN, ST_DONE, ST_LAST, ST_WORDS};
+
+// the cache permutation of a beam step (+ the history's when rules are on): slots [0, n), suffix rows up to `rows`
+static int beam_permute_launch(ss_llama* h, int rows, bool rules, hipStream_t s) {
+    const ss_llama_config& g = h->cfg;
+    const int ppr = (int)((size_t)h->hd * h->esz / 16);
+    const int64_t units = (int64_t)g.n_layers * g.n_heads, unit_stride = (int64_t)g.cache_cap * ppr;
+    hipLaunchKernelGGL(beam_permute_kernel, dim3((unsigned)cdiv((int64_t)rows * ppr, 256), (unsigned)units, 2), dim3(256), 0, s,
+                       (uint4*)h->kc, (uint4*)h->vc, units * unit_stride, unit_stride, ppr, h->state, kBeamSt, h->beam.hdr);
+    SS_LAUNCH_CHECK("beam_permute");
+    if (rules) {
+        const int m = h->bm_words() > rows ? h->bm_words() : rows;
+        hipLaunchKernelGGL(beam_hist_permute_kernel, dim3((unsigned)cdiv(m, 256)), dim3(256), 0, s, h->hist, h->hist_cap(), h->hist_bm,
+                           h->bm_words(), &h->rules[0].hist_len, h->state, kBeamSt, h->beam.hdr);
+        SS_LAUNCH_CHECK("beam_hist_permute");
+    }
+    return SS_OK;
+}
+
+// the opening of a beam-search token for slots [0, n): top-K per row, advance, permute
+template <typename T>
+static int beam_open_launch(ss_llama* h, int n, bool rules, hipStream_t s) {
+    const ss_llama_config& g = h->cfg;
+#define SS_BEAM_TOPK_ARGS dim3((unsigned)n), dim3(1024), 0, s, (T*)h->logits, g.vocab, h->state, kBeamSt, h->img_ids, g.n_img_ids,   \
+                          h->beam.hdr, h->beam.cand_score, h->beam.cand_tok
+    if (logprob_ept_half_fits(g.vocab)) hipLaunchKernelGGL((beam_topk_kernel<T, kLpEptFull / 2>), SS_BEAM_TOPK_ARGS);
+    else hipLaunchKernelGGL((beam_topk_kernel<T, kLpEptFull>), SS_BEAM_TOPK_ARGS);
+#undef SS_BEAM_TOPK_ARGS
+    SS_LAUNCH_CHECK("beam_topk");
+    hipLaunchKernelGGL(beam_advance_kernel<T>, dim3(1), dim3(1024), 0, s, h->beam.hdr, h->beam.cand_score, h->beam.cand_tok,
+                       h->beam.run_seq, h->beam.fin_seq, h->state, kBeamSt, h->gen_ids, (const T*)h->w.embed, (T*)h->x, g.hidden);
+    SS_LAUNCH_CHECK("beam_advance");
+    return beam_permute_launch(h, h->beam_rows, rules, s);
+}
+
 static int decode_token(ss_llama* h, hipStream_t s, ProfSink* prof, int seq0, int nb) {
     const ss_llama_config& g = h->cfg;
     const int dt = g.dtype;
@@ -716,8 +759,10 @@ static int decode_token(ss_llama* h, hipStream_t s, ProfSink* prof, int seq0, in
     if (lp && (rc = SS_DISPATCH(dt, logprob_raw_launch, h, seq0, nb, s))) return rc;
     // history rules on for a slot: its row is edited before the opening kernel reads it (off everywhere, the default: no launch)
     if (h->rules_in(seq0, nb) && (rc = SS_DISPATCH(dt, logits_rules_launch, h, seq0, nb, 0, s))) return rc;
+    // a beam search runs on these slots (seq0 = 0): its three kernels open the token
+    if (h->beam.hdr) rc = SS_DISPATCH(dt, beam_open_launch, h, nb, h->rules_in(seq0, nb), s);
     // greedy slots only (the default): the launch it has always been
-    if (h->sampling_in(seq0, nb)) rc = SS_DISPATCH(dt, sample_embed_draw_launch, h, seq0, nb, lp, s);
+    else if (h->sampling_in(seq0, nb)) rc = SS_DISPATCH(dt, sample_embed_draw_launch, h, seq0, nb, lp, s);
     else rc = SS_DISPATCH(dt, sample_embed_launch, h, seq0, nb, s);
     if (rc) return rc;
     if (lp && (rc = SS_DISPATCH(dt, logprob_tok_launch, h, seq0, nb, s))) return rc;
@@ -788,15 +833,17 @@ static int graph_for(ss_llama* h, int seq0, int nb, hipGraphExec_t* out) {
     const int rules = h->rules_in(seq0, nb) ? 1 : 0;
     const int kv8 = h->kq ? 1 : 0;
     const int logprobs = h->logprobs_in(seq0, nb) ? 1 : 0;
+    const int beam = h->beam.hdr ? h->beam_rows * 16 + nb : 0;
+    void* const beam_ws = h->beam.hdr;
     for (const SeqGraph& sg : h->graphs)
         if (sg.seq0 == seq0 && sg.nb == nb && sg.mode == mode && sg.capture == capture && sg.w8 == w8 && sg.sampling == sampling &&
-            sg.rules == rules && sg.kv8 == kv8 && sg.logprobs == logprobs) {
+            sg.rules == rules && sg.kv8 == kv8 && sg.logprobs == logprobs && sg.beam == beam && sg.beam_ws == beam_ws) {
             *out = sg.exec;
             return SS_OK;
         }
     SeqGraph sg;
     sg.seq0 = seq0; sg.nb = nb; sg.mode = mode; sg.capture = capture; sg.w8 = w8; sg.sampling = sampling; sg.rules = rules; sg.kv8 = kv8;
-    sg.logprobs = logprobs;
+    sg.logprobs = logprobs; sg.beam = beam; sg.beam_ws = beam_ws;
     sg.graph = nullptr; sg.exec = nullptr;
     SS_HIP(hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
     int rc = decode_token(h, h->cap_stream, nullptr, seq0, nb);
@@ -1334,6 +1381,8 @@ void* ss_llama_buffer(ss_llama* h, int which) {
         case 3: return h->hid_rows + q * (size_t)g.max_new * g.hidden * h->esz;
         case 4: return h->logits + q * (size_t)g.vocab * h->esz;
         case 5: return h->state + q * ST_WORDS;
+        case 6: return h->hist + q * (size_t)h->hist_cap();
+        case 7: return h->hist_bm + q * (size_t)h->bm_words();
         default: return nullptr;
     }
 }
@@ -1519,6 +1568,108 @@ int ss_llama_generate_batch(ss_llama* h, int64_t n_steps, const int32_t* last_pr
     if (host_n_generated)
         for (int b = 0; b < h->n_seq; ++b) host_n_generated[b] = h->pinned[b * ST_WORDS + ST_NGEN];
     return SS_OK;
+}
+
+size_t ss_llama_beam_bytes(const ss_llama_config* cfg, int32_t num_beams) {
+    if (!cfg || num_beams < 1 || num_beams > kBeamMax || cfg->max_new <= 0) return 0;
+    return beam_state_bytes(num_beams, cfg->max_new);
+}
+
+size_t ss_llama_beam_seq_offset(void) { return beam_seq_off(); }
+
+// what every beam entry point refuses, before anything is launched or changed
+static int beam_refusals(const ss_llama* h, const void* beam_ws, int n, const char* who) {
+    SS_REQUIRE(h && beam_ws, "%s: null argument", who);
+    SS_REQUIRE(((size_t)beam_ws & 15) == 0, "%s: the workspace must be 16-byte aligned", who);
+    SS_REQUIRE(n >= 1 && n <= h->n_seq && n <= kBeamMax, "%s: num_beams %d outside [1, min(n_seq = %d, %d)]", who, n, h->n_seq, kBeamMax);
+    SS_REQUIRE(h->cur == 0, "%s: the prompt must be on slot 0 (slot %d is selected)", who, h->cur);
+    SS_REQUIRE(!h->kq, "%s: the fp8 KV shadow is on; permuting the shadow is not built (ss_llama_set_kv8 off first)", who);
+    SS_REQUIRE(!h->cap.maps, "%s: attention capture is a single-sequence tool", who);
+    SS_REQUIRE(!h->logprobs_in(0, n), "%s: a slot of the group records log-probabilities", who);
+    SS_REQUIRE(!h->sampling_in(0, n), "%s: a slot of the group has sampling on (beam-search sampling is not built)", who);
+    for (int b = 1; b < n; ++b)
+        SS_REQUIRE(h->rules_on[b] == h->rules_on[0], "%s: history rules are on for only some slots of the group", who);
+    SS_REQUIRE(((size_t)h->hd * h->esz) % 16 == 0, "%s: a cache row of %zu bytes is no multiple of the 16-byte packet", who,
+               (size_t)h->hd * h->esz);
+    return SS_OK;
+}
+
+int ss_llama_beam_search(ss_llama* h, const ss_beam_params* p, void* beam_ws, int64_t n_steps, int32_t last_prompt_id,
+                         void* stream) {
+    SS_REQUIRE(h && p, "llama_beam_search: null argument");
+    const int n = p->num_beams;
+    if (int rc = beam_refusals(h, beam_ws, n, "llama_beam_search")) return rc;
+    const ss_llama_config& g = h->cfg;
+    hipStream_t s = (hipStream_t)stream;
+    SS_REQUIRE(n_steps >= 1 && n_steps <= g.max_new, "llama_beam_search: n_steps %lld outside [1, max_new = %d]", (long long)n_steps,
+               g.max_new);
+    SS_REQUIRE(p->length_penalty == p->length_penalty && p->length_penalty <= 3.4028234e38f && p->length_penalty >= -3.4028234e38f,
+               "llama_beam_search: length_penalty must be finite");
+    SS_REQUIRE(p->early_stopping >= 0 && p->early_stopping <= 2, "llama_beam_search: early_stopping %d outside 0..2 (False, True, never)",
+               (int)p->early_stopping);
+    SS_REQUIRE(h->kv_len[0] + n_steps <= g.cache_cap, "llama_beam_search: KV cache overflow (%lld + %lld > %d)", (long long)h->kv_len[0],
+               (long long)n_steps, g.cache_cap);
+    SS_REQUIRE(h->pos[0] + n_steps <= g.max_pos, "llama_beam_search: position overflow (%lld + %lld > %d)", (long long)h->pos[0],
+               (long long)n_steps, g.max_pos);
+    if (int hrc = history_fits(h, 0, n_steps, "llama_beam_search")) return hrc;
+    int rc;
+    if (n > 1) {
+        int32_t dst[kBeamMax];
+        for (int b = 1; b < n; ++b) dst[b - 1] = b;
+        if ((rc = ss_llama_fork(h, 0, dst, n - 1, stream))) return rc;
+    }
+    BeamHdr hd;
+    memset(&hd, 0, sizeof(hd));
+    hd.n = n;
+    hd.stop_ids[0] = hd.stop_ids[1] = -1;
+    if (g.eos_id >= 0) hd.stop_ids[hd.n_stop++] = g.eos_id;
+    if (h->stop2 >= 0 && h->stop2 != g.eos_id) hd.stop_ids[hd.n_stop++] = h->stop2;
+    hd.K = (hd.n_stop + 1 > 2 ? hd.n_stop + 1 : 2) * n;
+    hd.limit = (int32_t)n_steps; hd.max_new = g.max_new; hd.early_stopping = p->early_stopping;
+    hd.length_penalty = p->length_penalty;
+    hd.kv0 = (int32_t)h->kv_len[0]; hd.hist0 = (int32_t)h->hist_len[0];
+    hd.unsat = 1;
+    for (int b = 0; b < kBeamMax; ++b) {
+        hd.run_score[b] = b == 0 ? 0.f : -INFINITY;
+        hd.run_live[b] = b == 0 ? 1 : 0;
+        hd.fin_score[b] = -INFINITY;
+        hd.parent[b] = b;
+    }
+    // (pageable source: the copy is staged before the call returns)
+    SS_HIP(hipMemcpyAsync(beam_ws, &hd, sizeof(hd), hipMemcpyHostToDevice, s));
+    for (int b = 0; b < n; ++b) stage_seq(h, b, n_steps, last_prompt_id, nullptr, 0, true);
+    h->beam = beam_ptrs(beam_ws, n, g.max_new);
+    h->beam_rows = (int)n_steps;
+    rc = run_decode(h, 0, n, n_steps, s);
+    h->beam.hdr = nullptr;
+    return rc;
+}
+
+int ss_llama_beam_permute(ss_llama* h, void* beam_ws, const int32_t* host_parent, int32_t n, int64_t kv0, int64_t hist0,
+                          void* stream) {
+    SS_REQUIRE(host_parent, "llama_beam_permute: null argument");
+    if (int rc = beam_refusals(h, beam_ws, n, "llama_beam_permute")) return rc;
+    const int64_t kv = h->kv_len[0];
+    SS_REQUIRE(kv0 >= 0 && kv0 <= kv && hist0 >= 0 && hist0 <= h->hist_len[0], "llama_beam_permute: kv0 %lld / hist0 %lld out of range",
+               (long long)kv0, (long long)hist0);
+    BeamHdr hd;
+    memset(&hd, 0, sizeof(hd));
+    hd.n = n; hd.kv0 = (int32_t)kv0; hd.hist0 = (int32_t)hist0;
+    for (int b = 0; b < kBeamMax; ++b) hd.parent[b] = b;
+    for (int b = 0; b < n; ++b) {
+        SS_REQUIRE(host_parent[b] >= 0 && host_parent[b] < n, "llama_beam_permute: parent[%d] = %d outside [0, %d)", b, (int)host_parent[b], n);
+        hd.parent[b] = host_parent[b];
+    }
+    hipStream_t s = (hipStream_t)stream;
+    SS_HIP(hipMemcpyAsync(beam_ws, &hd, sizeof(hd), hipMemcpyHostToDevice, s));
+    // the device words the kernels read: slot 0 not done, its cache length
+    hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(64), 0, s, h->state, (int)ST_DONE, 0, (int)ST_KV_LEN, (int)kv);
+    SS_LAUNCH_CHECK("set_state");
+    const int64_t span = kv - kv0 > h->hist_len[0] - hist0 ? kv - kv0 : h->hist_len[0] - hist0;
+    h->beam = beam_ptrs(beam_ws, n, h->cfg.max_new);
+    int rc = span > 0 ? beam_permute_launch(h, (int)span, h->rules_on[0] != 0, s) : SS_OK;
+    h->beam.hdr = nullptr;
+    return rc;
 }
 
 int ss_llama_profile_decode(ss_llama* h, int64_t n_tokens, float out_ms[8], double out_bytes[4], void* stream) {

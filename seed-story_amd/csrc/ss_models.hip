@@ -11,6 +11,7 @@
 #include "ss_sample.h"
 #include "ss_rules.h"
 #include "ss_logprob.h"
+#include "ss_beam.h"
 
 namespace ss {
 int gemm_dev(const void* A, const void* W, void* C, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldw,
@@ -156,6 +157,20 @@ int token_logprobs_launch(const void* logits, int64_t rows, int64_t vocab, int64
     return SS_OK;
 }
 
+// ss_beam_step: one block, the rows one after the other
+template <typename T>
+int beam_step_launch(const void* logits, int64_t rows, int64_t vocab, int64_t ld, const float* beam_scores, int K, float* cand_score,
+                     int32_t* cand_beam, int32_t* cand_tok, hipStream_t s) {
+    if (logprob_ept_half_fits(vocab))
+        hipLaunchKernelGGL((beam_step_kernel<T, kLpEptFull / 2>), dim3(1), dim3(1024), 0, s, (const T*)logits, (int)rows, (int)vocab, ld,
+                           beam_scores, K, cand_score, cand_beam, cand_tok);
+    else
+        hipLaunchKernelGGL((beam_step_kernel<T, kLpEptFull>), dim3(1), dim3(1024), 0, s, (const T*)logits, (int)rows, (int)vocab, ld,
+                           beam_scores, K, cand_score, cand_beam, cand_tok);
+    SS_LAUNCH_CHECK("beam_step");
+    return SS_OK;
+}
+
 struct Bump {
     char* p; size_t off, cap;
     void* take(size_t bytes) { void* r = p + off; off += (bytes + 255) / 256 * 256; return r; }
@@ -218,6 +233,21 @@ int ss_token_logprobs(const void* logits, int64_t rows, int64_t vocab, int64_t l
         if (int rc = sampling_params(p, "token_logprobs", &sp)) return rc;
     return SS_DISPATCH(dtype, token_logprobs_launch, logits, rows, vocab, ld, ids_dev, p ? &sp : nullptr, (int)top_n, lp_out,
                        top_ids_out, top_lp_out, (hipStream_t)stream);
+}
+
+int ss_beam_step(const void* logits, int64_t rows, int64_t vocab, int64_t ld, const float* beam_scores_dev, int32_t n_stop,
+                 const int32_t* stop_ids, float* cand_score_out, int32_t* cand_beam_out, int32_t* cand_token_out, int dtype,
+                 void* stream) {
+    SS_REQUIRE(logits && beam_scores_dev && cand_score_out && cand_beam_out && cand_token_out, "beam_step: null argument");
+    SS_REQUIRE(rows > 0 && rows <= SS_BEAM_MAX && vocab > 0 && vocab <= 65535 && ld >= vocab,
+               "beam_step: bad shape (rows=%lld vocab=%lld ld=%lld; rows <= %d, vocab <= 65535)", (long long)rows, (long long)vocab,
+               (long long)ld, SS_BEAM_MAX);
+    SS_REQUIRE(n_stop >= 0 && n_stop <= 2 && (stop_ids || n_stop == 0), "beam_step: n_stop %d outside [0, 2]", (int)n_stop);
+    for (int i = 0; i < n_stop; ++i)
+        SS_REQUIRE(stop_ids[i] >= 0 && stop_ids[i] < vocab, "beam_step: stop id %d outside [0, %lld)", (int)stop_ids[i], (long long)vocab);
+    const int K = (n_stop + 1 > 2 ? n_stop + 1 : 2) * (int)rows;
+    return SS_DISPATCH(dtype, beam_step_launch, logits, rows, vocab, ld, beam_scores_dev, K, cand_score_out, cand_beam_out,
+                       cand_token_out, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -43,6 +43,22 @@ class LogitsRules(C.Structure):
     _fields_ = [("repetition_penalty", f32), ("no_repeat_ngram", i32), ("min_new_tokens", i32), ("spare_img_ids", i32)]
 
 
+class BeamParams(C.Structure):
+    _fields_ = [("num_beams", i32), ("length_penalty", f32), ("early_stopping", i32)]
+
+
+BEAM_MAX = 8
+
+
+class BeamState(C.Structure):
+    """``ss_beam_state``: the head of a beam-search workspace."""
+    _fields_ = [("n", i32), ("K", i32), ("n_stop", i32), ("stop_ids", i32 * 2), ("limit", i32), ("max_new", i32),
+                ("early_stopping", i32), ("length_penalty", f32), ("kv0", i32), ("hist0", i32), ("step", i32), ("unsat", i32),
+                ("ended", i32), ("pad", i32 * 2), ("run_score", f32 * BEAM_MAX), ("run_live", i32 * BEAM_MAX),
+                ("fin_score", f32 * BEAM_MAX), ("fin_len", i32 * BEAM_MAX), ("fin_flag", i32 * BEAM_MAX),
+                ("parent", i32 * BEAM_MAX), ("token", i32 * BEAM_MAX)]
+
+
 class LlamaWeights(C.Structure):
     _fields_ = [("embed", vp), ("lm_head", vp), ("final_norm", vp), ("rope_cos", vp), ("rope_sin", vp),
                 ("layers", C.POINTER(LlamaLayerWeights))]
@@ -126,6 +142,7 @@ PROTOTYPES = {
     "ss_sample_logits": (C.c_int, [vp, i64, i64, i64, C.POINTER(Sampling), vp, C.c_uint32, vp, vp, i64, vp, vp, C.c_int, vp]),
     "ss_process_logits": (C.c_int, [vp, i64, i64, i64, C.POINTER(LogitsRules), vp, i64, vp, vp, i32, vp, i64, C.c_int, vp]),
     "ss_token_logprobs": (C.c_int, [vp, i64, i64, i64, vp, C.POINTER(Sampling), i32, vp, vp, vp, C.c_int, vp]),
+    "ss_beam_step": (C.c_int, [vp, i64, i64, i64, vp, i32, i32p, vp, vp, vp, C.c_int, vp]),
     "ss_llama_workspace_bytes": (sz, [C.POINTER(LlamaConfig), i64]),
     "ss_llama_create": (C.c_int, [C.POINTER(LlamaConfig), C.POINTER(LlamaWeights), vp, sz, i64, i32p,
                                   C.POINTER(vp)]),
@@ -146,6 +163,10 @@ PROTOTYPES = {
     "ss_llama_get_lengths": (C.c_int, [vp, C.POINTER(i64), C.POINTER(i64)]),
     "ss_llama_kv_gather": (C.c_int, [vp, vp, i64, vp]),
     "ss_llama_fork": (C.c_int, [vp, i32, i32p, i32, vp]),
+    "ss_llama_beam_bytes": (sz, [C.POINTER(LlamaConfig), i32]),
+    "ss_llama_beam_seq_offset": (sz, []),
+    "ss_llama_beam_search": (C.c_int, [vp, C.POINTER(BeamParams), vp, i64, i32, vp]),
+    "ss_llama_beam_permute": (C.c_int, [vp, vp, i32p, i32, i64, i64, vp]),
     "ss_llama_prefill": (C.c_int, [vp, vp, i64, vp, vp, vp]),
     "ss_llama_prefill_batch": (C.c_int, [vp, vp, C.POINTER(i64), vp, vp]),
     "ss_llama_generate": (C.c_int, [vp, i64, i32, i32p, i64, C.POINTER(i64), vp]),

@@ -202,6 +202,17 @@ class LlamaEngine:
     def state(self):
         return self._buf(5, (8,), torch.int32)
 
+    @property
+    def history(self):
+        """int32 ``[cache_cap + max_new]`` view of the selected slot's token history (``set_history``); its length is the
+        engine's"""
+        return self._buf(6, (self.cache_cap + self.max_new,), torch.int32)
+
+    @property
+    def history_bitmap(self):
+        """int32 ``[ceil(vocab / 32)]`` view of the rule-1 bitmap of the selected slot's history (one bit per id)"""
+        return self._buf(7, ((self.vocab + 31) // 32,), torch.int32)
+
     # ---- lengths / cache management --------------------------------------------------------------
     def lengths(self):
         kv, pos = C.c_int64(), C.c_int64()
@@ -627,6 +638,63 @@ class LlamaEngine:
         check(lib().ss_llama_generate_batch(self._h, n_steps, last, flat, ld, nf, act, out, ops.stream()),
               "ss_llama_generate_batch")
         return [int(v) for v in out]
+
+    # ---- beam search --------------------------------------------------------------------------------------------
+    _EARLY = {False: 0, True: 1, "never": 2}
+
+    def _beam_ws(self, n):
+        """the engine's beam-search workspace for ``n`` beams (kept: its address is part of the captured graph's key)"""
+        ws = getattr(self, "_beam_bufs", None)
+        if ws is None:
+            ws = self._beam_bufs = {}
+        if n not in ws:
+            nbytes = lib().ss_llama_beam_bytes(C.byref(self._cfg), n)
+            if nbytes == 0:
+                raise _lib.SSError("beam_search: num_beams %d outside [1, 8]" % n)
+            ws[n] = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
+            torch.cuda.current_stream(self.device).synchronize()
+        return ws[n]
+
+    def beam_search(self, n_steps, last_prompt_id, num_beams, length_penalty=1.0, early_stopping=False):
+        """Beam search from the current logits of slot 0, on the device inside the captured decode token
+        (``ss_llama_beam_search``; the definition — Hugging Face's ``_beam_search`` on the log-softmax of the row after the
+        history rules and the image-token processor, ties by ascending ``beam * vocab + token`` — is in
+        include/seedstory_hip.h).  Slot 0 is forked to slots 1 .. ``num_beams`` - 1, which then carry the running hypotheses;
+        stop ids are the engine's ``eos_id`` and the id of ``set_stop_id``.  Returns ``{"sequences": list of n id lists,
+        "scores": float32 [n], "finished": bool [n]}``, the finished table best first (entries never filled: ``[]``, -inf,
+        False).  Afterwards the slots hold the RUNNING hypotheses' caches: rewind (``set_lengths``) and feed the winner to go on
+        from it.  Refused with ``SSError`` before anything changes: see the header."""
+        n = int(num_beams)
+        if early_stopping not in (False, True, "never"):
+            raise _lib.SSError("early_stopping must be False, True or 'never', not %r" % (early_stopping,))
+        if not -2 ** 31 <= n < 2 ** 31 or not -2 ** 63 <= int(n_steps) < 2 ** 63:
+            raise _lib.SSError("beam_search: num_beams / n_steps out of the integer range")
+        if not 1 <= n <= min(self.n_seq, _lib.BEAM_MAX):
+            raise _lib.SSError("beam_search: num_beams %d outside [1, min(n_seq = %d, %d)]" % (n, self.n_seq, _lib.BEAM_MAX))
+        ws = self._beam_ws(n)
+        bp = _lib.BeamParams(n, float(length_penalty), self._EARLY[early_stopping])
+        check(lib().ss_llama_beam_search(self._h, C.byref(bp), ws.data_ptr(), int(n_steps), int(last_prompt_id), ops.stream()),
+              "ss_llama_beam_search")
+        return self._beam_result(ws, n)
+
+    def _beam_result(self, ws, n):
+        host = ws.cpu()         # (the search has synchronised: the state is final)
+        st = _lib.BeamState.from_buffer_copy(host[:C.sizeof(_lib.BeamState)].numpy().tobytes())
+        off = lib().ss_llama_beam_seq_offset()
+        seqs = host[off:off + 4 * n * self.max_new * 4].view(torch.int32).view(2, 2, n, self.max_new)  # running | finished
+        fin = seqs[1, st.step & 1]
+        flags = [bool(st.fin_flag[i]) for i in range(n)]
+        self.last_beam_state = st
+        return {"sequences": [fin[i, :st.fin_len[i]].tolist() if flags[i] else [] for i in range(n)],
+                "scores": torch.tensor([st.fin_score[i] for i in range(n)], dtype=torch.float32),
+                "finished": torch.tensor(flags, dtype=torch.bool)}
+
+    def _beam_permute(self, parent, kv0, hist0=0):
+        """test hook (``ss_llama_beam_permute``): one cache / history permutation of slots [0, len(parent)) by ``parent``"""
+        n = len(parent)
+        arr = (C.c_int32 * max(1, n))(*[int(b) for b in parent])
+        check(lib().ss_llama_beam_permute(self._h, self._beam_ws(n).data_ptr(), arr, n, int(kv0), int(hist0), ops.stream()),
+              "ss_llama_beam_permute")
 
     # ---- image-token block decode ---------------------------------------------------------------------------
     # After ``<img>`` the logits processor FORCES the next 65 tokens (``<img_00000>`` .. ``<img_00063>``, ``</img>``:

@@ -498,6 +498,42 @@ def token_logprobs(logits, ids, sampling=None, top_n=0):
     return (lp, tid, tlp) if top_n > 0 else lp
 
 
+def beam_step(logits, beam_scores, stop_ids=(), out=None):
+    """One selection step of a beam search (``ss_beam_step`` in include/seedstory_hip.h): row b of ``logits`` [rows, vocab]
+    (rows <= 8; only read) is running hypothesis b's edited row, ``beam_scores`` float32 [rows] its accumulated score, -inf for
+    a dead row.  Returns ``(scores float32 [K], beams int32 [K], tokens int32 [K])``, the K = max(2, 1 + len(stop_ids)) * rows
+    best of ``beam_scores[b] + log_softmax(row b)[t]``, descending, equal scores by ascending ``b * vocab + t``; -inf / -1 / -1
+    where fewer candidates carry mass.  ``out`` = a caller's three buffers of those shapes."""
+    if not logits.is_cuda:
+        raise _lib.SSError("logits must live on the GPU (there is no CPU path)")
+    lg = logits if logits.dim() == 2 else logits.view(1, -1)
+    if lg.dim() != 2 or (lg.shape[1] > 1 and lg.stride(1) != 1) or (lg.shape[0] > 1 and lg.stride(0) < lg.shape[1]):
+        raise _lib.SSError("logits must be [rows, vocab] with unit stride inside a row")
+    rows, vocab = lg.shape
+    dev = lg.device
+    sc = torch.as_tensor(beam_scores, dtype=torch.float32, device=dev).reshape(-1).contiguous()
+    if sc.numel() != rows:
+        raise _lib.SSError("beam_scores must hold one score per row (%d), not %d" % (rows, sc.numel()))
+    stops = [int(t) for t in stop_ids]
+    for t in stops:
+        if not -2 ** 31 <= t < 2 ** 31:
+            raise _lib.SSError("beam_step: stop id %d is no int32" % t)
+    K = max(2, 1 + len(stops)) * rows
+    if out is None:
+        out = (torch.empty(K, dtype=torch.float32, device=dev), torch.empty(K, dtype=torch.int32, device=dev),
+               torch.empty(K, dtype=torch.int32, device=dev))
+    cs, cb, ct = out
+    for t, d in ((cs, torch.float32), (cb, torch.int32), (ct, torch.int32)):
+        _req(t, "beam_step(out=)")
+        if t.numel() != K or t.dtype != d or t.device != dev:
+            raise _lib.SSError("beam_step(out=): expected %d %s entries on %s" % (K, d, dev))
+    import ctypes as C
+    arr = (C.c_int32 * max(1, len(stops)))(*stops)
+    check(lib().ss_beam_step(p(lg), rows, vocab, lg.stride(0) if rows > 1 else vocab, p(sc), len(stops), arr, p(cs), p(cb), p(ct),
+                             dt(lg), stream()), "ss_beam_step")
+    return cs, cb, ct
+
+
 def logits_rules_struct(repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, spare_img_ids=False):
     """The C ABI's ``ss_logits_rules``.  Ranges are checked by the library (``SSError``); only what ctypes would mangle
     silently is checked here."""

@@ -181,6 +181,39 @@ def apply_best_of(args, llama):
         llama.n_seq = n
 
 
+def add_beams_arguments(ap):
+    """``--beams N [--length-penalty P]`` (shared with vis_george_sink.py)"""
+    ap.add_argument("--beams", type=int, default=1, metavar="N",
+                    help="beam search with N (at most 8) beams over every step's free tokens, on the device; deterministic; not with "
+                         "--sample, --best-of or --synthetic (whose captions are forced); prints each step's hypothesis scores")
+    ap.add_argument("--length-penalty", type=float, default=1.0, help="with --beams: a hypothesis scores sum / length ** P")
+
+
+def apply_beams(args, llama):
+    """``--beams N``: the engine gets at least N sequence slots and the model's beam-search switch goes on (before the first
+    generate builds the engine)"""
+    n = int(getattr(args, "beams", 1) or 1)
+    if not 1 <= n <= 8:
+        raise SystemExit("--beams must be 1 .. 8")
+    if n > 1:
+        if getattr(args, "sample", False) or int(getattr(args, "best_of", 1) or 1) > 1:
+            raise SystemExit("--beams cannot be combined with --sample / --best-of (beam-search sampling is not implemented)")
+        if getattr(args, "synthetic", False):
+            raise SystemExit("--beams cannot be combined with --synthetic: its captions are teacher-forced, a search has nothing to choose")
+        llama.n_seq = max(int(llama.n_seq), n)
+        llama.beam_search = True
+
+
+def beams_kwargs(args):
+    n = int(getattr(args, "beams", 1) or 1)
+    return dict(num_beams=n, length_penalty=getattr(args, "length_penalty", 1.0)) if n > 1 else {}
+
+
+def report_beams(args, j, step, out):
+    if 'beams' in out:
+        print("story %d step %d: %d beams, scores %s" % (j, step, len(out['beams']), " ".join("%.4f" % b['score'] for b in out['beams'])))
+
+
 def report_candidates(args, j, step, out):
     if 'candidates' in out:
         print("story %d step %d: best of %d = candidate %d, scores %s" % (
@@ -251,6 +284,7 @@ def run_story(args, j, question, image, tokenizer, transform, vit, agent, adapte
     llama = agent.llm.base_model.model if hasattr(agent.llm, "base_model") else agent.llm
     llama.use_kv_cache_head = False                                                         # :165
     apply_best_of(args, llama)
+    apply_beams(args, llama)
     if args.save_attn:                                           # the reference's switch: one merged attention map per layer
         llama.config.output_attentions = True
         os.makedirs(args.save_attn, exist_ok=True)
@@ -263,9 +297,11 @@ def run_story(args, j, question, image, tokenizer, transform, vit, agent, adapte
         ids_mask, emb_mask = ctx.masks(device)
         out = agent.generate(tokenizer=tokenizer, input_ids=ctx.input_ids(device), image_embeds=ctx.image_embeds,
                              embeds_cmp_mask=emb_mask, ids_cmp_mask=ids_mask, max_new_tokens=500, num_img_gen_tokens=64,
-                             forced_tokens=forced, **sample_kwargs(args, j, step), **rules_kwargs(args), **logprobs_kwargs(args))
+                             forced_tokens=forced, **sample_kwargs(args, j, step), **rules_kwargs(args), **logprobs_kwargs(args),
+                             **beams_kwargs(args))
         report_caption_logprobs(args, j, step, out, boi)
         report_candidates(args, j, step, out)
+        report_beams(args, j, step, out)
         if args.save_attn:                                       # [layers, rows, width], head 0 (NaN beyond each row's keys)
             torch.save(torch.stack([a[0] for a in out['attn_weights']]).cpu(),
                        os.path.join(args.save_attn, "val_%d_step_%02d.pt" % (j, step)))
@@ -312,6 +348,7 @@ def main():
     ap.add_argument("--top-p", type=float, default=0.5)
     ap.add_argument("--seed", type=int, default=None, help="with --sample: reproducible stories (default: torch.initial_seed())")
     add_best_of_argument(ap)
+    add_beams_arguments(ap)
     add_logprobs_argument(ap)
     add_rules_arguments(ap)
     args = ap.parse_args()

@@ -120,6 +120,9 @@ class LlamaForCausalLM(nn.Module):
         self.n_seq = 1                  # sequence slots of the engine: generate(num_return_sequences=n) needs n_seq >= n
         self._candidates = None         # (slots, kv_cache_head per candidate) of the last generate(num_return_sequences > 1)
 
+    # generate(num_beams=n > 1, do_sample=False) runs beam search on the device (needs n_seq >= n); False: num_beams stays inert
+    beam_search = False
+
     # ---- reference surface ------------------------------------------------------------------
     def get_input_embeddings(self):
         return self.model.embed_tokens
@@ -341,7 +344,7 @@ class LlamaForCausalLM(nn.Module):
                  max_new_tokens=120, output_hidden_states=True, return_dict_in_generate=True, forced_tokens=None,
                  output_attentions=None, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=None, num_beams=1,
                  repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, spare_img_ids=False, output_logprobs=False,
-                 top_logprobs=0, num_return_sequences=1, **unused):
+                 top_logprobs=0, num_return_sequences=1, length_penalty=1.0, early_stopping=False, **unused):
         """Greedy search as ``ContinuousLVLM.generate`` drives it (reference models.py:146-153): ``inputs_embeds`` feed
         step 0, ``input_ids`` is the running sequence, the image-token logits processor is applied on device.
         ``do_sample=False`` (the default): temperature / top_k / top_p / seed are inert, as in Hugging Face.
@@ -375,11 +378,43 @@ class LlamaForCausalLM(nn.Module):
         with ``config.pad_token_id`` (EOS when that is None); ``candidates`` holds n outputs in the batch-1 layout (candidate 0
         = the source slot, then ascending slots); the top-level ``hidden_states`` / log-probability fields are candidate 0's,
         ``self.past_key_values`` and the ``kv_cache_head`` advance refer to it, and ``select_candidate(i)`` switches to
-        another.  ``num_beams`` stays inert without ``do_sample``."""
+        another.  ``num_beams`` stays inert without ``do_sample`` while ``LlamaForCausalLM.beam_search`` is False (the default).
+        ``beam_search = True`` and ``num_beams=n`` (> 1, ``do_sample=False``, ``n <= self.n_seq``): the free tokens up to the first
+        stop — EOS, ``<img>`` or ``max_new_tokens`` — come from a beam search on the device inside the decode token
+        (``LlamaEngine.beam_search``; the definition, Hugging Face's ``_beam_search`` with ``length_penalty`` /
+        ``early_stopping`` on the log-softmax of the row AFTER the rules and the image-token processor, is in
+        include/seedstory_hip.h).  The prompt is prefilled once on slot 0; the winner ``t_1 .. t_m`` is then made real on
+        slot 0 — the cache rewound to the prompt end, ``t_1 .. t_{m-1}`` fed as one prefill — and everything behind it is the
+        existing greedy path with ``t_m`` forced: the image block behind a winner that ends in ``<img>`` and whatever follows
+        ``</img>``.  The winner's hidden rows therefore come from the prefill GEMMs while the search scored them with the
+        decode GEMVs (the image block already mixes the two).  The output is the usual batch-1 one, plus
+        ``sequences_scores`` (the winner's score) and ``beams`` (the n finished hypotheses, best first, as dicts of
+        ``sequence`` / ``score`` / ``finished``); ``past_key_values`` and the ``kv_cache_head`` advance are the winner's.  The
+        rules apply to every beam.  Raised before the engine is touched: ``ValueError`` for ``num_beams > n_seq``,
+        ``forced_tokens`` and ``num_return_sequences > 1``; ``NotImplementedError`` for ``output_attentions``,
+        ``output_logprobs`` and ``kv_cache == "fp8"``."""
         want_attn = bool(getattr(self.config, "output_attentions", False) if output_attentions is None else output_attentions)
         if do_sample and num_beams is not None and int(num_beams) > 1:
             raise NotImplementedError("beam-search sampling (do_sample=True with num_beams=%d) is not implemented" % int(num_beams))
         n_ret = 1 if num_return_sequences is None else int(num_return_sequences)
+        n_beams = int(num_beams) if (self.beam_search and not do_sample and num_beams is not None) else 1
+        if n_beams > 1:
+            if n_beams > int(self.n_seq) or n_beams > 8:
+                raise ValueError("num_beams=%d exceeds the engine's sequence slots: set LlamaForCausalLM.n_seq (now %d, at most 8) "
+                                 "before the first generate()" % (n_beams, int(self.n_seq)))
+            if forced_tokens:
+                raise ValueError("forced_tokens cannot be combined with beam search (num_beams=%d)" % n_beams)
+            if n_ret > 1:
+                raise ValueError("num_return_sequences=%d with beam search is not supported (the hypotheses are in `beams`)" % n_ret)
+            if early_stopping not in (False, True, "never"):
+                raise ValueError("early_stopping must be False, True or 'never', not %r" % (early_stopping,))
+            if want_attn:
+                raise NotImplementedError("attention maps are a single-sequence tool (output_attentions with num_beams=%d)" % n_beams)
+            if output_logprobs:
+                raise NotImplementedError("output_logprobs with beam search is not implemented (num_beams=%d)" % n_beams)
+            if self.kv_cache == "fp8":
+                raise NotImplementedError("beam search with kv_cache='fp8' is not implemented: the search does not permute the "
+                                          "fp8 shadow")
         if n_ret > 1:
             if not do_sample:
                 raise ValueError("num_return_sequences=%d needs do_sample=True: greedy search has one continuation" % n_ret)
@@ -398,7 +433,7 @@ class LlamaForCausalLM(nn.Module):
         if inputs_embeds is None:
             inputs_embeds = self.model.embed_tokens(input_ids)
         rows = inputs_embeds[0]
-        if n_ret > 1 and past_key_values is None:
+        if (n_ret > 1 or n_beams > 1) and past_key_values is None:
             eng.select(0)
         if do_sample:
             if seed is None:
@@ -418,6 +453,9 @@ class LlamaForCausalLM(nn.Module):
             if n_ret > 1:
                 return self._generate_candidates(eng, n_ret, input_ids, rows, S, img_ids, past_key_values, max_new_tokens,
                                                  output_hidden_states, forced_tokens, bool(output_logprobs))
+            if n_beams > 1:
+                return self._generate_beams(eng, n_beams, 1.0 if length_penalty is None else float(length_penalty), early_stopping,
+                                            input_ids, rows, S, img_ids, past_key_values, max_new_tokens, output_hidden_states, rules)
             return self._generate(eng, input_ids, rows, S, img_ids, past_key_values, max_new_tokens, output_hidden_states,
                                   forced_tokens, want_attn, **({"want_logprobs": True} if output_logprobs else {}))
         finally:
@@ -547,6 +585,61 @@ class LlamaForCausalLM(nn.Module):
                               model_logprobs=c0.model_logprobs, top_logprob_ids=c0.top_logprob_ids,
                               top_logprob_values=c0.top_logprob_values, candidates=cands)
 
+    def _generate_beams(self, eng, n_beams, length_penalty, early_stopping, input_ids, rows, S, img_ids, past_key_values,
+                        max_new_tokens, output_hidden_states, rules):
+        """``generate(num_beams=n_beams)`` with ``beam_search`` on: prefill on slot 0, the search, the winner made real on slot
+        0, the rest by the greedy path with the winner's last token forced.  The caller has set the rules and the history
+        and clears them."""
+        from seedstory import ops
+        from seedstory.llama import _prefill_chunked
+        dev = eng.device
+        _, _, fed0, hid0 = self._feed_prompt(eng, rows, S, past_key_values, max_new_tokens, output_hidden_states, False)
+        self._candidates = None
+        kv_end, pos_end = eng.lengths()
+        last = int(input_ids[0, -1])
+        has_img = bool(img_ids) and len(img_ids) >= 3
+        block = has_img and eng.img_block_enabled()
+        if has_img:
+            eng.set_stop_id(img_ids[0])             # a hypothesis that opens an image is finished: the ids behind <img> are forced
+        try:
+            res = eng.beam_search(max_new_tokens, last, n_beams, length_penalty=length_penalty, early_stopping=early_stopping)
+        finally:
+            if has_img:
+                eng.set_stop_id(-1)
+        win = [int(t) for t in res["sequences"][0]]
+        m = len(win)
+        # the winner on slot 0: back to the prompt end, t_1 .. t_{m-1} as one continuation (its history likewise)
+        eng.select(0)
+        eng.set_lengths(kv_end, pos_end)
+        if rules:
+            eng.set_history(input_ids[0].tolist())
+            if m > 1:
+                eng.set_history(win[:-1], append=True)
+        parts = []
+        if m > 1:
+            emb = ops.gather_rows(eng.embed, torch.tensor(win[:-1], dtype=torch.int32, device=dev))
+            parts.append(_prefill_chunked(eng, emb, True))
+        rem = max_new_tokens - (m - 1)
+        prev = win[-2] if m > 1 else last
+        if block:
+            tail, hr = eng.generate_img_block(rem, prev, [win[-1]])
+        else:
+            n = eng.generate(rem, prev, [win[-1]])
+            tail, hr = eng.gen_ids[:n].tolist(), eng.hidden_rows[:max(n - 1, 0)]
+        parts.append(hr)
+        gen_list = win[:-1] + [int(t) for t in tail]
+        gen = torch.tensor(gen_list, dtype=torch.long, device=dev)
+        hr = torch.cat([p.to(parts[-1].dtype) for p in parts]) if len(parts) > 1 else parts[0]
+        self.past_key_values = eng.past_key_values()
+        if self.use_kv_cache_head:
+            adv = fed0 + max(len(gen_list) - 1, 0)
+            self.kv_cache_head = adv if self.kv_cache_head is None else self.kv_cache_head + adv
+        out = self._output(input_ids, gen, hid0, hr, None, output_hidden_states)
+        out.sequences_scores = res["scores"][:1].clone()
+        out.beams = [dict(sequence=list(q), score=float(sc), finished=bool(f))
+                     for q, sc, f in zip(res["sequences"], res["scores"].tolist(), res["finished"].tolist())]
+        return out
+
     def select_candidate(self, i):
         """After ``generate(num_return_sequences=n)``: continue from candidate ``i`` — its slot becomes the selected one,
         ``past_key_values`` and ``kv_cache_head`` refer to it.  Returns the slot."""
@@ -597,3 +690,5 @@ class GenerateOutput:
         self.top_logprob_ids, self.top_logprob_values = top_logprob_ids, top_logprob_values
         # generate(num_return_sequences=n > 1): the n outputs in the batch-1 layout (`sequences` above is then [n, S + longest])
         self.candidates = candidates
+        # generate(num_beams=n > 1) with LlamaForCausalLM.beam_search on: the winner's score [1] and the n hypotheses, best first
+        self.sequences_scores, self.beams = None, None

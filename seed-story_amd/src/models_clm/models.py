@@ -130,7 +130,8 @@ class ContinuousLVLM(nn.Module):
                  ids_cmp_mask=None, logits_processor=None, num_img_gen_tokens=64, temperature=0.7, num_beams=1,
                  max_new_tokens=120, top_p=0.5, past_key_values=None, dtype=torch.float16, device='cuda',
                  forced_tokens=None, do_sample=False, top_k=0, seed=None, repetition_penalty=1.0, no_repeat_ngram_size=0,
-                 min_new_tokens=0, spare_img_ids=False, output_logprobs=False, top_logprobs=0, num_return_sequences=1):
+                 min_new_tokens=0, spare_img_ids=False, output_logprobs=False, top_logprobs=0, num_return_sequences=1,
+                 length_penalty=1.0, early_stopping=False):
         """``do_sample=False`` (the default, what the reference passes): greedy; ``temperature`` / ``top_p`` / ``top_k`` /
         ``seed`` are inert.  ``do_sample=True`` hands them to ``LlamaForCausalLM.generate``: on-device sampling
         (``top_k=0`` = off, ``seed=None`` = governed by ``torch.manual_seed``).  ``repetition_penalty`` /
@@ -144,7 +145,11 @@ class ContinuousLVLM(nn.Module):
         ``llm.select_candidate(best)`` makes its cache the one ``'past_key_values'`` returns, and the dict is the winner's,
         plus ``'candidates'`` (the n dicts with ``'score'``, ``'text'``, ``'generate_ids'``, ``'has_img_output'``,
         ``'img_gen_feat'``) and ``'best'``.  The output resampler runs once, on the stacked rows of every candidate that
-        produced an image."""
+        produced an image.
+        ``num_beams=n`` (> 1, ``do_sample=False``) with ``llm.beam_search = True`` and ``llm.n_seq >= n``: the free tokens come
+        from a beam search on the device (``LlamaForCausalLM.generate``); ``length_penalty`` / ``early_stopping`` (Hugging
+        Face's defaults 1.0 / False) are handed on only when one of them is set, and the dict gains ``'sequences_scores'``
+        (the winner's score) and ``'beams'`` (the n hypotheses).  While ``llm.beam_search`` is False ``num_beams`` is inert."""
         if logits_processor is None:
             logits_processor = LogitsProcessorList()
             logits_processor.append(
@@ -179,7 +184,9 @@ class ContinuousLVLM(nn.Module):
                                    temperature=temperature, num_beams=num_beams, top_p=top_p, do_sample=do_sample,
                                    forced_tokens=forced_tokens, **({"top_k": top_k, "seed": seed} if do_sample else {}), **rules,
                                    **({"output_logprobs": True, "top_logprobs": top_logprobs} if want_lp else {}),
-                                   **({"num_return_sequences": n_ret} if n_ret > 1 else {}))
+                                   **({"num_return_sequences": n_ret} if n_ret > 1 else {}),
+                                   **({"length_penalty": length_penalty, "early_stopping": early_stopping}
+                                      if (length_penalty not in (None, 1.0) or early_stopping not in (None, False)) else {}))
         boi_token_id = tokenizer.encode(BOI_TOKEN, add_special_tokens=False)[0]
         eoi_token_id = tokenizer.encode(EOI_TOKEN, add_special_tokens=False)[0]
         if n_ret > 1:
@@ -202,6 +209,8 @@ class ContinuousLVLM(nn.Module):
         if output_logprobs:
             scores = {'logprobs': output.logprobs, 'model_logprobs': output.model_logprobs,
                       'top_logprobs': (output.top_logprob_ids, output.top_logprob_values)}
+        if getattr(output, "beams", None) is not None:
+            scores.update({'sequences_scores': output.sequences_scores, 'beams': output.beams})
         return {
             **scores,
             'text': generate_text,
