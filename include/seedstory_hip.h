@@ -332,7 +332,8 @@ int ss_gemv_batched(const void* W, const void* x, void* y, int64_t N, int64_t K,
 #define SS_GEMV_PLAN_MAX 16
 enum { SS_GEMV_FORM_REG = 0, SS_GEMV_FORM_LDSX = 1, SS_GEMV_FORM_MFMA = 2, SS_GEMV_FORM_MFMA_EXACT16 = 3,
        SS_GEMV_FORM_MFMA_EXACT43 = 4, SS_GEMV_FORM_SPLIT_F32 = 5,
-       SS_GEMV_FORM_W8 = 6, SS_GEMV_FORM_W8_EXACT16 = 7, SS_GEMV_FORM_W8_EXACT43 = 8 /* ss_gemv_w8 only */ };
+       SS_GEMV_FORM_W8 = 6, SS_GEMV_FORM_W8_EXACT16 = 7, SS_GEMV_FORM_W8_EXACT43 = 8 /* ss_gemv_w8 only */,
+       SS_GEMV_FORM_MX4 = 9, SS_GEMV_FORM_MX4_EXACT16 = 10, SS_GEMV_FORM_MX4_EXACT43 = 11 /* ss_gemv_mx4 only */ };
 int ss_gemv_plan(int64_t N, int64_t K, int64_t nb, int dtype, int epilogue, int has_norm, int aligned16, int32_t* rows,
                  int64_t max_rows);
 
@@ -350,6 +351,29 @@ int ss_gemv_plan(int64_t N, int64_t K, int64_t nb, int dtype, int epilogue, int 
 int ss_gemv_w8(const void* Wq, const float* w_scale, const void* x, void* y, int64_t N, int64_t K, int64_t nb,
                const void* norm_w, float eps, const void* bias, const void* residual, int epilogue, int dtype, void* stream);
 int ss_gemv_w8_plan(int64_t N, int64_t K, int64_t nb, int dtype, int epilogue, int has_norm, int32_t* rows, int64_t max_rows);
+
+/* The decode projection over MXFP4 weights (OCP microscaling fp4, weight-only: activations and outputs stay in the 16-bit dtype):
+ *   y[b][n] = epilogue( sum_k dec(code[n][k]) * 2^(scales[n][k / 32] - 127) * x[b][k] ),  b < nb <= 16
+ * The format, for a weight W [N, K] with K % 32 == 0 ([2N, K] = [gate; up] for SS_EPI_SILU_MUL):
+ *   codes   uint8 [N, K / 2] row-major: byte j of a row holds k = 2j in bits 0-3 and k = 2j + 1 in bits 4-7.  A code is sign
+ *           (bit 3) and a magnitude index into {0, 0.5, 1, 1.5, 2, 3, 4, 6}: OCP e2m1, no Inf, no NaN.
+ *   scales  uint8 [N, K / 32] row-major: byte b is e8m0, the 32 values k = 32 b .. 32 b + 31 are multiplied by 2^(byte - 127).
+ * The exactness contract covers scale exponents X = byte - 127 in [-13, 13]: there every decoded value is a normal number of
+ * bf16 and of fp16 and exact in both; it is decoded in registers (v_cvt_scalef32_pk_{bf16,f16}_fp4) and multiplied in the
+ * bf16 / f16 MFMA with fp32 accumulation, every product exact in fp32; then the epilogue of ss_gemv (NONE, BIAS, RESIDUAL,
+ * BIAS | RESIDUAL, SILU_MUL alone).  Outside that range the result is whatever the conversion instruction yields, never an
+ * out-of-range access.  0.53 bytes per weight.  ss_quantize_rows_mxfp4 writes the format: per block, a = amax in fp32; the
+ * block exponent X = exponent(a) - 2 when the fp32 mantissa field of a is <= 0x400000, else exponent(a) - 1, clamped to
+ * [-13, 13] (an all-zero block: -13); codes = w / 2^X rounded to nearest on the e2m1 grid, ties to the even mantissa bit,
+ * saturated at +-6; a value that rounds to zero gets code 0.  x [M, K] 16-bit with row stride ld (elements), 16-byte aligned.
+ * Shapes of ss_gemv_mx4: K % 32 == 0 and K <= 4096, or K == 11008 (no norm_w there; 9..16 sequences run as two sweeps); codes,
+ * x and norm_w 16-byte aligned.  Anything else returns SS_EINVAL with a message before a launch.
+ * ss_gemv_mx4_plan: host only, the launches of that call as rows of ss_gemv_plan's layout (forms SS_GEMV_FORM_MX4*; the
+ * parameter column holds MFMA steps of 32 k per wave, four per 16-byte load). */
+int ss_gemv_mx4(const void* codes, const void* scales, const void* x, void* y, int64_t N, int64_t K, int64_t nb,
+                const void* norm_w, float eps, const void* bias, const void* residual, int epilogue, int dtype, void* stream);
+int ss_gemv_mx4_plan(int64_t N, int64_t K, int64_t nb, int dtype, int epilogue, int has_norm, int32_t* rows, int64_t max_rows);
+int ss_quantize_rows_mxfp4(const void* x, int64_t ld, int64_t M, int64_t K, void* codes_out, void* scales_out, int dtype, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Sampling: lm_head logits -> AutoImageTokenGenerationProcessor -> greedy argmax
@@ -617,6 +641,20 @@ typedef struct ss_llama_layer_w8 {
 } ss_llama_layer_w8;
 int ss_llama_set_decode_w8(ss_llama* h, const ss_llama_layer_w8* layers, const void* lm_head_q, const float* lm_head_scale);
 
+/* MXFP4 weight-only decode: ss_llama_set_decode_w8 with planes in the format of ss_gemv_mx4.  Per layer the four code planes
+ * ([rows, K / 2] bytes over the 16-bit weights' layouts) and the four scale planes ([rows, K / 32] bytes); lm_head_codes
+ * [vocab, hidden / 2] + lm_head_scales [vocab, hidden / 32].  The same ownership, scope (decode tokens only: prefill, the
+ * one-row lm_head at its end and the image-token block keep the 16-bit weights, which stay resident) and graph caching as the
+ * fp8 option; the two exclude each other: setting one clears the other.  layers = NULL turns it off.  A quarter of the
+ * weight bytes per generated token plus one scale byte per 32 weights.  SS_EINVAL: an fp32 engine, a projection shape
+ * ss_gemv_mx4 does not take (hidden / inter not a multiple of 32, wider than 4096 and not 11008), a NULL plane, a code plane
+ * that is not 16-byte aligned.  End quality on real checkpoints has not been measured. */
+typedef struct ss_llama_layer_mx4 {
+    const void *wqkv, *wo, *wgu, *wdown;            /* codes */
+    const void *s_qkv, *s_o, *s_gu, *s_down;        /* e8m0 scales */
+} ss_llama_layer_mx4;
+int ss_llama_set_decode_mx4(ss_llama* h, const ss_llama_layer_mx4* layers, const void* lm_head_codes, const void* lm_head_scales);
+
 /* fp8 (e4m3) KV shadow cache for decode attention (the quantisation: ss_kv_quantize_fp8).  k_codes, v_codes
  * [n_seq][n_layers][n_heads][cache_cap][hd] bytes and k_scale, v_scale [n_seq][n_layers][n_heads][cache_cap] fp32: device
  * memory owned by the caller and kept alive while the option is on (sizes: ss_llama_kv8_bytes; ss_llama_workspace_bytes does
@@ -774,7 +812,8 @@ int ss_llama_generate_batch(ss_llama* h, int64_t n_steps, const int32_t* last_pr
  *             GEMV launches (ss::gemv_ldsx_kernel), [3] = sampling + final norm, [4] = whole token;
  * out_bytes[0] = weight bytes streamed by the class-0 launches of one token, [1] = their count,
  * out_bytes[2] / [3] = the same for class 2.  With ss_llama_set_decode_w8 on, the token is the fp8 one and the bytes are
- * the bytes it streams: one per weight plus the fp32 row scales. */
+ * the bytes it streams: one per weight plus the fp32 row scales; with ss_llama_set_decode_mx4 on, the MXFP4 one: weights / 2
+ * of codes plus weights / 32 of block scales. */
 int ss_llama_profile_decode(ss_llama* h, int64_t n_tokens, float out_ms[8], double out_bytes[4],
                             void* stream);
 

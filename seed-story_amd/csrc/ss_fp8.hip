@@ -106,6 +106,61 @@ int quantize_launch(const void* x, int64_t ld, int64_t M, int64_t K, void* q, fl
     }
 }
 
+// MXFP4 rows (the format of ss_gemv_mx4): one thread per block of 32 consecutive k.  a = amax of the block in fp32 (exact from
+// 16-bit inputs); X = exponent(a) - 2 when a's mantissa field is <= 0x400000, else exponent(a) - 1 — the smallest power of two with
+// a / 2^X <= 6 — clamped to [-13, 13]; codes = |w| / 2^X (a power-of-two multiply: exact) rounded to nearest on the e2m1 grid
+// {0, .5, 1, 1.5, 2, 3, 4, 6}, ties to the even mantissa bit = the even grid index, saturated at 6; the sign is kept unless the
+// value rounds to zero.  An all-zero block gets X = -13 and codes 0.
+template <typename T>
+__global__ __launch_bounds__(256) void quantize_rows_mxfp4_kernel(const T* __restrict__ x, int64_t ld, int M, int KB,
+                                                                  uint8_t* __restrict__ codes, uint8_t* __restrict__ scales) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (int64_t)M * KB) return;
+    const int row = (int)(t / KB), b = (int)(t % KB);
+    const T* xr = x + (int64_t)row * ld + (int64_t)b * 32;
+    float f[32];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) unpack<T>(*reinterpret_cast<const uint4*>(xr + j * 8), f + j * 8);
+    float a = 0.f;
+#pragma unroll
+    for (int j = 0; j < 32; ++j) a = fmaxf(a, fabsf(f[j]));
+    const uint32_t bits = __float_as_uint(a);
+    int X = (int)((bits >> 23) & 0xffu) - 127 - ((bits & 0x7fffffu) <= 0x400000u ? 2 : 1);
+    X = X < -13 ? -13 : X > 13 ? 13 : X;
+    const float inv = __uint_as_float((uint32_t)(127 - X) << 23);      // 2^-X
+    uint32_t w[4];
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+        uint32_t v = 0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float e = f[d * 8 + j];
+            const float m = fabsf(e) * inv;
+            const uint32_t idx = (uint32_t)(m > 0.25f) + (uint32_t)(m >= 0.75f) + (uint32_t)(m > 1.25f) + (uint32_t)(m >= 1.75f) +
+                                 (uint32_t)(m > 2.5f) + (uint32_t)(m >= 3.5f) + (uint32_t)(m > 5.0f);
+            const uint32_t code = idx | ((idx && (__float_as_uint(e) >> 31)) ? 8u : 0u);
+            v |= code << (4 * j);
+        }
+        w[d] = v;
+    }
+    *reinterpret_cast<uint4*>(codes + t * 16) = make_uint4(w[0], w[1], w[2], w[3]);
+    scales[t] = (uint8_t)(X + 127);
+}
+
+template <typename T>
+int quantize_mxfp4_launch(const void* x, int64_t ld, int64_t M, int64_t K, void* codes, void* scales, hipStream_t s) {
+    if constexpr (Tr<T>::kVec != 8) {
+        set_error("ss_quantize_rows_mxfp4: 16-bit inputs only");
+        return SS_EINVAL;
+    } else {
+        const int64_t nblk = M * (K / 32);
+        hipLaunchKernelGGL(quantize_rows_mxfp4_kernel<T>, dim3((unsigned)((nblk + 255) / 256)), dim3(256), 0, s, (const T*)x, ld, (int)M,
+                           (int)(K / 32), (uint8_t*)codes, (uint8_t*)scales);
+        SS_LAUNCH_CHECK("quantize_rows_mxfp4");
+        return SS_OK;
+    }
+}
+
 // closed-form tile rule for the fp8 kernels (the shapes are the UNet's: M = batch x tokens, N, K multiples of 160 / 128)
 static int pick_cfg_fp8(int64_t M, int64_t N, int64_t K) {
     const int forced = knob(K_gemm_fp8_cfg);
@@ -131,6 +186,13 @@ int ss_quantize_rows_fp8(const void* x, int64_t ld, int64_t M, int64_t K, void* 
     SS_REQUIRE(x && q_out && scale_out && M > 0 && K > 0 && K % 8 == 0 && ld % 8 == 0 && ld >= K, "ss_quantize_rows_fp8: bad arguments");
     SS_REQUIRE((ln_gamma == nullptr) == (ln_beta == nullptr), "ss_quantize_rows_fp8: gamma and beta go together");
     return SS_DISPATCH(dtype, ss::quantize_launch, x, ld, M, K, q_out, scale_out, ln_gamma, ln_beta, ln_eps, (hipStream_t)stream);
+}
+
+int ss_quantize_rows_mxfp4(const void* x, int64_t ld, int64_t M, int64_t K, void* codes_out, void* scales_out, int dtype, void* stream) {
+    SS_REQUIRE(x && codes_out && scales_out && M > 0 && K > 0 && K % 32 == 0 && ld % 8 == 0 && ld >= K && M * (K / 32) < (1ll << 31),
+               "ss_quantize_rows_mxfp4: bad arguments (K a positive multiple of 32, row stride a multiple of 8 and >= K)");
+    SS_REQUIRE((((size_t)x | (size_t)codes_out) & 15) == 0, "ss_quantize_rows_mxfp4: x and codes_out must be 16-byte aligned");
+    return SS_DISPATCH(dtype, ss::quantize_mxfp4_launch, x, ld, M, K, codes_out, scales_out, (hipStream_t)stream);
 }
 
 int ss_gemm_fp8(const void* A8, const float* scale_a, const void* W8, const float* scale_w, void* C, int64_t M, int64_t N,

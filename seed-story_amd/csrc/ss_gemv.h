@@ -19,4 +19,11 @@ int gemv_w8_batched_dev(const void* Wq, const float* w_scale, const void* x, voi
                         int nb, int64_t x_ld, int64_t y_ld, int64_t res_ld, int dtype, hipStream_t s);
 int gemv_w8_check(int64_t N, int64_t K, int nb, int dtype, int epi, bool norm);
 
+// The same projection over MXFP4 weights: codes [N, K / 2] bytes (two e2m1 codes per byte, even k in the low nibble) and scales
+// [N, K / 32] e8m0 bytes, one per 32 consecutive k ([2N, ...] for the SiLU pair).  gemv_mx4_check: the shape rules alone (no launch).
+int gemv_mx4_batched_dev(const void* codes, const void* scales, const void* x, void* y, int64_t N, int64_t K, const void* norm_w,
+                         float eps, const void* bias, const void* residual, int epi, const int32_t* done_flag, int done_stride,
+                         int nb, int64_t x_ld, int64_t y_ld, int64_t res_ld, int dtype, hipStream_t s);
+int gemv_mx4_check(int64_t N, int64_t K, int nb, int dtype, int epi, bool norm);
+
 }  // namespace ss

@@ -15,6 +15,8 @@
 //     SiLU(gate)·up for the fused [gate; up] projection (LlamaMLP.forward, :190-191).
 // fp8 (OCP e4m3fn) weight-only variant (ss_gemv_w8, the opt-in decode_weights="fp8" of the LLaMA engine): the MFMA family below
 // over byte planes + one fp32 scale per row, codes converted to the 16-bit type in registers — see "fp8 weight forms".
+// MXFP4 weight-only variant (ss_gemv_mx4, decode_weights="mxfp4"): the same family over e2m1 code planes (two codes per byte) + one
+// e8m0 scale byte per 32 k, decoded and scaled by one conversion instruction per two codes — see "MXFP4 weight forms".
 // Reference call sites: modeling_llama_xformer.py:228-230 (q/k/v), :297 (o), :191 (MLP),
 // :759 (lm_head); LlamaRMSNorm :107-115 for the prologue.
 #include "ss_gemv.h"
@@ -921,6 +923,222 @@ __global__ __launch_bounds__(512) void gemv_w8_exact_kernel(const GemvArgs a, co
     tile_body(tile, it, std::false_type{});
 }
 
+// ---- MXFP4 weight forms (OCP e2m1 codes + e8m0 block scales): a quarter of the bytes per k, the same matrix instruction ------------
+// y[b][n] = epilogue( sum_k dec(code[n][k]) * 2^(scale[n][k / 32] - 127) * x[b][k] ):  codes [N, K / 2] bytes (k = 2j in bits 0-3
+// of byte j, k = 2j + 1 in bits 4-7), scales [N, K / 32] bytes.  A lane's 16-byte load holds 32 consecutive k = ONE MX block = one
+// scale byte = FOUR MFMA steps: load G of a row covers k = 128 G .. + 127, lane l (row l & 15, q = l >> 4) takes bytes 16 q .. + 15
+// of its 64, i.e. k = 128 G + 32 q .. + 31 under scale byte 4 G + q, and step h (dword h of the load) the 8 k behind 8 h.
+// v_cvt_scalef32_pk_{bf16,f16}_fp4 decodes two codes of a selected byte and applies 2^X in the same instruction (X in [-13, 13]:
+// every value is a normal number of both types and exact), the result feeds gv_mfma<T>; the activation fragments are laid out to
+// match (fragment 4 L + h = x[k of load L + 32 q + 8 h .. + 8]).  Every product is exact in fp32; there is no row scale, so the
+// folded sum goes straight into the shared epilogue.  The scale byte travels with its load (one byte load per lane and slot).
+template <typename T> __device__ __forceinline__ uint4 gv_dec8_mx4(uint32_t w, float sc);      // 8 codes of one dword -> 8 values of T
+template <> __device__ __forceinline__ uint4 gv_dec8_mx4<bf16_t>(uint32_t w, float sc) {
+    return make_uint4(__builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, sc, 0)),
+                      __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, sc, 1)),
+                      __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, sc, 2)),
+                      __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, sc, 3)));
+}
+template <> __device__ __forceinline__ uint4 gv_dec8_mx4<f16_t>(uint32_t w, float sc) {
+    return make_uint4(__builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, sc, 0)),
+                      __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, sc, 1)),
+                      __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, sc, 2)),
+                      __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, sc, 3)));
+}
+__device__ __forceinline__ float gv_e8m0(uint32_t byte) { return __uint_as_float(byte << 23); }   // 2^(byte - 127)
+__device__ __forceinline__ uint32_t gv_dword(const uint4& v, int h) { return h == 0 ? v.x : h == 1 ? v.y : h == 2 ? v.z : v.w; }
+
+// any K <= 4096 (multiple of 32), any N: predicated loads, LPW <= 4 loads of 128 k per wave (gemv_mfma_kernel's role)
+template <typename T, bool SILU>
+__global__ __launch_bounds__(512) void gemv_mx4_kernel(const GemvArgs a, const uint8_t* __restrict__ w_scale, const int lpw, const int ntiles) {
+    constexpr int NL = kGvSteps / 4, M = SILU ? 2 : 1;
+    __shared__ __attribute__((aligned(16))) float part[2][kGvWaves][M][256];
+    __shared__ float red[kGvWaves][16];
+    if (gemv_all_done(a)) return;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int i = lane & 15, q = lane >> 4;
+    const int K = a.K, N = a.N, nb = a.nb;
+    const uint8_t* __restrict__ W = (const uint8_t*)a.W;
+    const int k0 = wave * lpw * 128 + q * 32;                       // this lane's k at the wave's load 0
+    int nvalid = k0 < K ? (K - k0 + 127) / 128 : 0;                 // loads of this lane that lie inside K (K % 32 == 0: whole or not)
+    if (nvalid > lpw) nvalid = lpw;
+
+    uint4 xf[4 * NL];
+    {
+        const T* xr = (const T*)a.x + (int64_t)(i < nb ? i : 0) * a.x_ld + k0;
+        gv_static_for<4 * NL>([&](auto s_) {
+            constexpr int s = decltype(s_)::value;
+            xf[s] = (s >> 2) < nvalid ? ld16(xr + (s >> 2) * 128 + (s & 3) * 8) : make_uint4(0, 0, 0, 0);
+        });
+        if (a.norm_w) {
+            float ssq = 0.f;
+            gv_static_for<4 * NL>([&](auto s_) { ssq = gv_pack_ssq<T>(xf[decltype(s_)::value], ssq); });
+            const float rstd = gv_rstd_across_waves(ssq, red, wave, lane, K, a.eps);
+            const T* gw = (const T*)a.norm_w + k0;
+            gv_static_for<4 * NL>([&](auto s_) {
+                constexpr int s = decltype(s_)::value;
+                if ((s >> 2) < nvalid) xf[s] = gv_pack_norm<T>(xf[s], ld16(gw + (s >> 2) * 128 + (s & 3) * 8), rstd);
+            });
+        }
+    }
+    uint4 wa[M][NL];
+    uint32_t ws[M][NL];
+    int it = 0;
+    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x, ++it) {
+        int row = tile * 16 + i;
+        if (row >= N) row = N - 1;
+        f32x4_t acc[M];
+#pragma unroll
+        for (int m = 0; m < M; ++m) {
+            acc[m] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+            const int64_t r = (int64_t)row + (int64_t)m * N;
+            const uint8_t* p = W + r * (K >> 1) + (k0 >> 1);
+            const uint8_t* sp = w_scale + r * (K >> 5) + (k0 >> 5);
+            gv_static_for<NL>([&](auto s_) {
+                constexpr int s = decltype(s_)::value;
+                wa[m][s] = s < nvalid ? ld16(p + s * 64) : make_uint4(0, 0, 0, 0);      // code 0 is +0
+                ws[m][s] = s < nvalid ? (uint32_t)sp[s * 4] : 127u;
+            });
+        }
+        gv_static_for<NL>([&](auto s_) {
+            constexpr int s = decltype(s_)::value;
+#pragma unroll
+            for (int m = 0; m < M; ++m) {
+                const float sc = gv_e8m0(ws[m][s]);
+                gv_static_for<4>([&](auto h_) {
+                    constexpr int h = decltype(h_)::value;
+                    acc[m] = gv_mfma<T>(gv_dec8_mx4<T>(gv_dword(wa[m][s], h), sc), xf[4 * s + h], acc[m]);
+                });
+            }
+        });
+        GvEpi epi;
+        epi.vec = false;
+        gv_fold_store<T, SILU>(a, &part[it & 1][0][0][0], acc, tile, wave, lane, epi);
+    }
+}
+
+// the predicate-free stream loops.  K = 4096 (NL = 4): 32 loads of 128 k per row, four to a wave.  K = 11008 (NL = 11): 86 loads
+// per row do not divide among 8 waves, and a wave's 43 blocks would not divide among the four lane groups of a load either, so the
+// 86 loads are dealt 11 11 11 11 11 11 10 10: waves 0..5 run 11 load slots, waves 6 and 7 re-read their tenth load in the eleventh
+// slot (in range) against zero activation fragments and a unit scale: every load of every lane is in range, no predicate, no
+// branch.  Load slots are walked in chunks of CH through two register buffers; the loads of chunk c + 1 (or of the next tile's
+// chunk 0) are issued before the MFMAs of chunk c.  NL = 11 keeps the nb <= 8 packing of the 16-bit form (lanes 8..15 of a row
+// carry the fragments of steps 22..43 of sequences 0..7, handed down by a row_shl:8 move): 88 VGPRs of activations.  No RMSNorm
+// in that form.
+template <typename T, bool SILU, int NL>
+__global__ __launch_bounds__(512) void gemv_mx4_exact_kernel(const GemvArgs a, const uint8_t* __restrict__ w_scale, const int ntiles) {
+    constexpr int M = SILU ? 2 : 1;
+    constexpr bool PACK = NL > kGvSteps / 4;
+    constexpr int NLOADS = PACK ? 86 : 32;                  // 128-k loads per row
+    constexpr int FULL = NLOADS - kGvWaves * (NL - 1);      // waves that own NL loads; the others own NL - 1
+    constexpr bool HASDEAD = FULL < kGvWaves;
+    constexpr int NSTEP = 4 * NL;
+    constexpr int CH = PACK ? 3 : 2;                        // load slots per chunk
+    constexpr int NCH = (NL + CH - 1) / CH;
+    constexpr int HALF = PACK ? NSTEP / 2 : NSTEP;          // fragments a lane holds
+    static_assert(NCH % 2 == 0, "an even number of chunks keeps the buffer parity across tiles");
+    static_assert(FULL >= 0 && FULL <= kGvWaves && (!HASDEAD || (PACK && NSTEP - 4 >= HALF)), "the dead slot's fragments live in the upper lanes");
+    __shared__ __attribute__((aligned(16))) float part[2][kGvWaves][M][256];
+    __shared__ float red[kGvWaves][16];
+    if (gemv_all_done(a)) return;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int i = lane & 15, q = lane >> 4;
+    const int K = a.K, N = a.N, nb = a.nb;
+    const uint8_t* __restrict__ W = (const uint8_t*)a.W;
+    const bool dead = HASDEAD && wave >= FULL;                      // this wave's last slot carries no k
+    const int g0 = wave < FULL ? wave * NL : FULL * NL + (wave - FULL) * (NL - 1);     // the wave's first load
+    // load of slot L (the dead slot repeats the one before it)
+    auto gload = [&](int L) { return g0 + ((dead && L == NL - 1) ? L - 1 : L); };
+    // k of MFMA step s of this lane
+    auto koff = [&](int s) { return gload(s >> 2) * 128 + q * 32 + (s & 3) * 8; };
+    int tile = blockIdx.x, it = 0;
+    if (tile >= ntiles) return;
+
+    uint4 wa[2][M][CH];
+    uint32_t ws[2][M][CH];
+    auto load_chunk = [&](auto c_, int tl) {                        // chunk c of row tile tl -> buffer c & 1
+        constexpr int c = decltype(c_)::value;
+        int row = tl * 16 + i;
+        if (row >= N) row = N - 1;
+#pragma unroll
+        for (int m = 0; m < M; ++m) {
+            const int64_t r = (int64_t)row + (int64_t)m * N;
+            const uint8_t* p = W + r * (K >> 1) + q * 16;
+            const uint8_t* sp = w_scale + r * (K >> 5) + q;
+            gv_static_for<CH>([&](auto e_) {
+                constexpr int e = decltype(e_)::value, L = c * CH + e;
+                if constexpr (L < NL) {
+                    const int G = gload(L);
+                    wa[c & 1][m][e] = ld16(p + G * 64);
+                    ws[c & 1][m][e] = sp[G * 4];
+                }
+            });
+        }
+    };
+
+    // ---- the wave's slice of the activations, in B-operand order (+ fused RMSNorm) -----------------------------------
+    uint4 xf[HALF];
+    if constexpr (!PACK) {
+        // (lanes of sequences >= nb read sequence 0: their columns of D are never stored)
+        const T* xr = (const T*)a.x + (int64_t)(i < nb ? i : 0) * a.x_ld;
+        gv_static_for<HALF>([&](auto s_) { constexpr int s = decltype(s_)::value; xf[s] = ld16(xr + koff(s)); });
+        load_chunk(std::integral_constant<int, 0>{}, tile);         // the first weights travel while the statistic is formed
+        __builtin_amdgcn_sched_barrier(0);
+        if (a.norm_w) gv_norm_frags<T>(xf, (const T*)a.norm_w, koff, red, wave, lane, K, a.eps);
+    } else {
+        const int seq = i & 7, upper = i >> 3;
+        const T* xr = (const T*)a.x + (int64_t)(seq < nb ? seq : 0) * a.x_ld;
+        gv_static_for<HALF>([&](auto s_) {
+            constexpr int s = decltype(s_)::value;
+            const uint4 v = ld16(xr + koff(s + upper * HALF));
+            // the dead slot's four steps: zeros
+            xf[s] = (s + HALF >= NSTEP - 4 && dead && upper) ? make_uint4(0, 0, 0, 0) : v;
+        });
+        load_chunk(std::integral_constant<int, 0>{}, tile);
+    }
+    const bool vec_ok = ((a.y_ld | a.res_ld | N) & 3) == 0 && N >= 4 && (a.epi & (SS_EPI_RESIDUAL | SS_EPI_BIAS)) &&
+                        ((((size_t)a.y | (size_t)a.residual | (size_t)a.bias) & 7) == 0);
+
+    auto tile_body = [&](int tl, int itn, auto has_next_) {
+        constexpr bool has_next = decltype(has_next_)::value;
+        f32x4_t acc[M];
+#pragma unroll
+        for (int m = 0; m < M; ++m) acc[m] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+        GvEpi epi;
+        epi.vec = false;
+        if constexpr (!SILU) epi = gv_epi_prefetch<T>(a, tl, lane, vec_ok);
+        gv_static_for<NCH>([&](auto c_) {
+            constexpr int c = decltype(c_)::value;
+            if constexpr (c + 1 < NCH) load_chunk(std::integral_constant<int, c + 1>{}, tl);
+            else if constexpr (has_next) load_chunk(std::integral_constant<int, 0>{}, tl + (int)gridDim.x);
+            __builtin_amdgcn_sched_barrier(0);      // (as in gemv_mfma_exact_kernel: keeps two buffers in flight)
+            gv_static_for<CH>([&](auto e_) {
+                constexpr int e = decltype(e_)::value, L = c * CH + e;
+                if constexpr (L < NL) {
+#pragma unroll
+                    for (int m = 0; m < M; ++m) {
+                        float sc = gv_e8m0(ws[c & 1][m][e]);
+                        if constexpr (HASDEAD && L == NL - 1) sc = dead ? 1.0f : sc;    // (a re-read block times zeros: keep it finite)
+                        const uint4& w = wa[c & 1][m][e];
+                        gv_static_for<4>([&](auto h_) {
+                            constexpr int h = decltype(h_)::value, s = 4 * L + h;
+                            uint4 b;
+                            if constexpr (!PACK) b = xf[s];
+                            else if constexpr (s < HALF) b = xf[s];
+                            else b = gv_row_shift8(xf[s - HALF]);
+                            acc[m] = gv_mfma<T>(gv_dec8_mx4<T>(gv_dword(w, h), sc), b, acc[m]);
+                        });
+                    }
+                }
+            });
+            __builtin_amdgcn_sched_barrier(0);
+        });
+        gv_fold_store<T, SILU>(a, &part[itn & 1][0][0][0], acc, tl, wave, lane, epi);
+    };
+    for (; tile + (int)gridDim.x < ntiles; tile += gridDim.x, ++it) tile_body(tile, it, std::true_type{});
+    tile_body(tile, it, std::false_type{});
+}
+
 // ---- split-bf16 MFMA form for fp32 tensors (the gate mode, tuning knob gemm_f32_split; round 5) ---------------------------------
 // The exact fp32 decode has no MFMA form: 8 lock-step sequences run as TWO 4-sequence sweeps of the dot-product kernels, i.e. the
 // 26.4 GB of fp32 LLaMA weights are streamed twice per token (measured: ~700 of the 1093 ms the gate-mode MLLM half of a round of
@@ -1264,6 +1482,36 @@ static int gemv_w8_plan(int64_t N, int64_t K, int nb, int dtype, int epi, bool n
     return SS_OK;
 }
 
+// The MXFP4-weight call: always an MFMA form, with the grid rules of the fp8 plan.  K = 4096 and K = 11008 take the stream loops,
+// every other K <= 4096 (and the knob gemv_mfma_generic) the predicated kernel; the packed 11008-deep loop takes <= 8 sequences, so
+// 9..16 run as two sweeps.  The parameter column holds the MFMA steps of 32 k a wave walks (four per load slot).
+static int gemv_mx4_plan(int64_t N, int64_t K, int nb, int dtype, int epi, bool norm, GemvPlan& plan) {
+    SS_REQUIRE(dtype == SS_BF16 || dtype == SS_F16, "gemv_mx4: the model dtype must be bf16 or fp16 (got %d)", dtype);
+    constexpr int64_t K16 = kGvWaves * kGvSteps * 32, K43 = kGvWaves * 43 * 32;
+    SS_REQUIRE(N > 0 && K > 0 && K % 32 == 0 && (K <= K16 || K == K43),
+               "gemv_mx4: K=%lld must be a positive multiple of 32, at most %lld or exactly %lld (N=%lld)", (long long)K, (long long)K16,
+               (long long)K43, (long long)N);
+    SS_REQUIRE(N < (1ll << 30), "gemv_mx4: N=%lld too large", (long long)N);
+    SS_REQUIRE(!(epi & SS_EPI_SILU_MUL) || !(epi & (SS_EPI_BIAS | SS_EPI_RESIDUAL | SS_EPI_GELU)),
+               "gemv_mx4: SILU_MUL cannot be combined with other epilogues");
+    SS_REQUIRE(!(epi & ~(SS_EPI_BIAS | SS_EPI_RESIDUAL | SS_EPI_SILU_MUL)), "gemv_mx4: epilogue %d not supported", epi);
+    SS_REQUIRE(nb >= 1 && nb <= 16, "gemv_mx4: batch %d unsupported (1..16)", nb);
+    SS_REQUIRE(K != K43 || !norm, "gemv_mx4: no RMSNorm prologue at K=%lld", (long long)K);
+    const bool silu = (epi & SS_EPI_SILU_MUL) != 0;
+    const int ntiles = cdiv(N, 16), blocks = cdiv(ntiles, cdiv(ntiles, knob(K_gemv_mfma_blocks)));
+    const bool exact16 = K == K16 && !knob(K_gemv_mfma_generic);
+    const int sweeps = (K == K43 && nb > 8) ? 2 : 1;
+    for (int j = 0; j < sweeps; ++j) {
+        const int seq0 = j * (nb / 2), n = sweeps == 1 ? nb : (j ? nb - nb / 2 : nb / 2);
+        GemvLaunch l = {seq0, n, SS_GEMV_FORM_MX4, 0, blocks, 512, 0, 0, silu, 0};
+        if (K == K43) l.form = SS_GEMV_FORM_MX4_EXACT43, l.param = 44;
+        else if (exact16) l.form = SS_GEMV_FORM_MX4_EXACT16, l.param = kGvSteps;
+        else l.param = 4 * cdiv(cdiv(K, 128), kGvWaves);         // four per 16-byte load
+        plan.l[plan.n++] = l;
+    }
+    return SS_OK;
+}
+
 // ---- kernel tables --------------------------------------------------------------------------------------------------------------------
 using GemvKern = void (*)(GemvArgs);
 using GemvTileKern = void (*)(GemvArgs, int);
@@ -1291,6 +1539,11 @@ template <typename T, int SPW>
 static GemvW8Kern gv_w8_exact_kernel(const GemvLaunch& l) {
     return l.silu ? gemv_w8_exact_kernel<T, true, SPW> : gemv_w8_exact_kernel<T, false, SPW>;
 }
+using GemvMx4Kern = void (*)(GemvArgs, const uint8_t*, int);
+template <typename T, int NL>
+static GemvMx4Kern gv_mx4_exact_kernel(const GemvLaunch& l) {
+    return l.silu ? gemv_mx4_exact_kernel<T, true, NL> : gemv_mx4_exact_kernel<T, false, NL>;
+}
 template <bool SILU>
 static int gemv_run_split(const GemvLaunch& l, const GemvArgs& a, hipStream_t s) {
     SS_DYN_LDS(gemv_split_f32_kernel<SILU>, (size_t)GvSplitLds(kGsSlice, true).bytes);   // the largest request: full slice, SiLU pair
@@ -1299,7 +1552,7 @@ static int gemv_run_split(const GemvLaunch& l, const GemvArgs& a, hipStream_t s)
 }
 
 template <typename T>
-static int gemv_run(const GemvPlan& plan, const GemvArgs& args, hipStream_t s, const float* w_scale = nullptr) {
+static int gemv_run(const GemvPlan& plan, const GemvArgs& args, hipStream_t s, const float* w_scale = nullptr, const uint8_t* mx_scale = nullptr) {
     for (int j = 0; j < plan.n; ++j) {
         const GemvLaunch& l = plan.l[j];
         GemvArgs a = args;
@@ -1323,6 +1576,12 @@ static int gemv_run(const GemvPlan& plan, const GemvArgs& args, hipStream_t s, c
         } else if (l.form == SS_GEMV_FORM_W8_EXACT16 || l.form == SS_GEMV_FORM_W8_EXACT43) {
             const GemvW8Kern k = l.form == SS_GEMV_FORM_W8_EXACT16 ? gv_w8_exact_kernel<T, 16>(l) : gv_w8_exact_kernel<T, 43>(l);
             hipLaunchKernelGGL(k, g, b, 0, s, a, w_scale, cdiv(a.N, 16));
+        } else if (l.form == SS_GEMV_FORM_MX4) {
+            void (*const k)(GemvArgs, const uint8_t*, int, int) = l.silu ? gemv_mx4_kernel<T, true> : gemv_mx4_kernel<T, false>;
+            hipLaunchKernelGGL(k, g, b, 0, s, a, mx_scale, l.param / 4, cdiv(a.N, 16));
+        } else if (l.form == SS_GEMV_FORM_MX4_EXACT16 || l.form == SS_GEMV_FORM_MX4_EXACT43) {
+            const GemvMx4Kern k = l.form == SS_GEMV_FORM_MX4_EXACT16 ? gv_mx4_exact_kernel<T, 4>(l) : gv_mx4_exact_kernel<T, 11>(l);
+            hipLaunchKernelGGL(k, g, b, 0, s, a, mx_scale, cdiv(a.N, 16));
         } else if (l.form == SS_GEMV_FORM_MFMA) {
             void (*const k)(GemvArgs, int, int) = l.silu ? gemv_mfma_kernel<T, true> : gemv_mfma_kernel<T, false>;
             hipLaunchKernelGGL(k, g, b, 0, s, a, l.param, cdiv(a.N, 16));
@@ -1330,7 +1589,8 @@ static int gemv_run(const GemvPlan& plan, const GemvArgs& args, hipStream_t s, c
             const GemvTileKern k = l.form == SS_GEMV_FORM_MFMA_EXACT16 ? gv_exact_kernel<T, 16>(l) : gv_exact_kernel<T, 43>(l);
             hipLaunchKernelGGL(k, g, b, 0, s, a, cdiv(a.N, 16));
         }
-        static const char* const what[] = {"gemv", "gemv_ldsx", "gemv_mfma", "gemv_mfma", "gemv_mfma", "gemv_split_f32", "gemv_w8", "gemv_w8", "gemv_w8"};
+        static const char* const what[] = {"gemv", "gemv_ldsx", "gemv_mfma", "gemv_mfma", "gemv_mfma", "gemv_split_f32", "gemv_w8", "gemv_w8", "gemv_w8",
+                                           "gemv_mx4", "gemv_mx4", "gemv_mx4"};
         SS_LAUNCH_CHECK(what[l.form]);
     }
     return SS_OK;
@@ -1385,6 +1645,30 @@ int gemv_w8_batched_dev(const void* Wq, const float* w_scale, const void* x, voi
     return dtype == SS_BF16 ? gemv_run<bf16_t>(plan, a, s, w_scale) : gemv_run<f16_t>(plan, a, s, w_scale);
 }
 
+int gemv_mx4_check(int64_t N, int64_t K, int nb, int dtype, int epi, bool norm) {
+    GemvPlan plan;
+    return gemv_mx4_plan(N, K, nb, dtype, epi, norm, plan);
+}
+
+int gemv_mx4_batched_dev(const void* codes, const void* scales, const void* x, void* y, int64_t N, int64_t K, const void* norm_w,
+                         float eps, const void* bias, const void* residual, int epi, const int32_t* done_flag, int done_stride,
+                         int nb, int64_t x_ld, int64_t y_ld, int64_t res_ld, int dtype, hipStream_t s) {
+    GemvPlan plan;
+    const int rc = gemv_mx4_plan(N, K, nb, dtype, epi, norm_w != nullptr, plan);
+    if (rc) return rc;
+    SS_REQUIRE(codes && scales && x && y, "gemv_mx4: NULL argument");
+    SS_REQUIRE(!(epi & SS_EPI_BIAS) || bias, "gemv_mx4: BIAS epilogue without a bias");
+    SS_REQUIRE(!(epi & SS_EPI_RESIDUAL) || residual, "gemv_mx4: RESIDUAL epilogue without a residual");
+    SS_REQUIRE((((size_t)codes | (size_t)x | (size_t)norm_w) & 15) == 0 && (x_ld & 7) == 0,
+               "gemv_mx4: codes, x and norm_w must be 16-byte aligned (x row stride a multiple of 8 elements)");
+    GemvArgs a;
+    a.W = codes; a.x = x; a.y = y; a.norm_w = norm_w; a.bias = bias; a.residual = residual; a.done_flag = done_flag;
+    a.N = (int)N; a.K = (int)K; a.epi = epi; a.eps = eps; a.use_nt = 0;
+    a.nb = nb; a.done_stride = done_stride; a.x_ld = x_ld; a.y_ld = y_ld; a.res_ld = res_ld;
+    return dtype == SS_BF16 ? gemv_run<bf16_t>(plan, a, s, nullptr, (const uint8_t*)scales)
+                            : gemv_run<f16_t>(plan, a, s, nullptr, (const uint8_t*)scales);
+}
+
 int gemv_dev(const void* W, const void* x, void* y, int64_t N, int64_t K, const void* norm_w, float eps,
              const void* bias, const void* residual, int epi, const int32_t* done_flag, int dtype, hipStream_t s) {
     return gemv_batched_dev(W, x, y, N, K, norm_w, eps, bias, residual, epi, done_flag, 0, 1, K, N, N, dtype, s);
@@ -1425,6 +1709,23 @@ extern "C" int ss_gemv_w8_plan(int64_t N, int64_t K, int64_t nb, int dtype, int 
     const int rc = ss::gemv_w8_plan(N, K, (int)nb, dtype, epilogue, has_norm != 0, plan);
     if (rc) return rc;
     SS_REQUIRE(rows && max_rows >= plan.n, "ss_gemv_w8_plan: %d rows needed, room for %lld", plan.n, (long long)max_rows);
+    memcpy(rows, plan.l, (size_t)plan.n * sizeof(ss::GemvLaunch));
+    return plan.n;
+}
+
+extern "C" int ss_gemv_mx4(const void* codes, const void* scales, const void* x, void* y, int64_t N, int64_t K, int64_t nb,
+                           const void* norm_w, float eps, const void* bias, const void* residual, int epilogue, int dtype, void* stream) {
+    SS_REQUIRE(nb >= 1 && nb <= 16, "gemv_mx4: batch %lld unsupported (1..16)", (long long)nb);
+    return ss::gemv_mx4_batched_dev(codes, scales, x, y, N, K, norm_w, eps, bias, residual, epilogue, nullptr, 0, (int)nb, K, N, N, dtype,
+                                    (hipStream_t)stream);
+}
+
+extern "C" int ss_gemv_mx4_plan(int64_t N, int64_t K, int64_t nb, int dtype, int epilogue, int has_norm, int32_t* rows, int64_t max_rows) {
+    ss::GemvPlan plan;
+    SS_REQUIRE(nb >= 1 && nb <= 16, "gemv_mx4: batch %lld unsupported (1..16)", (long long)nb);
+    const int rc = ss::gemv_mx4_plan(N, K, (int)nb, dtype, epilogue, has_norm != 0, plan);
+    if (rc) return rc;
+    SS_REQUIRE(rows && max_rows >= plan.n, "ss_gemv_mx4_plan: %d rows needed, room for %lld", plan.n, (long long)max_rows);
     memcpy(rows, plan.l, (size_t)plan.n * sizeof(ss::GemvLaunch));
     return plan.n;
 }

@@ -454,7 +454,8 @@ struct SeqGraph {
     int seq0, nb;
     int mode;                // arithmetic knobs the captured kernels were chosen under (gemm_f32_split): part of the cache key
     int capture;             // attention-map capture on: one more launch per layer (a different graph; the buffer is NOT part of the key)
-    int w8;                  // fp8 decode weights on (ss_llama_set_decode_w8): other kernels, other weight pointers
+    int w8;                  // 1 = fp8 decode weights on (ss_llama_set_decode_w8), 2 = MXFP4 ones (ss_llama_set_decode_mx4): other
+                             // kernels, other weight pointers
     int sampling;            // a slot of [seq0, seq0+nb) has sampling on (ss_llama_set_sampling): the sampling kernel opens the token
     int rules;               // a slot of [seq0, seq0+nb) has history rules on (ss_llama_set_logits_rules): the rules kernel in front
     int kv8;                 // fp8 KV shadow on (ss_llama_set_kv8): another attention kernel, the planes' pointers
@@ -500,6 +501,11 @@ struct ss_llama {
     std::vector<ss_llama_layer_w8> w8;
     const void* w8_lm_head = nullptr;
     const float* w8_lm_scale = nullptr;
+    // MXFP4 decode weights (ss_llama_set_decode_mx4): empty = off; never on together with the fp8 planes
+    std::vector<ss_llama_layer_mx4> mx4;
+    const void* mx4_lm_head = nullptr;
+    const void* mx4_lm_scale = nullptr;
+    int decode_weights_kind() const { return !mx4.empty() ? 2 : !w8.empty() ? 1 : 0; }
     // fp8 shadow of the KV cache (ss_llama_set_kv8): caller-owned planes, kq == NULL = off.  Invariant: shadow rows
     // [0, kv8_rows[b]) of slot b equal the quantiser applied to its 16-bit rows (host-side watermark, <= kv_len[b] wherever
     // it matters: everything that rewrites 16-bit rows below it lowers it)
@@ -743,15 +749,18 @@ static int decode_token(ss_llama* h, hipStream_t s, ProfSink* prof, int seq0, in
     char* logits = h->logits + (size_t)seq0 * g.vocab * e;
     float* attn_ws = (float*)((char*)h->attn_ws + (size_t)seq0 * ss_attn_decode_workspace_bytes(g.n_heads, hd));
     int rc;
-    // the five decode projections: the 16-bit weights, or their fp8 planes + row scales while ss_llama_set_decode_w8 is on
-    const bool w8 = !h->w8.empty();
-    auto proj = [&](const void* W, const void* Wq, const float* sc, const char* x, char* y, int64_t N, int64_t K, const void* norm_w,
+    // the five decode projections: the 16-bit weights, their fp8 planes + row scales while ss_llama_set_decode_w8 is on, or their
+    // MXFP4 code + block-scale planes while ss_llama_set_decode_mx4 is
+    const bool w8 = !h->w8.empty(), mx4 = !h->mx4.empty();
+    auto proj = [&](const void* W, const void* Wq, const void* sc, const char* x, char* y, int64_t N, int64_t K, const void* norm_w,
                     const void* residual, int epi, int64_t y_ld, int64_t res_ld) {
+        if (mx4)
+            return gemv_mx4_batched_dev(Wq, sc, x, y, N, K, norm_w, g.rms_eps, nullptr, residual, epi, done, ST_WORDS, nb, K, y_ld, res_ld, dt, s);
         if (w8)
-            return gemv_w8_batched_dev(Wq, sc, x, y, N, K, norm_w, g.rms_eps, nullptr, residual, epi, done, ST_WORDS, nb, K, y_ld, res_ld, dt, s);
+            return gemv_w8_batched_dev(Wq, (const float*)sc, x, y, N, K, norm_w, g.rms_eps, nullptr, residual, epi, done, ST_WORDS, nb, K, y_ld, res_ld, dt, s);
         return gemv_batched_dev(W, x, y, N, K, norm_w, norm_w ? g.rms_eps : 0.f, nullptr, residual, epi, done, ST_WORDS, nb, K, y_ld, res_ld, dt, s);
     };
-    static const ss_llama_layer_w8 kNoW8 = {};
+    static const ss_llama_layer_mx4 kNoQ = {};
 #define MARK(c) do { if (prof) prof->mark(c); } while (0)
     MARK(-1);
     // a slot records log-probabilities: the raw row is read before anything edits it (off everywhere, the default: no launch)
@@ -769,7 +778,12 @@ static int decode_token(ss_llama* h, hipStream_t s, ProfSink* prof, int seq0, in
     MARK(3);
     for (int l = 0; l < g.n_layers; ++l) {
         const ss_llama_layer_weights& L = h->layers[l];
-        const ss_llama_layer_w8& Q = w8 ? h->w8[l] : kNoW8;
+        ss_llama_layer_mx4 Q = kNoQ;       // the quantised planes of this layer, either kind: codes, scales
+        if (mx4) Q = h->mx4[l];
+        else if (w8) {
+            const ss_llama_layer_w8& q8 = h->w8[l];
+            Q = {q8.wqkv, q8.wo, q8.wgu, q8.wdown, q8.s_qkv, q8.s_o, q8.s_gu, q8.s_down};
+        }
         char* kc = slot_k(h, seq0, l);
         char* vc = slot_v(h, seq0, l);
         MARK(-1);
@@ -806,7 +820,7 @@ static int decode_token(ss_llama* h, hipStream_t s, ProfSink* prof, int seq0, in
     }
     if ((rc = SS_DISPATCH(dt, final_norm_advance_launch, h, seq0, nb, s))) return rc;
     MARK(3);
-    rc = proj(h->w.lm_head, h->w8_lm_head, h->w8_lm_scale, h->xn, logits, g.vocab, H, nullptr, nullptr, SS_EPI_NONE, g.vocab, 0);
+    rc = proj(h->w.lm_head, mx4 ? h->mx4_lm_head : h->w8_lm_head, mx4 ? h->mx4_lm_scale : (const void*)h->w8_lm_scale, h->xn, logits, g.vocab, H, nullptr, nullptr, SS_EPI_NONE, g.vocab, 0);
     if (rc) return rc;
     MARK(0);
 #undef MARK
@@ -828,7 +842,7 @@ static int sync_lengths(ss_llama* h, int seq0, int nb, hipStream_t s) {
 static int graph_for(ss_llama* h, int seq0, int nb, hipGraphExec_t* out) {
     const int mode = knob(K_gemm_f32_split);
     const int capture = (h->cap.maps && nb == 1) ? 1 : 0;
-    const int w8 = h->w8.empty() ? 0 : 1;
+    const int w8 = h->decode_weights_kind();
     const int sampling = h->sampling_in(seq0, nb) ? 1 : 0;
     const int rules = h->rules_in(seq0, nb) ? 1 : 0;
     const int kv8 = h->kq ? 1 : 0;
@@ -1286,7 +1300,7 @@ int ss_llama_set_history(ss_llama* h, int32_t seq, const int32_t* host_ids, int6
 
 // the captured fp8 graphs hold the pointers of the planes they were captured over (weights: flag = &SeqGraph::w8, KV shadow:
 // &SeqGraph::kv8): dropped when those planes change
-static void drop_graphs(ss_llama* h, int SeqGraph::*flag) {
+static void drop_graphs(ss_llama* h, int SeqGraph::*flag) {      // (every graph whose flag is non-zero)
     size_t keep = 0;
     for (SeqGraph& sg : h->graphs) {
         if (!(sg.*flag)) { h->graphs[keep++] = sg; continue; }
@@ -1298,7 +1312,8 @@ static void drop_graphs(ss_llama* h, int SeqGraph::*flag) {
 
 int ss_llama_set_decode_w8(ss_llama* h, const ss_llama_layer_w8* layers, const void* lm_head_q, const float* lm_head_scale) {
     SS_REQUIRE(h, "llama_set_decode_w8: null handle");
-    if (!layers) {      // off: the 16-bit graphs are still cached; the fp8 ones go with their planes
+    if (!layers) {      // off: the 16-bit graphs are still cached; the fp8 ones go with their planes (MXFP4 planes, if on, stay)
+        if (h->w8.empty()) return SS_OK;
         drop_graphs(h, &SeqGraph::w8);
         h->w8.clear();
         h->w8_lm_head = nullptr;
@@ -1326,9 +1341,50 @@ int ss_llama_set_decode_w8(ss_llama* h, const ss_llama_layer_w8* layers, const v
     }
     SS_REQUIRE(((size_t)lm_head_q & 15) == 0, "llama_set_decode_w8: the lm_head plane must be 16-byte aligned");
     drop_graphs(h, &SeqGraph::w8);
+    h->mx4.clear();     // the two kinds of planes exclude each other
+    h->mx4_lm_head = h->mx4_lm_scale = nullptr;
     h->w8.assign(layers, layers + g.n_layers);
     h->w8_lm_head = lm_head_q;
     h->w8_lm_scale = lm_head_scale;
+    return SS_OK;
+}
+
+int ss_llama_set_decode_mx4(ss_llama* h, const ss_llama_layer_mx4* layers, const void* lm_head_codes, const void* lm_head_scales) {
+    SS_REQUIRE(h, "llama_set_decode_mx4: null handle");
+    if (!layers) {      // off (fp8 planes, if those are what is on, stay): the 16-bit graphs are still cached
+        if (h->mx4.empty()) return SS_OK;
+        drop_graphs(h, &SeqGraph::w8);
+        h->mx4.clear();
+        h->mx4_lm_head = h->mx4_lm_scale = nullptr;
+        return SS_OK;
+    }
+    const ss_llama_config& g = h->cfg;
+    SS_REQUIRE(g.dtype == SS_BF16 || g.dtype == SS_F16, "llama_set_decode_mx4: MXFP4 decode weights need a bf16 / fp16 engine (dtype %d)", g.dtype);
+    SS_REQUIRE(lm_head_codes && lm_head_scales, "llama_set_decode_mx4: NULL lm_head codes or scales");
+    const int64_t H = g.hidden, I = g.inter;
+    // the five projections, at one sequence and at all slots: every shape the decode loop will launch
+    const struct { int64_t N, K; int epi; bool norm; } shapes[5] = {
+        {3 * H, H, SS_EPI_NONE, true}, {H, H, SS_EPI_RESIDUAL, false}, {I, H, SS_EPI_SILU_MUL, true}, {H, I, SS_EPI_RESIDUAL, false},
+        {g.vocab, H, SS_EPI_NONE, false}};
+    for (const auto& sh : shapes) {
+        int rc = gemv_mx4_check(sh.N, sh.K, 1, g.dtype, sh.epi, sh.norm);
+        if (!rc) rc = gemv_mx4_check(sh.N, sh.K, h->n_seq, g.dtype, sh.epi, sh.norm);
+        if (rc) return rc;
+    }
+    for (int l = 0; l < g.n_layers; ++l) {
+        const ss_llama_layer_mx4& Q = layers[l];
+        SS_REQUIRE(Q.wqkv && Q.wo && Q.wgu && Q.wdown && Q.s_qkv && Q.s_o && Q.s_gu && Q.s_down, "llama_set_decode_mx4: NULL pointer in layer %d", l);
+        SS_REQUIRE((((size_t)Q.wqkv | (size_t)Q.wo | (size_t)Q.wgu | (size_t)Q.wdown) & 15) == 0,
+                   "llama_set_decode_mx4: layer %d: the code planes must be 16-byte aligned", l);
+    }
+    SS_REQUIRE(((size_t)lm_head_codes & 15) == 0, "llama_set_decode_mx4: the lm_head code plane must be 16-byte aligned");
+    drop_graphs(h, &SeqGraph::w8);
+    h->w8.clear();      // the two kinds of planes exclude each other
+    h->w8_lm_head = nullptr;
+    h->w8_lm_scale = nullptr;
+    h->mx4.assign(layers, layers + g.n_layers);
+    h->mx4_lm_head = lm_head_codes;
+    h->mx4_lm_scale = lm_head_scales;
     return SS_OK;
 }
 
@@ -1707,9 +1763,9 @@ int ss_llama_profile_decode(ss_llama* h, int64_t n_tokens, float out_ms[8], doub
     for (int i = 0; i < 8; ++i) out_ms[i] /= (float)n_tokens;
     const double H = g.hidden, I = g.inter;
     // class 0 = every GEMV except the down projection (qkv, o, gate|up per layer + lm_head); class 2 = down
-    // (fp8 decode weights: one byte per weight + the fp32 row scales)
-    const bool w8 = !h->w8.empty();
-    const double wb = w8 ? 1.0 : (double)h->esz;
+    // (fp8 decode weights: one byte per weight + the fp32 row scales; MXFP4: half a byte per weight + one scale byte per 32)
+    const bool w8 = !h->w8.empty(), mx4 = !h->mx4.empty();
+    const double wb = mx4 ? 0.5 + 1.0 / 32.0 : w8 ? 1.0 : (double)h->esz;
     out_bytes[0] = ((double)g.n_layers * (4.0 * H * H + 2.0 * H * I) + (double)g.vocab * H) * wb;
     out_bytes[1] = cnt[0] / (double)n_tokens;
     out_bytes[2] = (double)g.n_layers * H * I * wb;

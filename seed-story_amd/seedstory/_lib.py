@@ -35,6 +35,10 @@ class LlamaLayerW8(C.Structure):
     _fields_ = [("wqkv", vp), ("wo", vp), ("wgu", vp), ("wdown", vp), ("s_qkv", vp), ("s_o", vp), ("s_gu", vp), ("s_down", vp)]
 
 
+class LlamaLayerMx4(C.Structure):       # four code planes, four e8m0 scale planes
+    _fields_ = [("wqkv", vp), ("wo", vp), ("wgu", vp), ("wdown", vp), ("s_qkv", vp), ("s_o", vp), ("s_gu", vp), ("s_down", vp)]
+
+
 class Sampling(C.Structure):
     _fields_ = [("temperature", f32), ("top_p", f32), ("top_k", i32), ("seed", C.c_uint64)]
 
@@ -96,6 +100,7 @@ PROTOTYPES = {
     "ss_gemm_splitk_workspace_bytes": (C.c_size_t, [i64, i64, i64]),
     "ss_gemm_splitk": (C.c_int, [vp, vp, vp, i64, i64, i64, vp, vp, vp, C.c_size_t, C.c_int, vp]),
     "ss_quantize_rows_fp8": (C.c_int, [vp, i64, i64, i64, vp, vp, vp, vp, f32, C.c_int, vp]),
+    "ss_quantize_rows_mxfp4": (C.c_int, [vp, i64, i64, i64, vp, vp, C.c_int, vp]),
     "ss_gemm_fp8": (C.c_int, [vp, vp, vp, vp, vp, i64, i64, i64, i64, vp, vp, i64, C.c_int, vp]),
     "ss_create": (C.c_int, [C.c_int, C.POINTER(vp)]),
     "ss_context_info": (C.c_int, [vp, C.POINTER(i64)]),
@@ -138,6 +143,8 @@ PROTOTYPES = {
     "ss_gemv_plan": (C.c_int, [i64, i64, i64, C.c_int, C.c_int, C.c_int, C.c_int, i32p, i64]),
     "ss_gemv_w8": (C.c_int, [vp, vp, vp, vp, i64, i64, i64, vp, f32, vp, vp, C.c_int, C.c_int, vp]),
     "ss_gemv_w8_plan": (C.c_int, [i64, i64, i64, C.c_int, C.c_int, C.c_int, i32p, i64]),
+    "ss_gemv_mx4": (C.c_int, [vp, vp, vp, vp, i64, i64, i64, vp, f32, vp, vp, C.c_int, C.c_int, vp]),
+    "ss_gemv_mx4_plan": (C.c_int, [i64, i64, i64, C.c_int, C.c_int, C.c_int, i32p, i64]),
     "ss_imgproc_argmax": (C.c_int, [vp, i64, vp, vp, i64, vp, C.c_int, vp]),
     "ss_sample_logits": (C.c_int, [vp, i64, i64, i64, C.POINTER(Sampling), vp, C.c_uint32, vp, vp, i64, vp, vp, C.c_int, vp]),
     "ss_process_logits": (C.c_int, [vp, i64, i64, i64, C.POINTER(LogitsRules), vp, i64, vp, vp, i32, vp, i64, C.c_int, vp]),
@@ -151,6 +158,7 @@ PROTOTYPES = {
     "ss_llama_set_stop_id": (C.c_int, [vp, i32]),
     "ss_llama_set_attn_capture": (C.c_int, [vp, vp, i64, i64, i64, i32, i32]),
     "ss_llama_set_decode_w8": (C.c_int, [vp, C.POINTER(LlamaLayerW8), vp, vp]),
+    "ss_llama_set_decode_mx4": (C.c_int, [vp, C.POINTER(LlamaLayerMx4), vp, vp]),
     "ss_llama_kv8_bytes": (C.c_int, [C.POINTER(LlamaConfig), C.POINTER(sz), C.POINTER(sz)]),
     "ss_llama_set_kv8": (C.c_int, [vp, vp, vp, vp, vp]),
     "ss_llama_kv8_invalidate": (C.c_int, [vp, i64]),

@@ -44,12 +44,26 @@ def _prefill_chunked(eng, emb, want_hidden):
     return torch.cat([p.clone() for p in parts]) if want_hidden and len(parts) > 1 else parts[0]
 
 
+def knob_decode_weights(dtype):
+    """What ``decode_weights=None`` means for an engine of ``dtype``: the tuning knobs ``llama_decode_w8`` / ``llama_decode_mx4``
+    are a default for the engines that can take the option; fp32 (gate mode) engines stay as they are.  Both knobs set is an
+    error."""
+    w8, mx4 = _lib.get_tuning("llama_decode_w8", 0), _lib.get_tuning("llama_decode_mx4", 0)
+    if dtype not in (torch.bfloat16, torch.float16):
+        return None
+    if w8 and mx4:
+        raise ValueError("the tuning knobs llama_decode_w8 and llama_decode_mx4 are both set: fp8 and MXFP4 decode weights "
+                         "exclude each other (clear one, or pass decode_weights=)")
+    return "fp8" if w8 else "mxfp4" if mx4 else None
+
+
 class LlamaEngine:
     def __init__(self, state_dict, *, hidden, n_heads, n_layers, inter, vocab, dtype=torch.bfloat16, device="cuda:0",
                  rms_eps=1e-5, max_pos=4096, cache_cap=2048, max_new=512, max_prefill_rows=1024, img_ids=(),
                  eos_id=2, lora_scaling=2.0, n_seq=1, decode_weights=None, kv_cache=None):
-        """``decode_weights``: None = the ``llama_decode_w8`` tuning knob decides (default off), "fp8" = decode tokens
-        stream e4m3 copies of the five projections (``enable_decode_fp8``), "16bit" = off whatever the knob says.
+        """``decode_weights``: None = the ``llama_decode_w8`` / ``llama_decode_mx4`` tuning knobs decide (default off),
+        "fp8" = decode tokens stream e4m3 copies of the five projections (``enable_decode_fp8``), "mxfp4" = MXFP4 copies
+        (``enable_decode_mxfp4``), "16bit" = off whatever the knobs say.
         ``kv_cache``: the same three values for the e4m3 shadow of the KV cache that decode attention reads
         (``enable_kv_fp8``; knob ``llama_kv8``, default off)."""
         self.n_seq = int(n_seq)
@@ -308,13 +322,14 @@ class LlamaEngine:
 
     # ---- fp8 (e4m3) weight-only decode -------------------------------------------------------------------
     def _init_decode_weights(self, decode_weights):
-        if decode_weights is None:      # the knob is a default for the engines that can take it: fp32 (gate mode) engines stay as they are
-            on = _lib.get_tuning("llama_decode_w8", 0) and self.dtype in (torch.bfloat16, torch.float16)
-            decode_weights = "fp8" if on else None
-        if decode_weights not in (None, "16bit", "fp8"):
-            raise ValueError("decode_weights must be None, '16bit' or 'fp8', not %r" % (decode_weights,))
+        if decode_weights is None:
+            decode_weights = knob_decode_weights(self.dtype)
+        if decode_weights not in (None, "16bit", "fp8", "mxfp4"):
+            raise ValueError("decode_weights must be None, '16bit', 'fp8' or 'mxfp4', not %r" % (decode_weights,))
         if decode_weights == "fp8":
             self.enable_decode_fp8()
+        elif decode_weights == "mxfp4":
+            self.enable_decode_mxfp4()
 
     def enable_decode_fp8(self):
         """Quantise the engine's own merged weights on the device (one e4m3 scale per output row, ``amax / 448``) and
@@ -352,14 +367,67 @@ class LlamaEngine:
         ql, sl = plane(lm_head, (self.vocab, self.hidden), "lm_head")
         torch.cuda.current_stream(self.device).synchronize()
         check(lib().ss_llama_set_decode_w8(self._h, arr, ql.data_ptr(), sl.data_ptr()), "ss_llama_set_decode_w8")
-        self._w8 = keep
+        self._w8 = keep            # (the engine dropped the MXFP4 planes, if any, with this call)
         self.decode_weights = "fp8"
 
     def disable_decode_fp8(self):
         torch.cuda.current_stream(self.device).synchronize()
         check(lib().ss_llama_set_decode_w8(self._h, None, None, None), "ss_llama_set_decode_w8")
-        self._w8 = None
-        self.decode_weights = None
+        if self.decode_weights == "fp8":
+            self._w8 = None
+            self.decode_weights = None
+
+    # ---- MXFP4 (e2m1 codes + e8m0 block scales) weight-only decode ----------------------------------------
+    def enable_decode_mxfp4(self):
+        """Quantise the engine's own merged weights on the device to OCP MXFP4 (``ops.quantize_weight_rows_mxfp4``: two
+        e2m1 codes per byte, one power-of-two scale per 32 consecutive k) and switch the decode projections to them:
+        ``generate`` / ``generate_batch`` / ``profile_decode`` then stream 0.53 bytes per weight.  Prefill, the image-token
+        block and the one-row lm_head at the end of a prefill keep the 16-bit weights, so those stay resident: the option
+        COSTS memory, about 3.5 GB on top for LLaMA-7B.  Excludes the fp8 option (the later call wins).  Off by default:
+        what round-to-nearest MXFP4 weights do to stories on a real checkpoint has not been measured."""
+        layers = [tuple(ops.quantize_weight_rows_mxfp4(w) for w in lw) for lw in self._proj]
+        self.set_decode_mxfp4(layers, ops.quantize_weight_rows_mxfp4(self.lm_head))
+
+    def set_decode_mxfp4(self, layers, lm_head):
+        """Caller-supplied planes in the public layout (include/seedstory_hip.h, ss_gemv_mx4): ``layers[l]`` = four
+        ``(codes uint8 [N, K / 2], scales uint8 [N, K / 32])`` pairs for wqkv, wo, wgu (= [gate; up]) and wdown in the
+        engine's layouts, ``lm_head`` one such pair.  ``layers=None`` switches the option off.  Raises ``SSError`` on an fp32
+        engine or a projection shape the MXFP4 kernel does not take."""
+        if layers is None:
+            return self.disable_decode_mxfp4()
+        shapes = ((3 * self.hidden, self.hidden), (self.hidden, self.hidden), (2 * self.inter, self.hidden), (self.hidden, self.inter))
+        if len(layers) != self.n_layers:
+            raise _lib.SSError("set_decode_mxfp4: %d layers given, the engine has %d" % (len(layers), self.n_layers))
+        keep = []
+
+        def plane(pair, shape, what):
+            q, s = pair
+            N, K = shape
+            if (q.dtype != torch.uint8 or s.dtype != torch.uint8 or K % 32 or tuple(q.shape) != (N, K // 2)
+                    or tuple(s.shape) != (N, K // 32)):
+                raise _lib.SSError("set_decode_mxfp4: %s must be (uint8 codes [%d, %d / 2], uint8 scales [%d, %d / 32])"
+                                   % (what, N, K, N, K))
+            q = q.to(self.device).contiguous()
+            s = s.to(self.device).contiguous()
+            keep.extend((q, s))
+            return q, s
+
+        arr = (_lib.LlamaLayerMx4 * self.n_layers)()
+        for l, lw in enumerate(layers):
+            qs = [plane(pr, sh, "layer %d projection %d" % (l, j)) for j, (pr, sh) in enumerate(zip(lw, shapes))]
+            arr[l] = _lib.LlamaLayerMx4(*([q.data_ptr() for q, _ in qs] + [s.data_ptr() for _, s in qs]))
+        ql, sl = plane(lm_head, (self.vocab, self.hidden), "lm_head")
+        torch.cuda.current_stream(self.device).synchronize()
+        check(lib().ss_llama_set_decode_mx4(self._h, arr, ql.data_ptr(), sl.data_ptr()), "ss_llama_set_decode_mx4")
+        self._w8 = keep            # (the engine dropped the fp8 planes, if any, with this call)
+        self.decode_weights = "mxfp4"
+
+    def disable_decode_mxfp4(self):
+        torch.cuda.current_stream(self.device).synchronize()
+        check(lib().ss_llama_set_decode_mx4(self._h, None, None, None), "ss_llama_set_decode_mx4")
+        if self.decode_weights == "mxfp4":
+            self._w8 = None
+            self.decode_weights = None
 
     # ---- fp8 (e4m3) shadow of the KV cache for decode attention --------------------------------------------------
     def _init_kv_cache(self, kv_cache):

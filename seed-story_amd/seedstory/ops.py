@@ -412,6 +412,42 @@ def quantize_weight_rows_fp8(w):
     return quantize_rows_fp8(w.contiguous())
 
 
+def gemv_mx4(codes, scales, x, norm_w=None, eps=0.0, bias=None, residual=None, silu_mul=False, out=None):
+    """``gemv_batched`` over MXFP4 weights: codes uint8 [N, K / 2] (two OCP e2m1 codes per byte, k = 2j in bits 0-3 of byte j),
+    scales uint8 [N, K / 32] (e8m0: 32 consecutive k times ``2^(byte - 127)``); [2N, ...] = [gate; up] with ``silu_mul``.
+    x [nb, K] (nb <= 16) or [K] in bf16 / fp16 -> y [nb, N] or [N] in x's dtype:
+    ``epilogue(sum_k dec(codes[n, k]) * 2^(scales[n, k // 32] - 127) * x[b, k])``.  K % 32 == 0 and K <= 4096, or K == 11008."""
+    _req(codes); _req(x); _req(scales)
+    if (codes.dtype != torch.uint8 or scales.dtype != torch.uint8 or codes.dim() != 2 or scales.dim() != 2
+            or scales.shape[0] != codes.shape[0] or scales.shape[1] * 16 != codes.shape[1]):
+        raise _lib.SSError("gemv_mx4: codes must be uint8 [N, K / 2] and scales uint8 [N, K / 32]")
+    N, K = codes.shape[0], codes.shape[1] * 2
+    if silu_mul:
+        N //= 2
+    one = x.dim() == 1
+    nb = 1 if one else x.shape[0]
+    y = _out(out, (N,) if one else (nb, N), x, "gemv_mx4")
+    epi = (EPI_BIAS if bias is not None else 0) | (EPI_RESIDUAL if residual is not None else 0) | \
+          (EPI_SILU_MUL if silu_mul else 0)
+    check(lib().ss_gemv_mx4(p(codes), p(scales), p(x), p(y), N, K, nb, p(norm_w), eps, p(bias), p(residual), epi, dt(x), stream()),
+          "ss_gemv_mx4")
+    return y
+
+
+def quantize_weight_rows_mxfp4(w):
+    """w [N, K] (bf16 / fp16 on the GPU, K % 32 == 0) -> (codes uint8 [N, K / 2], scales uint8 [N, K / 32]) in the MXFP4 format
+    of ``gemv_mx4`` / ``LlamaEngine.set_decode_mxfp4``: per block of 32 k the smallest power of two 2^X (X clamped to
+    [-13, 13]) with ``amax / 2^X <= 6``, codes rounded to nearest on the e2m1 grid with ties to even (the bit-exact definition
+    is in include/seedstory_hip.h).  An all-zero block gets X = -13 and codes 0."""
+    _req(w)
+    w = w.contiguous()
+    N, K = w.shape
+    codes = torch.empty(N, K // 2, dtype=torch.uint8, device=w.device)
+    scales = torch.empty(N, max(K // 32, 1), dtype=torch.uint8, device=w.device)[:, :K // 32]
+    check(lib().ss_quantize_rows_mxfp4(p(w), w.stride(0), N, K, p(codes), p(scales), dt(w), stream()), "ss_quantize_rows_mxfp4")
+    return codes, scales
+
+
 def imgproc_argmax(logits, last_id, img_ids):
     """In-place processor + argmax; returns an int32 device scalar tensor."""
     _req(logits)

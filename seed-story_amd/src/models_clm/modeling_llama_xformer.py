@@ -115,7 +115,8 @@ class LlamaForCausalLM(nn.Module):
         self.cache_cap = 2048
         self.max_new = 512
         self.max_prefill_rows = 1280
-        self.decode_weights = None      # "fp8": e4m3 weight-only decode projections (LlamaEngine.enable_decode_fp8); None = the knob
+        self.decode_weights = None      # "fp8": e4m3 weight-only decode projections (LlamaEngine.enable_decode_fp8), "mxfp4": MXFP4
+                                        # ones (enable_decode_mxfp4); None = the knobs
         self.kv_cache = None            # "fp8": decode attention reads an e4m3 shadow of the KV cache (LlamaEngine.enable_kv_fp8); None = the knob
         self.n_seq = 1                  # sequence slots of the engine: generate(num_return_sequences=n) needs n_seq >= n
         self._candidates = None         # (slots, kv_cache_head per candidate) of the last generate(num_return_sequences > 1)
