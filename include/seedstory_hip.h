@@ -770,6 +770,64 @@ int ss_llama_beam_search(ss_llama* h, const ss_beam_params* p, void* beam_ws, in
 int ss_llama_beam_permute(ss_llama* h, void* beam_ws, const int32_t* host_parent, int32_t n, int64_t kv0, int64_t hist0,
                           void* stream);
 
+/* Prompt-lookup speculative decoding of ONE slot's greedy loop (off by default; ss_llama_generate only).
+ *
+ * A speculative step forwards R <= 8 rows of the selected slot in one sweep of the weights: row 0 carries the token greedy just
+ * chose, rows 1 .. A-1 drafted successors at the following cache / RoPE positions.  The next step's opening kernel walks the R
+ * logits rows: row r's arg max (image-token processor applied with row r's own token as predecessor, forced tokens first) is the
+ * token greedy would emit after row r's token; while it equals draft r + 1 the draft is emitted under greedy's stop rules, the
+ * first one that differs becomes row 0 of the next step.  Rejected rows' K/V and hidden rows lie beyond kv_len / n_generated and
+ * are overwritten.  The emitted ids are greedy's by construction wherever the R-row and the 1-row kernels agree on the arg max
+ * (they order their sums differently: equality holds away from near-ties).
+ *
+ *   spec_open         one block: settle the previous step, emit, append to the slot's token history, draft, write the R row-state
+ *                     blocks (kv_len = L + r, pos = P + r, done = row unused), embed the rows
+ *   per layer         the batched GEMVs at nb = R over the row-state blocks; ss_attn_decode_spec in the attention's place
+ *   spec_final_norm   hidden row n_generated_base + r per used row, then the lm_head GEMV -> R logits rows
+ *
+ * Draft sources.  SS_SPEC_LOOKUP: transformers' PromptLookupCandidateGenerator.get_candidates on the slot's history (the ids
+ * handed over with ss_llama_set_history plus everything generated, the token just chosen included): n-gram sizes from
+ * min(max_ngram, len - 1) down to 1, the leftmost match with a non-empty continuation, at most R - 1 tokens, cut in front of the
+ * first stop id (EOS / the second stop id); an empty cut gives no draft.  SS_SPEC_GIVEN: draft r of a step whose row 0 is
+ * generated index n is given_ids[n + r] (device int32[given_len]); cut in front of a stop id or an id outside the vocabulary.
+ * Either source: while generated indices lie below n_forced the drafts are the forced tokens themselves.  A row is never used
+ * beyond the call's limit (the last token of a call needs no forward), max_new, cache_cap or max_pos; without a draft the step is
+ * a plain token.
+ *
+ * ss_attn_decode_spec — the attention of such a step as an operator.  qkv: `rows` pre-RoPE q|k|v rows, 3 * n_heads * hd apart;
+ * L = *kv_len_dev cached keys, row r at RoPE position *pos_dev + r; A = min(*n_active_dev, rows, cache_cap - L) active rows.
+ * Row r < A attends keys [0, L + r]; the kernel rotates and stores the A new K/V rows at cache rows L .. L + A - 1 (the bits
+ * ss_rope_kv_append stores) and takes them from registers, each 16-byte packet of the old cache is loaded once for all rows.
+ * out [rows, n_heads * hd]: rows >= A are not written.  workspace: rows * ss_attn_decode_workspace_bytes(n_heads, hd).
+ * ss_spec_draft — the lookup draft alone: hist_dev int32[len] -> out_ids_dev[0 .. *out_count_dev), k <= 7 tokens at most.
+ *
+ * The workspace of ss_llama_spec_bytes is caller-owned device memory (256-byte aligned), as the planes of ss_llama_set_kv8 are: it
+ * holds the R-row activations, R logits rows, attention partials, row states, drafts and counters, so an n_seq = 1 engine can
+ * speculate.  ss_llama_set_speculation(h, NULL, NULL) turns the option off.  While it is on, ss_llama_generate runs speculative
+ * steps (eager or captured; the captured graph is keyed by the parameters and the workspace) and appends every emitted token to
+ * the slot's history; ss_llama_generate_batch, ss_llama_fork and ss_llama_beam_search run as they always do.
+ * ss_llama_generate returns SS_EINVAL before anything is launched when the selected slot also has sampling, history rules,
+ * log-probability recording, the fp8 KV shadow or attention-map capture on (none of these is built for R rows).
+ * ss_llama_spec_stats: out[4] = speculative steps, rows drafted, drafts accepted, tokens emitted by the last ss_llama_generate. */
+#define SS_SPEC_LOOKUP 0
+#define SS_SPEC_GIVEN 1
+#define SS_SPEC_MAX_ROWS 8
+typedef struct ss_spec_params {
+    int32_t rows;               /* 2 .. 8 */
+    int32_t max_ngram;          /* 1 .. 8 (SS_SPEC_LOOKUP) */
+    int32_t source;             /* SS_SPEC_LOOKUP | SS_SPEC_GIVEN */
+    int32_t given_len;
+    const int32_t* given_ids;   /* device, SS_SPEC_GIVEN */
+} ss_spec_params;
+int ss_llama_spec_bytes(const ss_llama_config* cfg, int32_t rows, size_t* bytes);
+int ss_llama_set_speculation(ss_llama* h, const ss_spec_params* p, void* spec_ws);
+int ss_llama_spec_stats(ss_llama* h, int32_t seq, int64_t out[4]);
+int ss_attn_decode_spec(const void* qkv, void* kcache, void* vcache, const void* cos, const void* sin, void* out, void* workspace,
+                        const int32_t* kv_len_dev, const int32_t* pos_dev, const int32_t* n_active_dev, int64_t rows,
+                        int64_t n_heads, int64_t hd, int64_t cache_cap, int dtype, void* stream);
+int ss_spec_draft(const int32_t* hist_dev, int64_t len, int32_t max_ngram, int32_t k, int32_t n_stop, const int32_t* stop_ids,
+                  int32_t* out_ids_dev, int32_t* out_count_dev, void* stream);
+
 /* LlamaModel.forward on M new rows against the cached prefix (prefill when the cache is
  * empty, bottom-right-causal continuation otherwise) — modeling_llama_xformer.py:532-666.
  * embeds [M, hidden]; pos_ids device int32[M] or NULL (pos, pos+1, …).  Writes the

@@ -20,6 +20,9 @@
 //    each packet read once and written to all of them — n sampled continuations of one prompt cost one prefill.
 //  * beam search (ss_llama_beam_search, ss_beam.h): slots [0, n) carry the running hypotheses; the token is opened by top-K,
 //    advance and a cycle-safe permutation of the slots' cache suffixes instead of the arg max, inside the same captured graph.
+//  * prompt-lookup speculative decoding (ss_llama_set_speculation, ss_spec.h, off by default): the token of ss_llama_generate forwards
+//    R <= 8 rows of the one slot — the chosen token and drafted successors — through the same batched GEMVs over R row-state blocks
+//    and a decode attention for R rows of one slot (ss_attn_spec.hip); the next opening kernel keeps the prefix greedy agrees with.
 #include <stddef.h>
 #include <string.h>
 
@@ -32,6 +35,7 @@
 #include "ss_kv8.h"
 #include "ss_logprob.h"
 #include "ss_beam.h"
+#include "ss_spec.h"
 
 namespace ss {
 
@@ -47,6 +51,9 @@ int attn_decode_fused_dev(const void* qkv_raw, void* kc, void* vc, const void* c
                           void* ws, const int32_t* kv_len_dev, const int32_t* pos_dev, const int32_t* done_flag,
                           int64_t n_heads, int64_t hd, int64_t cache_cap, int nb, int state_stride,
                           int64_t cache_stride, int dtype, hipStream_t s);
+int attn_decode_spec_dev(const void* qkv, void* kc, void* vc, const void* cos_t, const void* sin_t, void* out, void* ws,
+                         const int32_t* kv_len_dev, const int32_t* pos_dev, const int32_t* n_active_dev, int rows, int64_t n_heads,
+                         int64_t hd, int64_t cache_cap, int dtype, hipStream_t s);
 int attn_scores_dev(const void* q, int64_t ldq, const void* k, int64_t ldk, void* out, int64_t ldo, int64_t M, int64_t kv,
                     int64_t hd, int row_calls, int dtype, hipStream_t s);
 int attn_scores_decode_dev(const void* qkv_raw, const void* kplane, const void* cos_t, const void* sin_t,
@@ -462,6 +469,8 @@ struct SeqGraph {
     int logprobs;            // a slot of [seq0, seq0+nb) records log-probabilities (ss_llama_set_logprobs): two more kernels; the buffers are NOT part of the key
     int beam;                // beam search (ss_llama_beam_search): other opening kernels; 0 = none, else n_steps * 16 + n (the permute's grid)
     void* beam_ws;           // ... over this workspace (its pointers are kernel arguments)
+    int spec;                // speculative token (ss_llama_set_speculation): other kernels at nb = rows; 0 = plain, else the row count
+    void* spec_ws;           // ... over this workspace (its pointers are kernel arguments; the parameters live in its header)
     hipGraph_t graph;
     hipGraphExec_t exec;
 };
@@ -541,6 +550,10 @@ struct ss_llama {
     // beam search (ss_llama_beam_search): the caller's workspace while a search runs, hdr == NULL otherwise
     BeamPtrs beam = {nullptr, nullptr, nullptr, nullptr, nullptr};
     int beam_rows = 0;                  // its n_steps: the suffix rows the permute's grid covers
+    // speculative decoding (ss_llama_set_speculation): the caller's workspace, hdr == NULL = off
+    SpecPtrs spec = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    int spec_rows = 0;
+    bool spec_run = false;              // inside ss_llama_generate with the option on: decode_token takes the speculative branch
     int64_t hist_cap() const { return (int64_t)cfg.cache_cap + cfg.max_new; }
     int bm_words() const { return rules_bitmap_words(cfg.vocab); }
     size_t plane_bytes() const { return (size_t)cfg.n_heads * cfg.cache_cap * hd * esz; }       // one layer of one slot
@@ -738,15 +751,47 @@ static int beam_open_launch(ss_llama* h, int n, bool rules, hipStream_t s) {
     return beam_permute_launch(h, h->beam_rows, rules, s);
 }
 
+static const SpecSt kSpecSt = {ST_KV_LEN, ST_POS, ST_NGEN, ST_DONE, ST_LAST, ST_NFORCED, ST_LIMIT, ST_EOS, ST_WORDS};
+
+// the opening of a speculative step for slot `q`: settle, emit, draft, row states, embed
+template <typename T>
+static int spec_open_launch(ss_llama* h, int q, hipStream_t s) {
+    const ss_llama_config& g = h->cfg;
+    hipLaunchKernelGGL(spec_open_kernel<T>, dim3(1), dim3(1024), 0, s, (T*)h->logits + (size_t)q * g.vocab, (const T*)h->spec.logits,
+                       g.vocab, h->state + (size_t)q * ST_WORDS, kSpecSt, h->spec.hdr, h->spec.row_st, h->img_ids, g.n_img_ids,
+                       h->forced + (size_t)q * g.max_new, h->gen_ids + (size_t)q * g.max_new, h->hist + (size_t)q * h->hist_cap(),
+                       (int)h->hist_cap(), &h->rules[q].hist_len, &h->rules[q].n_app, h->hist_bm + (size_t)q * h->bm_words(),
+                       (const T*)h->w.embed, (T*)h->spec.x, g.hidden, g.max_new, g.cache_cap, g.max_pos);
+    SS_LAUNCH_CHECK("spec_open");
+    return SS_OK;
+}
+
+template <typename T>
+static int spec_final_norm_launch(ss_llama* h, int q, hipStream_t s) {
+    const ss_llama_config& g = h->cfg;
+    hipLaunchKernelGGL(spec_final_norm_kernel<T>, dim3((unsigned)h->spec_rows), dim3(256), 0, s, (const T*)h->spec.x,
+                       (const T*)h->w.final_norm, (T*)h->spec.xn, (T*)h->hid_rows + (size_t)q * g.max_new * g.hidden, h->spec.hdr,
+                       g.hidden, g.rms_eps, g.max_new);
+    SS_LAUNCH_CHECK("spec_final_norm");
+    return SS_OK;
+}
+
 static int decode_token(ss_llama* h, hipStream_t s, ProfSink* prof, int seq0, int nb) {
     const ss_llama_config& g = h->cfg;
     const int dt = g.dtype;
     const int H = g.hidden, I = g.inter, hd = h->hd;
     const size_t e = h->esz;
     int32_t* st = h->state + (size_t)seq0 * ST_WORDS;
-    const int32_t* done = st + ST_DONE;
+    // a speculative step of ss_llama_generate: the launchers below run at nb = rows over the row-state blocks and the workspace's
+    // activation rows (off, the default: nothing below changes)
+    const bool spec = h->spec_run && h->spec.hdr && nb == 1;
+    const int nslots = nb;      // the slots of the launch; nb: the rows its GEMVs serve
+    if (spec) nb = h->spec_rows;
+    char *const ax = spec ? h->spec.x : h->x, *const axn = spec ? h->spec.xn : h->xn, *const aqkv = spec ? h->spec.qkv : h->qkv;
+    char *const aattn = spec ? h->spec.attn : h->attn, *const ahm = spec ? h->spec.hm : h->hm;
+    const int32_t* done = (spec ? h->spec.row_st : st) + ST_DONE;
     const int64_t cache_stride = (int64_t)(h->seq_kv_bytes() / e);
-    char* logits = h->logits + (size_t)seq0 * g.vocab * e;
+    char* logits = spec ? h->spec.logits : h->logits + (size_t)seq0 * g.vocab * e;
     float* attn_ws = (float*)((char*)h->attn_ws + (size_t)seq0 * ss_attn_decode_workspace_bytes(g.n_heads, hd));
     int rc;
     // the five decode projections: the 16-bit weights, their fp8 planes + row scales while ss_llama_set_decode_w8 is on, or their
@@ -764,17 +809,19 @@ static int decode_token(ss_llama* h, hipStream_t s, ProfSink* prof, int seq0, in
 #define MARK(c) do { if (prof) prof->mark(c); } while (0)
     MARK(-1);
     // a slot records log-probabilities: the raw row is read before anything edits it (off everywhere, the default: no launch)
-    const bool lp = h->logprobs_in(seq0, nb);
-    if (lp && (rc = SS_DISPATCH(dt, logprob_raw_launch, h, seq0, nb, s))) return rc;
+    const bool lp = h->logprobs_in(seq0, nslots);
+    if (lp && (rc = SS_DISPATCH(dt, logprob_raw_launch, h, seq0, nslots, s))) return rc;
     // history rules on for a slot: its row is edited before the opening kernel reads it (off everywhere, the default: no launch)
-    if (h->rules_in(seq0, nb) && (rc = SS_DISPATCH(dt, logits_rules_launch, h, seq0, nb, 0, s))) return rc;
+    if (h->rules_in(seq0, nslots) && (rc = SS_DISPATCH(dt, logits_rules_launch, h, seq0, nslots, 0, s))) return rc;
+    // a speculative step: its opening kernel (the refusals of ss_llama_generate keep the option kernels above out of it)
+    if (spec) rc = SS_DISPATCH(dt, spec_open_launch, h, seq0, s);
     // a beam search runs on these slots (seq0 = 0): its three kernels open the token
-    if (h->beam.hdr) rc = SS_DISPATCH(dt, beam_open_launch, h, nb, h->rules_in(seq0, nb), s);
+    else if (h->beam.hdr) rc = SS_DISPATCH(dt, beam_open_launch, h, nslots, h->rules_in(seq0, nslots), s);
     // greedy slots only (the default): the launch it has always been
-    else if (h->sampling_in(seq0, nb)) rc = SS_DISPATCH(dt, sample_embed_draw_launch, h, seq0, nb, lp, s);
-    else rc = SS_DISPATCH(dt, sample_embed_launch, h, seq0, nb, s);
+    else if (h->sampling_in(seq0, nslots)) rc = SS_DISPATCH(dt, sample_embed_draw_launch, h, seq0, nslots, lp, s);
+    else rc = SS_DISPATCH(dt, sample_embed_launch, h, seq0, nslots, s);
     if (rc) return rc;
-    if (lp && (rc = SS_DISPATCH(dt, logprob_tok_launch, h, seq0, nb, s))) return rc;
+    if (lp && (rc = SS_DISPATCH(dt, logprob_tok_launch, h, seq0, nslots, s))) return rc;
     MARK(3);
     for (int l = 0; l < g.n_layers; ++l) {
         const ss_llama_layer_weights& L = h->layers[l];
@@ -787,12 +834,15 @@ static int decode_token(ss_llama* h, hipStream_t s, ProfSink* prof, int seq0, in
         char* kc = slot_k(h, seq0, l);
         char* vc = slot_v(h, seq0, l);
         MARK(-1);
-        rc = proj(L.wqkv, Q.wqkv, Q.s_qkv, h->x, h->qkv, 3 * H, H, L.ln1, nullptr, SS_EPI_NONE, 3 * H, 0);
+        rc = proj(L.wqkv, Q.wqkv, Q.s_qkv, ax, aqkv, 3 * H, H, L.ln1, nullptr, SS_EPI_NONE, 3 * H, 0);
         if (rc) return rc;
         MARK(0);
         // RoPE(q,k) + KV append + split-KV attention in one kernel (+ the split merge); with the fp8 shadow on, its sibling
         // that reads the shadow and appends to both
-        if (h->kq) {
+        if (spec) {
+            rc = attn_decode_spec_dev(aqkv, kc, vc, h->w.rope_cos, h->w.rope_sin, aattn, h->spec.attn_ws, h->spec.row_st + ST_KV_LEN,
+                                      h->spec.row_st + ST_POS, &h->spec.hdr->n_active, nb, g.n_heads, hd, g.cache_cap, dt, s);
+        } else if (h->kq) {
             const size_t so = ((size_t)seq0 * g.n_layers + l) * g.n_heads * g.cache_cap;        // rows in front of this plane
             rc = attn_decode_kv8_fused_dev(h->qkv, kc, vc, h->kq + so * hd, h->vq + so * hd, h->kscale + so, h->vscale + so,
                                            h->w.rope_cos, h->w.rope_sin, h->attn, attn_ws, st + ST_KV_LEN, st + ST_POS, done,
@@ -802,25 +852,27 @@ static int decode_token(ss_llama* h, hipStream_t s, ProfSink* prof, int seq0, in
                                        st + ST_POS, done, g.n_heads, hd, g.cache_cap, nb, ST_WORDS, cache_stride, dt, s);
         }
         if (rc) return rc;
-        if (h->cap.maps && nb == 1) {   // attention-map capture: this layer's row of head cap.head (capture off: no launch)
+        if (h->cap.maps && nslots == 1 && !spec) {   // attention-map capture: this layer's row of head cap.head (capture off: no launch)
             rc = attn_scores_decode_dev(h->qkv, kc, h->w.rope_cos, h->w.rope_sin, st + ST_KV_LEN, st + ST_POS, done, h->cap_desc,
                                         l, g.n_heads, hd, g.cache_cap, dt, s);
             if (rc) return rc;
         }
         MARK(1);
-        rc = proj(L.wo, Q.wo, Q.s_o, h->attn, h->xn, H, H, nullptr, h->x, SS_EPI_RESIDUAL, H, H);
+        rc = proj(L.wo, Q.wo, Q.s_o, aattn, axn, H, H, nullptr, ax, SS_EPI_RESIDUAL, H, H);
         if (rc) return rc;
         MARK(0);
-        rc = proj(L.wgu, Q.wgu, Q.s_gu, h->xn, h->hm, I, H, L.ln2, nullptr, SS_EPI_SILU_MUL, I, 0);
+        rc = proj(L.wgu, Q.wgu, Q.s_gu, axn, ahm, I, H, L.ln2, nullptr, SS_EPI_SILU_MUL, I, 0);
         if (rc) return rc;
         MARK(0);
-        rc = proj(L.wdown, Q.wdown, Q.s_down, h->hm, h->x, H, I, nullptr, h->xn, SS_EPI_RESIDUAL, H, H);
+        rc = proj(L.wdown, Q.wdown, Q.s_down, ahm, ax, H, I, nullptr, axn, SS_EPI_RESIDUAL, H, H);
         if (rc) return rc;
         MARK(2);
     }
-    if ((rc = SS_DISPATCH(dt, final_norm_advance_launch, h, seq0, nb, s))) return rc;
+    if (spec) rc = SS_DISPATCH(dt, spec_final_norm_launch, h, seq0, s);
+    else rc = SS_DISPATCH(dt, final_norm_advance_launch, h, seq0, nslots, s);
+    if (rc) return rc;
     MARK(3);
-    rc = proj(h->w.lm_head, mx4 ? h->mx4_lm_head : h->w8_lm_head, mx4 ? h->mx4_lm_scale : (const void*)h->w8_lm_scale, h->xn, logits, g.vocab, H, nullptr, nullptr, SS_EPI_NONE, g.vocab, 0);
+    rc = proj(h->w.lm_head, mx4 ? h->mx4_lm_head : h->w8_lm_head, mx4 ? h->mx4_lm_scale : (const void*)h->w8_lm_scale, axn, logits, g.vocab, H, nullptr, nullptr, SS_EPI_NONE, g.vocab, 0);
     if (rc) return rc;
     MARK(0);
 #undef MARK
@@ -849,15 +901,17 @@ static int graph_for(ss_llama* h, int seq0, int nb, hipGraphExec_t* out) {
     const int logprobs = h->logprobs_in(seq0, nb) ? 1 : 0;
     const int beam = h->beam.hdr ? h->beam_rows * 16 + nb : 0;
     void* const beam_ws = h->beam.hdr;
+    const int spec = (h->spec_run && h->spec.hdr && nb == 1) ? h->spec_rows : 0;
+    void* const spec_ws = spec ? (void*)h->spec.hdr : nullptr;
     for (const SeqGraph& sg : h->graphs)
         if (sg.seq0 == seq0 && sg.nb == nb && sg.mode == mode && sg.capture == capture && sg.w8 == w8 && sg.sampling == sampling &&
-            sg.rules == rules && sg.kv8 == kv8 && sg.logprobs == logprobs && sg.beam == beam && sg.beam_ws == beam_ws) {
+            sg.rules == rules && sg.kv8 == kv8 && sg.logprobs == logprobs && sg.beam == beam && sg.beam_ws == beam_ws && sg.spec == spec && sg.spec_ws == spec_ws) {
             *out = sg.exec;
             return SS_OK;
         }
     SeqGraph sg;
     sg.seq0 = seq0; sg.nb = nb; sg.mode = mode; sg.capture = capture; sg.w8 = w8; sg.sampling = sampling; sg.rules = rules; sg.kv8 = kv8;
-    sg.logprobs = logprobs; sg.beam = beam; sg.beam_ws = beam_ws;
+    sg.logprobs = logprobs; sg.beam = beam; sg.beam_ws = beam_ws; sg.spec = spec; sg.spec_ws = spec_ws;
     sg.graph = nullptr; sg.exec = nullptr;
     SS_HIP(hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
     int rc = decode_token(h, h->cap_stream, nullptr, seq0, nb);
@@ -1581,13 +1635,28 @@ int ss_llama_generate(ss_llama* h, int64_t n_steps, int32_t last_prompt_id, cons
                (long long)limit, g.max_pos);
     if (int crc = capture_fits(h, h->kv_len[q], limit, "llama_generate")) return crc;
     if (int hrc = history_fits(h, q, limit, "llama_generate")) return hrc;
+    const bool spec = h->spec.hdr != nullptr;
+    if (spec) {         // what a speculative step is not built for: refused before anything is launched
+        SS_REQUIRE(!h->samp_on[q], "llama_generate: speculation is on and slot %d has sampling on (speculative sampling is not built)", q);
+        SS_REQUIRE(!h->rules_on[q], "llama_generate: speculation is on and slot %d has logits rules on (the rules read one row)", q);
+        SS_REQUIRE(!h->lp_on[q], "llama_generate: speculation is on and slot %d records log-probabilities", q);
+        SS_REQUIRE(!h->kq, "llama_generate: speculation is on and so is the fp8 KV shadow (ss_llama_set_kv8 off first)");
+        SS_REQUIRE(!h->cap.maps, "llama_generate: speculation is on and so is attention-map capture");
+        SS_REQUIRE(h->hist_len[q] + limit <= h->hist_cap(),
+                   "llama_generate: speculation is on and the token history of slot %d would outgrow its buffer (%lld + %lld > %lld)", q,
+                   (long long)h->hist_len[q], (long long)limit, (long long)h->hist_cap());
+        SS_HIP(hipMemsetAsync(&h->spec.hdr->pending, 0, sizeof(SpecHdr) - offsetof(SpecHdr, pending), s));
+    }
     if (n_forced > 0)
         SS_HIP(hipMemcpyAsync(h->forced + (size_t)q * g.max_new, host_forced, (size_t)n_forced * sizeof(int32_t),
                               hipMemcpyHostToDevice, s));
     // state upload staged in pinned memory; consumed before this call returns (sync_lengths syncs)
     const int64_t eff_limit = stage_seq(h, q, n_steps, last_prompt_id, host_forced, n_forced, true);
+    h->spec_run = spec;
     int rc = run_decode(h, q, 1, eff_limit, s);
+    h->spec_run = false;
     if (rc) return rc;
+    if (spec) h->hist_len[q] += h->pinned[q * ST_WORDS + ST_NGEN];      // every emitted token joined the history on the device
     if (host_n_generated) *host_n_generated = h->pinned[q * ST_WORDS + ST_NGEN];
     return SS_OK;
 }
@@ -1623,6 +1692,75 @@ int ss_llama_generate_batch(ss_llama* h, int64_t n_steps, const int32_t* last_pr
     if (rc) return rc;
     if (host_n_generated)
         for (int b = 0; b < h->n_seq; ++b) host_n_generated[b] = h->pinned[b * ST_WORDS + ST_NGEN];
+    return SS_OK;
+}
+
+static size_t spec_carve_cfg(const ss_llama_config& g, int rows, void* ws, SpecPtrs* p) {
+    const int hd = g.hidden / g.n_heads;
+    return spec_carve(ws, rows, ST_WORDS, (size_t)g.hidden, (size_t)g.inter, (size_t)g.vocab, dtype_size(g.dtype),
+                      ss_attn_decode_workspace_bytes(g.n_heads, hd), p);
+}
+
+int ss_llama_spec_bytes(const ss_llama_config* cfg, int32_t rows, size_t* bytes) {
+    SS_REQUIRE(cfg && bytes, "llama_spec_bytes: null argument");
+    SS_REQUIRE(rows >= 2 && rows <= kSpecMaxRows, "llama_spec_bytes: rows %d outside [2, %d]", (int)rows, kSpecMaxRows);
+    SS_REQUIRE(cfg->hidden > 0 && cfg->n_heads > 0 && cfg->inter > 0 && cfg->vocab > 0, "llama_spec_bytes: bad config");
+    *bytes = spec_carve_cfg(*cfg, rows, nullptr, nullptr);
+    return SS_OK;
+}
+
+int ss_llama_set_speculation(ss_llama* h, const ss_spec_params* p, void* spec_ws) {
+    SS_REQUIRE(h, "llama_set_speculation: null handle");
+    if (!p) {           // off: the graphs captured over the workspace go with it
+        drop_graphs(h, &SeqGraph::spec);
+        h->spec.hdr = nullptr;
+        h->spec_rows = 0;
+        return SS_OK;
+    }
+    SS_REQUIRE(spec_ws, "llama_set_speculation: null workspace");
+    SS_REQUIRE(((size_t)spec_ws & 255) == 0, "llama_set_speculation: the workspace must be 256-byte aligned");
+    SS_REQUIRE(p->rows >= 2 && p->rows <= kSpecMaxRows, "llama_set_speculation: rows %d outside [2, %d]", (int)p->rows, kSpecMaxRows);
+    SS_REQUIRE(p->source == SS_SPEC_LOOKUP || p->source == SS_SPEC_GIVEN, "llama_set_speculation: unknown draft source %d", (int)p->source);
+    SS_REQUIRE(p->source != SS_SPEC_LOOKUP || (p->max_ngram >= 1 && p->max_ngram <= 8), "llama_set_speculation: max_ngram %d outside [1, 8]",
+               (int)p->max_ngram);
+    SS_REQUIRE(p->source != SS_SPEC_GIVEN || (p->given_ids && p->given_len >= 0),
+               "llama_set_speculation: given drafts need a device array (given_ids) and given_len >= 0");
+    // every decode loop of this engine has synchronised before it returned: nothing in flight reads the workspace
+    drop_graphs(h, &SeqGraph::spec);
+    SpecPtrs ptrs;
+    spec_carve_cfg(h->cfg, p->rows, spec_ws, &ptrs);
+    SpecHdr hdr;
+    memset(&hdr, 0, sizeof(hdr));
+    hdr.rows = p->rows; hdr.max_ngram = p->source == SS_SPEC_LOOKUP ? p->max_ngram : 0; hdr.source = p->source;
+    hdr.given_len = p->source == SS_SPEC_GIVEN ? p->given_len : 0;
+    hdr.given = p->source == SS_SPEC_GIVEN ? p->given_ids : nullptr;
+    SS_HIP(hipMemcpy(ptrs.hdr, &hdr, sizeof(hdr), hipMemcpyHostToDevice));
+    h->spec = ptrs;
+    h->spec_rows = p->rows;
+    return SS_OK;
+}
+
+int ss_llama_spec_stats(ss_llama* h, int32_t seq, int64_t out[4]) {
+    SS_REQUIRE(h && out, "llama_spec_stats: null argument");
+    SS_REQUIRE(seq >= -1 && seq < h->n_seq, "llama_spec_stats: sequence slot %d out of range (-1 = the selected slot, < %d)", (int)seq,
+               h->n_seq);
+    SS_REQUIRE(h->spec.hdr, "llama_spec_stats: speculation is off");
+    int32_t v[4];
+    SS_HIP(hipMemcpy(v, h->spec.hdr->stats, sizeof(v), hipMemcpyDeviceToHost));
+    for (int i = 0; i < 4; ++i) out[i] = v[i];
+    return SS_OK;
+}
+
+int ss_spec_draft(const int32_t* hist_dev, int64_t len, int32_t max_ngram, int32_t k, int32_t n_stop, const int32_t* stop_ids,
+                  int32_t* out_ids_dev, int32_t* out_count_dev, void* stream) {
+    SS_REQUIRE(hist_dev && out_ids_dev && out_count_dev, "spec_draft: null argument");
+    SS_REQUIRE(len >= 1 && len <= 0x7fffffff && max_ngram >= 1 && k >= 1 && k < kSpecMaxRows,
+               "spec_draft: bad arguments (len=%lld max_ngram=%d k=%d; len >= 1, max_ngram >= 1, 1 <= k <= %d)", (long long)len,
+               (int)max_ngram, (int)k, kSpecMaxRows - 1);
+    SS_REQUIRE(n_stop >= 0 && n_stop <= 2 && (stop_ids || n_stop == 0), "spec_draft: n_stop %d outside [0, 2]", (int)n_stop);
+    hipLaunchKernelGGL(spec_draft_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, hist_dev, (int)len, (int)max_ngram, (int)k,
+                       n_stop > 0 ? stop_ids[0] : -1, n_stop > 1 ? stop_ids[1] : -1, out_ids_dev, out_count_dev);
+    SS_LAUNCH_CHECK("spec_draft");
     return SS_OK;
 }
 

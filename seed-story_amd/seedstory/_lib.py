@@ -54,6 +54,14 @@ class BeamParams(C.Structure):
 BEAM_MAX = 8
 
 
+class SpecParams(C.Structure):
+    """``ss_spec_params``: rows, max n-gram, draft source, the given drafts (device int32) and their count."""
+    _fields_ = [("rows", i32), ("max_ngram", i32), ("source", i32), ("given_len", i32), ("given_ids", vp)]
+
+
+SPEC_LOOKUP, SPEC_GIVEN, SPEC_MAX_ROWS = 0, 1, 8
+
+
 class BeamState(C.Structure):
     """``ss_beam_state``: the head of a beam-search workspace."""
     _fields_ = [("n", i32), ("K", i32), ("n_stop", i32), ("stop_ids", i32 * 2), ("limit", i32), ("max_new", i32),
@@ -175,6 +183,11 @@ PROTOTYPES = {
     "ss_llama_beam_seq_offset": (sz, []),
     "ss_llama_beam_search": (C.c_int, [vp, C.POINTER(BeamParams), vp, i64, i32, vp]),
     "ss_llama_beam_permute": (C.c_int, [vp, vp, i32p, i32, i64, i64, vp]),
+    "ss_llama_spec_bytes": (C.c_int, [C.POINTER(LlamaConfig), i32, C.POINTER(sz)]),
+    "ss_llama_set_speculation": (C.c_int, [vp, C.POINTER(SpecParams), vp]),
+    "ss_llama_spec_stats": (C.c_int, [vp, i32, C.POINTER(i64)]),
+    "ss_attn_decode_spec": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, C.c_int, vp]),
+    "ss_spec_draft": (C.c_int, [vp, i64, i32, i32, i32, i32p, vp, vp, vp]),
     "ss_llama_prefill": (C.c_int, [vp, vp, i64, vp, vp, vp]),
     "ss_llama_prefill_batch": (C.c_int, [vp, vp, C.POINTER(i64), vp, vp]),
     "ss_llama_generate": (C.c_int, [vp, i64, i32, i32p, i64, C.POINTER(i64), vp]),

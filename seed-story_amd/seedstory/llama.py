@@ -60,8 +60,10 @@ def knob_decode_weights(dtype):
 class LlamaEngine:
     def __init__(self, state_dict, *, hidden, n_heads, n_layers, inter, vocab, dtype=torch.bfloat16, device="cuda:0",
                  rms_eps=1e-5, max_pos=4096, cache_cap=2048, max_new=512, max_prefill_rows=1024, img_ids=(),
-                 eos_id=2, lora_scaling=2.0, n_seq=1, decode_weights=None, kv_cache=None):
-        """``decode_weights``: None = the ``llama_decode_w8`` / ``llama_decode_mx4`` tuning knobs decide (default off),
+                 eos_id=2, lora_scaling=2.0, n_seq=1, decode_weights=None, kv_cache=None, speculate=None):
+        """``speculate``: rows (2..8) of a prompt-lookup speculative step of ``generate`` (``set_speculation``); None = the
+        ``llama_spec_rows`` tuning knob decides (default 0 = off), 0 = off whatever the knob says.
+        ``decode_weights``: None = the ``llama_decode_w8`` / ``llama_decode_mx4`` tuning knobs decide (default off),
         "fp8" = decode tokens stream e4m3 copies of the five projections (``enable_decode_fp8``), "mxfp4" = MXFP4 copies
         (``enable_decode_mxfp4``), "16bit" = off whatever the knobs say.
         ``kv_cache``: the same three values for the e4m3 shadow of the KV cache that decode attention reads
@@ -107,11 +109,12 @@ class LlamaEngine:
         self._init_engine(max_pos, rms_eps)
         self._init_decode_weights(decode_weights)
         self._init_kv_cache(kv_cache)
+        self._init_speculation(speculate)
 
     @classmethod
     def from_prebuilt(cls, *, embed, lm_head, final_norm, layers, hidden, n_heads, n_layers, inter, vocab,
                       dtype=torch.bfloat16, device="cuda:0", rms_eps=1e-5, max_pos=4096, cache_cap=2048, max_new=512,
-                      max_prefill_rows=1024, img_ids=(), eos_id=2, n_seq=1, decode_weights=None, kv_cache=None):
+                      max_prefill_rows=1024, img_ids=(), eos_id=2, n_seq=1, decode_weights=None, kv_cache=None, speculate=None):
         """Engine over already merged/concatenated device tensors: ``layers`` is a list of
         ``(wqkv, wo, wgu, wdown, ln1, ln2)`` (used by the synthetic-weight benchmark, which
         creates the 13.5 GB of weights directly on the GPU)."""
@@ -136,6 +139,7 @@ class LlamaEngine:
         self._init_engine(max_pos, rms_eps)
         self._init_decode_weights(decode_weights)
         self._init_kv_cache(kv_cache)
+        self._init_speculation(speculate)
         return self
 
     def _init_engine(self, max_pos, rms_eps):
@@ -164,6 +168,8 @@ class LlamaEngine:
         self._lp = None            # the result tensors of set_logprobs (model, policy, top ids, top values) while any slot records
         self._lp_slots = {}        # slot -> top_n of the slots that record
         self.last_logprobs = None  # what the image-block generate methods assembled for their last call
+        self._spec = None          # (workspace, given-draft tensor or None) while speculation is on
+        self.speculate = 0         # rows of a speculative step, 0 = off
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -494,6 +500,58 @@ class LlamaEngine:
     def v_scale(self):
         return self._kv8_plane(3)
 
+    # ---- prompt-lookup speculative decoding ------------------------------------------------------------------------
+    def _init_speculation(self, speculate):
+        if speculate is None:
+            speculate = _lib.get_tuning("llama_spec_rows", 0)
+        if speculate:
+            self.set_speculation(int(speculate))
+
+    def set_speculation(self, rows, max_ngram=2, draft_ids=None):
+        """Speculative steps in ``generate`` (and so in the free tokens of ``generate_img_block``): each decode launch
+        forwards ``rows`` (2..8) rows of the selected slot in one sweep of the weights — the token greedy chose plus drafted
+        successors — and the next one keeps the prefix the model agrees with, so a launch emits 1..``rows`` tokens and the ids
+        are greedy's (away from near-ties of the top two logits).  Drafts: prompt lookup with n-grams of up to
+        ``max_ngram`` (1..8) tokens in the slot's history — hand the prompt ids over with ``set_history``; generated tokens join
+        it on the device — or, with ``draft_ids`` (a list or int32 tensor indexed by generated position), the caller's own.
+        ``generate_batch``, ``fork``, best-of-n and ``beam_search`` run as they always do.  ``generate`` raises ``SSError``
+        before anything is launched when the slot also has sampling, logits rules, log-probability recording, the fp8 KV shadow
+        or attention-map capture on.  Off by default: what prompt lookup accepts on real captions has not been measured."""
+        rows, max_ngram = int(rows), int(max_ngram)
+        if not 2 <= rows <= _lib.SPEC_MAX_ROWS:
+            raise ValueError("set_speculation: rows %d outside [2, %d]" % (rows, _lib.SPEC_MAX_ROWS))
+        if not 1 <= max_ngram <= 8:
+            raise ValueError("set_speculation: max_ngram %d outside [1, 8]" % max_ngram)
+        given = None
+        if draft_ids is not None:
+            given = torch.as_tensor(draft_ids, dtype=torch.int32).reshape(-1).to(self.device).contiguous()
+            if given.numel() == 0:
+                given = torch.zeros(1, dtype=torch.int32, device=self.device)[:0]
+        nbytes = C.c_size_t()
+        check(lib().ss_llama_spec_bytes(C.byref(self._cfg), rows, C.byref(nbytes)), "ss_llama_spec_bytes")
+        ws = torch.zeros(nbytes.value, dtype=torch.uint8, device=self.device)
+        sp = _lib.SpecParams(rows, max_ngram, _lib.SPEC_LOOKUP if given is None else _lib.SPEC_GIVEN,
+                             0 if given is None else given.numel(),
+                             None if given is None else (given.data_ptr() or ws.data_ptr()))
+        torch.cuda.current_stream(self.device).synchronize()
+        check(lib().ss_llama_set_speculation(self._h, C.byref(sp), ws.data_ptr()), "ss_llama_set_speculation")
+        self._spec = (ws, given)
+        self.speculate = rows
+
+    def clear_speculation(self):
+        """Speculation off (the default): ``generate`` launches the plain decode token again."""
+        torch.cuda.current_stream(self.device).synchronize()
+        check(lib().ss_llama_set_speculation(self._h, None, None), "ss_llama_set_speculation")
+        self._spec = None
+        self.speculate = 0
+
+    def spec_stats(self, slot=None):
+        """Counters of the last ``generate`` call with speculation on: ``{"steps", "drafted", "accepted", "emitted"}`` —
+        speculative forwards, rows drafted, drafts accepted, tokens emitted."""
+        out = (C.c_int64 * 4)()
+        check(lib().ss_llama_spec_stats(self._h, -1 if slot is None else int(slot), out), "ss_llama_spec_stats")
+        return dict(zip(("steps", "drafted", "accepted", "emitted"), (int(v) for v in out)))
+
     # ---- sampling ------------------------------------------------------------------------------------------------
     def set_sampling(self, temperature=1.0, top_k=0, top_p=1.0, seed=0, slot=None):
         """Sampling instead of the arg max in ``generate`` / ``generate_batch`` (and the image-block variants), for ``slot``
@@ -555,7 +613,8 @@ class LlamaEngine:
 
     def _history_append(self, slot, toks):
         """image-block tokens of ``slot`` join its history (they were fed as one batched forward, outside the decode loop)"""
-        if toks and slot in getattr(self, "_rules_slots", ()):     # getattr: tests bind the block methods onto stand-in engines
+        # getattr: tests bind the block methods onto stand-in engines.  With speculation on the history feeds the drafts.
+        if toks and (slot in getattr(self, "_rules_slots", ()) or getattr(self, "_spec", None) is not None):
             self.set_history(toks, slot=slot, append=True)
 
     # ---- token log-probabilities -----------------------------------------------------------------------------------

@@ -177,6 +177,48 @@ def attn_decode(q, kcache, vcache, kv_len_dev, out=None):
     return out
 
 
+def attn_decode_spec(qkv, kcache, vcache, cos, sin, kv_len_dev, pos_dev, n_active_dev, out=None):
+    """Decode attention of one speculative step (``ss_attn_decode_spec``): ``qkv`` [R, 3*E] pre-RoPE rows (R <= 8) of ONE slot
+    whose cache planes [n_heads, cap, hd] hold ``kv_len_dev[0]`` keys; row r sits at RoPE position ``pos_dev[0] + r`` and
+    attends keys [0, L + r].  The first ``n_active_dev[0]`` rows are active: their rotated K / V rows are stored at cache rows
+    L .. L + A - 1 and their outputs written to ``out`` [R, E]; everything else is left as it is.  The three scalars are
+    int32 device tensors."""
+    _req(qkv, "qkv"); _req(kcache, "kcache"); _req(vcache, "vcache"); _req(cos, "cos"); _req(sin, "sin")
+    for t, name in ((kv_len_dev, "kv_len_dev"), (pos_dev, "pos_dev"), (n_active_dev, "n_active_dev")):
+        _req(t, name)
+        if t.dtype != torch.int32 or t.numel() < 1:
+            raise _lib.SSError("%s must be an int32 device tensor" % name)
+    n_heads, cap, hd = kcache.shape
+    R = qkv.shape[0]
+    if qkv.dim() != 2 or qkv.shape[1] != 3 * n_heads * hd or tuple(vcache.shape) != tuple(kcache.shape):
+        raise _lib.SSError("attn_decode_spec: qkv %s does not fit cache planes %s" % (tuple(qkv.shape), tuple(kcache.shape)))
+    if not 1 <= R <= _lib.SPEC_MAX_ROWS:
+        raise _lib.SSError("attn_decode_spec: %d rows outside [1, %d]" % (R, _lib.SPEC_MAX_ROWS))
+    ws = torch.empty(R * lib().ss_attn_decode_workspace_bytes(n_heads, hd), dtype=torch.uint8, device=qkv.device)
+    out = _out(out, (R, n_heads * hd), qkv, "attn_decode_spec")
+    check(lib().ss_attn_decode_spec(p(qkv), p(kcache), p(vcache), p(cos), p(sin), p(out), p(ws), p(kv_len_dev), p(pos_dev),
+                                    p(n_active_dev), R, n_heads, hd, cap, dt(qkv), stream()), "ss_attn_decode_spec")
+    return out
+
+
+def spec_draft(history, max_ngram=2, num_tokens=3, stop_ids=()):
+    """The prompt-lookup draft (``ss_spec_draft``): transformers' ``PromptLookupCandidateGenerator.get_candidates`` on the int32
+    device tensor ``history`` — n-gram sizes from ``min(max_ngram, len - 1)`` down to 1, the leftmost match with a non-empty
+    continuation, at most ``num_tokens`` (<= 7) ids, cut in front of the first of ``stop_ids`` (at most two).  Returns the
+    drafted ids as a list (empty: no draft)."""
+    import ctypes as C
+    _req(history, "history")
+    if history.dtype != torch.int32 or history.dim() != 1:
+        raise _lib.SSError("history must be a 1-D int32 device tensor")
+    stops = [int(t) for t in stop_ids]
+    arr = (C.c_int32 * max(1, len(stops)))(*stops)
+    out = torch.full((_lib.SPEC_MAX_ROWS,), -1, dtype=torch.int32, device=history.device)
+    cnt = torch.zeros(1, dtype=torch.int32, device=history.device)
+    check(lib().ss_spec_draft(p(history), history.numel(), int(max_ngram), int(num_tokens), len(stops), arr, p(out), p(cnt),
+                              stream()), "ss_spec_draft")
+    return out[:int(cnt.item())].tolist()
+
+
 def kv_quantize_fp8(k, v, lo=0, hi=None, out=None):
     """e4m3 codes + power-of-two fp32 scales of rows [lo, hi) of one layer's cache planes k, v [n_heads, cap, hd]
     (ss_kv_quantize_fp8; the definition is in include/seedstory_hip.h).  Returns ``(k_codes, v_codes, k_scale, v_scale)``:

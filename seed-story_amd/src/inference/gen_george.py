@@ -189,6 +189,25 @@ def add_beams_arguments(ap):
     ap.add_argument("--length-penalty", type=float, default=1.0, help="with --beams: a hypothesis scores sum / length ** P")
 
 
+def add_speculate_argument(ap):
+    """``--speculate K`` (shared with vis_george_sink.py)"""
+    ap.add_argument("--speculate", type=int, default=0, metavar="K",
+                    help="prompt-lookup speculative decoding of every step's free tokens with K (1 .. 7) drafted tokens per decode "
+                         "launch, on the device; the ids stay greedy's; not with --sample / --best-of / --beams")
+
+
+def speculate_kwargs(args, llama=None):
+    """``--speculate K``: with ``llama`` given, the model's switch goes on (once, before the first generate); returns the keyword"""
+    k = int(getattr(args, "speculate", 0) or 0)
+    if not 0 <= k <= 7:
+        raise SystemExit("--speculate must be 0 .. 7")
+    if k and (getattr(args, "sample", False) or int(getattr(args, "best_of", 1) or 1) > 1 or int(getattr(args, "beams", 1) or 1) > 1):
+        raise SystemExit("--speculate cannot be combined with --sample / --best-of / --beams")
+    if k and llama is not None:
+        llama.speculative = 1
+    return dict(prompt_lookup_num_tokens=k) if k else {}
+
+
 def apply_beams(args, llama):
     """``--beams N``: the engine gets at least N sequence slots and the model's beam-search switch goes on (before the first
     generate builds the engine)"""
@@ -285,6 +304,7 @@ def run_story(args, j, question, image, tokenizer, transform, vit, agent, adapte
     llama.use_kv_cache_head = False                                                         # :165
     apply_best_of(args, llama)
     apply_beams(args, llama)
+    speculate_kwargs(args, llama)
     if args.save_attn:                                           # the reference's switch: one merged attention map per layer
         llama.config.output_attentions = True
         os.makedirs(args.save_attn, exist_ok=True)
@@ -298,7 +318,7 @@ def run_story(args, j, question, image, tokenizer, transform, vit, agent, adapte
         out = agent.generate(tokenizer=tokenizer, input_ids=ctx.input_ids(device), image_embeds=ctx.image_embeds,
                              embeds_cmp_mask=emb_mask, ids_cmp_mask=ids_mask, max_new_tokens=500, num_img_gen_tokens=64,
                              forced_tokens=forced, **sample_kwargs(args, j, step), **rules_kwargs(args), **logprobs_kwargs(args),
-                             **beams_kwargs(args))
+                             **beams_kwargs(args), **speculate_kwargs(args))
         report_caption_logprobs(args, j, step, out, boi)
         report_candidates(args, j, step, out)
         report_beams(args, j, step, out)
@@ -349,6 +369,7 @@ def main():
     ap.add_argument("--seed", type=int, default=None, help="with --sample: reproducible stories (default: torch.initial_seed())")
     add_best_of_argument(ap)
     add_beams_arguments(ap)
+    add_speculate_argument(ap)
     add_logprobs_argument(ap)
     add_rules_arguments(ap)
     args = ap.parse_args()

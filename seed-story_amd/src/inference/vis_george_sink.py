@@ -21,6 +21,7 @@ import torch
 
 from seedstory.story import StoryContext
 from src.inference.gen_george import (BOI_TOKEN, EOI_TOKEN, IMG_TOKEN, add_beams_arguments, add_best_of_argument, add_logprobs_argument,
+                                      add_speculate_argument, speculate_kwargs,
                                       add_rules_arguments, apply_beams, apply_best_of, beams_kwargs, build, logprobs_kwargs, report_beams,
                                       report_candidates, report_caption_logprobs, rules_kwargs, sample_kwargs)
 
@@ -39,6 +40,7 @@ def run_story(args, j, start_text, captions, image, tokenizer, transform, vit, a
     llama.use_kv_cache_head = sink
     apply_best_of(args, llama)          # --best-of N: the winner's slot is the one the next step's cache continues from
     apply_beams(args, llama)            # --beams N: refused with --synthetic, where <img> itself is forced behind the given caption
+    speculate_kwargs(args, llama)       # --speculate K: the model's switch goes on
     if args.save_attn:                                           # the reference's switch: one merged attention map per layer
         llama.config.output_attentions = True
         os.makedirs(args.save_attn, exist_ok=True)
@@ -56,7 +58,7 @@ def run_story(args, j, start_text, captions, image, tokenizer, transform, vit, a
         out = agent.generate(tokenizer=tokenizer, input_ids=ctx.input_ids(device), image_embeds=ctx.image_embeds,
                              embeds_cmp_mask=emb_mask, ids_cmp_mask=ids_mask, max_new_tokens=500, num_img_gen_tokens=64,
                              past_key_values=past, forced_tokens=forced, **sample_kwargs(args, j, step), **rules_kwargs(args),
-                             **logprobs_kwargs(args), **beams_kwargs(args))
+                             **logprobs_kwargs(args), **beams_kwargs(args), **speculate_kwargs(args))
         report_caption_logprobs(args, j, step, out, boi)
         report_candidates(args, j, step, out)
         report_beams(args, j, step, out)
@@ -113,6 +115,7 @@ def main():
     add_logprobs_argument(ap)
     add_best_of_argument(ap)
     add_beams_arguments(ap)
+    add_speculate_argument(ap)
     ap.add_argument("--temperature", type=float, default=0.7, help="with --best-of")
     ap.add_argument("--top-k", type=int, default=0, help="with --best-of; 0 = off")
     ap.add_argument("--top-p", type=float, default=0.5, help="with --best-of")

@@ -123,6 +123,9 @@ class LlamaForCausalLM(nn.Module):
 
     # generate(num_beams=n > 1, do_sample=False) runs beam search on the device (needs n_seq >= n); False: num_beams stays inert
     beam_search = False
+    # generate(prompt_lookup_num_tokens=k) runs prompt-lookup speculative steps of k + 1 rows (at most 8) in the single-sequence
+    # greedy loop (LlamaEngine.set_speculation); 0: prompt_lookup_num_tokens stays inert and no new call is made
+    speculative = 0
 
     # ---- reference surface ------------------------------------------------------------------
     def get_input_embeddings(self):
@@ -345,7 +348,8 @@ class LlamaForCausalLM(nn.Module):
                  max_new_tokens=120, output_hidden_states=True, return_dict_in_generate=True, forced_tokens=None,
                  output_attentions=None, do_sample=False, temperature=1.0, top_k=0, top_p=1.0, seed=None, num_beams=1,
                  repetition_penalty=1.0, no_repeat_ngram_size=0, min_new_tokens=0, spare_img_ids=False, output_logprobs=False,
-                 top_logprobs=0, num_return_sequences=1, length_penalty=1.0, early_stopping=False, **unused):
+                 top_logprobs=0, num_return_sequences=1, length_penalty=1.0, early_stopping=False, prompt_lookup_num_tokens=None,
+                 max_matching_ngram_size=None, **unused):
         """Greedy search as ``ContinuousLVLM.generate`` drives it (reference models.py:146-153): ``inputs_embeds`` feed
         step 0, ``input_ids`` is the running sequence, the image-token logits processor is applied on device.
         ``do_sample=False`` (the default): temperature / top_k / top_p / seed are inert, as in Hugging Face.
@@ -424,6 +428,20 @@ class LlamaForCausalLM(nn.Module):
                                  "(now %d, at most 8) before the first generate()" % (n_ret, int(self.n_seq)))
             if want_attn:
                 raise NotImplementedError("attention maps are a single-sequence tool (output_attentions with num_return_sequences=%d)" % n_ret)
+        # prompt-lookup speculation (Hugging Face's names): only with the switch on, only for the single greedy sequence
+        spec_rows = 0
+        if self.speculative and prompt_lookup_num_tokens and n_ret == 1 and n_beams == 1:
+            spec_rows = min(int(prompt_lookup_num_tokens) + 1, 8)
+            ngram = 2 if max_matching_ngram_size is None else int(max_matching_ngram_size)
+            if spec_rows < 2 or not 1 <= ngram <= 8:
+                raise ValueError("prompt_lookup_num_tokens=%r / max_matching_ngram_size=%r: at least 1 token, n-grams of 1..8"
+                                 % (prompt_lookup_num_tokens, max_matching_ngram_size))
+            rules_on = (repetition_penalty not in (None, 1.0) or no_repeat_ngram_size not in (None, 0) or min_new_tokens not in (None, 0))
+            for bad, what in ((do_sample, "do_sample=True (speculative sampling)"), (rules_on, "the logits rules"),
+                              (output_logprobs, "output_logprobs"), (want_attn, "output_attentions"),
+                              (self.kv_cache == "fp8", "kv_cache='fp8'")):
+                if bad:
+                    raise NotImplementedError("prompt-lookup speculation with %s is not implemented" % what)
         img_ids = ()
         for proc in (logits_processor or []):
             img_ids = tuple(getattr(proc, "img_ids_list", ()))
@@ -444,6 +462,9 @@ class LlamaForCausalLM(nn.Module):
         # (Hugging Face also takes None for "off")
         rules = (repetition_penalty not in (None, 1.0) or no_repeat_ngram_size not in (None, 0) or min_new_tokens not in (None, 0))
         try:
+            if spec_rows:
+                eng.set_speculation(spec_rows, max_ngram=ngram)
+                eng.set_history(input_ids[0].tolist())
             if output_logprobs:
                 eng.set_logprobs(True, top_n=top_logprobs)                            # raises on a bad value
             if rules:
@@ -460,6 +481,8 @@ class LlamaForCausalLM(nn.Module):
             return self._generate(eng, input_ids, rows, S, img_ids, past_key_values, max_new_tokens, output_hidden_states,
                                   forced_tokens, want_attn, **({"want_logprobs": True} if output_logprobs else {}))
         finally:
+            if spec_rows:
+                eng.clear_speculation()
             if output_logprobs:
                 eng.set_logprobs(False)
             if rules:

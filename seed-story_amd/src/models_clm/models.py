@@ -131,8 +131,11 @@ class ContinuousLVLM(nn.Module):
                  max_new_tokens=120, top_p=0.5, past_key_values=None, dtype=torch.float16, device='cuda',
                  forced_tokens=None, do_sample=False, top_k=0, seed=None, repetition_penalty=1.0, no_repeat_ngram_size=0,
                  min_new_tokens=0, spare_img_ids=False, output_logprobs=False, top_logprobs=0, num_return_sequences=1,
-                 length_penalty=1.0, early_stopping=False):
-        """``do_sample=False`` (the default, what the reference passes): greedy; ``temperature`` / ``top_p`` / ``top_k`` /
+                 length_penalty=1.0, early_stopping=False, prompt_lookup_num_tokens=None, max_matching_ngram_size=None):
+        """``prompt_lookup_num_tokens=k`` / ``max_matching_ngram_size`` (Hugging Face's names) are handed to
+        ``LlamaForCausalLM.generate``: prompt-lookup speculative steps in the greedy loop while ``llm.speculative`` is set, inert
+        (and not passed on) otherwise.
+        ``do_sample=False`` (the default, what the reference passes): greedy; ``temperature`` / ``top_p`` / ``top_k`` /
         ``seed`` are inert.  ``do_sample=True`` hands them to ``LlamaForCausalLM.generate``: on-device sampling
         (``top_k=0`` = off, ``seed=None`` = governed by ``torch.manual_seed``).  ``repetition_penalty`` /
         ``no_repeat_ngram_size`` / ``min_new_tokens`` (Hugging Face's defaults: inert) and ``spare_img_ids`` are handed on only
@@ -186,7 +189,9 @@ class ContinuousLVLM(nn.Module):
                                    **({"output_logprobs": True, "top_logprobs": top_logprobs} if want_lp else {}),
                                    **({"num_return_sequences": n_ret} if n_ret > 1 else {}),
                                    **({"length_penalty": length_penalty, "early_stopping": early_stopping}
-                                      if (length_penalty not in (None, 1.0) or early_stopping not in (None, False)) else {}))
+                                      if (length_penalty not in (None, 1.0) or early_stopping not in (None, False)) else {}),
+                                   **({"prompt_lookup_num_tokens": prompt_lookup_num_tokens,
+                                       "max_matching_ngram_size": max_matching_ngram_size} if prompt_lookup_num_tokens else {}))
         boi_token_id = tokenizer.encode(BOI_TOKEN, add_special_tokens=False)[0]
         eoi_token_id = tokenizer.encode(EOI_TOKEN, add_special_tokens=False)[0]
         if n_ret > 1:
