@@ -103,7 +103,9 @@ int ss_gemm_lnfold(const void* A, const void* Wg, void* C, int64_t M, int64_t N,
  * rowpart[(m * strips + strip) * 2 .. +1] (fp32; strips = ss_gemm_rowpart_strips(M, N, K, dtype) = N / strip width of the
  * tile ss_gemm_rowpart will run, 0 = shape not eligible: N must be a multiple of the tile width, operands 16-byte aligned);
  * nothing needs zeroing.  ss_gemm_lnfold_part is ss_gemm_lnfold whose epilogue sums the `strips` partials of its rows and
- * forms rstd / -mean * rstd itself (mean = s / width, var = q / width - mean^2 in fp64). */
+ * forms rstd / -mean * rstd itself (mean = s / width, var = q / width - mean^2 in fp64).  Only the LDS-staged epilogue does
+ * that, so every wave must take it: N a multiple of 160 or 128 (a wider tile gives way to the 160- / 128-wide one), C and a
+ * non-null bias pointer (whether or not the epilogue uses it) 16-byte aligned, ldc % 8 == 0; anything else is SS_EINVAL. */
 int64_t ss_gemm_rowpart_strips(int64_t M, int64_t N, int64_t K, int dtype);
 int ss_gemm_rowpart(const void* A, const void* W, void* C, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldw,
                     int64_t ldc, const void* bias, const void* residual, int64_t ldr, int epilogue, float* rowpart,

@@ -841,6 +841,17 @@ int gemm_lnfold_launch(const void* A, const void* Wg, void* C, int64_t M, int64_
         // tiles 261 / 265 / 267 (and 262) gave 0 bad statistics rows and 0 bad value rows, and the plain epilogue on cfg 61 none.
         if (const GemmTile t = sp_tile(cfg); t.WM * t.WN == 4 && !knob(K_lnfold_w4))
             cfg = (t.BN == 160 || N % 160 == 0) ? 62 : 66;
+        if (ln_part) {
+            // Only gemm_epilogue_staged forms (rstd, shift) from the partials.  A wave that takes gemm_epilogue instead (a ragged
+            // column strip; C or a non-null bias pointer off 16 bytes, whether the epilogue uses the bias or not; ldc % 8) would
+            // read the rstd / shift vectors, which are null in this form: a tile whose width does not divide N gives way to the
+            // 160- / 128-wide 8-wave tile, anything else is refused.
+            if (const GemmTile t0 = sp_tile(cfg); !t0.id || N % t0.BN != 0) cfg = N % 160 == 0 ? 62 : 66;
+            const GemmTile t = sp_tile(cfg);
+            SS_REQUIRE(N % t.BN == 0 && ((((size_t)C | (size_t)bias) & 15) == 0) && (ldc & 7) == 0,
+                       "ss_gemm_lnfold_part: N %% %d != 0, or C / the bias pointer (used or not) off 16 bytes, or ldc %% 8 != 0 (N=%lld): "
+                       "statistics from partials need the staged epilogue on every wave", t.BN, (long long)N);
+        }
         const int rc = gemm_sp_dispatch<T>(cfg + 100, g, s);
         if (rc == 1) {
             set_error("ss_gemm_lnfold: no kernel for cfg %d / shape [%lld, %lld, %lld]", cfg + 100, (long long)M, (long long)N, (long long)K);

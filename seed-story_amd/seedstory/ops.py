@@ -326,13 +326,13 @@ def rowstats(x, eps):
     return st[0], st[1]
 
 
-def gemm_lnfold(x, wg, rstd, shift, colsum, bias_d=None, gelu=False, geglu=False):
+def gemm_lnfold(x, wg, rstd, shift, colsum, bias_d=None, gelu=False, geglu=False, out=None):
     """LN(x) @ W^T + b with the LayerNorm folded: x raw rows, wg = gamma-scaled weight, colsum = wg.sum(1) fp32, bias_d = d."""
     _req(x); _req(wg)
     M, K = x.shape
     N = wg.shape[0]
     No = N // 2 if geglu else N
-    out = torch.empty(M, No, dtype=x.dtype, device=x.device)
+    out = _out(out, (M, No), x, "gemm_lnfold")
     epi = (EPI_BIAS if bias_d is not None else 0) | (EPI_GELU if gelu else 0) | (_lib.EPI_GEGLU_PAIR if geglu else 0)
     tune.ensure_gemm(M, N, K, dt(x), epi, x.device)
     check(lib().ss_gemm_lnfold(p(x), p(wg), p(out), M, N, K, No, p(rstd), p(shift), p(colsum), p(bias_d), epi, dt(x), stream()),
@@ -350,14 +350,14 @@ def rowpart_strips(M, N, K, dtype):
     return int(lib().ss_gemm_rowpart_strips(M, N, K, dt(dtype)))
 
 
-def gemm_lnfold_part(x, wg, rowpart, width, eps, colsum, bias_d=None, gelu=False, geglu=False):
+def gemm_lnfold_part(x, wg, rowpart, width, eps, colsum, bias_d=None, gelu=False, geglu=False, out=None):
     """`gemm_lnfold` fed by the producer's per-strip partials ``rowpart`` [M, strips, 2]: the row statistics are formed in the
     GEMM's own epilogue (no finalize launch)."""
     _req(x); _req(wg); _req(rowpart)
     M, K = x.shape
     N = wg.shape[0]
     No = N // 2 if geglu else N
-    out = torch.empty(M, No, dtype=x.dtype, device=x.device)
+    out = _out(out, (M, No), x, "gemm_lnfold_part")
     epi = (EPI_BIAS if bias_d is not None else 0) | (EPI_GELU if gelu else 0) | (_lib.EPI_GEGLU_PAIR if geglu else 0)
     tune.ensure_gemm(M, N, K, dt(x), epi, x.device)
     check(lib().ss_gemm_lnfold_part(p(x), p(wg), p(out), M, N, K, No, p(rowpart), rowpart.shape[1], int(width), float(eps),

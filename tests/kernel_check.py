@@ -98,6 +98,45 @@ Norms, softmax, point-wise kernels and loss heads (tests/test_pointwise_edges_gp
                (2 u32 + n 2^-52) sum|term| / count; the count is an exact integer; an all-zero mask gives (0, 0) exactly.
   euler_scale_dup  inv = 1 / sqrtf(sigma^2 + 1) formed on the host in fp32: four fp32 ops.  x inv: one fp32 op, final round.
 
+GEMM variants with extra epilogue arithmetic (tests/test_gemm_variants_edges_gpu.py).  The rounding points are read from
+gemm_epilogue / gemm_epilogue_staged (ss_gemm_common.h, `EM`) and splitk_reduce_kernel (ss_gemm.hip); every variant ends in the
+epilogue() above.
+
+  fp8          the operands are the kernel's own inputs: e4m3 code values (exact in fp64) and fp32 scales, so the quantisation
+               error is not part of the bound.  A product of two e4m3 values has 4 + 4 significand bits and is exact in fp32:
+               `accumulate` on the code values, Kacc = K.  Its factor 2 IS taken over for v_mfma_scale_f32_16x16x128_f8f6f4: the
+               instruction sums 128 products per lane group in a tree whose internal roundings are not specified, exactly the
+               reason the factor exists (with unit block scales the scaling itself is exact).  Then t = acc * (sa * sw): s =
+               fl(sa sw) is mirrored in fp32 (one operation on two known numbers, no error against the mirror), fl(acc s) is one
+               fp32 op; then epilogue() with T = bf16.
+  LN-fold      the reference is the kernel's own formula on the fp32 vectors it was handed: fma(acc, rstd, fl(shift colsum))
+               (+ bias_d).  p = acc rstd is exact inside the fma and carries t_acc |rstd|; c = shift colsum is one fp32 op:
+               u32 |c|; the fma rounds once: u32 |p + c| <= u32 (|p| + |c|).  On a row with |mean| >> std p and c cancel, so the
+               bound carries u32 (|p| + |c|) + u32 |c| and NOT u32 |result|: that is the price of the folded form.  Statistics
+               known only to (t_rstd, t_shift) (the producer-partial form) add (|acc| + t_acc) t_rstd + |colsum| t_shift:
+               charged independently, although the two errors are correlated (loose by |p| / |result| on offset rows, valid).
+  part stats   (rstd, shift) formed by the consumer from fp32 (sum, sum of squares) partials: the partials are summed in fp64
+               (n 2^-53, charged as e64 = 2^-48), mean = a iw, var = max(b iw - mean^2, 0), rstd = (float)(1 / sqrt(var + eps)),
+               shift = -(float)mean * rstd, where iw is the FP32 1.0f / width widened: off from 1 / width by up to u32 relative.
+               It scales a and b alike: t_mean = (u32 + e64) |mean|, t_var = (u32 + e64) E[x^2] + 2 |mean| t_mean + t_mean^2
+               ~ u32 (E[x^2] + 2 mean^2), NOT u32 var: a row with mean 9 and spread 1 pays 240 u32 on a variance of 1.
+               |d r| <= t_var / 2 (var + eps - t_var)^-3/2; one narrowing for rstd (u32 |r|), two for shift (the narrowed mean,
+               the fp32 product).  ss_rowstat_finalize is the same formula with an fp64 1 / width: u_inv = 2^-53 instead of u32.
+  rowstats     ss_rowstats is the first half of the two-pass LayerNorm (mean: sum32 and a division; squared deviations: fma,
+               sum32; / cols, + eps, sqrt, 1 / ) and one fp32 product -mean rstd: shared code with layernorm_bound.
+  row sums     the producers' statistics are sums over the STORED output y of the launch under test (exact inputs), per strip
+               (ss_gemm_rowpart, the fallback kernel) or per row (the fp64 accumulator): |S1 - sum y| <= gamma_n sum |y| and
+               |S2 - sum y^2| <= gamma_(n+1) sum y^2 (an fma per term; the + 1 covers a kernel that rounds the square first),
+               n = the fp32 terms of one strip, or of the whole row for the accumulator, whose fp32 pieces (16 or TN columns)
+               are added in fp64 by atomics in any order: + e64 sum |.|.
+  split-K      every slice's fp32 accumulator is stored exactly, splitk_reduce_kernel adds the S slices in fp32 (S - 1 ops):
+               `accumulate` with Kacc = K + S, then epilogue(bias, residual).  An empty K range stores exact zeros.
+  LN quantiser quantize_rows_fp8(x, ln=...): o = rnd_T(LayerNorm) as layernorm_bound (the squares are rounded before they are
+               added: gamma_(cols + 1); rsqrtf is within 1 ulp = the two roundings of sqrt and 1 / ), amax' = max |o| moves by
+               at most max_row t_ln, s = fl(amax' / 448): t_s = max t_ln / 448 + u32 s.  q = RNE_e4m3(fl(o fl(448 / amax'))):
+               relative 2^-4 (3 mantissa bits) plus 2^-10 in code units (half the subnormal spacing 2^-9) plus 3 u32; times s:
+               |q s - ln| <= t_ln + (2^-4 + 4 u32)(|ln| + t_ln) + 2^-10 (s + t_s).
+
 Exact expectations (no bound; mirrored in fp32 on the CPU with the kernel's rnd points, so double rounding cannot differ): every
 data mover; add_bcast (one correctly rounded fp32 add, stored); RoPE q / k (rnd(rnd(a c) + rnd(-b s)) in T); euler_cfg_step
 (rnd(eu + rnd(g rnd(ec - eu))), x + rnd(e dsigma), stored); image_to_u8 (rnd_T(0.5 x + 0.5), clamp, rintf(255 v): 255 v is exact
@@ -693,17 +732,25 @@ def rmsnorm_bound(x, w, eps, dtype):
     return final_round(wd * h, wd.abs() * th, dtype)
 
 
-def layernorm_bound(x, w, b, eps, dtype):
-    """x [rows, cols], w / b [cols] -> (reference, bound) of ss_layernorm (block and wave kernels)"""
-    xd, wd, bd = x.double(), w.double(), b.double()
-    cols = x.shape[1]
+def _two_pass_stats(xd, eps, fma_squares=True):
+    """the first half of the two-pass LayerNorm kernels (layernorm, ss_rowstats, the LN-fused fp8 quantiser) on xd [rows, cols]
+    fp64 -> (mean, t_mean, d, t_d, rstd, t_rstd).  fma_squares=False: d * d is rounded before it is added (one more rounding per
+    term: the quantiser's `ss2 += d * d` under -ffp-contract=off)."""
+    cols = xd.shape[1]
     mean, tm = op32(xd.mean(1, keepdim=True), gamma(cols) * xd.abs().mean(1, keepdim=True))
     d, td = op32(xd - mean, tm.expand_as(xd))
     s2 = (d * d).sum(1, keepdim=True)
-    ts2 = (2.0 * d.abs() * td + td * td).sum(1, keepdim=True) + gamma(cols) * ((d.abs() + td) ** 2).sum(1, keepdim=True)
+    ts2 = (2.0 * d.abs() * td + td * td).sum(1, keepdim=True) + gamma(cols if fma_squares else cols + 1) * ((d.abs() + td) ** 2).sum(1, keepdim=True)
     v, t = op32(s2 / cols, ts2 / cols)
     v, t = op32(v + float(np.float32(eps)), t)
     rv, rt = recip32(*sqrt32(v, t))
+    return mean, tm, d, td, rv, rt
+
+
+def layernorm_bound(x, w, b, eps, dtype, fma_squares=True):
+    """x [rows, cols], w / b [cols] -> (reference, bound) of ss_layernorm (block and wave kernels)"""
+    xd, wd, bd = x.double(), w.double(), b.double()
+    _, _, d, td, rv, rt = _two_pass_stats(xd, eps, fma_squares)
     v, t = product(d, td, rv.expand_as(d), rt.expand_as(d))
     v, t = op32(v * wd, t * wd.abs())
     v, t = op32(v + bd, t)
@@ -1050,3 +1097,237 @@ MEAN_N = [1, 255, 65536, 65537, 200001]
 def randn_t(shape, dtype, seed, std=1.0, mean=0.0):
     g = torch.Generator().manual_seed(16000 + seed)
     return (torch.randn(*shape, generator=g) * std + mean).to(dtype)
+
+
+# ==== GEMM variants: fp8, LN-folded, statistics producers, split-K (tests/test_gemm_variants_edges_gpu.py) ====================
+F8 = torch.float8_e4m3fn
+E64 = 2.0 ** -48          # what an fp64 sum / product chain of a few thousand terms can lose, relative
+U8 = 2.0 ** -4            # unit roundoff of e4m3 (3 mantissa bits)
+ETA8 = 2.0 ** -10         # half the e4m3 subnormal spacing (2^-9), in code units
+
+
+def f8_values(codes):
+    """e4m3 bytes (uint8) -> their values in fp64"""
+    return codes.view(F8).double()
+
+
+def quantize_rows_e4m3(x):
+    """the quantiser restated on the CPU in fp32 (s = amax / 448, q = RNE(x * (448 / amax))) -> (codes uint8, scale fp32)"""
+    xf = x.float()
+    amax = xf.abs().amax(1)
+    inv = torch.where(amax > 0, torch.full_like(amax, 448.0) / amax, torch.zeros_like(amax))
+    return (xf * inv[:, None]).to(F8).view(torch.uint8), amax / 448.0
+
+
+def gemm_fp8_bound(a8, sa, w8, sw, bias=None, residual=None, gelu_=False, geglu=False):
+    """a8 [M, K] / w8 [N, K] e4m3 bytes, sa [M] / sw [N] fp32 -> (reference, bound) of ss_gemm_fp8 (bf16 out)"""
+    v, t = accumulate(f8_values(a8), f8_values(w8))
+    s = (sa.float()[:, None] * sw.float()[None, :]).double()        # fl(sa sw): the kernel's own fp32 product
+    v, t = op32(v * s, t * s.abs())
+    return epilogue(v, t, torch.bfloat16, bias=bias, gelu_=gelu_, residual=residual, geglu=geglu)
+
+
+def gemm_lnfold_bound(x, wg, rstd, shift, colsum, dtype, bias_d=None, gelu_=False, geglu=False, t_rstd=None, t_shift=None):
+    """x [M, K], wg [N, K] (T), rstd / shift [M], colsum [N] fp32 -> (reference, bound) of ss_gemm_lnfold.  t_rstd / t_shift [M]:
+    the statistics are known to these tolerances only (ss_gemm_lnfold_part)."""
+    av, at = accumulate(x, wg)
+    rs, sh, cs = rstd.double()[:, None], shift.double()[:, None], colsum.double()[None, :]
+    trs = torch.zeros_like(rs) if t_rstd is None else t_rstd.double()[:, None]
+    tsh = torch.zeros_like(sh) if t_shift is None else t_shift.double()[:, None]
+    p, tp = av * rs, at * rs.abs() + (av.abs() + at) * trs
+    c, tc = op32(sh * cs, cs.abs() * tsh)
+    v = p + c
+    t = tp + tc + U32 * (p.abs() + c.abs() + tp + tc)
+    return epilogue(v, t, dtype, bias=bias_d, gelu_=gelu_, geglu=geglu)
+
+
+def _stats_from_sums(a, b, width, eps, u_inv):
+    """a = sum x, b = sum x^2 [M] fp64 (exact inputs) -> ((rstd, t), (shift, t)) of the fp64 E[x^2] - mean^2 form narrowed to
+    fp32; u_inv: relative error of the kernel's 1 / width"""
+    e = u_inv + E64
+    mean, ex2 = a / width, b / width
+    tmean = e * mean.abs()
+    var = (ex2 - mean * mean).clamp_min(0.0)
+    tvar = e * ex2.abs() + 2.0 * mean.abs() * tmean + tmean * tmean + E64 * (ex2.abs() + mean * mean)
+    ve = var + float(np.float32(eps))
+    r = 1.0 / ve.sqrt()
+    lo = (ve - tvar).clamp_min(1e-300)
+    r, tr = op32(r, 0.5 * tvar * lo ** -1.5 + E64 * r)
+    m32, tm32 = op32(mean, tmean)
+    s, ts = op32(-m32 * r, m32.abs() * tr + r.abs() * tm32 + tr * tm32)
+    return (r, tr), (s, ts)
+
+
+def lnfold_part_stats_bound(part, width, eps):
+    """part [M, strips, 2] fp32 -> ((rstd, t_rstd), (shift, t_shift)) the consumer's epilogue forms (ln_inv_width is fp32)"""
+    pd = part.double()
+    return _stats_from_sums(pd[:, :, 0].sum(1), pd[:, :, 1].sum(1), width, eps, U32)
+
+
+def rowstat_finalize_bound(acc, width, eps):
+    """acc [M, 2] fp64 -> ((rstd, t), (shift, t)) of ss_rowstat_finalize (1 / width in fp64)"""
+    return _stats_from_sums(acc[:, 0].double(), acc[:, 1].double(), width, eps, 2.0 ** -53)
+
+
+def rowstats_bound(x, eps, dtype):
+    """x [M, K] (T) -> ((rstd, t), (shift, t)) [M] of ss_rowstats"""
+    mean, tm, _, _, rv, rt = _two_pass_stats(x.double(), eps)
+    s, ts = product(-mean, tm, rv, rt)
+    return (rv[:, 0], rt[:, 0]), (s[:, 0], ts[:, 0])
+
+
+def rowsum_bound(y, tn=None):
+    """y [M, N]: the STORED output -> ((S1, t1), (S2, t2)), [M, N / tn] per strip of tn columns, or [M] per row (tn=None: the
+    fp64 accumulator over fp32 pieces)"""
+    yd = y.double()
+    M, N = yd.shape
+    if tn is None:
+        s1, a1, s2, n, extra = yd.sum(1), yd.abs().sum(1), (yd * yd).sum(1), N, E64
+    else:
+        assert N % tn == 0
+        ys = yd.view(M, N // tn, tn)
+        s1, a1, s2, n, extra = ys.sum(2), ys.abs().sum(2), (ys * ys).sum(2), tn, 0.0
+    return (s1, (gamma(n) + extra) * a1), (s2, (gamma(n + 1) + extra) * s2)
+
+
+def gemm_splitk_bound(a, w, dtype, S, bias=None, residual=None):
+    """(reference, bound) of ss_gemm_splitk at S slices"""
+    v, t = accumulate(a, w, kacc=a.shape[1] + S)
+    return epilogue(v, t, dtype, bias=bias, residual=residual)
+
+
+def quantize_ln_bound(x, g, b, eps, dtype):
+    """x [M, K], g / b [K] -> ((LayerNorm reference, bound of q * s), (scale reference, bound)) of quantize_rows_fp8(x, ln=)"""
+    v, t = layernorm_bound(x, g, b, eps, dtype, fma_squares=False)
+    tmax = t.amax(1)
+    s = v.abs().amax(1) / 448.0
+    ts = tmax / 448.0 + U32 * (s + tmax / 448.0)
+    tq = t + (U8 + 4.0 * U32) * (v.abs() + t) + ETA8 * (s + ts)[:, None]
+    return (v, tq), (s, ts)
+
+
+def fp8_probe(kind, M, N, K, seed=0):
+    """exact fp8 probes: operands that quantise exactly.  One-hot (or all-ones) rows: code value 448, scale fl(1 / 448); integer
+    rows in [-4, 4] with one entry +-7: code values 64 w, scale 7 / 448 = 2^-6.  -> (a8, sa, w8, sw, expected bf16): the two
+    de-quantisation products mirrored in fp32 (every partial sum is 2^12 x an integer below 2^24: exact in any order)."""
+    g = torch.Generator().manual_seed(3500 + seed)
+
+    def ints(R):
+        w = torch.randint(-4, 5, (R, K), generator=g).float()
+        w[torch.arange(R), (torch.arange(R) * 5 + seed) % K] = torch.where(torch.arange(R) % 2 == 0, 7.0, -7.0)
+        return w * 64.0, torch.full((R,), 2.0 ** -6)
+
+    def onehot(R, sd):
+        return selector_probe(R, 1, K, torch.float32, sd)[0] * 448.0, torch.full((R,), 1.0) / 448.0
+    if kind == "selector":
+        (a, sa), (w, sw) = onehot(M, seed), ints(N)
+    elif kind == "selector_w":
+        (a, sa), (w, sw) = ints(M), onehot(N, seed + 500)
+    else:
+        (a, sa), (w, sw) = (torch.full((M, K), 448.0), torch.full((M,), 1.0) / 448.0), ints(N)
+    acc = a.double() @ w.double().t()
+    assert float(acc.abs().max()) < 2.0 ** 36 and torch.equal(acc.float().double(), acc)
+    exp = (acc.float() * (sa[:, None] * sw[None, :])).to(torch.bfloat16)
+    return a.to(F8).view(torch.uint8), sa, w.to(F8).view(torch.uint8), sw, exp
+
+
+# ---- cases ---------------------------------------------------------------------------------------------------------------------
+FP8_TILES = [0, 80, 81, 82, 85, 86, 88]
+# every M of {63, 64, 65, 129, 257, 520}, N of {160, 320, 640 | 64, 208 | 72, 330} and K of {1, 2, 3, 5 K tiles} at least once
+FP8_SHAPES = [(63, 160, 128), (64, 320, 256), (65, 640, 384), (129, 64, 640), (257, 208, 128), (520, 72, 256), (129, 330, 384),
+              (257, 160, 640)]
+FP8_EPILOGUES = ["plain", "bias", "bias+residual", "gelu", "geglu"]
+FP8_PROBE_SHAPES = [(129, 160, 384), (257, 330, 128)]
+FP8_STRIDE_SHAPE = (129, 208, 256)
+FP8_STRIDE_CASES = [(8, 0, False), (4, 0, False), (1, 0, False), (0, 4, False), (8, 4, True), (1, 0, True)]   # ldc - width, bias offset, geglu
+LNFOLD_TILES = [0, 60, 62, 63, 64, 66, 68, 69, 71, 72]
+LNFOLD_SHAPES = [(129, 160, 64), (257, 640, 192), (520, 208, 640)]
+LNFOLD_EPILOGUES = ["plain", "bias", "gelu", "geglu"]
+# the partial form: N = 208 is the refused shape (no folded tile width divides it); (520, 320, 640) gives it M = 520 and K = 640
+LNFOLD_PART_SHAPES = LNFOLD_SHAPES + [(520, 320, 640)]
+LNFOLD_PART_WIDTH = 32                                # strip width of the synthetic partials: 2, 6 and 20 strips (> 16: the
+#                                                       consumer's loop takes 16 at a time, the second batch has a masked tail)
+ROWSTATS_SHAPES = [(5, 8), (129, 64), (257, 192), (130, 640), (67, 2048), (4, 1032)]
+PRODUCER_SHAPES = [(129, 160, 64), (257, 640, 192), (333, 200, 64), (257, 128, 192), (333, 640, 64)]
+SPLITK_SHAPES = [(129, 64, 1024), (257, 128, 1088), (512, 192, 2048)]
+SPLITK_S = [0, 2, 3, 5, 8]
+SPLITK_EPILOGUES = ["bias", "residual", "bias+residual"]
+QUANT_LN_SHAPES = [(5, 8), (130, 640), (67, 1288)]
+LN_EPS = 1e-5
+
+
+# ---- seeds: one function per family, used by the GPU file and by the CPU simulation alike ------------------------------------------
+def fp8_seeds(cfg, i, j):
+    """(operands, epilogue inputs) of shape i, epilogue j on tile cfg"""
+    return cfg * 1000 + i, cfg * 1000 + i * 10 + j
+
+
+def fp8_stride_seed(cfg, c):
+    return cfg * 1000 + 500 + c
+
+
+def lnfold_seed(cfg, i, part=False):
+    return cfg * 100 + (50 if part else 0) + i
+
+
+def producer_seed(fallback, i):
+    return 100 * fallback + i
+
+
+def splitk_seed(i, S):
+    return 300 + 10 * i + S
+
+
+LNFOLD_REFUSAL_CASE = (129, 160, 64, 77)            # M, N, K, seed of the alignment cases of ss_gemm_lnfold_part
+PRODUCER_CHAIN_CASES = [(257, 640, 192, 200), (129, 128, 64, 201)]      # M, N, K, seed of producer -> folded consumer (160 wide)
+
+
+def splitk_planned(M, N, K):
+    """the split count splitk_plan (ss_gemm.hip) gives the shapes above (2, 2, 4): a hand copy, asserted against the workspace
+    size the library reports"""
+    base = -(-M // 128) * -(-N // 64)
+    s = min(-(-512 // base), (K // 64) // 8, 8)
+    kt = K // 64
+    while s > 2 and (s - 1) * -(-kt // s) >= kt:
+        s -= 1
+    return s
+
+
+def splitk_ranges(K, S):
+    """[(k0, k1)] of the S slices: ceil(tiles / S) K tiles of 64 each, the last ranges short or empty"""
+    kt = K // 64
+    per = -(-kt // S)
+    return [(min(i * per, kt) * 64, min((i + 1) * per, kt) * 64) for i in range(S)]
+
+
+def fp8_inputs(M, N, K, seed):
+    """fresh quantised operands: a ~ N(0, 1) rows scaled over two decades, w ~ N(0, 1 / K) -> (a8, sa, w8, sw)"""
+    g = torch.Generator().manual_seed(17000 + seed)
+    a = torch.randn(M, K, generator=g) * torch.logspace(-1, 1, M)[:, None]
+    w = torch.randn(N, K, generator=g) / K ** 0.5
+    return quantize_rows_e4m3(a.to(torch.bfloat16)) + quantize_rows_e4m3(w.to(torch.bfloat16))
+
+
+def lnfold_inputs(M, N, K, dtype, seed):
+    """x: N(0.7, 3^2) rows; rows 1 (mod 16) sit at |mean| ~ 9 std, row 2 is constant.  -> (x, wg, colsum fp32, bias_d)"""
+    g = torch.Generator().manual_seed(18000 + seed)
+    x = torch.randn(M, K, generator=g) * 3.0 + 0.7
+    x[1::16] = torch.randn(len(range(1, M, 16)), K, generator=g) * 1.4 + 12.6
+    x[2] = 1.75
+    wg = ((torch.randn(N, K, generator=g) / K ** 0.5) * (1.0 + 0.1 * torch.randn(K, generator=g))[None, :]).to(dtype)
+    bias_d = (torch.randn(N, generator=g) * 0.5).to(dtype)
+    return x.to(dtype), wg, wg.float().sum(1).contiguous(), bias_d
+
+
+def lnfold_parts(x, width=LNFOLD_PART_WIDTH):
+    """per-strip (sum, sum of squares) of x's rows as a producer would leave them: fp64 sums rounded to fp32 -> [M, strips, 2]"""
+    xs = x.double().view(x.shape[0], x.shape[1] // width, width)
+    return torch.stack([xs.sum(2), (xs * xs).sum(2)], 2).float().contiguous()
+
+
+def producer_inputs(M, N, K, dtype, seed):
+    """a, w, bias (+9: |row mean| ~ 9 std of the output), residual"""
+    g = torch.Generator().manual_seed(19000 + seed)
+    a = torch.randn(M, K, generator=g).to(dtype)
+    w = (torch.randn(N, K, generator=g) / K ** 0.5).to(dtype)
+    return a, w, (torch.randn(N, generator=g) * 0.3 + 9.0).to(dtype), torch.randn(M, N, generator=g).to(dtype)

@@ -1,7 +1,8 @@
 """The checker (tests/kernel_check.py) is tested before it judges a kernel: a correct kernel SIMULATED on the CPU (fp32 math,
 chunked and reversed summation, the kernels' rounding points; attention: a tile-64 online softmax with P rounded to T) must
-produce zero violations on every case tests/test_kernel_edges_gpu.py and tests/test_pointwise_edges_gpu.py run (the grid-stride
-shapes of the latter reduced to a small shape of the same family), and every seeded mutant must be flagged."""
+produce zero violations on every case tests/test_kernel_edges_gpu.py, tests/test_pointwise_edges_gpu.py and
+tests/test_gemm_variants_edges_gpu.py run (the grid-stride shapes of the second reduced to a small shape of the same family),
+and every seeded mutant must be flagged."""
 import math
 
 import pytest
@@ -792,3 +793,396 @@ def test_guarded_out_guards_only_mode():
     g.flat[g.start - 1] = 0
     with pytest.raises(AssertionError):
         g.check("before", payload=False)
+
+
+# ==== GEMM variants: fp8, LN-folded, statistics producers, split-K: simulated kernels ==========================================
+BF = torch.bfloat16
+
+
+def sim_fp8(a8, sa, w8, sw, drop=None):
+    """fp32 accumulation of the code values (K tiles of 128, last first) -> (acc, fl(sa sw)); fp8_out applies the rest"""
+    a, w = a8.view(KC.F8).float(), w8.view(KC.F8).float()
+    acc = sim_acc(a, w, chunk=128)
+    if drop is not None:                    # (rows, cols, k0): one K tile missing in one fragment
+        rs, cs, k0 = drop
+        a2 = a.clone()
+        a2[:, k0:k0 + 128] = 0
+        acc[rs, cs] = sim_acc(a2[rs], w[cs], chunk=128)
+    return acc, sa.float()[:, None] * sw.float()[None, :]
+
+
+def fp8_out(acc, s, trunc=False, **epi):
+    """acc * fl(sa sw), the usual epilogue in bf16"""
+    return sim_epilogue(acc * s, BF, trunc=trunc, **epi)
+
+
+def sim_lnfold(acc, rstd, shift, colsum, dtype, skip=None, trunc=False, **epi):
+    """fma(acc, rstd, fl(shift colsum)) (the product exact in fp64, one narrowing), the usual epilogue"""
+    c = shift.float()[:, None] * colsum.float()[None, :]
+    if skip is not None:
+        c[skip] = 0.0
+    t = (acc.double() * rstd.double()[:, None] + c.double()).float()
+    return sim_epilogue(t, dtype, trunc=trunc, **{{"bias_d": "bias"}.get(k, k): v for k, v in epi.items()})
+
+
+def sim_part_stats(part, width, eps):
+    """the consumer's epilogue: fp64 sums 16 partials at a time, the fp32 1 / width, E[x^2] - mean^2 in fp64, fp32 narrowings"""
+    a = torch.zeros(part.shape[0], dtype=torch.float64)
+    b = torch.zeros_like(a)
+    for k0 in range(0, part.shape[1], 16):
+        for k in range(k0, min(k0 + 16, part.shape[1])):
+            a, b = a + part[:, k, 0].double(), b + part[:, k, 1].double()
+    iw = (torch.ones((), dtype=torch.float32) / torch.tensor(float(width), dtype=torch.float32)).double()
+    mean = a * iw
+    var = (b * iw - mean * mean).clamp_min(0.0)
+    r = (1.0 / torch.sqrt(var + f32(eps).double())).float()
+    return r, -mean.float() * r
+
+
+def sim_finalize(acc, width, eps):
+    mean = acc[:, 0] * (1.0 / width)
+    var = (acc[:, 1] * (1.0 / width) - mean * mean).clamp_min(0.0)
+    r = (1.0 / torch.sqrt(var + f32(eps).double())).float()
+    return r, -mean.float() * r
+
+
+def sim_rowstats(x, eps, cols=None):
+    """two-pass fp32 statistics (cols: the mutant that stops short)"""
+    xf = x.float()[:, :cols]
+    n = f32(float(x.shape[1]))
+    mean = fsum(xf, 8) / n
+    d = xf - mean[:, None]
+    r = 1.0 / torch.sqrt(fsum(d * d, 8) / n + f32(eps))
+    return r, -mean * r
+
+
+def sim_rowsums(y, tn):
+    """per-strip fp32 (sum, sum of squares) of the stored rows: 8-wide pieces, folded last piece first -> [M, N / tn, 2]"""
+    ys = y.float().view(y.shape[0], y.shape[1] // tn, tn)
+    return torch.stack([fsum(ys, 8), fsum(ys * ys, 8)], 2)
+
+
+def sim_splitk(a, w, dtype, S, bias=None, residual=None, drop=None, twice=None):
+    """one fp32 accumulator per K range (stored exactly), the slices added in fp32 in order, the epilogue of the reduce kernel"""
+    tot = torch.zeros(a.shape[0], w.shape[0], dtype=torch.float32)
+    for i, (k0, k1) in enumerate(KC.splitk_ranges(a.shape[1], S)):
+        p = sim_acc(a[:, k0:k1], w[:, k0:k1], chunk=64) if k1 > k0 else torch.zeros_like(tot)
+        if i == drop:
+            continue
+        tot = tot + p + (p if i == twice else 0.0)
+    return sim_epilogue(tot, dtype, bias=bias, residual=residual)
+
+
+def sim_quant_ln(x, g, b, eps, dtype):
+    """quantize_rows_fp8(x, ln=): fp32 two-pass LayerNorm rounded to T, amax, s = amax / 448, q = RNE_e4m3(o (448 / amax))"""
+    xf, n = x.float(), f32(float(x.shape[1]))
+    mean = fsum(xf, 8) / n
+    d = xf - mean[:, None]
+    rstd = 1.0 / torch.sqrt(fsum(d * d, 8) / n + f32(eps))
+    o = r(d * rstd[:, None] * g.float() + b.float(), dtype)
+    amax = o.abs().amax(1)
+    inv = torch.where(amax > 0, f32(448.0) / amax, torch.zeros_like(amax))
+    return (o * inv[:, None]).to(KC.F8).view(torch.uint8), amax / 448.0
+
+
+# ---- zero violations on every case of tests/test_gemm_variants_edges_gpu.py -------------------------------------------------------
+@pytest.mark.parametrize("cfg", KC.FP8_TILES)
+def test_simulated_fp8_gemm_stays_inside_the_bound(cfg):
+    """the inputs of test_fp8_gemm_bound_every_tile[cfg] and test_fp8_gemm_strides_and_alignment[cfg] (same seed functions)"""
+    worst = 0.0
+    for i, (M, N, K) in enumerate(KC.FP8_SHAPES):
+        q = KC.fp8_inputs(M, N, K, KC.fp8_seeds(cfg, i, 0)[0])
+        acc, s = sim_fp8(*q)
+        for j, epi in enumerate(KC.FP8_EPILOGUES):
+            kw = KC.epilogue_inputs(epi, M, N, BF, KC.fp8_seeds(cfg, i, j)[1])
+            ref, tol = KC.gemm_fp8_bound(*q, **kw)
+            worst = max(worst, KC.check(fp8_out(acc, s, **kw), ref, tol, "sim fp8 cfg %d %s %s" % (cfg, epi, (M, N, K))))
+    M, N, K = KC.FP8_STRIDE_SHAPE
+    for c, (_, _, geglu) in enumerate(KC.FP8_STRIDE_CASES):
+        q = KC.fp8_inputs(M, N, K, KC.fp8_stride_seed(cfg, c))
+        kw = KC.epilogue_inputs("geglu" if geglu else "bias+residual", M, N, BF, KC.fp8_stride_seed(cfg, c))
+        ref, tol = KC.gemm_fp8_bound(*q, **kw)
+        KC.check(fp8_out(*sim_fp8(*q), **kw), ref, tol, "sim fp8 strided cfg %d case %d" % (cfg, c))
+    print("simulated fp8 gemm, inputs of cfg %d: worst error / bound %.3f" % (cfg, worst))
+    assert worst > 0.05
+
+
+def test_exact_fp8_probes():
+    for (M, N, K) in KC.FP8_PROBE_SHAPES:
+        for kind in ("selector", "selector_w", "counter"):
+            a8, sa, w8, sw, exp = KC.fp8_probe(kind, M, N, K, seed=K)
+            # the operands quantise exactly: the quantiser gives these bytes and scales back from the de-quantised matrices
+            for q, s in ((a8, sa), (w8, sw)):
+                q2, s2 = KC.quantize_rows_e4m3((KC.f8_values(q) * s.double()[:, None]).float())
+                assert torch.equal(q2, q) and torch.equal(s2, s), kind
+            assert torch.equal(fp8_out(*sim_fp8(a8, sa, w8, sw)), exp), kind
+            w2 = w8.clone()
+            w2[:, K - 8:] = 0                                  # the K tail dropped
+            a2 = a8.clone()
+            a2[:, K - 8:] = 0
+            assert not torch.equal(fp8_out(*sim_fp8(a2, sa, w2, sw)), exp), kind
+
+
+def lnfold_kw(epi, bias_d):
+    return dict(bias_d=None if epi == "plain" else bias_d, gelu_=epi == "gelu", geglu=epi == "geglu")
+
+
+@pytest.mark.parametrize("dtype", DTYPES16, ids=lambda d: KC.NAME[d])
+@pytest.mark.parametrize("cfg", KC.LNFOLD_TILES)
+def test_simulated_lnfold_gemm_stays_inside_the_bound(cfg, dtype):
+    """the inputs of test_lnfold_gemm_bound_every_tile[cfg] (statistics from the simulated ss_rowstats, handed over as the
+    kernel's inputs) and of test_lnfold_part_gemm_bound_every_tile[cfg] (statistics from partials, known to a tolerance; the
+    shape the library refuses is simulated all the same)"""
+    worst = 0.0
+    for i, (M, N, K) in enumerate(KC.LNFOLD_SHAPES):
+        x, wg, colsum, bias_d = KC.lnfold_inputs(M, N, K, dtype, KC.lnfold_seed(cfg, i))
+        acc = sim_acc(x, wg, chunk=64)
+        rstd, shift = sim_rowstats(x, KC.LN_EPS)
+        for epi in KC.LNFOLD_EPILOGUES:
+            kw = lnfold_kw(epi, bias_d)
+            ref, tol = KC.gemm_lnfold_bound(x, wg, rstd, shift, colsum, dtype, **kw)
+            worst = max(worst, KC.check(sim_lnfold(acc, rstd, shift, colsum, dtype, **kw), ref, tol, "sim lnfold cfg %d %s %s" % (cfg, epi, (M, N, K))))
+    for i, (M, N, K) in enumerate(KC.LNFOLD_PART_SHAPES):
+        x, wg, colsum, bias_d = KC.lnfold_inputs(M, N, K, dtype, KC.lnfold_seed(cfg, i, part=True))
+        lnfold_part_case(x, wg, colsum, bias_d, KC.lnfold_parts(x), K, dtype, KC.LNFOLD_EPILOGUES, "sim lnfold_part cfg %d %s" % (cfg, (M, N, K)))
+    print("simulated lnfold, inputs of cfg %d %s: worst error / bound %.3f" % (cfg, KC.NAME[dtype], worst))
+    assert worst > 0.05
+
+
+def lnfold_part_case(x, wg, colsum, bias_d, part, width, dtype, epis, what):
+    (rv, rt), (sv, st) = KC.lnfold_part_stats_bound(part, width, KC.LN_EPS)
+    r2, s2 = sim_part_stats(part, width, KC.LN_EPS)
+    KC.check(r2, rv, rt, what + " rstd")
+    KC.check(s2, sv, st, what + " shift")
+    acc = sim_acc(x, wg, chunk=64)
+    for epi in epis:
+        kw = lnfold_kw(epi, bias_d)
+        ref, tol = KC.gemm_lnfold_bound(x, wg, rv, sv, colsum, dtype, t_rstd=rt, t_shift=st, **kw)
+        KC.check(sim_lnfold(acc, r2, s2, colsum, dtype, **kw), ref, tol, what + " " + epi)
+
+
+@pytest.mark.parametrize("dtype", DTYPES16, ids=lambda d: KC.NAME[d])
+def test_simulated_lnfold_part_alignment_and_chain_cases_stay_inside_the_bound(dtype):
+    """the one launch test_lnfold_part_refuses_what_the_staged_epilogue_cannot_take lets through, and the producer -> consumer
+    chain of test_producer_partials_into_folded_consumer (the producer's strips are 64 or 80 wide there)"""
+    M, N, K, seed = KC.LNFOLD_REFUSAL_CASE
+    x, wg, colsum, bias_d = KC.lnfold_inputs(M, N, K, dtype, seed)
+    lnfold_part_case(x, wg, colsum, bias_d, KC.lnfold_parts(x), K, dtype, ["bias"], "sim lnfold_part aligned")
+    for (M, N, K, seed) in KC.PRODUCER_CHAIN_CASES:
+        a, w, bias, res = KC.producer_inputs(M, N, K, dtype, seed)
+        y = sim_gemm(a, w, dtype, bias=bias, residual=res)
+        _, wg, colsum, bias_d = KC.lnfold_inputs(8, 160, N, dtype, seed)
+        lnfold_part_case(y, wg, colsum, bias_d, sim_rowsums(y, 64 if N % 80 else 80), N, dtype, ["bias"], "sim chain %s" % ((M, N, K),))
+
+
+@pytest.mark.parametrize("dtype", DTYPES16, ids=lambda d: KC.NAME[d])
+def test_simulated_rowstats_and_finalize_stay_inside_the_bound(dtype):
+    for i, (M, K) in enumerate(KC.ROWSTATS_SHAPES):
+        x = KC.lnfold_inputs(M, 16, K, dtype, 50 + i)[0]
+        (rv, rt), (sv, st) = KC.rowstats_bound(x, KC.LN_EPS, dtype)
+        r1, s1 = sim_rowstats(x, KC.LN_EPS)
+        KC.check(r1, rv, rt, "sim rowstats rstd %s" % ((M, K),))
+        KC.check(s1, sv, st, "sim rowstats shift %s" % ((M, K),))
+        xd = x.double()
+        acc = torch.stack([xd.sum(1), (xd * xd).sum(1)], 1)
+        (rv, rt), (sv, st) = KC.rowstat_finalize_bound(acc, K, KC.LN_EPS)
+        r2, s2 = sim_finalize(acc, K, KC.LN_EPS)
+        KC.check(r2, rv, rt, "sim finalize rstd")
+        KC.check(s2, sv, st, "sim finalize shift")
+
+
+@pytest.mark.parametrize("dtype", DTYPES16, ids=lambda d: KC.NAME[d])
+def test_simulated_producer_sums_stay_inside_the_bound(dtype):
+    for fallback, (i, (M, N, K)) in [(f, c) for f in (0, 1) for c in enumerate(KC.PRODUCER_SHAPES)]:
+        a, w, bias, res = KC.producer_inputs(M, N, K, dtype, KC.producer_seed(fallback, i))
+        for residual in (None, res):
+            y = sim_gemm(a, w, dtype, bias=bias, residual=residual)
+            ref, tol = KC.gemm_bound(a, w, dtype, bias=bias, residual=residual)
+            KC.check(y, ref, tol, "sim producer %s" % ((M, N, K),))
+            for tn in (8, 64, 80):
+                if N % tn:
+                    continue
+                part = sim_rowsums(y, tn)
+                (s1, t1), (s2, t2) = KC.rowsum_bound(y, tn)
+                KC.check(part[:, :, 0], s1, t1, "sim strip sums")
+                KC.check(part[:, :, 1], s2, t2, "sim strip squares")
+            part = sim_rowsums(y, 8).double().sum(1)            # the accumulator form: fp32 pieces added in fp64
+            (s1, t1), (s2, t2) = KC.rowsum_bound(y)
+            KC.check(part[:, 0], s1, t1, "sim row sums")
+            KC.check(part[:, 1], s2, t2, "sim row squares")
+
+
+@pytest.mark.parametrize("dtype", DTYPES16, ids=lambda d: KC.NAME[d])
+def test_simulated_splitk_stays_inside_the_bound(dtype):
+    for i, (M, N, K) in enumerate(KC.SPLITK_SHAPES):
+        for S in KC.SPLITK_S:
+            a, w = KC.gemm_inputs(M, N, K, dtype, KC.splitk_seed(i, S))
+            for epi in KC.SPLITK_EPILOGUES:
+                kw = KC.epilogue_inputs(epi, M, N, dtype, KC.splitk_seed(i, S))
+                Su = S or KC.splitk_planned(M, N, K)
+                ref, tol = KC.gemm_splitk_bound(a, w, dtype, Su, **kw)
+                KC.check(sim_splitk(a, w, dtype, Su, **kw), ref, tol, "sim splitk %s S %d %s" % ((M, N, K), Su, epi))
+    assert [KC.splitk_planned(*s) for s in KC.SPLITK_SHAPES] == [2, 2, 4]
+    assert KC.splitk_ranges(1088, 8)[-2:] == [(1088, 1088)] * 2 and KC.splitk_ranges(1024, 3) == [(0, 384), (384, 768), (768, 1024)]
+
+
+@pytest.mark.parametrize("dtype", DTYPES16, ids=lambda d: KC.NAME[d])
+def test_simulated_ln_quantiser_stays_inside_the_bound(dtype):
+    for i, (M, K) in enumerate(KC.QUANT_LN_SHAPES):
+        x, g, b = KC.norm_inputs(M, K, dtype, 70 + i)
+        (v, tq), (s, ts) = KC.quantize_ln_bound(x, g, b, KC.LN_EPS, dtype)
+        q, sc = sim_quant_ln(x, g, b, KC.LN_EPS, dtype)
+        KC.check(sc, s, ts, "sim ln quantiser scale %s" % ((M, K),))
+        KC.check(KC.f8_values(q) * sc.double()[:, None], v, tq, "sim ln quantiser q * s %s" % ((M, K),))
+        q2 = q.clone()
+        q2[M // 2, K - 1] ^= 2                                   # two code steps away
+        assert count(KC.f8_values(q2) * sc.double()[:, None], v, tq) == 1
+        assert count(sc * 1.01, s, ts) >= M - 2                  # a scale 1 % off (bf16 leaves amax 0.4 %; the offset and the
+        #                                                          constant row pay for their fp32 mean and are wider)
+
+
+# ---- mutants ------------------------------------------------------------------------------------------------------------------
+def inside(coords, rows, cols):
+    return all(rows.start <= c[0] < rows.stop and cols.start <= c[1] < cols.stop for c, _ in coords)
+
+
+def test_mutants_fp8():
+    M, N, K = 257, 160, 640
+    a8, sa, w8, sw = KC.fp8_inputs(M, N, K, 7)
+    kw = KC.epilogue_inputs("bias", M, N, BF, 7)
+    ref, tol = KC.gemm_fp8_bound(a8, sa, w8, sw, **kw)
+    acc, s = sim_fp8(a8, sa, w8, sw)
+    assert count(fp8_out(acc, s, **kw), ref, tol) == 0
+    rows, cols = slice(64, 80), slice(32, 48)
+    # one K tile dropped in one 16x16 fragment
+    n, _, coords = KC.violations(fp8_out(*sim_fp8(a8, sa, w8, sw, drop=(rows, cols, 256)), **kw), ref, tol)
+    assert n >= 128 and inside(coords, rows, cols)
+    # scale_w shifted by one column in one 4-column group
+    s2 = s.clone()
+    s2[rows, 36:40] = s[rows, 37:41]
+    n, _, coords = KC.violations(fp8_out(acc, s2, **kw), ref, tol)
+    assert n >= 16 and inside(coords, rows, slice(36, 40))
+    # scale_a taken from row m + 16
+    s2 = s.clone()
+    s2[rows, cols] = s[80:96, cols]
+    n, _, coords = KC.violations(fp8_out(acc, s2, **kw), ref, tol)
+    assert n >= 200 and inside(coords, rows, cols)
+    # a truncating store (K = 128: the rounding dominates)
+    a8, sa, w8, sw = KC.fp8_inputs(257, 208, 128, 8)
+    ref, tol = KC.gemm_fp8_bound(a8, sa, w8, sw)
+    assert count(fp8_out(*sim_fp8(a8, sa, w8, sw)), ref, tol) == 0
+    assert count(fp8_out(*sim_fp8(a8, sa, w8, sw), trunc=True), ref, tol) > 0.15 * ref.numel()
+
+
+@pytest.mark.parametrize("dtype", DTYPES16, ids=lambda d: KC.NAME[d])
+def test_mutants_lnfold(dtype):
+    M, N, K = 257, 640, 192
+    x, wg, colsum, bias_d = KC.lnfold_inputs(M, N, K, dtype, 9)
+    rstd, shift = sim_rowstats(x, KC.LN_EPS)
+    ref, tol = KC.gemm_lnfold_bound(x, wg, rstd, shift, colsum, dtype, bias_d=bias_d)
+    acc = sim_acc(x, wg, chunk=64)
+    assert count(sim_lnfold(acc, rstd, shift, colsum, dtype, bias_d=bias_d), ref, tol) == 0
+    rows, cols = slice(64, 80), slice(32, 48)
+    # one K tile dropped in one 16x16 fragment
+    x2 = x.clone()
+    x2[:, 64:128] = 0
+    acc2 = acc.clone()
+    acc2[rows, cols] = sim_acc(x2[rows], wg[cols], chunk=64)
+    n, _, coords = KC.violations(sim_lnfold(acc2, rstd, shift, colsum, dtype, bias_d=bias_d), ref, tol)
+    assert n >= 128 and inside(coords, rows, cols)
+    # colsum shifted by one column in one 4-column group
+    y = sim_lnfold(acc, rstd, shift, colsum, dtype, bias_d=bias_d)
+    cs2 = colsum.clone()
+    cs2[36:40] = colsum[37:41]
+    z = y.clone()
+    z[rows, 36:40] = sim_lnfold(acc, rstd, shift, cs2, dtype, bias_d=bias_d)[rows, 36:40]
+    n, _, coords = KC.violations(z, ref, tol)
+    assert n >= 32 and inside(coords, rows, slice(36, 40))
+    # rstd taken from row m + 16
+    r2 = rstd.clone()
+    r2[rows] = rstd[80:96]
+    z = y.clone()
+    z[rows, cols] = sim_lnfold(acc, r2, shift, colsum, dtype, bias_d=bias_d)[rows, cols]
+    n, _, coords = KC.violations(z, ref, tol)
+    assert n >= 64 and inside(coords, rows, cols)
+    # shift * colsum omitted for one element (row 65: |mean| ~ 9 std, the term the product cancels against)
+    skip = torch.zeros(M, N, dtype=torch.bool)
+    skip[65, 37] = True
+    n, _, coords = KC.violations(sim_lnfold(acc, rstd, shift, colsum, dtype, skip=skip, bias_d=bias_d), ref, tol)
+    assert n == 1 and coords[0][0] == (65, 37)
+    # a truncating store (K = 64)
+    x, wg, colsum, bias_d = KC.lnfold_inputs(129, 160, 64, dtype, 10)
+    rstd, shift = sim_rowstats(x, KC.LN_EPS)
+    ref, tol = KC.gemm_lnfold_bound(x, wg, rstd, shift, colsum, dtype)
+    assert count(sim_lnfold(sim_acc(x, wg), rstd, shift, colsum, dtype), ref, tol) == 0
+    assert count(sim_lnfold(sim_acc(x, wg), rstd, shift, colsum, dtype, trunc=True), ref, tol) > 0.15 * ref.numel()
+
+
+@pytest.mark.parametrize("dtype", DTYPES16, ids=lambda d: KC.NAME[d])
+def test_mutants_statistics(dtype):
+    M, N, K = 257, 640, 192
+    a, w, bias, res = KC.producer_inputs(M, N, K, dtype, 11)
+    y = sim_gemm(a, w, dtype, bias=bias, residual=res)
+    part = sim_rowsums(y, 80)
+    (s1, t1), (s2, t2) = KC.rowsum_bound(y, 80)
+    assert count(part[:, :, 0], s1, t1) == 0 and count(part[:, :, 1], s2, t2) == 0
+    # one stale strip partial (the previous case's)
+    a0, w0, b0, r0 = KC.producer_inputs(M, N, K, dtype, 10)
+    stale = part.clone()
+    stale[100, 3] = sim_rowsums(sim_gemm(a0, w0, dtype, bias=b0, residual=r0), 80)[100, 3]
+    n, _, coords = KC.violations(stale[:, :, 0], s1, t1)
+    assert n == 1 and coords[0][0] == (100, 3) and count(stale[:, :, 1], s2, t2) == 1
+    # ... and what the consumer makes of it
+    (rv, rt), (sv, st) = KC.lnfold_part_stats_bound(part, N, KC.LN_EPS)
+    r2, sh2 = sim_part_stats(stale, N, KC.LN_EPS)
+    assert KC.violations(r2, rv, rt)[2][0][0] == (100,) and count(sh2, sv, st) == 1
+    # a statistics row that misses its last 8 columns: the accumulator form, the strip form, ss_rowstats
+    short = sim_rowsums(y, 8)
+    short[77, -1] = 0.0
+    (a1, ta1), (a2, ta2) = KC.rowsum_bound(y)
+    full = sim_rowsums(y, 8).double().sum(1)
+    assert count(full[:, 0], a1, ta1) == 0 and count(full[:, 1], a2, ta2) == 0
+    sh = short.double().sum(1)
+    assert KC.violations(sh[:, 0], a1, ta1)[2][0][0] == (77,) and count(sh[:, 1], a2, ta2) == 1
+    x = y
+    (rv, rt), (sv, st) = KC.rowstats_bound(x, KC.LN_EPS, dtype)
+    r1, sh1 = sim_rowstats(x, KC.LN_EPS)
+    assert count(r1, rv, rt) == 0 and count(sh1, sv, st) == 0
+    r3, sh3 = sim_rowstats(x[77:78], KC.LN_EPS, cols=N - 8)
+    r1[77], sh1[77] = r3[0], sh3[0]
+    assert count(r1, rv, rt) == 1 and count(sh1, sv, st) == 1
+    # finalize with the wrong width (N + 1): every row's statistics move by 1 / N, far outside the finalize bound
+    yd = y.double()
+    acc = torch.stack([yd.sum(1), (yd * yd).sum(1)], 1)
+    (rv, rt), (sv, st) = KC.rowstat_finalize_bound(acc, N, KC.LN_EPS)
+    assert count(sim_finalize(acc, N, KC.LN_EPS)[0], rv, rt) == 0
+    wrong = sim_finalize(acc, N + 1, KC.LN_EPS)
+    assert count(wrong[0], rv, rt) > 0.9 * M
+
+
+@pytest.mark.parametrize("dtype", DTYPES16, ids=lambda d: KC.NAME[d])
+def test_mutants_splitk(dtype):
+    M, N, K = 257, 128, 1088
+    a, w = KC.gemm_inputs(M, N, K, dtype, 12)
+    kw = KC.epilogue_inputs("bias+residual", M, N, dtype, 12)
+    for S in (2, 8):
+        ref, tol = KC.gemm_splitk_bound(a, w, dtype, S, **kw)
+        assert count(sim_splitk(a, w, dtype, S, **kw), ref, tol) == 0
+        # one slice dropped / added twice (the last non-empty one: 2 of 17 K tiles at S = 8)
+        last = max(i for i, (k0, k1) in enumerate(KC.splitk_ranges(K, S)) if k1 > k0)
+        assert count(sim_splitk(a, w, dtype, S, drop=last, **kw), ref, tol) > 0.8 * ref.numel()
+        assert count(sim_splitk(a, w, dtype, S, twice=last, **kw), ref, tol) > 0.8 * ref.numel()
+        # one K tile dropped in one 16x16 fragment
+        a2 = a.clone()
+        a2[:, 1024:] = 0
+        z = sim_splitk(a, w, dtype, S, **kw)
+        z[64:80, 32:48] = sim_splitk(a2[64:80], w[32:48], dtype, S, bias=kw["bias"][32:48], residual=kw["residual"][64:80, 32:48])
+        n, _, coords = KC.violations(z, ref, tol)
+        assert n >= 128 and inside(coords, slice(64, 80), slice(32, 48))
+        # the counter probe spans every K range: a range taken twice or never changes the integer
+        ca, cw, exp = KC.counter_probe(M, N, K, dtype, seed=S)
+        assert torch.equal(sim_splitk(ca, cw, dtype, S), exp)
+        for i, (k0, k1) in enumerate(KC.splitk_ranges(K, S)):
+            if k1 > k0:
+                assert not torch.equal(sim_splitk(ca, cw, dtype, S, drop=i), exp)
+                assert not torch.equal(sim_splitk(ca, cw, dtype, S, twice=i), exp)

@@ -5,7 +5,8 @@ element the kernel never wrote); inputs are fresh per case and seeded by the til
 store cannot find the previous case's answer in a recycled block.  References are fp64 evaluations of the same formula on the
 same (already rounded) inputs — never another kernel.  The bounds are derived in kernel_check.py's docstring, not tuned here.
 
-Out of scope: the experimental 4-wave tiles, fp8, the gate-mode split GEMM.
+Out of scope: the experimental 4-wave tiles, the gate-mode split GEMM (fp8, the LN-folded, statistics and split-K GEMMs:
+tests/test_gemm_variants_edges_gpu.py).
 
 Worst error / bound per kernel family and dtype, measured on an MI355X against the fp64 reference (test_zz_worst_ratios prints
 this table; a ratio above 1 fails the case that produced it):
