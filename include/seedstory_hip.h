@@ -988,6 +988,21 @@ int ss_euler_scale_dup(const void* x, void* xin, int64_t n, float sigma, int dty
  * EulerDiscreteScheduler.step, epsilon prediction). eps = [uncond; cond], n elements each. */
 int ss_euler_cfg_step(void* x, const void* eps, int64_t n, float guidance, float sigma, float sigma_next,
                       int dtype, void* stream);
+/* One step of a linear multistep sampler with classifier-free guidance, fused with the NEXT step's
+ * scale_model_input + CFG duplication (DPMSolverMultistepScheduler: dpmsolver++, midpoint, order <= 2):
+ *   e = eps[0] + guidance * (eps[1] - eps[0]);  d = x - sigma * e;  x' = a * x + b * d + c * d_prev
+ * state fp32 [2, n]: row 0 = x, row 1 = d_prev; rewritten as (x', d).  The arithmetic is fp32 end to end: the solver
+ * state is never rounded to `dtype` between steps.  eps [2, n] in `dtype` = [uncond; cond].
+ *   x_out [n] | NULL          receives rnd(x')
+ *   xin_next [2, n] | NULL    both rows receive rnd(x' * inv_next)   (inv_next = 1 / sqrt(sigma_next^2 + 1))
+ * c == 0 (first step, first-order step, last step): row 1 of state is NOT read (it may be uninitialised).  (a, b, c) are
+ * the host's (computed in double): DPM++ 2M, first order (s'/s, E, 0), second order (s'/s, E (1 + 1/2r), -E/2r), last step
+ * (0, 1, 0); Euler is (s'/s, 1 - s'/s, 0).  Any n >= 1: 16-byte packets over the first rows (second rows too when n is a
+ * multiple of the packet), single elements for the tail, and for everything when a base pointer is not 16-byte aligned.
+ * SS_EINVAL before anything is launched or written: n <= 0, NULL state or eps, a non-finite guidance / sigma / a / b /
+ * c / inv_next, an unknown dtype. */
+int ss_multistep_cfg_step(float* state, const void* eps, void* x_out, void* xin_next, int64_t n, float guidance,
+                          float sigma, float a, float b, float c, float inv_next, int dtype, void* stream);
 /* Image pre-processing on the device: the reference's `image_transform(image).to(device, dtype)`
  * (src/processer/transforms.py:4-19 = torchvision Resize [+ CenterCrop] on a PIL image, ToTensor, Normalize;
  * gen_george.py:166).  The resize is Pillow's 8-bit separable resampler restated bit-exactly: 22-bit fixed-point

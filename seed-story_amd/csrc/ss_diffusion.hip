@@ -5,6 +5,8 @@
 // channels (ss_gemm.hip) and the transformer blocks need no permutes.
 #include "ss_common.h"
 
+#include <cmath>
+
 namespace ss {
 
 __device__ __forceinline__ float silu_d(float g) { return g / (1.0f + expf(-g)); }
@@ -373,6 +375,97 @@ __global__ void euler_cfg_step_kernel(T* __restrict__ x, const T* __restrict__ e
     }
 }
 
+// Linear multistep sampler step + CFG, fused with the NEXT step's scale_model_input + CFG duplication (DPM-Solver++ 2M; Euler
+// fits the same form).  fp32 end to end, in this operation order (tests/test_dpmpp_gpu.py derives its bound from it):
+//   e = eu + g (ec - eu);  d = x - sigma e;  x' = (a x + b d) [+ c d_prev];  state <- (x', d);  x_out = rnd_T(x');
+//   xin_next[0] = xin_next[1] = rnd_T(x' inv_next)
+// The solver state is fp32 and is never rounded to T between steps (a second-order difference of rounded states is where bf16
+// would hurt).  c == 0: d_prev is not read (first step: uninitialised).
+__device__ __forceinline__ void multistep_one(float& x, float& dprev, float eu, float ec, bool prev, float g, float sigma,
+                                              float a, float b, float c) {
+    const float e = eu + g * (ec - eu);
+    const float d = x - sigma * e;
+    float xn = a * x + b * d;
+    if (prev) xn += c * dprev;
+    x = xn;
+    dprev = d;
+}
+// V fp32 values at p: 16-byte accesses when `vec`, single elements otherwise (second rows of an n that is no multiple of V)
+template <int V>
+__device__ __forceinline__ void ld_f32(const float* p, bool vec, float* f) {
+    if (vec) {
+#pragma unroll
+        for (int k = 0; k < V; k += 4) unpack<float>(ld16(p + k), f + k);
+    } else {
+#pragma unroll
+        for (int j = 0; j < V; ++j) f[j] = p[j];
+    }
+}
+template <int V>
+__device__ __forceinline__ void st_f32(float* p, bool vec, const float* f) {
+    if (vec) {
+#pragma unroll
+        for (int k = 0; k < V; k += 4) st16(p + k, pack<float>(f + k));
+    } else {
+#pragma unroll
+        for (int j = 0; j < V; ++j) p[j] = f[j];
+    }
+}
+// npack packets of V elements (row 0 of every buffer is 16-byte aligned; row 1 only when row1_vec), then n - npack V single elements
+template <typename T>
+__global__ __launch_bounds__(256) void multistep_cfg_step_kernel(float* __restrict__ state, const T* __restrict__ eps,
+                                                                 T* __restrict__ x_out, T* __restrict__ xin_next, int64_t n,
+                                                                 int64_t npack, int row1_vec, float g, float sigma, float a,
+                                                                 float b, float c, float inv_next) {
+    constexpr int V = Tr<T>::kVec;
+    const bool prev = c != 0.0f;
+    const bool v1 = row1_vec != 0;
+    const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t p = tid; p < npack; p += stride) {
+        const int64_t i = p * V;
+        float x[V], dp[V], eu[V], ec[V], xs[V];
+        ld_f32<V>(state + i, true, x);
+        unpack<T>(ld16(eps + i), eu);
+        if (v1) {
+            unpack<T>(ld16(eps + n + i), ec);
+        } else {
+#pragma unroll
+            for (int j = 0; j < V; ++j) ec[j] = Tr<T>::ld(eps + n + i + j);
+        }
+        if (prev) ld_f32<V>(state + n + i, v1, dp);
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            multistep_one(x[j], dp[j], eu[j], ec[j], prev, g, sigma, a, b, c);
+            xs[j] = x[j] * inv_next;
+        }
+        st_f32<V>(state + i, true, x);
+        st_f32<V>(state + n + i, v1, dp);
+        if (x_out) st16(x_out + i, pack<T>(x));
+        if (xin_next) {
+            const uint4 u = pack<T>(xs);
+            st16(xin_next + i, u);
+            if (v1) {
+                st16(xin_next + n + i, u);
+            } else {
+#pragma unroll
+                for (int j = 0; j < V; ++j) Tr<T>::st(xin_next + n + i + j, xs[j]);
+            }
+        }
+    }
+    for (int64_t i = npack * V + tid; i < n; i += stride) {
+        float x = state[i], dp = prev ? state[n + i] : 0.f;
+        multistep_one(x, dp, Tr<T>::ld(eps + i), Tr<T>::ld(eps + n + i), prev, g, sigma, a, b, c);
+        state[i] = x;
+        state[n + i] = dp;
+        if (x_out) Tr<T>::st(x_out + i, x);
+        if (xin_next) {
+            const float v = x * inv_next;
+            Tr<T>::st(xin_next + i, v);
+            Tr<T>::st(xin_next + n + i, v);
+        }
+    }
+}
+
 // VAE output NHWC [B, HW, Cpad] (first 3 channels) -> uint8 HWC: round(clamp(x/2 + 0.5, 0, 1) * 255)
 template <typename T>
 __global__ void image_to_u8_kernel(const T* __restrict__ in, uint8_t* __restrict__ out, int64_t pixels, int Cpad) {
@@ -468,6 +561,18 @@ int euler_cfg_step_launch(void* x, const void* eps, int64_t n, float guidance, f
     return SS_OK;
 }
 template <typename T>
+int multistep_cfg_step_launch(float* state, const void* eps, void* x_out, void* xin_next, int64_t n, float g, float sigma,
+                              float a, float b, float c, float inv_next, hipStream_t s) {
+    constexpr int V = Tr<T>::kVec;
+    const uintptr_t bases = (uintptr_t)state | (uintptr_t)eps | (uintptr_t)x_out | (uintptr_t)xin_next;   // NULL: no bits
+    const int64_t npack = (bases & 15) == 0 ? n / V : 0;
+    const int row1_vec = npack > 0 && n % V == 0;
+    hipLaunchKernelGGL(multistep_cfg_step_kernel<T>, dim3(egrid(npack + (n - npack * V))), dim3(256), 0, s, state,
+                       (const T*)eps, (T*)x_out, (T*)xin_next, n, npack, row1_vec, g, sigma, a, b, c, inv_next);
+    SS_LAUNCH_CHECK("multistep_cfg_step");
+    return SS_OK;
+}
+template <typename T>
 int image_to_u8_launch(const void* in, void* out, int64_t pixels, int64_t Cpad, hipStream_t s) {
     hipLaunchKernelGGL(image_to_u8_kernel<T>, dim3(egrid(pixels * 3)), dim3(256), 0, s, (const T*)in, (uint8_t*)out, pixels,
                        (int)Cpad);
@@ -516,6 +621,19 @@ int ss_euler_scale_dup(const void* x, void* xin, int64_t n, float sigma, int dty
 int ss_euler_cfg_step(void* x, const void* eps, int64_t n, float guidance, float sigma, float sigma_next, int dtype,
                       void* stream) {
     return SS_DISPATCH(dtype, euler_cfg_step_launch, x, eps, n, guidance, sigma, sigma_next, (hipStream_t)stream);
+}
+int ss_multistep_cfg_step(float* state, const void* eps, void* x_out, void* xin_next, int64_t n, float guidance, float sigma,
+                          float a, float b, float c, float inv_next, int dtype, void* stream) {
+    SS_REQUIRE(n > 0, "multistep_cfg_step: n = %lld", (long long)n);
+    SS_REQUIRE(state != nullptr && eps != nullptr, "multistep_cfg_step: NULL state or eps");
+    SS_REQUIRE(std::isfinite(guidance) && std::isfinite(sigma) && std::isfinite(a) && std::isfinite(b) && std::isfinite(c) &&
+                   std::isfinite(inv_next),
+               "multistep_cfg_step: non-finite coefficient (guidance %g sigma %g a %g b %g c %g inv_next %g)", (double)guidance,
+               (double)sigma, (double)a, (double)b, (double)c, (double)inv_next);
+    SS_REQUIRE((uintptr_t)state % sizeof(float) == 0 && (dtype == SS_F32 || dtype == SS_BF16 || dtype == SS_F16),
+               "multistep_cfg_step: unknown dtype %d or misaligned state", dtype);
+    return SS_DISPATCH(dtype, multistep_cfg_step_launch, state, eps, x_out, xin_next, n, guidance, sigma, a, b, c, inv_next,
+                       (hipStream_t)stream);
 }
 int ss_image_to_u8(const void* in, void* out_u8, int64_t pixels, int64_t cpad, int dtype, void* stream) {
     return SS_DISPATCH(dtype, image_to_u8_launch, in, out_u8, pixels, cpad, (hipStream_t)stream);

@@ -60,7 +60,8 @@
     X(llama_decode_w8, 0, "LlamaEngine default of decode_weights: 1 = fp8 (e4m3) weight-only decode projections")                \
     X(llama_decode_mx4, 0, "LlamaEngine default of decode_weights: 1 = MXFP4 weight-only decode projections (not with llama_decode_w8)") \
     X(llama_kv8, 0, "LlamaEngine default of kv_cache: 1 = decode attention reads an fp8 (e4m3) shadow of the KV cache")                  \
-    X(llama_spec_rows, 0, "LlamaEngine default of speculate: rows (2..8) of a prompt-lookup speculative step of generate; 0 = off")
+    X(llama_spec_rows, 0, "LlamaEngine default of speculate: rows (2..8) of a prompt-lookup speculative step of generate; 0 = off") \
+    X(sdxl_solver, 0, "SDXL render sampler: 0 = the scheduler object as given, 2 = DPM-Solver++ 2M, 3 = DPM-Solver++ 2M on Karras sigmas")
 
 namespace ss {
 
@@ -79,7 +80,7 @@ inline constexpr KnobInfo kKnobs[] = {
     SS_KNOB_LIST(X)
 #undef X
 };
-static_assert(sizeof(kKnobs) / sizeof(kKnobs[0]) == K_COUNT && K_COUNT == 46, "knob list and enum out of step");
+static_assert(sizeof(kKnobs) / sizeof(kKnobs[0]) == K_COUNT && K_COUNT == 47, "knob list and enum out of step");
 
 extern std::atomic<int> g_knobs[K_COUNT];   // ss_runtime.hip, constant-initialised from the defaults
 

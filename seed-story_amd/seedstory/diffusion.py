@@ -13,6 +13,9 @@ diffusers itself is absent from this image.  The modules keep the diffusers para
 3x3 convolutions are implicit GEMMs on the matrix cores (``ss_conv3x3``: fused bias / time-embedding /
 residual / nearest-2x upsample), GroupNorm+SiLU, fused-QKV flash attention, GEGLU, and the Euler/CFG
 update are hand-written kernels.  No torch compute on the device, no CPU path.
+
+Besides the reference's Euler sampler: ``DPMSolverMultistepScheduler`` (DPM-Solver++ 2M, optionally on Karras sigmas), the
+one-line swap diffusers users make to render in 15 - 20 steps instead of 30; an option, the default is what the caller builds.
 """
 import json
 import math
@@ -741,6 +744,105 @@ class EulerDiscreteScheduler:
         self.init_noise_sigma = mx if self.timestep_spacing in ("linspace", "trailing") else float((mx ** 2 + 1) ** 0.5)
 
 
+class DPMSolverMultistepScheduler:
+    """DPM-Solver++ 2M ("DPM++ 2M", with ``use_karras_sigmas`` "DPM++ 2M Karras"): diffusers' DPMSolverMultistepScheduler for
+    algorithm_type "dpmsolver++", solver_type "midpoint", solver_order 1 | 2, epsilon prediction, final_sigmas_type "zero" —
+    k-diffusion's ``sample_dpmpp_2m`` (definition: tests/dpmpp_ref.py; derivation: DESIGN §6.0j).  Parity against diffusers
+    itself is UNPINNED (diffusers is not installed here): the mathematics is pinned by an exact solution instead.
+
+    The base timesteps and sigmas are EulerDiscreteScheduler's (an instance of it is the base: same betas, same spacing).
+    ``set_timesteps(n)`` fills ``timesteps``, ``sigmas`` [n + 1] (final 0), ``init_noise_sigma`` = sqrt(sigma_0^2 + 1) and
+    ``coefficients`` [n, 3]: step i is x <- a x + b d + c d_prev with d = x - sigma_i eps, computed here in double."""
+
+    _BASE_KEYS = ("num_train_timesteps", "beta_start", "beta_end", "beta_schedule", "timestep_spacing", "steps_offset",
+                  "prediction_type")
+    # keys of diffusers' config that select something this class does not implement: accepted only at the value that means "off"
+    _OFF = {"trained_betas": None, "thresholding": False, "euler_at_final": False, "use_lu_lambdas": False,
+            "use_exponential_sigmas": False, "use_beta_sigmas": False, "use_flow_sigmas": False, "variance_type": None,
+            "rescale_betas_zero_snr": False, "lambda_min_clipped": -float("inf")}
+    _UNUSED = ("dynamic_thresholding_ratio", "sample_max_value", "flow_shift")     # read only by the options above
+
+    def __init__(self, algorithm_type="dpmsolver++", solver_order=2, solver_type="midpoint", use_karras_sigmas=False,
+                 lower_order_final=True, final_sigmas_type="zero", **kw):
+        for key, value, allowed in (("algorithm_type", algorithm_type, ("dpmsolver++",)), ("solver_order", solver_order, (1, 2)),
+                                    ("solver_type", solver_type, ("midpoint",)), ("final_sigmas_type", final_sigmas_type, ("zero",)),
+                                    ("prediction_type", kw.get("prediction_type", "epsilon"), ("epsilon",)),
+                                    ("beta_schedule", kw.get("beta_schedule", "scaled_linear"), ("scaled_linear",)),
+                                    ("timestep_spacing", kw.get("timestep_spacing", "leading"), ("leading", "linspace", "trailing"))):
+            if value not in allowed or isinstance(value, bool):
+                raise ValueError("DPMSolverMultistepScheduler: %s=%r is not supported (supported: %s)"
+                                 % (key, value, ", ".join(repr(a) for a in allowed)))
+        base = {}
+        for key, value in kw.items():
+            if key in self._BASE_KEYS:
+                base[key] = value
+            elif key in self._OFF:
+                if value != self._OFF[key]:
+                    raise ValueError("DPMSolverMultistepScheduler: %s=%r is not supported (only %r)" % (key, value, self._OFF[key]))
+            elif key not in self._UNUSED:
+                raise ValueError("DPMSolverMultistepScheduler: unknown config key %r" % key)
+        # lower_order_final needs no code: with a final sigma of 0 the last step is x <- d, first order, whatever it says
+        self.solver_order, self.use_karras_sigmas = int(solver_order), bool(use_karras_sigmas)
+        self._base = EulerDiscreteScheduler(**base)
+        self.timesteps = self.sigmas = self.coefficients = self.init_noise_sigma = None
+
+    @classmethod
+    def from_pretrained(cls, path, subfolder=None, **kw):
+        folder = os.path.join(path, subfolder) if subfolder else path
+        with open(os.path.join(folder, "scheduler_config.json")) as f:
+            jc = json.load(f)
+        cfg = {k: v for k, v in jc.items() if not k.startswith("_")}
+        cfg.update(kw)
+        return cls(**cfg)
+
+    @classmethod
+    def from_base(cls, scheduler, use_karras_sigmas=False, solver_order=2):
+        """The sampler over the betas and spacing of an existing scheduler object (Euler, or this class)."""
+        import copy
+        m = cls(use_karras_sigmas=use_karras_sigmas, solver_order=solver_order)
+        m._base = copy.copy(scheduler._base if isinstance(scheduler, cls) else scheduler)
+        return m
+
+    @staticmethod
+    def _sigma_to_t(sigmas, table):
+        """log-sigma interpolation into the training table, rounded to the nearest integer, clipped to the table."""
+        logt = np.log(table.astype(np.float64))
+        ls = np.log(np.maximum(sigmas, 1e-10))
+        low = np.clip(np.searchsorted(logt, ls, side="right") - 1, 0, len(logt) - 2)
+        w = np.clip((logt[low] - ls) / (logt[low] - logt[low + 1]), 0.0, 1.0)
+        return np.clip(np.round((1.0 - w) * low + w * (low + 1)), 0, len(table) - 1).astype(np.float32)
+
+    def set_timesteps(self, n):
+        self._base.set_timesteps(n)
+        s = self._base.sigmas[:n].astype(np.float64)
+        ts = self._base.timesteps
+        if self.use_karras_sigmas:
+            rho = 7.0
+            if n > 1:
+                lo, hi = float(s[n - 1]) ** (1.0 / rho), float(s[0]) ** (1.0 / rho)
+                s = (hi + np.arange(n, dtype=np.float64) / (n - 1) * (lo - hi)) ** rho
+            ts = self._sigma_to_t(s, self._base._sigmas_all)
+        self.sigmas = np.concatenate([s, [0.0]])
+        self.timesteps = ts
+        self.init_noise_sigma = float((float(s[0]) ** 2 + 1.0) ** 0.5)
+        coef = np.zeros((n, 3), dtype=np.float64)
+        h_prev = None
+        for i in range(n):
+            si, sn = float(self.sigmas[i]), float(self.sigmas[i + 1])
+            if sn == 0.0:
+                coef[i] = (0.0, 1.0, 0.0)
+                continue
+            h = math.log(si) - math.log(sn)
+            E = -math.expm1(-h)
+            if i == 0 or self.solver_order == 1:
+                coef[i] = (sn / si, E, 0.0)
+            else:
+                r = h_prev / h
+                coef[i] = (sn / si, E * (1.0 + 1.0 / (2.0 * r)), -E / (2.0 * r))
+            h_prev = h
+        self.coefficients = coef
+
+
 class _PipeOut:
     def __init__(self, images):
         self.images = images
@@ -814,6 +916,12 @@ class StableDiffusionXLPipeline:
         lh, lw = height // 8, width // 8
         B = prompt_embeds.shape[0]           # images rendered together (UNet batch 2B: [B uncond; B cond])
         self.unet._ctx_key = None            # new conditioning: recompute the cached cross-attention K/V
+        sampler = self._sampler()
+        if isinstance(sampler, DPMSolverMultistepScheduler):
+            x = self._denoise_multistep(sampler, prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds,
+                                        negative_pooled_prompt_embeds, guidance_scale, num_inference_steps, generator, height,
+                                        width, latents)
+            return self._finish(x, output_type)
         self.scheduler.set_timesteps(num_inference_steps)
         sig, ts = self.scheduler.sigmas, self.scheduler.timesteps
         if latents is None:
@@ -844,6 +952,71 @@ class StableDiffusionXLPipeline:
                     graph["g"].replay()
                     eps = graph["eps"]
             ops.euler_cfg_step_(x, eps.contiguous(), guidance_scale, float(sig[i]), float(sig[i + 1]))
+        return self._finish(x, output_type)
+
+    def _sampler(self):
+        """The scheduler object as given, or (knob ``sdxl_solver`` 2 | 3) DPM-Solver++ 2M | 2M on Karras sigmas over the given
+        object's own betas and spacing."""
+        mode = _lib.get_tuning("sdxl_solver", 0)
+        if mode == 0:
+            return self.scheduler
+        if mode not in (2, 3):
+            raise _lib.SSError("sdxl_solver=%d: 0 (the scheduler as given), 2 (DPM++ 2M) or 3 (DPM++ 2M Karras)" % mode)
+        src, smode, obj = self.__dict__.get("_sampler_cache", (None, 0, None))
+        if src is not self.scheduler or smode != mode:
+            obj = DPMSolverMultistepScheduler.from_base(self.scheduler, use_karras_sigmas=mode == 3)
+            self._sampler_cache = (self.scheduler, mode, obj)
+        return obj
+
+    def _denoise_multistep(self, sched, prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds,
+                           negative_pooled_prompt_embeds, guidance_scale, num_inference_steps, generator, height, width, latents):
+        """The denoising loop of DPMSolverMultistepScheduler: ONE point-wise launch per step (``ss_multistep_cfg_step``: CFG +
+        solver update of the fp32 state + the next step's scaled, duplicated UNet input) where the Euler loop has two and a
+        copy; the kernel writes that input straight into the buffer the next forward reads (the captured graph's ``x``).  Step 0
+        runs eagerly, steps >= 1 replay the captured forward, as in the Euler loop."""
+        dev, dt = prompt_embeds.device, prompt_embeds.dtype
+        lh, lw = height // 8, width // 8
+        B = prompt_embeds.shape[0]
+        sched.set_timesteps(num_inference_steps)
+        sig, ts, coef = sched.sigmas, sched.timesteps, sched.coefficients
+        if latents is None:
+            latents = torch.randn((B, 4, lh, lw), generator=generator, device=dev, dtype=dt)
+        assert latents.shape[0] == B
+        x = (latents.to(device=dev, dtype=dt) * sched.init_noise_sigma).contiguous()
+        n = x.numel()
+        bufs = self.__dict__.setdefault("_ms_state", {})
+        state = bufs.get((n, str(dev)))      # the fp32 solver state (x, d_prev) keeps its address from render to render
+        if state is None:
+            state = bufs[(n, str(dev))] = torch.empty(2, n, dtype=torch.float32, device=dev)
+        state[0].copy_(x.view(-1))
+        x_out = torch.empty_like(x)
+        time_ids = torch.tensor([[height, width, 0, 0, height, width]] * (2 * B), dtype=torch.float32)
+        ctx = self._stable("ctx", torch.cat([negative_prompt_embeds, prompt_embeds], dim=0))
+        pooled = self._stable("pooled", torch.cat([negative_pooled_prompt_embeds, pooled_prompt_embeds], dim=0))
+        cond = {"text_embeds": pooled, "time_ids": time_ids}
+        use_graph = _lib.get_tuning("unet_graph", 1) != 0 and num_inference_steps > 2
+        graph = None
+        xin = ops.euler_scale_dup(x, float(sig[0])).view(2 * B, 4, lh, lw)        # step 0's input; later ones come from the kernel
+        for i in range(num_inference_steps):
+            if i == 0 or graph is None:
+                eps = self.unet(xin, float(ts[i]), ctx, added_cond_kwargs=cond, return_dict=False)[0]
+                if i == 0 and use_graph:
+                    # captured (or found) right after the eager step 0 — which refreshed the cross-attention K/V and let the
+                    # GEMM autotuner see the shapes — so that step 0's update already writes into the graph's input buffer
+                    graph = self._unet_graph(xin, ctx, cond, ts, num_inference_steps)
+            else:
+                graph["temb"].copy_(graph["temb_table"][i])
+                graph["g"].replay()
+                eps = graph["eps"]
+            last = i + 1 == num_inference_steps
+            nxt = None if last else (graph["x"] if graph is not None else xin)
+            a, b, c = (float(v) for v in coef[i])
+            ops.multistep_cfg_step_(state, eps.contiguous(), guidance_scale, float(sig[i]), a, b, c,
+                                    1.0 / math.sqrt(float(sig[i + 1]) ** 2 + 1.0), x_out=x_out if last else None, xin_next=nxt)
+        return x_out
+
+    def _finish(self, x, output_type):
+        B = x.shape[0]
         if output_type == "latent":
             return _PipeOut(x)
         # latents / scaling_factor is folded into the 1x1 post_quant_conv weights (linear, exact in fp32)

@@ -830,6 +830,24 @@ def euler_cfg_step_(x, eps, guidance, sigma, sigma_next):
     return x
 
 
+def multistep_cfg_step_(state, eps, guidance, sigma, a, b, c, inv_next, x_out=None, xin_next=None):
+    """One sampler step on the fp32 state [2, n] = (x, d_prev) from eps [2, ...] = [uncond; cond] (``ss_multistep_cfg_step``):
+    x' = a x + b d + c d_prev with d = x - sigma (eu + g (ec - eu)); state <- (x', d).  ``x_out`` (n elements of eps's dtype)
+    receives x', ``xin_next`` (2 n elements) the next step's scaled, CFG-duplicated UNet input x' * inv_next."""
+    _req(state, "state"); _req(eps, "eps")
+    n = eps.numel() // 2
+    if state.dtype != torch.float32 or state.numel() != 2 * n or eps.numel() != 2 * n:
+        raise _lib.SSError("multistep_cfg_step: state must be fp32 [2, n] for eps [2, n]")
+    for t, name, cnt in ((x_out, "x_out", n), (xin_next, "xin_next", 2 * n)):
+        if t is not None:
+            _req(t, name)
+            if t.dtype != eps.dtype or t.numel() != cnt or t.device != eps.device:
+                raise _lib.SSError("multistep_cfg_step: %s must hold %d %s elements on %s" % (name, cnt, eps.dtype, eps.device))
+    check(lib().ss_multistep_cfg_step(p(state), p(eps), p(x_out), p(xin_next), n, float(guidance), float(sigma), float(a),
+                                      float(b), float(c), float(inv_next), dt(eps), stream()), "ss_multistep_cfg_step")
+    return state
+
+
 def image_to_u8(x, pixels):
     _req(x)
     out = torch.empty(pixels, 3, dtype=torch.uint8, device=x.device)

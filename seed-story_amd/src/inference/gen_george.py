@@ -92,8 +92,8 @@ def build(args, device, dtype):
         vit = I.instantiate(I.load(os.path.join(CFG, "visual_tokenizer/qwen_vitg_448.yaml"))).eval().to(device, dtype=dtype)
         llm = I.instantiate(I.load(os.path.join(CFG, "clm_models/llama2chat7b_lora.yaml")), torch_dtype=args.dtype)
         agent = I.instantiate(I.load(os.path.join(CFG, "clm_models/agent_7b_sft.yaml")), llm=llm).eval().to(device, dtype=dtype)
-        from seedstory.diffusion import AutoencoderKL, EulerDiscreteScheduler, UNet2DConditionModel
-        sched = EulerDiscreteScheduler.from_pretrained(args.sdxl, subfolder="scheduler")
+        from seedstory.diffusion import AutoencoderKL, UNet2DConditionModel
+        sched = make_scheduler(args, args.sdxl)
         vae = AutoencoderKL.from_pretrained(args.sdxl, subfolder="vae").to(device, dtype=dtype)
         unet = UNet2DConditionModel.from_pretrained(args.sdxl, subfolder="unet").to(device, dtype=dtype)
         adapter = I.instantiate(I.load(os.path.join(CFG, "detokenizer/detokenizer_sdxl_qwen_vit_adapted.yaml")), unet=unet)
@@ -103,7 +103,7 @@ def build(args, device, dtype):
                           dtype=dtype, device=device)
         return tokenizer, transform, vit, agent, adapter
     # ---- synthetic weights (no checkpoints on this box) -------------------------------------------------
-    from seedstory.diffusion import AutoencoderKL, EulerDiscreteScheduler, UNet2DConditionModel
+    from seedstory.diffusion import AutoencoderKL, UNet2DConditionModel
     from src.models.discrete_models import DiscreteModleIdentity
     from src.models.qwen_visual import Resampler, VisionTransformerWithAttnPool
     from src.models_clm.modeling_llama_xformer import LlamaConfig, LlamaForCausalLM
@@ -144,7 +144,7 @@ def build(args, device, dtype):
                         output2_dim=1280, ff_mult=4)).to(device, dtype=dtype).init_synthetic(6)
     adapter = SDXLAdapter.from_pretrained(unet=unet, resampler=rs).eval()
     size = 224 if t else 448
-    adapter.init_pipe(vae=vae, scheduler=EulerDiscreteScheduler(), visual_encoder=vit,
+    adapter.init_pipe(vae=vae, scheduler=make_scheduler(args), visual_encoder=vit,
                       image_transform=get_transform('clip', image_size=size, keep_ratio=False),
                       discrete_model=DiscreteModleIdentity(), dtype=dtype, device=device)
     return tokenizer, adapter.image_transform, vit, agent, adapter
@@ -187,6 +187,29 @@ def add_beams_arguments(ap):
                     help="beam search with N (at most 8) beams over every step's free tokens, on the device; deterministic; not with "
                          "--sample, --best-of or --synthetic (whose captions are forced); prints each step's hypothesis scores")
     ap.add_argument("--length-penalty", type=float, default=1.0, help="with --beams: a hypothesis scores sum / length ** P")
+
+
+SCHEDULERS = ("euler", "dpmpp2m", "dpmpp2m-karras")
+
+
+def add_scheduler_argument(ap):
+    """``--scheduler`` (shared with vis_george_sink.py)"""
+    ap.add_argument("--scheduler", default="euler", choices=SCHEDULERS,
+                    help="SDXL sampler: euler (the reference's), dpmpp2m = DPM-Solver++ 2M, dpmpp2m-karras = the same on Karras "
+                         "sigmas (second order: 15 - 20 --diffusion-steps instead of 30; end quality on real weights unverified)")
+
+
+def make_scheduler(args, path=None):
+    """The scheduler object ``--scheduler`` names, from the checkpoint's scheduler_config.json when ``path`` is given."""
+    from seedstory.diffusion import DPMSolverMultistepScheduler, EulerDiscreteScheduler
+    name = getattr(args, "scheduler", "euler") or "euler"
+    if name not in SCHEDULERS:
+        raise SystemExit("--scheduler must be one of %s" % ", ".join(SCHEDULERS))
+    euler = EulerDiscreteScheduler.from_pretrained(path, subfolder="scheduler") if path else EulerDiscreteScheduler()
+    if name == "euler":
+        return euler
+    # over the checkpoint's own betas and spacing (its Euler config carries keys the multistep class has no use for)
+    return DPMSolverMultistepScheduler.from_base(euler, use_karras_sigmas=name == "dpmpp2m-karras")
 
 
 def add_speculate_argument(ap):
@@ -372,6 +395,7 @@ def main():
     add_speculate_argument(ap)
     add_logprobs_argument(ap)
     add_rules_arguments(ap)
+    add_scheduler_argument(ap)
     args = ap.parse_args()
     device = "cuda:0"
     dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float16

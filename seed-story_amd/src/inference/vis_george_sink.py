@@ -21,7 +21,7 @@ import torch
 
 from seedstory.story import StoryContext
 from src.inference.gen_george import (BOI_TOKEN, EOI_TOKEN, IMG_TOKEN, add_beams_arguments, add_best_of_argument, add_logprobs_argument,
-                                      add_speculate_argument, speculate_kwargs,
+                                      add_scheduler_argument, add_speculate_argument, speculate_kwargs,
                                       add_rules_arguments, apply_beams, apply_best_of, beams_kwargs, build, logprobs_kwargs, report_beams,
                                       report_candidates, report_caption_logprobs, rules_kwargs, sample_kwargs)
 
@@ -116,6 +116,7 @@ def main():
     add_best_of_argument(ap)
     add_beams_arguments(ap)
     add_speculate_argument(ap)
+    add_scheduler_argument(ap)
     ap.add_argument("--temperature", type=float, default=0.7, help="with --best-of")
     ap.add_argument("--top-k", type=int, default=0, help="with --best-of; 0 = off")
     ap.add_argument("--top-p", type=float, default=0.5, help="with --best-of")
