@@ -13,10 +13,11 @@
 //     statistic redundantly from its registers: cheaper than a kernel boundary);
 //   * epilogues: +bias, +residual (in T, like `residual + hidden`, :352,:359),
 //     SiLU(gate)·up for the fused [gate; up] projection (LlamaMLP.forward, :190-191).
-// fp8 (OCP e4m3fn) weight-only variant (ss_gemv_w8, the opt-in decode_weights="fp8" of the LLaMA engine): the MFMA family below
-// over byte planes + one fp32 scale per row, codes converted to the 16-bit type in registers — see "fp8 weight forms".
-// MXFP4 weight-only variant (ss_gemv_mx4, decode_weights="mxfp4"): the same family over e2m1 code planes (two codes per byte) + one
-// e8m0 scale byte per 32 k, decoded and scaled by one conversion instruction per two codes — see "MXFP4 weight forms".
+// Weight-only quantised variants (opt-in decode_weights of the LLaMA engine): ss_gemv_w8 over fp8 (OCP e4m3fn) byte planes + one fp32
+// scale per row, ss_gemv_mx4 over MXFP4 planes (e2m1 codes, two per byte, + one e8m0 scale byte per 32 k).  Both run the MFMA family
+// below: ONE predicated tile loop serves 16-bit, fp8 and MXFP4 weights through a small policy type per format (how a 16-byte load
+// slot is addressed, loaded and decoded into the 16-bit MFMA operand — "the weight formats of the MFMA forms"); the stream loops
+// of the LLaMA-7B depths are one kernel per format.
 // Reference call sites: modeling_llama_xformer.py:228-230 (q/k/v), :297 (o), :191 (MLP),
 // :759 (lm_head); LlamaRMSNorm :107-115 for the prologue.
 #include "ss_gemv.h"
@@ -371,6 +372,8 @@ __global__ __launch_bounds__(1024) void gemv_ldsx_kernel(const GemvArgs a) {
 //     and across the barrier: 8 - 16 KB per wave stay in flight the whole launch;
 //   * per tile the 8 partial accumulators meet in LDS (double-buffered: one barrier per tile) and wave 0 applies the
 //     epilogue (gv_epilogue: bias, rounding, residual | gv_silu_pair with the [gate; up] rows as two MFMA chains).
+// (Written for 16-bit weights, one MFMA step per 16-byte load; fp8 and MXFP4 weights have 2 / 4 steps per load and take every
+// sequence count from 1.)
 template <int N, typename F, int... I>
 __device__ __forceinline__ void gv_static_for_impl(F&& f, std::integer_sequence<int, I...>) {
     (f(std::integral_constant<int, I>{}), ...);
@@ -461,7 +464,7 @@ __device__ __forceinline__ void gv_tile_store(const GemvArgs& a, const f32x4_t (
     }
     gv_store4<T>(a, i, row0, o);
 }
-// (`post` sees the folded sums before the epilogue: the fp8-weight forms apply their row scales there)
+// (`post`, the weight format's hook, sees the folded sums before the epilogue: fp8 weights apply their row scales there)
 template <typename T, bool SILU, typename P>
 __device__ __forceinline__ void gv_fold_store(const GemvArgs& a, float* part, const f32x4_t (&acc)[SILU ? 2 : 1], int tile,
                                               int wave, int lane, const GvEpi& epi, P&& post) {
@@ -492,67 +495,113 @@ __device__ __forceinline__ float gv_rstd_across_waves(float ssq, float (*red)[16
     return gv_rstd(tot, K, eps);
 }
 
-// any K <= 4096 (multiple of 8), any N: predicated loads — correct for every shape, with the prefetch serialised by the
-// predicates' branches (the tiny test models and odd widths; the LLaMA-7B depths take gemv_mfma_exact_kernel below)
-template <typename T, bool SILU>
-__global__ __launch_bounds__(512) void gemv_mfma_kernel(const GemvArgs a, const int spw, const int ntiles) {
-    constexpr int NS = kGvSteps, CH = kGvChunk, M = SILU ? 2 : 1;
+// ---- the weight formats of the MFMA forms: what differs between 16-bit, fp8 and MXFP4 weights ---------------------------------------
+// A lane's 16-byte weight load (a SLOT) feeds SPS MFMA steps of 8 k each: 1 (16-bit), 2 (fp8), 4 (MXFP4), so a format's K comes in
+// multiples of 8 SPS, one slot of the 4 lane groups q = lane >> 4 covers 32 SPS consecutive k, and a row's slots lie 64 bytes
+// apart.  A policy (used by the predicated tile loop below) finds a row at the lane's first k, loads slot L of it, turns step h of
+// a slot into the A operand of gv_mfma<T>, and may hand the folded sums to a hook in front of the shared epilogue.  Step s of a
+// lane = step s % SPS of slot s / SPS sees k = kb + 32 SPS (s / SPS) + 8 (s % SPS): the activation fragments follow from that.
+struct GvNoPost { template <int M> __device__ __forceinline__ void operator()(f32x4_t (&)[M]) const {} };
+template <int SPS_>
+struct GvFmtBase {
+    static constexpr int SPS = SPS_;
+    static __device__ __forceinline__ uint4 zero() { return make_uint4(0, 0, 0, 0); }           // a slot of +0 codes
+    template <int M> __device__ __forceinline__ GvNoPost post(int, int) const { return {}; }
+};
+
+// 16-bit weights [N, K]: a slot IS the operand (lane l: row l & 15, k-chunk l >> 4 of the step's 32 k)
+template <typename T>
+struct GvW16 : GvFmtBase<1> {
+    using Slot = uint4;
+    using Row = const T*;
+    const T* __restrict__ W;
+    int K;
+    __device__ __forceinline__ GvW16(const GemvArgs& a) : W((const T*)a.W), K(a.K) {}
+    __device__ __forceinline__ Row row(int64_t r, int kb) const { return W + r * K + kb; }
+    template <int L> __device__ __forceinline__ Slot load(Row p) const { return ld16(p + L * 32); }
+    template <int h> __device__ __forceinline__ uint4 operand(const Slot& w) const { return w; }
+};
+
+// ---- the predicated form: any K <= 4096 (a multiple of 8 SPS), any N -------------------------------------------------------------
+// lpw <= 16 / SPS load slots per wave; loads predicated on the slots of this lane that lie inside K — correct for every shape, with
+// the prefetch serialised by the predicates' branches (the tiny test models and odd widths; the LLaMA-7B depths take the stream
+// loops below)
+template <typename T, bool SILU, typename Fmt>
+__device__ __forceinline__ void gv_mfma_tile_loop(const GemvArgs& a, Fmt fmt, const int lpw, const int ntiles) {
+    constexpr int NS = kGvSteps, SPS = Fmt::SPS, NL = NS / SPS, M = SILU ? 2 : 1;
     __shared__ __attribute__((aligned(16))) float part[2][kGvWaves][M][256];
     __shared__ float red[kGvWaves][16];
     if (gemv_all_done(a)) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int i = lane & 15, q = lane >> 4;
     const int K = a.K, N = a.N, nb = a.nb;
-    const T* __restrict__ W = (const T*)a.W;
-    const int k0 = wave * spw * 32 + q * 8;                         // this lane's k at the wave's step 0
-    int nvalid = k0 < K ? (K - k0 + 31) / 32 : 0;                   // steps of this lane that lie inside K
-    if (nvalid > spw) nvalid = spw;
+    const int kb = wave * lpw * 32 * SPS + q * 8 * SPS;                 // this lane's k at its wave's slot 0
+    int nvalid = kb < K ? (K - kb + 32 * SPS - 1) / (32 * SPS) : 0;     // slots of this lane that lie inside K (whole or not at all)
+    if (nvalid > lpw) nvalid = lpw;
+    auto koff = [&](int s) { return kb + (s / SPS) * 32 * SPS + (s % SPS) * 8; };                        // k of MFMA step s of this lane
 
     // ---- the wave's slice of the activations, in B-operand order (+ fused RMSNorm) -----------------------------------
     // (lanes of sequences >= nb read sequence 0: their columns of D are never stored)
     uint4 xf[NS];
     {
-        const T* xr = (const T*)a.x + (int64_t)(i < nb ? i : 0) * a.x_ld + k0;
+        const T* xr = (const T*)a.x + (int64_t)(i < nb ? i : 0) * a.x_ld;
         gv_static_for<NS>([&](auto s_) {
             constexpr int s = decltype(s_)::value;
-            xf[s] = s < nvalid ? ld16(xr + s * 32) : make_uint4(0, 0, 0, 0);
+            xf[s] = s / SPS < nvalid ? ld16(xr + koff(s)) : make_uint4(0, 0, 0, 0);
         });
         if (a.norm_w) {
             float ssq = 0.f;
             gv_static_for<NS>([&](auto s_) { ssq = gv_pack_ssq<T>(xf[decltype(s_)::value], ssq); });
             const float rstd = gv_rstd_across_waves(ssq, red, wave, lane, K, a.eps);
-            const T* gw = (const T*)a.norm_w + k0;
             gv_static_for<NS>([&](auto s_) {
                 constexpr int s = decltype(s_)::value;
-                if (s < nvalid) xf[s] = gv_pack_norm<T>(xf[s], ld16(gw + s * 32), rstd);
+                if (s / SPS < nvalid) xf[s] = gv_pack_norm<T>(xf[s], ld16((const T*)a.norm_w + koff(s)), rstd);
             });
         }
     }
-    uint4 wa[M][NS];
+    typename Fmt::Slot wa[M][NL];
     int it = 0;
     for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x, ++it) {
         int row = tile * 16 + i;
         if (row >= N) row = N - 1;
+        const auto post = fmt.template post<M>(tile, lane);
         f32x4_t acc[M];
 #pragma unroll
         for (int m = 0; m < M; ++m) {
             acc[m] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-            const T* p = W + ((int64_t)row + (int64_t)m * N) * K + k0;
-            gv_static_for<NS>([&](auto s_) {
+            const typename Fmt::Row p = fmt.row((int64_t)row + (int64_t)m * N, kb);
+            gv_static_for<NL>([&](auto s_) {
                 constexpr int s = decltype(s_)::value;
-                wa[m][s] = s < nvalid ? ld16(p + s * 32) : make_uint4(0, 0, 0, 0);
+                wa[m][s] = s < nvalid ? fmt.template load<s>(p) : Fmt::zero();
             });
         }
-        gv_static_for<NS>([&](auto s_) {
+        gv_static_for<NL>([&](auto s_) {
             constexpr int s = decltype(s_)::value;
 #pragma unroll
-            for (int m = 0; m < M; ++m) acc[m] = gv_mfma<T>(wa[m][s], xf[s], acc[m]);
+            for (int m = 0; m < M; ++m)
+                gv_static_for<SPS>([&](auto h_) {
+                    constexpr int h = decltype(h_)::value;
+                    acc[m] = gv_mfma<T>(fmt.template operand<h>(wa[m][s]), xf[SPS * s + h], acc[m]);
+                });
         });
         GvEpi epi;
         epi.vec = false;
-        gv_fold_store<T, SILU>(a, &part[it & 1][0][0][0], acc, tile, wave, lane, epi);
+        gv_fold_store<T, SILU>(a, &part[it & 1][0][0][0], acc, tile, wave, lane, epi, post);
     }
 }
+template <typename T, bool SILU>
+__global__ __launch_bounds__(512) void gemv_mfma_kernel(const GemvArgs a, const int spw, const int ntiles) {
+    gv_mfma_tile_loop<T, SILU>(a, GvW16<T>(a), spw, ntiles);
+}
+
+// ---- the stream loops: one kernel per weight format ----------------------------------------------------------------------------------
+// The three kernels below are one algorithm too (two register buffers walked in chunks, the next tile's chunk 0 requested behind
+// the last chunk, the nb <= 8 packing of the 11008-deep slice, vec_ok, the tile body), and differ in the points the format
+// policies name plus how an odd slice is made to fit without a predicate (fp8's 8-byte tail load, MXFP4's dead eleventh slot).  They stay
+// apart on purpose: one shared body over the policies was written and gave bit-identical results, but these launches are the decode
+// token, and where a wave waits for its kernel arguments and in which order the compiler issues a slot's loads moved their times
+// by 0.3 - 0.8 us per launch (profiles/gemv_formats_bench.json); two such effects were found and repaired, a third (the 16-bit
+// SiLU pair, 1 %) was not.  A change of schedule here is made in all three.
 
 // ---- the predicate-free stream loop for the two LLaMA-7B depths ---------------------------------------------------------------
 // K == 8 waves x SPW steps x 32 exactly (SPW = 16: K = 4096, hidden; SPW = 43: K = 11008, the MLP width): every load of
@@ -717,7 +766,14 @@ template <> __device__ __forceinline__ uint4 gv_dec8<f16_t>(uint32_t lo, uint32_
 
 // the row scales of wave 0's four output rows (lane l: rows 4 (l >> 4) + r of the tile), requested at the top of the tile like
 // gv_epi_prefetch and for the same reason.  vec (kernel-uniform): N % 4 == 0 and a 16-byte aligned scale vector -> one load.
-template <int M> struct GvScale { f32x4_t s[M]; };
+template <int M>
+struct GvScale {
+    f32x4_t s[M];
+    __device__ __forceinline__ void operator()(f32x4_t (&v)[M]) const {
+#pragma unroll
+        for (int m = 0; m < M; ++m) v[m] = v[m] * s[m];
+    }
+};
 template <int M>
 __device__ __forceinline__ GvScale<M> gv_scale_prefetch(const float* w_scale, int N, int tile, int lane, bool vec) {
     GvScale<M> r;
@@ -735,72 +791,26 @@ __device__ __forceinline__ GvScale<M> gv_scale_prefetch(const float* w_scale, in
     return r;
 }
 __device__ __forceinline__ bool gv_scale_vec_ok(const float* w_scale, int N) { return (N & 3) == 0 && N >= 4 && ((size_t)w_scale & 15) == 0; }
+// any K <= 4096 (multiple of 16), any N: the predicated tile loop over the fp8 policy, LPW <= 8 loads of 64 k per wave
+template <typename T>
+struct GvW8 : GvFmtBase<2> {
+    using Slot = uint4;
+    using Row = const uint8_t*;
+    const uint8_t* __restrict__ W;
+    const float* __restrict__ scale;
+    int K, N;
+    bool svec;
+    __device__ __forceinline__ GvW8(const GemvArgs& a, const float* w_scale)
+        : W((const uint8_t*)a.W), scale(w_scale), K(a.K), N(a.N), svec(gv_scale_vec_ok(w_scale, a.N)) {}
+    __device__ __forceinline__ Row row(int64_t r, int kb) const { return W + r * K + kb; }
+    template <int L> __device__ __forceinline__ Slot load(Row p) const { return ld16(p + L * 64); }
+    template <int h> __device__ __forceinline__ uint4 operand(const Slot& w) const { return h ? gv_dec8<T>(w.z, w.w) : gv_dec8<T>(w.x, w.y); }
+    template <int M> __device__ __forceinline__ GvScale<M> post(int tile, int lane) const { return gv_scale_prefetch<M>(scale, N, tile, lane, svec); }
+};
 
-// any K <= 4096 (multiple of 16), any N: predicated loads, LPW <= 8 loads of 64 k per wave (gemv_mfma_kernel's role)
 template <typename T, bool SILU>
 __global__ __launch_bounds__(512) void gemv_w8_kernel(const GemvArgs a, const float* __restrict__ w_scale, const int lpw, const int ntiles) {
-    constexpr int NL = kGvSteps / 2, M = SILU ? 2 : 1;
-    __shared__ __attribute__((aligned(16))) float part[2][kGvWaves][M][256];
-    __shared__ float red[kGvWaves][16];
-    if (gemv_all_done(a)) return;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int i = lane & 15, q = lane >> 4;
-    const int K = a.K, N = a.N, nb = a.nb;
-    const uint8_t* __restrict__ W = (const uint8_t*)a.W;
-    const int k0 = wave * lpw * 64 + q * 16;                        // this lane's k at the wave's load 0
-    int nvalid = k0 < K ? (K - k0 + 63) / 64 : 0;                   // loads of this lane that lie inside K (K % 16 == 0: whole or not)
-    if (nvalid > lpw) nvalid = lpw;
-
-    uint4 xf[2 * NL];
-    {
-        const T* xr = (const T*)a.x + (int64_t)(i < nb ? i : 0) * a.x_ld + k0;
-        gv_static_for<2 * NL>([&](auto s_) {
-            constexpr int s = decltype(s_)::value;
-            xf[s] = (s >> 1) < nvalid ? ld16(xr + (s >> 1) * 64 + (s & 1) * 8) : make_uint4(0, 0, 0, 0);
-        });
-        if (a.norm_w) {
-            float ssq = 0.f;
-            gv_static_for<2 * NL>([&](auto s_) { ssq = gv_pack_ssq<T>(xf[decltype(s_)::value], ssq); });
-            const float rstd = gv_rstd_across_waves(ssq, red, wave, lane, K, a.eps);
-            const T* gw = (const T*)a.norm_w + k0;
-            gv_static_for<2 * NL>([&](auto s_) {
-                constexpr int s = decltype(s_)::value;
-                if ((s >> 1) < nvalid) xf[s] = gv_pack_norm<T>(xf[s], ld16(gw + (s >> 1) * 64 + (s & 1) * 8), rstd);
-            });
-        }
-    }
-    const bool svec = gv_scale_vec_ok(w_scale, N);
-    uint4 wa[M][NL];
-    int it = 0;
-    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x, ++it) {
-        int row = tile * 16 + i;
-        if (row >= N) row = N - 1;
-        const GvScale<M> sc = gv_scale_prefetch<M>(w_scale, N, tile, lane, svec);
-        f32x4_t acc[M];
-#pragma unroll
-        for (int m = 0; m < M; ++m) {
-            acc[m] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-            const uint8_t* p = W + ((int64_t)row + (int64_t)m * N) * K + k0;
-            gv_static_for<NL>([&](auto s_) {
-                constexpr int s = decltype(s_)::value;
-                wa[m][s] = s < nvalid ? ld16(p + s * 64) : make_uint4(0, 0, 0, 0);      // code 0 is +0
-            });
-        }
-        gv_static_for<NL>([&](auto s_) {
-            constexpr int s = decltype(s_)::value;
-#pragma unroll
-            for (int m = 0; m < M; ++m) {
-                acc[m] = gv_mfma<T>(gv_dec8<T>(wa[m][s].x, wa[m][s].y), xf[2 * s], acc[m]);
-                acc[m] = gv_mfma<T>(gv_dec8<T>(wa[m][s].z, wa[m][s].w), xf[2 * s + 1], acc[m]);
-            }
-        });
-        GvEpi epi;
-        epi.vec = false;
-        gv_fold_store<T, SILU>(a, &part[it & 1][0][0][0], acc, tile, wave, lane, epi, [&](f32x4_t (&v)[M]) {
-#pragma unroll
-            for (int m = 0; m < M; ++m) v[m] = v[m] * sc.s[m];
-        });
-    }
+    gv_mfma_tile_loop<T, SILU>(a, GvW8<T>(a, w_scale), lpw, ntiles);
 }
 
 // the predicate-free stream loops: K == 8 waves x SPW MFMA steps x 32 (SPW = 16: K = 4096; SPW = 43: K = 11008), the structure of
@@ -947,74 +957,24 @@ template <> __device__ __forceinline__ uint4 gv_dec8_mx4<f16_t>(uint32_t w, floa
 }
 __device__ __forceinline__ float gv_e8m0(uint32_t byte) { return __uint_as_float(byte << 23); }   // 2^(byte - 127)
 __device__ __forceinline__ uint32_t gv_dword(const uint4& v, int h) { return h == 0 ? v.x : h == 1 ? v.y : h == 2 ? v.z : v.w; }
+// any K <= 4096 (multiple of 32), any N: the predicated tile loop over the MXFP4 policy, LPW <= 4 loads of 128 k per wave
+template <typename T>
+struct GvMx4 : GvFmtBase<4> {
+    struct Slot { uint4 w; uint32_t sc; };
+    struct Row { const uint8_t *c, *s; };
+    const uint8_t* __restrict__ W;
+    const uint8_t* __restrict__ scale;
+    int K;
+    __device__ __forceinline__ GvMx4(const GemvArgs& a, const uint8_t* w_scale) : W((const uint8_t*)a.W), scale(w_scale), K(a.K) {}
+    static __device__ __forceinline__ Slot zero() { return {make_uint4(0, 0, 0, 0), 127u}; }    // +0 codes under a unit scale
+    __device__ __forceinline__ Row row(int64_t r, int kb) const { return {W + r * (K >> 1) + (kb >> 1), scale + r * (K >> 5) + (kb >> 5)}; }
+    template <int L> __device__ __forceinline__ Slot load(Row p) const { return {ld16(p.c + L * 64), (uint32_t)p.s[L * 4]}; }
+    template <int h> __device__ __forceinline__ uint4 operand(const Slot& w) const { return gv_dec8_mx4<T>(gv_dword(w.w, h), gv_e8m0(w.sc)); }
+};
 
-// any K <= 4096 (multiple of 32), any N: predicated loads, LPW <= 4 loads of 128 k per wave (gemv_mfma_kernel's role)
 template <typename T, bool SILU>
 __global__ __launch_bounds__(512) void gemv_mx4_kernel(const GemvArgs a, const uint8_t* __restrict__ w_scale, const int lpw, const int ntiles) {
-    constexpr int NL = kGvSteps / 4, M = SILU ? 2 : 1;
-    __shared__ __attribute__((aligned(16))) float part[2][kGvWaves][M][256];
-    __shared__ float red[kGvWaves][16];
-    if (gemv_all_done(a)) return;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int i = lane & 15, q = lane >> 4;
-    const int K = a.K, N = a.N, nb = a.nb;
-    const uint8_t* __restrict__ W = (const uint8_t*)a.W;
-    const int k0 = wave * lpw * 128 + q * 32;                       // this lane's k at the wave's load 0
-    int nvalid = k0 < K ? (K - k0 + 127) / 128 : 0;                 // loads of this lane that lie inside K (K % 32 == 0: whole or not)
-    if (nvalid > lpw) nvalid = lpw;
-
-    uint4 xf[4 * NL];
-    {
-        const T* xr = (const T*)a.x + (int64_t)(i < nb ? i : 0) * a.x_ld + k0;
-        gv_static_for<4 * NL>([&](auto s_) {
-            constexpr int s = decltype(s_)::value;
-            xf[s] = (s >> 2) < nvalid ? ld16(xr + (s >> 2) * 128 + (s & 3) * 8) : make_uint4(0, 0, 0, 0);
-        });
-        if (a.norm_w) {
-            float ssq = 0.f;
-            gv_static_for<4 * NL>([&](auto s_) { ssq = gv_pack_ssq<T>(xf[decltype(s_)::value], ssq); });
-            const float rstd = gv_rstd_across_waves(ssq, red, wave, lane, K, a.eps);
-            const T* gw = (const T*)a.norm_w + k0;
-            gv_static_for<4 * NL>([&](auto s_) {
-                constexpr int s = decltype(s_)::value;
-                if ((s >> 2) < nvalid) xf[s] = gv_pack_norm<T>(xf[s], ld16(gw + (s >> 2) * 128 + (s & 3) * 8), rstd);
-            });
-        }
-    }
-    uint4 wa[M][NL];
-    uint32_t ws[M][NL];
-    int it = 0;
-    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x, ++it) {
-        int row = tile * 16 + i;
-        if (row >= N) row = N - 1;
-        f32x4_t acc[M];
-#pragma unroll
-        for (int m = 0; m < M; ++m) {
-            acc[m] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-            const int64_t r = (int64_t)row + (int64_t)m * N;
-            const uint8_t* p = W + r * (K >> 1) + (k0 >> 1);
-            const uint8_t* sp = w_scale + r * (K >> 5) + (k0 >> 5);
-            gv_static_for<NL>([&](auto s_) {
-                constexpr int s = decltype(s_)::value;
-                wa[m][s] = s < nvalid ? ld16(p + s * 64) : make_uint4(0, 0, 0, 0);      // code 0 is +0
-                ws[m][s] = s < nvalid ? (uint32_t)sp[s * 4] : 127u;
-            });
-        }
-        gv_static_for<NL>([&](auto s_) {
-            constexpr int s = decltype(s_)::value;
-#pragma unroll
-            for (int m = 0; m < M; ++m) {
-                const float sc = gv_e8m0(ws[m][s]);
-                gv_static_for<4>([&](auto h_) {
-                    constexpr int h = decltype(h_)::value;
-                    acc[m] = gv_mfma<T>(gv_dec8_mx4<T>(gv_dword(wa[m][s], h), sc), xf[4 * s + h], acc[m]);
-                });
-            }
-        });
-        GvEpi epi;
-        epi.vec = false;
-        gv_fold_store<T, SILU>(a, &part[it & 1][0][0][0], acc, tile, wave, lane, epi);
-    }
+    gv_mfma_tile_loop<T, SILU>(a, GvMx4<T>(a, w_scale), lpw, ntiles);
 }
 
 // the predicate-free stream loops.  K = 4096 (NL = 4): 32 loads of 128 k per row, four to a wave.  K = 11008 (NL = 11): 86 loads
@@ -1452,61 +1412,43 @@ static int gemv_plan(int64_t N, int64_t K, int nb, int dtype, int epi, bool norm
     return SS_OK;
 }
 
-// The fp8-weight call: always an MFMA form (one sequence too).  K = 4096 and K = 11008 take the stream loops, every other
-// K <= 4096 (and the knob gemv_mfma_generic) the predicated kernel; the packed 11008-deep loop takes <= 8 sequences, so 9..16
-// run as two sweeps.  Anything else is refused here, before a launch.
-static int gemv_w8_plan(int64_t N, int64_t K, int nb, int dtype, int epi, bool norm, GemvPlan& plan) {
-    SS_REQUIRE(dtype == SS_BF16 || dtype == SS_F16, "gemv_w8: the model dtype must be bf16 or fp16 (got %d)", dtype);
-    constexpr int64_t K16 = kGvWaves * kGvSteps * 32, K43 = kGvWaves * 43 * 32;
-    SS_REQUIRE(N > 0 && K > 0 && K % 16 == 0 && (K <= K16 || K == K43),
-               "gemv_w8: K=%lld must be a positive multiple of 16, at most %lld or exactly %lld (N=%lld)", (long long)K, (long long)K16,
-               (long long)K43, (long long)N);
-    SS_REQUIRE(N < (1ll << 30), "gemv_w8: N=%lld too large", (long long)N);
-    SS_REQUIRE(!(epi & SS_EPI_SILU_MUL) || !(epi & (SS_EPI_BIAS | SS_EPI_RESIDUAL | SS_EPI_GELU)),
-               "gemv_w8: SILU_MUL cannot be combined with other epilogues");
-    SS_REQUIRE(!(epi & ~(SS_EPI_BIAS | SS_EPI_RESIDUAL | SS_EPI_SILU_MUL)), "gemv_w8: epilogue %d not supported", epi);
-    SS_REQUIRE(nb >= 1 && nb <= 16, "gemv_w8: batch %d unsupported (1..16)", nb);
-    SS_REQUIRE(K != K43 || !norm, "gemv_w8: no RMSNorm prologue at K=%lld", (long long)K);
-    const bool silu = (epi & SS_EPI_SILU_MUL) != 0;
-    const int ntiles = cdiv(N, 16), blocks = cdiv(ntiles, cdiv(ntiles, knob(K_gemv_mfma_blocks)));
-    const bool exact16 = K == K16 && !knob(K_gemv_mfma_generic);
-    const int sweeps = (K == K43 && nb > 8) ? 2 : 1;
-    for (int j = 0; j < sweeps; ++j) {
-        const int seq0 = j * (nb / 2), n = sweeps == 1 ? nb : (j ? nb - nb / 2 : nb / 2);
-        GemvLaunch l = {seq0, n, SS_GEMV_FORM_W8, 0, blocks, 512, 0, 0, silu, 0};
-        if (K == K43) l.form = SS_GEMV_FORM_W8_EXACT43, l.param = 43;
-        else if (exact16) l.form = SS_GEMV_FORM_W8_EXACT16, l.param = kGvSteps;
-        else l.param = 2 * cdiv(cdiv(K, 64), kGvWaves);          // MFMA steps per wave: two per 16-byte load
-        plan.l[plan.n++] = l;
-    }
-    return SS_OK;
-}
+// The weight formats of the MFMA kernels on the host: 16-bit (chosen by gemv_plan above), then the quantised ones in the order of
+// GEMV_WQ_*.  plane: what the refusals call the weight argument; forms: the predicated kernel, the stream loops of K = 4096 and
+// K = 11008.  A plan row's param counts MFMA steps of 32 k per wave, `sps` of them to a 16-byte load slot (MXFP4 rounds the 43 of
+// K = 11008 up to whole slots: 44).
+struct GvFormat { const char *name, *plane; int kmult, sps, forms[3], param43; };
+static const GvFormat kGvFormats[3] = {
+    {"gemv", "W", 8, 1, {SS_GEMV_FORM_MFMA, SS_GEMV_FORM_MFMA_EXACT16, SS_GEMV_FORM_MFMA_EXACT43}, 43},
+    {"gemv_w8", "Wq", 16, 2, {SS_GEMV_FORM_W8, SS_GEMV_FORM_W8_EXACT16, SS_GEMV_FORM_W8_EXACT43}, 43},
+    {"gemv_mx4", "codes", 32, 4, {SS_GEMV_FORM_MX4, SS_GEMV_FORM_MX4_EXACT16, SS_GEMV_FORM_MX4_EXACT43}, 44}};
 
-// The MXFP4-weight call: always an MFMA form, with the grid rules of the fp8 plan.  K = 4096 and K = 11008 take the stream loops,
-// every other K <= 4096 (and the knob gemv_mfma_generic) the predicated kernel; the packed 11008-deep loop takes <= 8 sequences, so
-// 9..16 run as two sweeps.  The parameter column holds the MFMA steps of 32 k a wave walks (four per load slot).
-static int gemv_mx4_plan(int64_t N, int64_t K, int nb, int dtype, int epi, bool norm, GemvPlan& plan) {
-    SS_REQUIRE(dtype == SS_BF16 || dtype == SS_F16, "gemv_mx4: the model dtype must be bf16 or fp16 (got %d)", dtype);
+// The quantised-weight calls (kind = GEMV_WQ_*): always an MFMA form (one sequence too).  K = 4096 and K = 11008 take the stream
+// loops, every other K <= 4096 (and the knob gemv_mfma_generic) the predicated kernel; the packed 11008-deep loop takes <= 8
+// sequences, so 9..16 run as two sweeps.  Anything else is refused here, before a launch.
+static int gemv_wq_plan(int kind, int64_t N, int64_t K, int nb, int dtype, int epi, bool norm, GemvPlan& plan) {
+    SS_REQUIRE(kind == GEMV_WQ_FP8 || kind == GEMV_WQ_MXFP4, "gemv: unknown weight format %d", kind);
+    const GvFormat& f = kGvFormats[kind];
+    SS_REQUIRE(dtype == SS_BF16 || dtype == SS_F16, "%s: the model dtype must be bf16 or fp16 (got %d)", f.name, dtype);
     constexpr int64_t K16 = kGvWaves * kGvSteps * 32, K43 = kGvWaves * 43 * 32;
-    SS_REQUIRE(N > 0 && K > 0 && K % 32 == 0 && (K <= K16 || K == K43),
-               "gemv_mx4: K=%lld must be a positive multiple of 32, at most %lld or exactly %lld (N=%lld)", (long long)K, (long long)K16,
-               (long long)K43, (long long)N);
-    SS_REQUIRE(N < (1ll << 30), "gemv_mx4: N=%lld too large", (long long)N);
+    SS_REQUIRE(N > 0 && K > 0 && K % f.kmult == 0 && (K <= K16 || K == K43),
+               "%s: K=%lld must be a positive multiple of %d, at most %lld or exactly %lld (N=%lld)", f.name, (long long)K, f.kmult,
+               (long long)K16, (long long)K43, (long long)N);
+    SS_REQUIRE(N < (1ll << 30), "%s: N=%lld too large", f.name, (long long)N);
     SS_REQUIRE(!(epi & SS_EPI_SILU_MUL) || !(epi & (SS_EPI_BIAS | SS_EPI_RESIDUAL | SS_EPI_GELU)),
-               "gemv_mx4: SILU_MUL cannot be combined with other epilogues");
-    SS_REQUIRE(!(epi & ~(SS_EPI_BIAS | SS_EPI_RESIDUAL | SS_EPI_SILU_MUL)), "gemv_mx4: epilogue %d not supported", epi);
-    SS_REQUIRE(nb >= 1 && nb <= 16, "gemv_mx4: batch %d unsupported (1..16)", nb);
-    SS_REQUIRE(K != K43 || !norm, "gemv_mx4: no RMSNorm prologue at K=%lld", (long long)K);
+               "%s: SILU_MUL cannot be combined with other epilogues", f.name);
+    SS_REQUIRE(!(epi & ~(SS_EPI_BIAS | SS_EPI_RESIDUAL | SS_EPI_SILU_MUL)), "%s: epilogue %d not supported", f.name, epi);
+    SS_REQUIRE(nb >= 1 && nb <= 16, "%s: batch %d unsupported (1..16)", f.name, nb);
+    SS_REQUIRE(K != K43 || !norm, "%s: no RMSNorm prologue at K=%lld", f.name, (long long)K);
     const bool silu = (epi & SS_EPI_SILU_MUL) != 0;
     const int ntiles = cdiv(N, 16), blocks = cdiv(ntiles, cdiv(ntiles, knob(K_gemv_mfma_blocks)));
     const bool exact16 = K == K16 && !knob(K_gemv_mfma_generic);
     const int sweeps = (K == K43 && nb > 8) ? 2 : 1;
     for (int j = 0; j < sweeps; ++j) {
         const int seq0 = j * (nb / 2), n = sweeps == 1 ? nb : (j ? nb - nb / 2 : nb / 2);
-        GemvLaunch l = {seq0, n, SS_GEMV_FORM_MX4, 0, blocks, 512, 0, 0, silu, 0};
-        if (K == K43) l.form = SS_GEMV_FORM_MX4_EXACT43, l.param = 44;
-        else if (exact16) l.form = SS_GEMV_FORM_MX4_EXACT16, l.param = kGvSteps;
-        else l.param = 4 * cdiv(cdiv(K, 128), kGvWaves);         // four per 16-byte load
+        GemvLaunch l = {seq0, n, f.forms[0], 0, blocks, 512, 0, 0, silu, 0};
+        if (K == K43) l.form = f.forms[2], l.param = f.param43;
+        else if (exact16) l.form = f.forms[1], l.param = kGvSteps;
+        else l.param = f.sps * cdiv(cdiv(K, 32 * f.sps), kGvWaves);
         plan.l[plan.n++] = l;
     }
     return SS_OK;
@@ -1514,7 +1456,6 @@ static int gemv_mx4_plan(int64_t N, int64_t K, int nb, int dtype, int epi, bool 
 
 // ---- kernel tables --------------------------------------------------------------------------------------------------------------------
 using GemvKern = void (*)(GemvArgs);
-using GemvTileKern = void (*)(GemvArgs, int);
 // ROWS = 2 keeps 16 x 16 B per lane in flight at NIT = 8 (and SiLU pairs need exactly 2 rows)
 template <typename T, int NB>
 static GemvKern gv_dot_kernel_nb(const GemvLaunch& l) {
@@ -1528,21 +1469,18 @@ static GemvKern gv_dot_kernel(const GemvLaunch& l) {
     static constexpr GemvKern (*by_nb[4])(const GemvLaunch&) = {gv_dot_kernel_nb<T, 1>, gv_dot_kernel_nb<T, 2>, gv_dot_kernel_nb<T, 3>, gv_dot_kernel_nb<T, 4>};
     return by_nb[l.nseq - 1](l);
 }
-template <typename T, int SPW>
-static GemvTileKern gv_exact_kernel(const GemvLaunch& l) {
-    static constexpr GemvTileKern k[2][2] = {{gemv_mfma_exact_kernel<T, false, SPW, false>, gemv_mfma_exact_kernel<T, false, SPW, true>},
-                                             {gemv_mfma_exact_kernel<T, true, SPW, false>, gemv_mfma_exact_kernel<T, true, SPW, true>}};
-    return k[l.silu][l.nt];
-}
-using GemvW8Kern = void (*)(GemvArgs, const float*, int);
-template <typename T, int SPW>
-static GemvW8Kern gv_w8_exact_kernel(const GemvLaunch& l) {
-    return l.silu ? gemv_w8_exact_kernel<T, true, SPW> : gemv_w8_exact_kernel<T, false, SPW>;
-}
-using GemvMx4Kern = void (*)(GemvArgs, const uint8_t*, int);
-template <typename T, int NL>
-static GemvMx4Kern gv_mx4_exact_kernel(const GemvLaunch& l) {
-    return l.silu ? gemv_mx4_exact_kernel<T, true, NL> : gemv_mx4_exact_kernel<T, false, NL>;
+// the MFMA kernel of role 0 (predicated) / 1 (stream loop, K = 4096) / 2 (K = 11008), by format (the index of kGvFormats)
+template <typename T, bool SILU>
+static const void* gv_mfma_kernel(int role, int fmt, bool nt) {
+#define GV_K(...) ((const void*)&__VA_ARGS__)
+    const void* const k[3][3] = {
+        {GV_K(gemv_mfma_kernel<T, SILU>), GV_K(gemv_w8_kernel<T, SILU>), GV_K(gemv_mx4_kernel<T, SILU>)},
+        {nt ? GV_K(gemv_mfma_exact_kernel<T, SILU, 16, true>) : GV_K(gemv_mfma_exact_kernel<T, SILU, 16, false>), GV_K(gemv_w8_exact_kernel<T, SILU, 16>),
+         GV_K(gemv_mx4_exact_kernel<T, SILU, 4>)},
+        {nt ? GV_K(gemv_mfma_exact_kernel<T, SILU, 43, true>) : GV_K(gemv_mfma_exact_kernel<T, SILU, 43, false>), GV_K(gemv_w8_exact_kernel<T, SILU, 43>),
+         GV_K(gemv_mx4_exact_kernel<T, SILU, 11>)}};
+#undef GV_K
+    return k[role][fmt];
 }
 template <bool SILU>
 static int gemv_run_split(const GemvLaunch& l, const GemvArgs& a, hipStream_t s) {
@@ -1551,8 +1489,9 @@ static int gemv_run_split(const GemvLaunch& l, const GemvArgs& a, hipStream_t s)
     return SS_OK;
 }
 
+// w_scale: the scale plane of a quantised call (fp32 row scales | e8m0 block scales), an extra argument of its kernels
 template <typename T>
-static int gemv_run(const GemvPlan& plan, const GemvArgs& args, hipStream_t s, const float* w_scale = nullptr, const uint8_t* mx_scale = nullptr) {
+static int gemv_run(const GemvPlan& plan, const GemvArgs& args, hipStream_t s, const void* w_scale = nullptr) {
     for (int j = 0; j < plan.n; ++j) {
         const GemvLaunch& l = plan.l[j];
         GemvArgs a = args;
@@ -1570,30 +1509,39 @@ static int gemv_run(const GemvPlan& plan, const GemvArgs& args, hipStream_t s, c
         } else if constexpr (sizeof(T) == 4) {
             const int rc = l.silu ? gemv_run_split<true>(l, a, s) : gemv_run_split<false>(l, a, s);
             if (rc) return rc;
-        } else if (l.form == SS_GEMV_FORM_W8) {
-            void (*const k)(GemvArgs, const float*, int, int) = l.silu ? gemv_w8_kernel<T, true> : gemv_w8_kernel<T, false>;
-            hipLaunchKernelGGL(k, g, b, 0, s, a, w_scale, l.param / 2, cdiv(a.N, 16));
-        } else if (l.form == SS_GEMV_FORM_W8_EXACT16 || l.form == SS_GEMV_FORM_W8_EXACT43) {
-            const GemvW8Kern k = l.form == SS_GEMV_FORM_W8_EXACT16 ? gv_w8_exact_kernel<T, 16>(l) : gv_w8_exact_kernel<T, 43>(l);
-            hipLaunchKernelGGL(k, g, b, 0, s, a, w_scale, cdiv(a.N, 16));
-        } else if (l.form == SS_GEMV_FORM_MX4) {
-            void (*const k)(GemvArgs, const uint8_t*, int, int) = l.silu ? gemv_mx4_kernel<T, true> : gemv_mx4_kernel<T, false>;
-            hipLaunchKernelGGL(k, g, b, 0, s, a, mx_scale, l.param / 4, cdiv(a.N, 16));
-        } else if (l.form == SS_GEMV_FORM_MX4_EXACT16 || l.form == SS_GEMV_FORM_MX4_EXACT43) {
-            const GemvMx4Kern k = l.form == SS_GEMV_FORM_MX4_EXACT16 ? gv_mx4_exact_kernel<T, 4>(l) : gv_mx4_exact_kernel<T, 11>(l);
-            hipLaunchKernelGGL(k, g, b, 0, s, a, mx_scale, cdiv(a.N, 16));
-        } else if (l.form == SS_GEMV_FORM_MFMA) {
-            void (*const k)(GemvArgs, int, int) = l.silu ? gemv_mfma_kernel<T, true> : gemv_mfma_kernel<T, false>;
-            hipLaunchKernelGGL(k, g, b, 0, s, a, l.param, cdiv(a.N, 16));
         } else {
-            const GemvTileKern k = l.form == SS_GEMV_FORM_MFMA_EXACT16 ? gv_exact_kernel<T, 16>(l) : gv_exact_kernel<T, 43>(l);
-            hipLaunchKernelGGL(k, g, b, 0, s, a, cdiv(a.N, 16));
+            int fmt = -1, role = 0;
+            for (int f = 0; f < 3; ++f)
+                for (int r = 0; r < 3; ++r)
+                    if (kGvFormats[f].forms[r] == l.form) fmt = f, role = r;
+            SS_REQUIRE(fmt >= 0, "gemv: no kernel for form %d", l.form);
+            // The arguments in the order of the six wrappers' parameter lists (hipLaunchKernel checks nothing):
+            //   predicated   (GemvArgs, [scale plane,] load slots per wave, row tiles)      gemv_mfma_kernel | gemv_w8_kernel | gemv_mx4_kernel
+            //   stream loop  (GemvArgs, [scale plane,] row tiles)                           gemv_*_exact_kernel
+            // the scale plane (const float* | const uint8_t*) only where fmt > 0.
+            int slots = l.param / kGvFormats[fmt].sps, ntiles = cdiv(a.N, 16), n = 0;
+            void* kargs[4];
+            kargs[n++] = &a;
+            if (fmt) kargs[n++] = &w_scale;
+            if (role == 0) kargs[n++] = &slots;
+            kargs[n++] = &ntiles;
+            SS_HIP(hipLaunchKernel(l.silu ? gv_mfma_kernel<T, true>(role, fmt, l.nt) : gv_mfma_kernel<T, false>(role, fmt, l.nt), g, b, kargs, 0, s));
         }
         static const char* const what[] = {"gemv", "gemv_ldsx", "gemv_mfma", "gemv_mfma", "gemv_mfma", "gemv_split_f32", "gemv_w8", "gemv_w8", "gemv_w8",
                                            "gemv_mx4", "gemv_mx4", "gemv_mx4"};
         SS_LAUNCH_CHECK(what[l.form]);
     }
     return SS_OK;
+}
+
+static GemvArgs gemv_args(const void* W, const void* x, void* y, int64_t N, int64_t K, const void* norm_w, float eps, const void* bias,
+                          const void* residual, int epi, const int32_t* done_flag, int done_stride, int nb, int64_t x_ld, int64_t y_ld,
+                          int64_t res_ld) {
+    GemvArgs a;
+    a.W = W; a.x = x; a.y = y; a.norm_w = norm_w; a.bias = bias; a.residual = residual; a.done_flag = done_flag;
+    a.N = (int)N; a.K = (int)K; a.epi = epi; a.eps = eps; a.use_nt = 0;
+    a.nb = nb; a.done_stride = done_stride; a.x_ld = x_ld; a.y_ld = y_ld; a.res_ld = res_ld;
+    return a;
 }
 
 int gemv_batched_dev(const void* W, const void* x, void* y, int64_t N, int64_t K, const void* norm_w, float eps,
@@ -1615,63 +1563,42 @@ int gemv_batched_dev(const void* W, const void* x, void* y, int64_t N, int64_t K
                     (epi & SS_EPI_SILU_MUL) ? " +SiLU" : "", kGsSlice);
         }
     }
-    GemvArgs a;
-    a.W = W; a.x = x; a.y = y; a.norm_w = norm_w; a.bias = bias; a.residual = residual; a.done_flag = done_flag;
-    a.N = (int)N; a.K = (int)K; a.epi = epi; a.eps = eps; a.use_nt = 0;
-    a.nb = nb; a.done_stride = done_stride; a.x_ld = x_ld; a.y_ld = y_ld; a.res_ld = res_ld;
+    const GemvArgs a = gemv_args(W, x, y, N, K, norm_w, eps, bias, residual, epi, done_flag, done_stride, nb, x_ld, y_ld, res_ld);
     return SS_DISPATCH(dtype, gemv_run, plan, a, s);
 }
 
-int gemv_w8_check(int64_t N, int64_t K, int nb, int dtype, int epi, bool norm) {
+int gemv_wq_check(int kind, int64_t N, int64_t K, int nb, int dtype, int epi, bool norm) {
     GemvPlan plan;
-    return gemv_w8_plan(N, K, nb, dtype, epi, norm, plan);
+    return gemv_wq_plan(kind, N, K, nb, dtype, epi, norm, plan);
 }
 
-int gemv_w8_batched_dev(const void* Wq, const float* w_scale, const void* x, void* y, int64_t N, int64_t K, const void* norm_w,
+int gemv_wq_batched_dev(int kind, const void* codes, const void* scales, const void* x, void* y, int64_t N, int64_t K, const void* norm_w,
                         float eps, const void* bias, const void* residual, int epi, const int32_t* done_flag, int done_stride,
                         int nb, int64_t x_ld, int64_t y_ld, int64_t res_ld, int dtype, hipStream_t s) {
     GemvPlan plan;
-    const int rc = gemv_w8_plan(N, K, nb, dtype, epi, norm_w != nullptr, plan);
+    const int rc = gemv_wq_plan(kind, N, K, nb, dtype, epi, norm_w != nullptr, plan);
     if (rc) return rc;
-    SS_REQUIRE(Wq && w_scale && x && y, "gemv_w8: NULL argument");
-    SS_REQUIRE(!(epi & SS_EPI_BIAS) || bias, "gemv_w8: BIAS epilogue without a bias");
-    SS_REQUIRE(!(epi & SS_EPI_RESIDUAL) || residual, "gemv_w8: RESIDUAL epilogue without a residual");
-    SS_REQUIRE((((size_t)Wq | (size_t)x | (size_t)norm_w) & 15) == 0 && (x_ld & 7) == 0 && ((size_t)w_scale & 3) == 0,
-               "gemv_w8: Wq, x and norm_w must be 16-byte aligned (x row stride a multiple of 8 elements)");
-    GemvArgs a;
-    a.W = Wq; a.x = x; a.y = y; a.norm_w = norm_w; a.bias = bias; a.residual = residual; a.done_flag = done_flag;
-    a.N = (int)N; a.K = (int)K; a.epi = epi; a.eps = eps; a.use_nt = 0;
-    a.nb = nb; a.done_stride = done_stride; a.x_ld = x_ld; a.y_ld = y_ld; a.res_ld = res_ld;
-    return dtype == SS_BF16 ? gemv_run<bf16_t>(plan, a, s, w_scale) : gemv_run<f16_t>(plan, a, s, w_scale);
-}
-
-int gemv_mx4_check(int64_t N, int64_t K, int nb, int dtype, int epi, bool norm) {
-    GemvPlan plan;
-    return gemv_mx4_plan(N, K, nb, dtype, epi, norm, plan);
-}
-
-int gemv_mx4_batched_dev(const void* codes, const void* scales, const void* x, void* y, int64_t N, int64_t K, const void* norm_w,
-                         float eps, const void* bias, const void* residual, int epi, const int32_t* done_flag, int done_stride,
-                         int nb, int64_t x_ld, int64_t y_ld, int64_t res_ld, int dtype, hipStream_t s) {
-    GemvPlan plan;
-    const int rc = gemv_mx4_plan(N, K, nb, dtype, epi, norm_w != nullptr, plan);
-    if (rc) return rc;
-    SS_REQUIRE(codes && scales && x && y, "gemv_mx4: NULL argument");
-    SS_REQUIRE(!(epi & SS_EPI_BIAS) || bias, "gemv_mx4: BIAS epilogue without a bias");
-    SS_REQUIRE(!(epi & SS_EPI_RESIDUAL) || residual, "gemv_mx4: RESIDUAL epilogue without a residual");
-    SS_REQUIRE((((size_t)codes | (size_t)x | (size_t)norm_w) & 15) == 0 && (x_ld & 7) == 0,
-               "gemv_mx4: codes, x and norm_w must be 16-byte aligned (x row stride a multiple of 8 elements)");
-    GemvArgs a;
-    a.W = codes; a.x = x; a.y = y; a.norm_w = norm_w; a.bias = bias; a.residual = residual; a.done_flag = done_flag;
-    a.N = (int)N; a.K = (int)K; a.epi = epi; a.eps = eps; a.use_nt = 0;
-    a.nb = nb; a.done_stride = done_stride; a.x_ld = x_ld; a.y_ld = y_ld; a.res_ld = res_ld;
-    return dtype == SS_BF16 ? gemv_run<bf16_t>(plan, a, s, nullptr, (const uint8_t*)scales)
-                            : gemv_run<f16_t>(plan, a, s, nullptr, (const uint8_t*)scales);
+    const char *name = kGvFormats[kind].name, *plane = kGvFormats[kind].plane;
+    SS_REQUIRE(codes && scales && x && y, "%s: NULL argument", name);
+    SS_REQUIRE(!(epi & SS_EPI_BIAS) || bias, "%s: BIAS epilogue without a bias", name);
+    SS_REQUIRE(!(epi & SS_EPI_RESIDUAL) || residual, "%s: RESIDUAL epilogue without a residual", name);
+    SS_REQUIRE((((size_t)codes | (size_t)x | (size_t)norm_w) & 15) == 0 && (x_ld & 7) == 0 && (kind != GEMV_WQ_FP8 || ((size_t)scales & 3) == 0),
+               "%s: %s, x and norm_w must be 16-byte aligned (x row stride a multiple of 8 elements)", name, plane);
+    const GemvArgs a = gemv_args(codes, x, y, N, K, norm_w, eps, bias, residual, epi, done_flag, done_stride, nb, x_ld, y_ld, res_ld);
+    return dtype == SS_BF16 ? gemv_run<bf16_t>(plan, a, s, scales) : gemv_run<f16_t>(plan, a, s, scales);
 }
 
 int gemv_dev(const void* W, const void* x, void* y, int64_t N, int64_t K, const void* norm_w, float eps,
              const void* bias, const void* residual, int epi, const int32_t* done_flag, int dtype, hipStream_t s) {
     return gemv_batched_dev(W, x, y, N, K, norm_w, eps, bias, residual, epi, done_flag, 0, 1, K, N, N, dtype, s);
+}
+
+// the rows of a plan -> the caller's array (ss_gemv_plan and its quantised siblings)
+static int gemv_plan_out(const char* who, int rc, const GemvPlan& plan, int32_t* rows, int64_t max_rows) {
+    if (rc) return rc;
+    SS_REQUIRE(rows && max_rows >= plan.n, "%s: %d rows needed, room for %lld", who, plan.n, (long long)max_rows);
+    memcpy(rows, plan.l, (size_t)plan.n * sizeof(GemvLaunch));
+    return plan.n;
 }
 
 }  // namespace ss
@@ -1689,43 +1616,33 @@ extern "C" int ss_gemv_batched(const void* W, const void* x, void* y, int64_t N,
 extern "C" int ss_gemv_plan(int64_t N, int64_t K, int64_t nb, int dtype, int epilogue, int has_norm, int aligned16, int32_t* rows,
                             int64_t max_rows) {
     ss::GemvPlan plan;
-    const int rc = ss::gemv_plan(N, K, (int)nb, dtype, epilogue, has_norm != 0, aligned16 != 0, plan);
-    if (rc) return rc;
-    SS_REQUIRE(rows && max_rows >= plan.n, "ss_gemv_plan: %d rows needed, room for %lld", plan.n, (long long)max_rows);
-    memcpy(rows, plan.l, (size_t)plan.n * sizeof(ss::GemvLaunch));
-    return plan.n;
+    return ss::gemv_plan_out("ss_gemv_plan", ss::gemv_plan(N, K, (int)nb, dtype, epilogue, has_norm != 0, aligned16 != 0, plan), plan, rows, max_rows);
 }
 
 extern "C" int ss_gemv_w8(const void* Wq, const float* w_scale, const void* x, void* y, int64_t N, int64_t K, int64_t nb,
                           const void* norm_w, float eps, const void* bias, const void* residual, int epilogue, int dtype, void* stream) {
     SS_REQUIRE(nb >= 1 && nb <= 16, "gemv_w8: batch %lld unsupported (1..16)", (long long)nb);
-    return ss::gemv_w8_batched_dev(Wq, w_scale, x, y, N, K, norm_w, eps, bias, residual, epilogue, nullptr, 0, (int)nb, K, N, N, dtype,
-                                   (hipStream_t)stream);
+    return ss::gemv_wq_batched_dev(ss::GEMV_WQ_FP8, Wq, w_scale, x, y, N, K, norm_w, eps, bias, residual, epilogue, nullptr, 0, (int)nb, K, N, N,
+                                   dtype, (hipStream_t)stream);
 }
 
 extern "C" int ss_gemv_w8_plan(int64_t N, int64_t K, int64_t nb, int dtype, int epilogue, int has_norm, int32_t* rows, int64_t max_rows) {
     ss::GemvPlan plan;
     SS_REQUIRE(nb >= 1 && nb <= 16, "gemv_w8: batch %lld unsupported (1..16)", (long long)nb);
-    const int rc = ss::gemv_w8_plan(N, K, (int)nb, dtype, epilogue, has_norm != 0, plan);
-    if (rc) return rc;
-    SS_REQUIRE(rows && max_rows >= plan.n, "ss_gemv_w8_plan: %d rows needed, room for %lld", plan.n, (long long)max_rows);
-    memcpy(rows, plan.l, (size_t)plan.n * sizeof(ss::GemvLaunch));
-    return plan.n;
+    return ss::gemv_plan_out("ss_gemv_w8_plan", ss::gemv_wq_plan(ss::GEMV_WQ_FP8, N, K, (int)nb, dtype, epilogue, has_norm != 0, plan), plan, rows,
+                             max_rows);
 }
 
 extern "C" int ss_gemv_mx4(const void* codes, const void* scales, const void* x, void* y, int64_t N, int64_t K, int64_t nb,
                            const void* norm_w, float eps, const void* bias, const void* residual, int epilogue, int dtype, void* stream) {
     SS_REQUIRE(nb >= 1 && nb <= 16, "gemv_mx4: batch %lld unsupported (1..16)", (long long)nb);
-    return ss::gemv_mx4_batched_dev(codes, scales, x, y, N, K, norm_w, eps, bias, residual, epilogue, nullptr, 0, (int)nb, K, N, N, dtype,
-                                    (hipStream_t)stream);
+    return ss::gemv_wq_batched_dev(ss::GEMV_WQ_MXFP4, codes, scales, x, y, N, K, norm_w, eps, bias, residual, epilogue, nullptr, 0, (int)nb, K, N,
+                                   N, dtype, (hipStream_t)stream);
 }
 
 extern "C" int ss_gemv_mx4_plan(int64_t N, int64_t K, int64_t nb, int dtype, int epilogue, int has_norm, int32_t* rows, int64_t max_rows) {
     ss::GemvPlan plan;
     SS_REQUIRE(nb >= 1 && nb <= 16, "gemv_mx4: batch %lld unsupported (1..16)", (long long)nb);
-    const int rc = ss::gemv_mx4_plan(N, K, (int)nb, dtype, epilogue, has_norm != 0, plan);
-    if (rc) return rc;
-    SS_REQUIRE(rows && max_rows >= plan.n, "ss_gemv_mx4_plan: %d rows needed, room for %lld", plan.n, (long long)max_rows);
-    memcpy(rows, plan.l, (size_t)plan.n * sizeof(ss::GemvLaunch));
-    return plan.n;
+    return ss::gemv_plan_out("ss_gemv_mx4_plan", ss::gemv_wq_plan(ss::GEMV_WQ_MXFP4, N, K, (int)nb, dtype, epilogue, has_norm != 0, plan), plan, rows,
+                             max_rows);
 }

@@ -796,16 +796,21 @@ static int decode_token(ss_llama* h, hipStream_t s, ProfSink* prof, int seq0, in
     int rc;
     // the five decode projections: the 16-bit weights, their fp8 planes + row scales while ss_llama_set_decode_w8 is on, or their
     // MXFP4 code + block-scale planes while ss_llama_set_decode_mx4 is
-    const bool w8 = !h->w8.empty(), mx4 = !h->mx4.empty();
-    auto proj = [&](const void* W, const void* Wq, const void* sc, const char* x, char* y, int64_t N, int64_t K, const void* norm_w,
-                    const void* residual, int epi, int64_t y_ld, int64_t res_ld) {
-        if (mx4)
-            return gemv_mx4_batched_dev(Wq, sc, x, y, N, K, norm_w, g.rms_eps, nullptr, residual, epi, done, ST_WORDS, nb, K, y_ld, res_ld, dt, s);
-        if (w8)
-            return gemv_w8_batched_dev(Wq, (const float*)sc, x, y, N, K, norm_w, g.rms_eps, nullptr, residual, epi, done, ST_WORDS, nb, K, y_ld, res_ld, dt, s);
+    const int wq = h->decode_weights_kind();
+    static_assert(GEMV_WQ_FP8 == 1 && GEMV_WQ_MXFP4 == 2, "decode_weights_kind() is the GEMV's weight format");
+    struct QPlanes { const void *codes, *scales; };
+    auto proj = [&](const void* W, QPlanes q, const char* x, char* y, int64_t N, int64_t K, const void* norm_w, const void* residual, int epi,
+                    int64_t y_ld, int64_t res_ld) {
+        if (wq) return gemv_wq_batched_dev(wq, q.codes, q.scales, x, y, N, K, norm_w, g.rms_eps, nullptr, residual, epi, done, ST_WORDS, nb, K, y_ld, res_ld, dt, s);
         return gemv_batched_dev(W, x, y, N, K, norm_w, norm_w ? g.rms_eps : 0.f, nullptr, residual, epi, done, ST_WORDS, nb, K, y_ld, res_ld, dt, s);
     };
-    static const ss_llama_layer_mx4 kNoQ = {};
+    // the quantised planes of one projection of layer l, either kind: `pick` names the projection's two members
+    auto qplanes = [&](int l, auto pick) { return wq == GEMV_WQ_MXFP4 ? pick(h->mx4[l]) : wq ? pick(h->w8[l]) : QPlanes{nullptr, nullptr}; };
+    const auto q_qkv = [](const auto& q) { return QPlanes{q.wqkv, q.s_qkv}; };
+    const auto q_o = [](const auto& q) { return QPlanes{q.wo, q.s_o}; };
+    const auto q_gu = [](const auto& q) { return QPlanes{q.wgu, q.s_gu}; };
+    const auto q_down = [](const auto& q) { return QPlanes{q.wdown, q.s_down}; };
+    const QPlanes q_lm = wq == GEMV_WQ_MXFP4 ? QPlanes{h->mx4_lm_head, h->mx4_lm_scale} : QPlanes{h->w8_lm_head, h->w8_lm_scale};
 #define MARK(c) do { if (prof) prof->mark(c); } while (0)
     MARK(-1);
     // a slot records log-probabilities: the raw row is read before anything edits it (off everywhere, the default: no launch)
@@ -825,16 +830,10 @@ static int decode_token(ss_llama* h, hipStream_t s, ProfSink* prof, int seq0, in
     MARK(3);
     for (int l = 0; l < g.n_layers; ++l) {
         const ss_llama_layer_weights& L = h->layers[l];
-        ss_llama_layer_mx4 Q = kNoQ;       // the quantised planes of this layer, either kind: codes, scales
-        if (mx4) Q = h->mx4[l];
-        else if (w8) {
-            const ss_llama_layer_w8& q8 = h->w8[l];
-            Q = {q8.wqkv, q8.wo, q8.wgu, q8.wdown, q8.s_qkv, q8.s_o, q8.s_gu, q8.s_down};
-        }
         char* kc = slot_k(h, seq0, l);
         char* vc = slot_v(h, seq0, l);
         MARK(-1);
-        rc = proj(L.wqkv, Q.wqkv, Q.s_qkv, ax, aqkv, 3 * H, H, L.ln1, nullptr, SS_EPI_NONE, 3 * H, 0);
+        rc = proj(L.wqkv, qplanes(l, q_qkv), ax, aqkv, 3 * H, H, L.ln1, nullptr, SS_EPI_NONE, 3 * H, 0);
         if (rc) return rc;
         MARK(0);
         // RoPE(q,k) + KV append + split-KV attention in one kernel (+ the split merge); with the fp8 shadow on, its sibling
@@ -858,13 +857,13 @@ static int decode_token(ss_llama* h, hipStream_t s, ProfSink* prof, int seq0, in
             if (rc) return rc;
         }
         MARK(1);
-        rc = proj(L.wo, Q.wo, Q.s_o, aattn, axn, H, H, nullptr, ax, SS_EPI_RESIDUAL, H, H);
+        rc = proj(L.wo, qplanes(l, q_o), aattn, axn, H, H, nullptr, ax, SS_EPI_RESIDUAL, H, H);
         if (rc) return rc;
         MARK(0);
-        rc = proj(L.wgu, Q.wgu, Q.s_gu, axn, ahm, I, H, L.ln2, nullptr, SS_EPI_SILU_MUL, I, 0);
+        rc = proj(L.wgu, qplanes(l, q_gu), axn, ahm, I, H, L.ln2, nullptr, SS_EPI_SILU_MUL, I, 0);
         if (rc) return rc;
         MARK(0);
-        rc = proj(L.wdown, Q.wdown, Q.s_down, ahm, ax, H, I, nullptr, axn, SS_EPI_RESIDUAL, H, H);
+        rc = proj(L.wdown, qplanes(l, q_down), ahm, ax, H, I, nullptr, axn, SS_EPI_RESIDUAL, H, H);
         if (rc) return rc;
         MARK(2);
     }
@@ -872,7 +871,7 @@ static int decode_token(ss_llama* h, hipStream_t s, ProfSink* prof, int seq0, in
     else rc = SS_DISPATCH(dt, final_norm_advance_launch, h, seq0, nslots, s);
     if (rc) return rc;
     MARK(3);
-    rc = proj(h->w.lm_head, mx4 ? h->mx4_lm_head : h->w8_lm_head, mx4 ? h->mx4_lm_scale : (const void*)h->w8_lm_scale, axn, logits, g.vocab, H, nullptr, nullptr, SS_EPI_NONE, g.vocab, 0);
+    rc = proj(h->w.lm_head, q_lm, axn, logits, g.vocab, H, nullptr, nullptr, SS_EPI_NONE, g.vocab, 0);
     if (rc) return rc;
     MARK(0);
 #undef MARK
@@ -1383,8 +1382,8 @@ int ss_llama_set_decode_w8(ss_llama* h, const ss_llama_layer_w8* layers, const v
         {3 * H, H, SS_EPI_NONE, true}, {H, H, SS_EPI_RESIDUAL, false}, {I, H, SS_EPI_SILU_MUL, true}, {H, I, SS_EPI_RESIDUAL, false},
         {g.vocab, H, SS_EPI_NONE, false}};
     for (const auto& sh : shapes) {
-        int rc = gemv_w8_check(sh.N, sh.K, 1, g.dtype, sh.epi, sh.norm);
-        if (!rc) rc = gemv_w8_check(sh.N, sh.K, h->n_seq, g.dtype, sh.epi, sh.norm);
+        int rc = gemv_wq_check(GEMV_WQ_FP8, sh.N, sh.K, 1, g.dtype, sh.epi, sh.norm);
+        if (!rc) rc = gemv_wq_check(GEMV_WQ_FP8, sh.N, sh.K, h->n_seq, g.dtype, sh.epi, sh.norm);
         if (rc) return rc;
     }
     for (int l = 0; l < g.n_layers; ++l) {
@@ -1421,8 +1420,8 @@ int ss_llama_set_decode_mx4(ss_llama* h, const ss_llama_layer_mx4* layers, const
         {3 * H, H, SS_EPI_NONE, true}, {H, H, SS_EPI_RESIDUAL, false}, {I, H, SS_EPI_SILU_MUL, true}, {H, I, SS_EPI_RESIDUAL, false},
         {g.vocab, H, SS_EPI_NONE, false}};
     for (const auto& sh : shapes) {
-        int rc = gemv_mx4_check(sh.N, sh.K, 1, g.dtype, sh.epi, sh.norm);
-        if (!rc) rc = gemv_mx4_check(sh.N, sh.K, h->n_seq, g.dtype, sh.epi, sh.norm);
+        int rc = gemv_wq_check(GEMV_WQ_MXFP4, sh.N, sh.K, 1, g.dtype, sh.epi, sh.norm);
+        if (!rc) rc = gemv_wq_check(GEMV_WQ_MXFP4, sh.N, sh.K, h->n_seq, g.dtype, sh.epi, sh.norm);
         if (rc) return rc;
     }
     for (int l = 0; l < g.n_layers; ++l) {

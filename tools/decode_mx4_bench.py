@@ -3,7 +3,7 @@ bench.py (weights created on the GPU): whole-token time of ``LlamaEngine.profile
 16-bit / fp8 / MXFP4 for --repeats rounds; per projection shape the GEMV time of the three options over the 32 layers' planes
 in rotation (they never sit in L2 / Infinity Cache); and the relative error of the fp8 and MXFP4 decodes' logits and hidden rows
 against the 16-bit decode of the same weights under teacher-forced tokens.
-  python tools/decode_mx4_bench.py [--repeats 5] [--tokens 8] [--layers 32] [--out FILE] [--quality FILE]  ->  JSON lines
+  python tools/decode_mx4_bench.py [--repeats 5] [--tokens 8] [--layers 32] [--gemv-only] [--out FILE] [--quality FILE]  ->  JSON lines
 MXFP4 "pays" in a cell when the fp8 token time minus the MXFP4 token time exceeds the spread (max - min) of the fp8 repeats."""
 import argparse
 import json
@@ -20,6 +20,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--repeats", type=int, default=5)
 ap.add_argument("--tokens", type=int, default=8)
 ap.add_argument("--layers", type=int, default=32)
+ap.add_argument("--gemv-only", action="store_true", help="the per-projection GEMV times alone")
 ap.add_argument("--out", default=None, help="also write the records as one JSON list to this file")
 ap.add_argument("--quality", default=None, help="also write the quality records as text lines to this file")
 args = ap.parse_args()
@@ -95,7 +96,7 @@ for n_seq in (1, 8):
               "us": {m: round(us[m], 2) for m in MODES}, "GBps_own_bytes": {m: round(by[m] / us[m] / 1e3, 1) for m in MODES}})
 
 quality = []
-for n_seq in (1, 8):
+for n_seq in (() if args.gemv_only else (1, 8)):
     eng = LlamaEngine.from_prebuilt(hidden=H, n_heads=NH, n_layers=NL, inter=INTER, vocab=VOCAB, dtype=dt, device=dev, cache_cap=512,
                                     max_new=64, max_prefill_rows=128, img_ids=(), eos_id=2, n_seq=n_seq, **shared)
     runs = {m: [] for m in MODES}

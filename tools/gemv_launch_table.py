@@ -8,7 +8,8 @@ The first command runs the grid (no other tracing, no counters); the second join
 case the kernels' names, workgroups, workgroup size and LDS bytes as the trace reports them (static LDS only).
 tests/golden/gemv_launches.json is that output for the library BEFORE the launch-plan refactor of ss_gemv.hip;
 test_gemv_plan_matches_recorded_launches holds ss_gemv_plan to it on a CPU machine.  tools/gemv_hash.py walks the same grid
-and hashes the outputs."""
+and hashes the outputs.  quant_grid() is the grid of the quantised calls (ss_gemv_w8 / ss_gemv_mx4, cases with a "fmt" key):
+run() feeds them codes and scales from seeded CPU generators, never from the library's own quantisers."""
 import csv
 import json
 import os
@@ -71,6 +72,53 @@ def coverage_grid():
                         yield dict(dtype=dtype, nb=nb, rows=rows, K=K, variant=v, knobs=knobs)
 
 
+# the quantised calls: the five LLaMA-7B projections + the four small shapes of tests/test_gemv_w8_gpu.py / test_gemv_mx4_gpu.py
+# (the partial last load, a partial wave slice, the 16-step loop with a partial row tile, the packed loop with fp8's tail and
+# MXFP4's dead slot); an odd row count gains a row for the SiLU pair; no RMSNorm prologue at K = 11008 (the call refuses it)
+Q_SMALL = {"fp8": [(33, 16), (100, 272), (37, 4096), (40, 11008)], "mxfp4": [(33, 32), (100, 288), (37, 4096), (40, 11008)]}
+Q_NBS = [1, 2, 3, 8, 16]
+Q_KNOB_SETS = [{}, {"gemv_mfma_generic": 1}, EDGE_KNOBS]
+
+
+def quant_grid():
+    """-> dicts {fmt, dtype, nb, rows, K, variant, knobs}"""
+    for fmt, small in Q_SMALL.items():
+        for dtype in DTYPES[:2]:
+            for knobs in Q_KNOB_SETS:
+                for rows, K in SHAPES[:5] + small:
+                    for nb in Q_NBS:
+                        for v in VARIANTS:
+                            if "norm" in v and K == 11008:
+                                continue
+                            yield dict(fmt=fmt, dtype=dtype, nb=nb, rows=rows + rows % 2 if "silu" in v else rows, K=K, variant=v, knobs=knobs)
+
+
+def seeded_bytes(seed, n):
+    """n bytes, each a pure function of (seed, index) (oracle/synth.py's generator), filled chunk by chunk"""
+    import numpy as np
+    import synth
+    out = np.empty(n, dtype=np.uint8)
+    for s in range(0, n, 1 << 23):
+        m = min(1 << 23, n - s)
+        out[s:s + m] = np.floor(synth.uniform01(seed, m, start=s) * 256.0)
+    return out
+
+
+def quant_planes(nel, nrows):
+    """CPU planes the quantised cases cut their weights from: every e4m3 code but the two NaNs (0x7f, 0xff -> 0x7e, 0xfe) with
+    fp32 row scales in [0.001, 0.004); e2m1 code pairs with e8m0 scale bytes 127 + X, X in [-13, 7] (triangular around -6: the
+    range of the contract skewed low, so that fp16 outputs stay finite)"""
+    import numpy as np
+    import torch
+    import synth
+    q8 = seeded_bytes(201, nel)
+    q8[(q8 & 0x7f) == 0x7f] ^= 1
+    sb = seeded_bytes(203, nel // 32).astype(np.int64)
+    X = np.clip(((sb & 15) + (sb >> 4) - 15) * 13 // 15 - 6, -13, 13)
+    return {"q8": torch.from_numpy(q8), "s8": synth.uniform(202, (nrows,), 0.001, 0.004),
+            "q4": torch.from_numpy(seeded_bytes(204, nel // 2)), "s4": torch.from_numpy((127 + X).astype(np.uint8))}
+
+
 def run(cases, on_case):
     """one ops.gemv (nb 1) / ops.gemv_batched call per case into a guarded output; on_case(index, case, guarded output) follows,
     then a non-GEMV kernel"""
@@ -87,6 +135,9 @@ def run(cases, on_case):
     base = {"w": synth.normal_like(101, (nel,), std=0.02), "x": synth.normal_like(102, (16, kmax), std=1.0),
             "g": synth.normal_like(103, (kmax,), std=0.1, mean=1.0), "b": synth.normal_like(104, (nmax,), std=0.5),
             "r": synth.normal_like(105, (16, nmax), std=1.0)}
+    qp = {}
+    if any("fmt" in c for c in cases):
+        qp = {k: v.to(dev) for k, v in quant_planes(max(c["rows"] * c["K"] for c in cases if "fmt" in c), nmax).items()}
     marker = torch.zeros(64, device=dev)
     cur = None
     for idx, c in enumerate(cases):
@@ -96,7 +147,13 @@ def run(cases, on_case):
         rows, K, nb, v = c["rows"], c["K"], c["nb"], c["variant"]
         silu = "silu" in v
         N = rows // 2 if silu else rows
-        w = t["w"][:rows * K].view(rows, K)
+        fmt = c.get("fmt")
+        if fmt == "fp8":
+            w = (qp["q8"][:rows * K].view(rows, K), qp["s8"][:rows])
+        elif fmt == "mxfp4":
+            w = (qp["q4"][:rows * K // 2].view(rows, K // 2), qp["s4"][:rows * K // 32].view(rows, K // 32))
+        else:
+            w = t["w"][:rows * K].view(rows, K)
         x = t["x"][:nb, :K].contiguous()
         kw = dict(norm_w=t["g"][:K].contiguous() if "norm" in v else None, eps=1e-5, silu_mul=silu)
         if v == "bias+res":
@@ -108,7 +165,9 @@ def run(cases, on_case):
         torch.cuda.synchronize()
         marker.add_(1.0)                                   # the cut between two cases' GEMV kernels
         try:
-            if nb == 1:
+            if fmt:
+                (ops.gemv_w8 if fmt == "fp8" else ops.gemv_mx4)(*w, x, out=g.out, **kw)
+            elif nb == 1:
                 ops.gemv(w, x[0], out=g.view(N), **kw)
             else:
                 ops.gemv_batched(w, x, out=g.out, **kw)
