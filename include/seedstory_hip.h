@@ -1003,6 +1003,23 @@ int ss_euler_cfg_step(void* x, const void* eps, int64_t n, float guidance, float
  * c / inv_next, an unknown dtype. */
 int ss_multistep_cfg_step(float* state, const void* eps, void* x_out, void* xin_next, int64_t n, float guidance,
                           float sigma, float a, float b, float c, float inv_next, int dtype, void* stream);
+/* Limited-interval guidance (CFG only while sigma_lo < sigma <= sigma_hi): the same step for a forward that
+ * ran on [uncond; cond] (eps_rows 2) or on the conditional rows alone (eps_rows 1), writing the next step's input once
+ * (xin_rows 1: the next step is unguided) or twice (xin_rows 2).
+ *   eps_rows 2: e = eps[0] + guidance * (eps[1] - eps[0])     eps_rows 1: e = eps[0] as loaded, guidance is not used
+ *   d = x - sigma * e;  x' = a * x + b * d + c * d_prev;  state <- (x', d);  x_out = rnd(x');
+ *   xin_next[0 .. xin_rows) = rnd(x' * inv_next)
+ * eps is [eps_rows, n] and xin_next [xin_rows, n]: a row the form does not have is neither read nor written.  Operation
+ * order, packets, tail, unaligned bases and the c == 0 rule are ss_multistep_cfg_step's; (2, 2) is bit-equal to it.
+ * SS_EINVAL before anything is launched or written: as ss_multistep_cfg_step, and eps_rows or xin_rows outside {1, 2}. */
+int ss_multistep_step(float* state, const void* eps, void* x_out, void* xin_next, int64_t n, int eps_rows, int xin_rows,
+                      float guidance, float sigma, float a, float b, float c, float inv_next, int dtype, void* stream);
+/* Unguided Euler step: x += rnd(eps * (sigma_next - sigma)), eps [n] the conditional prediction (ss_euler_cfg_step
+ * without its guidance arithmetic, same rounding point).  SS_EINVAL: n <= 0, NULL x or eps, unknown dtype. */
+int ss_euler_step(void* x, const void* eps, int64_t n, float sigma, float sigma_next, int dtype, void* stream);
+/* scale_model_input into `rows` copies: xin[0 .. rows) = x / sqrt(sigma^2+1); rows 2 is bit-equal to ss_euler_scale_dup,
+ * rows 1 writes n elements only.  SS_EINVAL: n <= 0, NULL x or xin, rows outside {1, 2}, unknown dtype. */
+int ss_euler_scale(const void* x, void* xin, int64_t n, int rows, float sigma, int dtype, void* stream);
 /* Image pre-processing on the device: the reference's `image_transform(image).to(device, dtype)`
  * (src/processer/transforms.py:4-19 = torchvision Resize [+ CenterCrop] on a PIL image, ToTensor, Normalize;
  * gen_george.py:166).  The resize is Pillow's 8-bit separable resampler restated bit-exactly: 22-bit fixed-point

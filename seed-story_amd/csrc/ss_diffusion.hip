@@ -381,14 +381,18 @@ __global__ void euler_cfg_step_kernel(T* __restrict__ x, const T* __restrict__ e
 //   xin_next[0] = xin_next[1] = rnd_T(x' inv_next)
 // The solver state is fp32 and is never rounded to T between steps (a second-order difference of rounded states is where bf16
 // would hurt).  c == 0: d_prev is not read (first step: uninitialised).
-__device__ __forceinline__ void multistep_one(float& x, float& dprev, float eu, float ec, bool prev, float g, float sigma,
-                                              float a, float b, float c) {
-    const float e = eu + g * (ec - eu);
+// the solver update for a given e (the guided combination, or the conditional prediction alone)
+__device__ __forceinline__ void multistep_apply(float& x, float& dprev, float e, bool prev, float sigma, float a, float b,
+                                                float c) {
     const float d = x - sigma * e;
     float xn = a * x + b * d;
     if (prev) xn += c * dprev;
     x = xn;
     dprev = d;
+}
+__device__ __forceinline__ void multistep_one(float& x, float& dprev, float eu, float ec, bool prev, float g, float sigma,
+                                              float a, float b, float c) {
+    multistep_apply(x, dprev, eu + g * (ec - eu), prev, sigma, a, b, c);
 }
 // V fp32 values at p: 16-byte accesses when `vec`, single elements otherwise (second rows of an n that is no multiple of V)
 template <int V>
@@ -463,6 +467,86 @@ __global__ __launch_bounds__(256) void multistep_cfg_step_kernel(float* __restri
             Tr<T>::st(xin_next + i, v);
             Tr<T>::st(xin_next + n + i, v);
         }
+    }
+}
+
+// The same step for limited-interval guidance (ss_multistep_step): ER rows of eps are read, XR rows of xin_next written.
+// ER == 2: e = eu + g (ec - eu) as above.  ER == 1: eps holds the conditional prediction alone and e is that value as loaded
+// (no arithmetic, g unused).  XR == 1: the next step is unguided and takes one copy of rnd_T(x' inv_next).  Rows that a form
+// does not use are never addressed: eps and xin_next may be one row long.  Packets as above: second rows (state row 1 always,
+// eps / xin_next row 1 when the form has one) are 16-byte accesses only when row1_vec.
+template <typename T, int ER, int XR>
+__global__ __launch_bounds__(256) void multistep_step_kernel(float* __restrict__ state, const T* __restrict__ eps,
+                                                             T* __restrict__ x_out, T* __restrict__ xin_next, int64_t n,
+                                                             int64_t npack, int row1_vec, float g, float sigma, float a, float b,
+                                                             float c, float inv_next) {
+    constexpr int V = Tr<T>::kVec;
+    const bool prev = c != 0.0f;
+    const bool v1 = row1_vec != 0;
+    const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t p = tid; p < npack; p += stride) {
+        const int64_t i = p * V;
+        float x[V], dp[V], e0[V], ec[V], xs[V];      // e0: row 0 of eps (uncond when ER == 2, cond when ER == 1)
+        ld_f32<V>(state + i, true, x);
+        unpack<T>(ld16(eps + i), e0);
+        if (ER == 2) {
+            if (v1) {
+                unpack<T>(ld16(eps + n + i), ec);
+            } else {
+#pragma unroll
+                for (int j = 0; j < V; ++j) ec[j] = Tr<T>::ld(eps + n + i + j);
+            }
+        }
+        if (prev) ld_f32<V>(state + n + i, v1, dp);
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            if (ER == 2) multistep_one(x[j], dp[j], e0[j], ec[j], prev, g, sigma, a, b, c);
+            else multistep_apply(x[j], dp[j], e0[j], prev, sigma, a, b, c);
+            xs[j] = x[j] * inv_next;
+        }
+        st_f32<V>(state + i, true, x);
+        st_f32<V>(state + n + i, v1, dp);
+        if (x_out) st16(x_out + i, pack<T>(x));
+        if (xin_next) {
+            const uint4 u = pack<T>(xs);
+            st16(xin_next + i, u);
+            if (XR == 2) {
+                if (v1) {
+                    st16(xin_next + n + i, u);
+                } else {
+#pragma unroll
+                    for (int j = 0; j < V; ++j) Tr<T>::st(xin_next + n + i + j, xs[j]);
+                }
+            }
+        }
+    }
+    for (int64_t i = npack * V + tid; i < n; i += stride) {
+        float x = state[i], dp = prev ? state[n + i] : 0.f;
+        if (ER == 2) multistep_one(x, dp, Tr<T>::ld(eps + i), Tr<T>::ld(eps + n + i), prev, g, sigma, a, b, c);
+        else multistep_apply(x, dp, Tr<T>::ld(eps + i), prev, sigma, a, b, c);
+        state[i] = x;
+        state[n + i] = dp;
+        if (x_out) Tr<T>::st(x_out + i, x);
+        if (xin_next) {
+            const float v = x * inv_next;
+            Tr<T>::st(xin_next + i, v);
+            if (XR == 2) Tr<T>::st(xin_next + n + i, v);
+        }
+    }
+}
+// Unguided Euler step: x += rnd_T(ec dsigma) (euler_cfg_step_kernel without its CFG lines); scale_model_input into `rows`
+// copies (rows == 2 is euler_scale_dup_kernel)
+template <typename T>
+__global__ void euler_step_kernel(T* __restrict__ x, const T* __restrict__ eps, int64_t n, float dsigma) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        Tr<T>::st(x + i, Tr<T>::ld(x + i) + Tr<T>::rnd(Tr<T>::ld(eps + i) * dsigma));
+}
+template <typename T>
+__global__ void euler_scale_kernel(const T* __restrict__ x, T* __restrict__ xin, int64_t n, int rows, float inv) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const float v = Tr<T>::ld(x + i) * inv;
+        Tr<T>::st(xin + i, v);
+        if (rows == 2) Tr<T>::st(xin + n + i, v);
     }
 }
 
@@ -573,6 +657,38 @@ int multistep_cfg_step_launch(float* state, const void* eps, void* x_out, void* 
     return SS_OK;
 }
 template <typename T>
+int multistep_step_launch(float* state, const void* eps, void* x_out, void* xin_next, int64_t n, int eps_rows, int xin_rows,
+                          float g, float sigma, float a, float b, float c, float inv_next, hipStream_t s) {
+    constexpr int V = Tr<T>::kVec;
+    const uintptr_t bases = (uintptr_t)state | (uintptr_t)eps | (uintptr_t)x_out | (uintptr_t)xin_next;   // NULL: no bits
+    const int64_t npack = (bases & 15) == 0 ? n / V : 0;
+    const int row1_vec = npack > 0 && n % V == 0;
+    const dim3 grid(egrid(npack + (n - npack * V)));
+#define SS_MS_FORM(ER, XR)                                                                                              \
+    hipLaunchKernelGGL((multistep_step_kernel<T, ER, XR>), grid, dim3(256), 0, s, state, (const T*)eps, (T*)x_out,        \
+                       (T*)xin_next, n, npack, row1_vec, g, sigma, a, b, c, inv_next)
+    if (eps_rows == 2 && xin_rows == 2) SS_MS_FORM(2, 2);
+    else if (eps_rows == 2) SS_MS_FORM(2, 1);
+    else if (xin_rows == 2) SS_MS_FORM(1, 2);
+    else SS_MS_FORM(1, 1);
+#undef SS_MS_FORM
+    SS_LAUNCH_CHECK("multistep_step");
+    return SS_OK;
+}
+template <typename T>
+int euler_step_launch(void* x, const void* eps, int64_t n, float sigma, float sigma_next, hipStream_t s) {
+    hipLaunchKernelGGL(euler_step_kernel<T>, dim3(egrid(n)), dim3(256), 0, s, (T*)x, (const T*)eps, n, sigma_next - sigma);
+    SS_LAUNCH_CHECK("euler_step");
+    return SS_OK;
+}
+template <typename T>
+int euler_scale_launch(const void* x, void* xin, int64_t n, int rows, float sigma, hipStream_t s) {
+    hipLaunchKernelGGL(euler_scale_kernel<T>, dim3(egrid(n)), dim3(256), 0, s, (const T*)x, (T*)xin, n, rows,
+                       1.0f / sqrtf(sigma * sigma + 1.0f));
+    SS_LAUNCH_CHECK("euler_scale");
+    return SS_OK;
+}
+template <typename T>
 int image_to_u8_launch(const void* in, void* out, int64_t pixels, int64_t Cpad, hipStream_t s) {
     hipLaunchKernelGGL(image_to_u8_kernel<T>, dim3(egrid(pixels * 3)), dim3(256), 0, s, (const T*)in, (uint8_t*)out, pixels,
                        (int)Cpad);
@@ -634,6 +750,30 @@ int ss_multistep_cfg_step(float* state, const void* eps, void* x_out, void* xin_
                "multistep_cfg_step: unknown dtype %d or misaligned state", dtype);
     return SS_DISPATCH(dtype, multistep_cfg_step_launch, state, eps, x_out, xin_next, n, guidance, sigma, a, b, c, inv_next,
                        (hipStream_t)stream);
+}
+int ss_multistep_step(float* state, const void* eps, void* x_out, void* xin_next, int64_t n, int eps_rows, int xin_rows,
+                      float guidance, float sigma, float a, float b, float c, float inv_next, int dtype, void* stream) {
+    SS_REQUIRE(n > 0, "multistep_step: n = %lld", (long long)n);
+    SS_REQUIRE(state != nullptr && eps != nullptr, "multistep_step: NULL state or eps");
+    SS_REQUIRE((eps_rows == 1 || eps_rows == 2) && (xin_rows == 1 || xin_rows == 2),
+               "multistep_step: eps_rows %d / xin_rows %d (1 or 2)", eps_rows, xin_rows);
+    SS_REQUIRE(std::isfinite(guidance) && std::isfinite(sigma) && std::isfinite(a) && std::isfinite(b) && std::isfinite(c) &&
+                   std::isfinite(inv_next),
+               "multistep_step: non-finite coefficient (guidance %g sigma %g a %g b %g c %g inv_next %g)", (double)guidance,
+               (double)sigma, (double)a, (double)b, (double)c, (double)inv_next);
+    SS_REQUIRE((uintptr_t)state % sizeof(float) == 0 && (dtype == SS_F32 || dtype == SS_BF16 || dtype == SS_F16),
+               "multistep_step: unknown dtype %d or misaligned state", dtype);
+    return SS_DISPATCH(dtype, multistep_step_launch, state, eps, x_out, xin_next, n, eps_rows, xin_rows, guidance, sigma, a, b,
+                       c, inv_next, (hipStream_t)stream);
+}
+int ss_euler_step(void* x, const void* eps, int64_t n, float sigma, float sigma_next, int dtype, void* stream) {
+    SS_REQUIRE(n > 0 && x != nullptr && eps != nullptr, "euler_step: n = %lld or NULL x / eps", (long long)n);
+    return SS_DISPATCH(dtype, euler_step_launch, x, eps, n, sigma, sigma_next, (hipStream_t)stream);
+}
+int ss_euler_scale(const void* x, void* xin, int64_t n, int rows, float sigma, int dtype, void* stream) {
+    SS_REQUIRE(n > 0 && x != nullptr && xin != nullptr, "euler_scale: n = %lld or NULL x / xin", (long long)n);
+    SS_REQUIRE(rows == 1 || rows == 2, "euler_scale: rows %d (1 or 2)", rows);
+    return SS_DISPATCH(dtype, euler_scale_launch, x, xin, n, rows, sigma, (hipStream_t)stream);
 }
 int ss_image_to_u8(const void* in, void* out_u8, int64_t pixels, int64_t cpad, int dtype, void* stream) {
     return SS_DISPATCH(dtype, image_to_u8_launch, in, out_u8, pixels, cpad, (hipStream_t)stream);

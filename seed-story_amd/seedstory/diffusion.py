@@ -428,7 +428,9 @@ class UNet2DConditionModel(nn.Module):
             self._kv_gen = getattr(self, "_kv_gen", 0) + 1      # a captured forward does not know this buffer
         return {"buf": b, "cur": None}
 
-    def _transformer(self, P, n, x, B, HW, ctx2d, Lctx, heads, layers, groups):
+    def _transformer(self, P, n, x, B, HW, ctx2d, Lctx, heads, layers, groups, kv_row0=0):
+        """``ctx2d`` is the context the cross-attention K/V are computed over and cached for; this forward attends to its rows
+        ``kv_row0 : kv_row0 + B * Lctx`` (0 and everything, unless the forward is the half-batch form, see ``forward``)."""
         h = ops.groupnorm(x, P[n + ".norm.weight"], P[n + ".norm.bias"], B, groups, 1e-6, silu=False)
         # producer-carried LayerNorm statistics: every GEMM that writes h (proj_in, attn1/attn2 to_out, ff.net.2)
         # accumulates the row sums the NEXT norm needs while it stores h; requires the folded form of all three norms
@@ -457,6 +459,8 @@ class UNet2DConditionModel(nn.Module):
                     buf = self._ctx_kv_buf[b] = torch.empty(ctx2d.shape[0], w.shape[0], dtype=ctx2d.dtype, device=ctx2d.device)
                     self._kv_gen = getattr(self, "_kv_gen", 0) + 1      # a captured forward holding the old address is stale
                 kv = self._ctx_kv[b] = ops.gemm(ctx2d, w, out=buf)
+            if kv_row0:
+                kv = kv[kv_row0:]      # the conditional half: a contiguous view of the block's buffer, no GEMM, no copy
             a = ops.attention_q_kvpacked(q, kv, B, HW, Lctx, heads)
             h = self._lin(P, b + ".attn2.to_out.0.weight", a, bias=P[b + ".attn2.to_out.0.bias"], residual=h, rowstat=rs)
             u = self._lin_ln(P, b + ".ff.net.0.proj.pairs.weight", h, (P[b + ".norm3.weight"], P[b + ".norm3.bias"], 1e-5),
@@ -467,7 +471,13 @@ class UNet2DConditionModel(nn.Module):
 
     @torch.no_grad()
     def forward(self, sample, timestep, encoder_hidden_states, added_cond_kwargs=None, return_dict=True, **kw):
-        """sample [B,4,h,w] NCHW (diffusers convention) -> eps [B,4,h,w]."""
+        """sample [B,4,h,w] NCHW (diffusers convention) -> eps [B,4,h,w].
+
+        Private keywords: ``temb_in`` (the timestep embedding as a device tensor, for graph replay) and ``ctx_kv_of`` — the
+        half-batch form of limited-interval guidance: ``encoder_hidden_states`` is the trailing B rows (a view) of the context
+        ``ctx_kv_of``, and the cross-attention K/V are computed, cached and keyed over that FULL context exactly as a forward on
+        it does; this forward reads the trailing ``B * Lctx`` rows of each block's K/V buffer.  So alternating the two forms
+        neither recomputes the K/V nor reallocates the buffers captured forwards read, whichever form runs first."""
         c = self.cfg
         P = self._prepare()
         dt, dev = sample.dtype, sample.device
@@ -485,17 +495,28 @@ class UNet2DConditionModel(nn.Module):
         tid = self._tid_cache.get(tkey) if tkey is not None and hasattr(self, "_tid_cache") else None
         if tid is None:                   # constant of (height, width): embedded on the host once, kept on the device
             tid = timestep_embedding(tids.flatten().cpu(), c["addition_time_embed_dim"]).reshape(B, -1).to(device=dev, dtype=dt)
-            if tkey is not None:
-                self._tid_cache = {tkey: tid}
+            if tkey is not None:       # one entry per form of the forward (batch 2B / B): a captured forward reads its entry
+                if not hasattr(self, "_tid_cache") or len(self._tid_cache) >= 8:
+                    if getattr(self, "_tid_cache", None):
+                        self._kv_gen = getattr(self, "_kv_gen", 0) + 1      # captured forwards read the dropped tensors
+                    self._tid_cache = {}
+                self._tid_cache[tkey] = tid
         add = torch.cat([added_cond_kwargs["text_embeds"].to(dt), tid], dim=-1).contiguous()
         emb = ops.gemm(ops.silu(ops.gemm(add, P["add_embedding.linear_1.weight"], bias=P["add_embedding.linear_1.bias"])),
                        P["add_embedding.linear_2.weight"], bias=P["add_embedding.linear_2.bias"], residual=emb)
         temb_act = ops.silu(emb)                                            # F.silu(temb) feeds every ResBlock
         temb_act = ops.gemm(temb_act, P["temb_all.weight"], bias=P["temb_all.bias"])   # all time_emb_proj at once
-        ctx = encoder_hidden_states.to(dt).contiguous()
-        Lctx = ctx.shape[1]
-        ctx2d = ctx.view(B * Lctx, -1)
-        ckey = (encoder_hidden_states.data_ptr(), encoder_hidden_states._version, tuple(ctx.shape), dt, id(P))
+        Lctx = encoder_hidden_states.shape[1]
+        kv_src = kw.get("ctx_kv_of")
+        if kv_src is None:
+            kv_src = encoder_hidden_states
+        elif kv_src.shape[0] < B or tuple(kv_src.shape[1:]) != tuple(encoder_hidden_states.shape[1:]):
+            raise _lib.SSError("ctx_kv_of %s does not contain the %d context rows %s" % (tuple(kv_src.shape), B,
+                                                                                         tuple(encoder_hidden_states.shape)))
+        ctx = kv_src.to(dt).contiguous()
+        kv_row0 = (ctx.shape[0] - B) * Lctx if kv_src is not encoder_hidden_states else 0
+        ctx2d = ctx.view(kv_row0 + B * Lctx, -1)
+        ckey = (kv_src.data_ptr(), kv_src._version, tuple(ctx.shape), dt, id(P))
         if getattr(self, "_ctx_key", None) != ckey:       # new conditioning (new image): drop the cached cross-attn K/V
             self._ctx_key, self._ctx_kv = ckey, {}
 
@@ -507,7 +528,7 @@ class UNet2DConditionModel(nn.Module):
                 h = self._resnet(P, "down_blocks.%d.resnets.%d" % (i, j), h, B, H, W, temb_act, G)
                 if c["transformer_layers"][i]:
                     h = self._transformer(P, "down_blocks.%d.attentions.%d" % (i, j), h, B, H * W, ctx2d, Lctx,
-                                          c["num_heads"][i], c["transformer_layers"][i], G)
+                                          c["num_heads"][i], c["transformer_layers"][i], G, kv_row0)
                 skips.append((h, H, W))
             if i < len(boc) - 1:
                 n = "down_blocks.%d.downsamplers.0.conv" % i
@@ -515,7 +536,7 @@ class UNet2DConditionModel(nn.Module):
                 skips.append((h, H, W))
         h = self._resnet(P, "mid_block.resnets.0", h, B, H, W, temb_act, G)
         h = self._transformer(P, "mid_block.attentions.0", h, B, H * W, ctx2d, Lctx, c["num_heads"][-1],
-                              c["transformer_layers"][-1], G)
+                              c["transformer_layers"][-1], G, kv_row0)
         h = self._resnet(P, "mid_block.resnets.1", h, B, H, W, temb_act, G)
         for i in range(len(boc)):
             ri = len(boc) - 1 - i
@@ -525,7 +546,7 @@ class UNet2DConditionModel(nn.Module):
                 h = self._resnet(P, "up_blocks.%d.resnets.%d" % (i, j), h, B, H, W, temb_act, G)
                 if c["transformer_layers"][ri]:
                     h = self._transformer(P, "up_blocks.%d.attentions.%d" % (i, j), h, B, H * W, ctx2d, Lctx,
-                                          c["num_heads"][ri], c["transformer_layers"][ri], G)
+                                          c["num_heads"][ri], c["transformer_layers"][ri], G, kv_row0)
             if i < len(boc) - 1:
                 n = "up_blocks.%d.upsamplers.0.conv" % i
                 h, H, W = ops.conv3x3(h, P[n + ".weight"], B, H, W, upsample=True, bias=P[n + ".bias"])
@@ -843,6 +864,25 @@ class DPMSolverMultistepScheduler:
         self.coefficients = coef
 
 
+def guidance_mask(sigmas, interval):
+    """Limited-interval guidance (Kynkäänniemi et al., NeurIPS 2024): which steps apply classifier-free guidance.
+
+    ``sigmas[i]`` is the level the UNet is evaluated at in step i, in the sampler's own units; ``interval`` is None (every
+    step is guided) or ``(sigma_lo, sigma_hi)``: step i is guided iff ``sigma_lo < sigmas[i] <= sigma_hi``.  An unguided step
+    runs the UNet on the conditional rows alone and takes that prediction as it is.  ``sigma_hi`` may be ``math.inf``; an
+    interval that holds no step of the schedule is legal (no step is guided).  ValueError: a NaN bound, ``sigma_lo < 0``,
+    ``sigma_hi <= sigma_lo``, or anything that is not a pair of numbers."""
+    if interval is None:
+        return [True] * len(sigmas)
+    try:
+        lo, hi = (float(v) for v in interval)
+    except (TypeError, ValueError):
+        raise ValueError("guidance_interval must be None or (sigma_lo, sigma_hi), not %r" % (interval,))
+    if math.isnan(lo) or math.isnan(hi) or lo < 0.0 or hi <= lo:
+        raise ValueError("guidance_interval=(%r, %r): needs 0 <= sigma_lo < sigma_hi (sigma_hi may be inf)" % (lo, hi))
+    return [lo < float(s) <= hi for s in sigmas]
+
+
 class _PipeOut:
     def __init__(self, images):
         self.images = images
@@ -855,6 +895,8 @@ class StableDiffusionXLPipeline:
     def __init__(self, vae, unet, scheduler, tokenizer=None, tokenizer_2=None, text_encoder=None, text_encoder_2=None,
                  **kw):
         self.vae, self.unet, self.scheduler = vae, unet, scheduler
+        self.guidance_interval = None        # default of __call__(guidance_interval=): None = guide every step
+        self.last_guidance = None            # what the last call did: {"mask": [guided?], "unet_batches": [rows per forward]}
 
     def _stable(self, name, value):
         """Conditioning lives in buffers that keep their address across calls (same shape/dtype): the captured UNet
@@ -872,10 +914,11 @@ class StableDiffusionXLPipeline:
             cur.copy_(value)
         return cur
 
-    def _unet_graph(self, xin, ctx, cond, ts, n_steps):
+    def _unet_graph(self, xin, ctx, cond, ts, n_steps, unet_kw=None):
         """hipGraph of ONE UNet forward (all ~1700 launches), captured once per (shape, conditioning buffers) and
         replayed for steps 1..n-1 of every render: removes the per-launch gaps (~5 % of a forward at batch 8, ~10 %
-        at batch 2).  Returns None (eager fallback) if capture is not possible."""
+        at batch 2).  Returns None (eager fallback) if capture is not possible.  ``unet_kw``: further keywords of the forward
+        (the half-batch form of limited-interval guidance; its shapes give it an entry of its own)."""
         graphs = self.__dict__.setdefault("_graphs", {})
         # identity = shapes + GENERATION counters of every buffer the captured launches read (conditioning buffers,
         # per-block cross-attention K/V buffers, prepared weights) — never raw addresses or id(): those are reused
@@ -898,7 +941,7 @@ class StableDiffusionXLPipeline:
             torch.cuda.synchronize()
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                eps = self.unet(sx, None, ctx, added_cond_kwargs=cond, return_dict=False, temb_in=st)[0]
+                eps = self.unet(sx, None, ctx, added_cond_kwargs=cond, return_dict=False, temb_in=st, **(unet_kw or {}))[0]
             ent = graphs[key] = {"g": g, "x": sx, "temb": st, "eps": eps, "temb_table": table}
             return ent
         except Exception as ex:      # keep rendering eagerly
@@ -911,12 +954,25 @@ class StableDiffusionXLPipeline:
     @torch.no_grad()
     def __call__(self, prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds,
                  guidance_scale=7.5, num_inference_steps=30, generator=None, height=1024, width=1024, latents=None,
-                 output_type="pil", **kw):
+                 output_type="pil", guidance_interval=None, **kw):
+        """``guidance_interval`` = (sigma_lo, sigma_hi), default ``self.guidance_interval``: classifier-free guidance only on the
+        steps with sigma_lo < sigma <= sigma_hi (``guidance_mask``); the other steps run the UNet on the B conditional rows and
+        take that prediction.  None: every step is guided, on the code path that knows nothing of the option."""
         dev, dt = prompt_embeds.device, prompt_embeds.dtype
         lh, lw = height // 8, width // 8
         B = prompt_embeds.shape[0]           # images rendered together (UNet batch 2B: [B uncond; B cond])
+        interval = self.guidance_interval if guidance_interval is None else guidance_interval
+        guidance_mask((), interval)          # a bad interval is refused before anything is launched
         self.unet._ctx_key = None            # new conditioning: recompute the cached cross-attention K/V
         sampler = self._sampler()
+        sampler.set_timesteps(num_inference_steps)
+        mask = guidance_mask(sampler.sigmas[:num_inference_steps], interval)
+        self.last_guidance = {"mask": mask, "unet_batches": [2 * B if g else B for g in mask]}
+        if not all(mask):
+            x = self._denoise_interval(sampler, mask, prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds,
+                                       negative_pooled_prompt_embeds, guidance_scale, num_inference_steps, generator, height,
+                                       width, latents)
+            return self._finish(x, output_type)
         if isinstance(sampler, DPMSolverMultistepScheduler):
             x = self._denoise_multistep(sampler, prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds,
                                         negative_pooled_prompt_embeds, guidance_scale, num_inference_steps, generator, height,
@@ -1014,6 +1070,84 @@ class StableDiffusionXLPipeline:
             ops.multistep_cfg_step_(state, eps.contiguous(), guidance_scale, float(sig[i]), a, b, c,
                                     1.0 / math.sqrt(float(sig[i + 1]) ** 2 + 1.0), x_out=x_out if last else None, xin_next=nxt)
         return x_out
+
+    def _denoise_interval(self, sched, mask, prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds,
+                          negative_pooled_prompt_embeds, guidance_scale, num_inference_steps, generator, height, width, latents):
+        """The denoising loop when ``mask`` has unguided steps, for both samplers.  The UNet has two forms over the SAME stable
+        conditioning buffers: guided, batch 2B on [uncond; cond], and unguided, batch B on views of the conditional half
+        (rows B: of ctx and pooled, the last B rows of time_ids; cross-attention K/V: the trailing rows of the buffers computed
+        once over the full context, ``ctx_kv_of``).  Each form has its own captured graph: its first occurrence in a render
+        runs eagerly (refreshes the K/V if it is the render's first forward, lets the GEMM autotuner see its shapes), the
+        graph is captured — or found — right after, later occurrences replay it.  Every step's update writes the next input,
+        in one copy or two, straight into the buffer the next step's form reads: its graph's ``x``, or a plain tensor while
+        that form has not run yet.  DPM++: one launch per step (``ss_multistep_step``), d_prev is the previous step's d,
+        guided or not.  Euler: ``ss_euler_cfg_step`` | ``ss_euler_step``, then ``ss_euler_scale``."""
+        dev, dt = prompt_embeds.device, prompt_embeds.dtype
+        lh, lw = height // 8, width // 8
+        B = prompt_embeds.shape[0]
+        multistep = isinstance(sched, DPMSolverMultistepScheduler)
+        sig, ts = sched.sigmas, sched.timesteps                # set_timesteps ran in __call__
+        if latents is None:
+            latents = torch.randn((B, 4, lh, lw), generator=generator, device=dev, dtype=dt)
+        assert latents.shape[0] == B
+        x = (latents.to(device=dev, dtype=dt) * sched.init_noise_sigma).contiguous()
+        n = x.numel()
+        if multistep:
+            bufs = self.__dict__.setdefault("_ms_state", {})
+            state = bufs.get((n, str(dev)))
+            if state is None:
+                state = bufs[(n, str(dev))] = torch.empty(2, n, dtype=torch.float32, device=dev)
+            state[0].copy_(x.view(-1))
+            x_out = torch.empty_like(x)
+        time_ids = torch.tensor([[height, width, 0, 0, height, width]] * (2 * B), dtype=torch.float32)
+        ctx = self._stable("ctx", torch.cat([negative_prompt_embeds, prompt_embeds], dim=0))
+        pooled = self._stable("pooled", torch.cat([negative_pooled_prompt_embeds, pooled_prompt_embeds], dim=0))
+        # form (guided?) -> rows of the UNet batch per image, context, added conditioning, private keywords
+        forms = {True: (2, ctx, {"text_embeds": pooled, "time_ids": time_ids}, {}),
+                 False: (1, ctx[B:], {"text_embeds": pooled[B:], "time_ids": time_ids[B:]}, {"ctx_kv_of": ctx})}
+        use_graph = _lib.get_tuning("unet_graph", 1) != 0 and num_inference_steps > 2
+        graph = {True: None, False: None}        # this render's graph of each form, once the form has run eagerly
+        graphs = self.__dict__.setdefault("_graphs", {})
+
+        def target(g):                            # where the input of a step of form g is written
+            if graph[g] is not None:
+                return graph[g]["x"]
+            return torch.empty(forms[g][0] * B, 4, lh, lw, dtype=dt, device=dev)
+
+        xin = ops.euler_scale(x, float(sig[0]), forms[mask[0]][0], out=target(mask[0]))
+        for i in range(num_inference_steps):
+            g = mask[i]
+            rows, fctx, fcond, fkw = forms[g]
+            if graph[g] is None:
+                eps = self.unet(xin.view(rows * B, 4, lh, lw), float(ts[i]), fctx, added_cond_kwargs=fcond, return_dict=False,
+                                **fkw)[0]
+                if use_graph and any(mask[j] == g for j in range(i + 1, num_inference_steps)):
+                    graph[g] = self._unet_graph(xin.view(rows * B, 4, lh, lw), fctx, fcond, ts, num_inference_steps, fkw)
+                    use_graph = graph[g] is not None          # capture is not possible: render eagerly
+                    # a generation that moved during this form's eager run (a buffer it had to allocate) has dropped the other
+                    # form's entry: that form then runs eagerly once more and is captured again, in this render
+                    if graph[not g] is not None and not any(v is graph[not g] for v in graphs.values()):
+                        graph[not g] = None
+            else:
+                graph[g]["temb"].copy_(graph[g]["temb_table"][i])
+                graph[g]["g"].replay()
+                eps = graph[g]["eps"]
+            last = i + 1 == num_inference_steps
+            gn = None if last else mask[i + 1]
+            if multistep:
+                a, b, c = (float(v) for v in sched.coefficients[i])
+                xin = None if last else target(gn)
+                ops.multistep_step_(state, eps.contiguous(), guidance_scale, float(sig[i]), a, b, c,
+                                    1.0 / math.sqrt(float(sig[i + 1]) ** 2 + 1.0), eps_rows=rows, x_out=x_out if last else None,
+                                    xin_next=xin, xin_rows=1 if last else forms[gn][0])
+            else:
+                if g:
+                    ops.euler_cfg_step_(x, eps.contiguous(), guidance_scale, float(sig[i]), float(sig[i + 1]))
+                else:
+                    ops.euler_step_(x, eps.contiguous(), float(sig[i]), float(sig[i + 1]))
+                if not last:
+                    xin = ops.euler_scale(x, float(sig[i + 1]), forms[gn][0], out=target(gn))
+        return x_out if multistep else x
 
     def _finish(self, x, output_type):
         B = x.shape[0]

@@ -848,6 +848,51 @@ def multistep_cfg_step_(state, eps, guidance, sigma, a, b, c, inv_next, x_out=No
     return state
 
 
+def multistep_step_(state, eps, guidance, sigma, a, b, c, inv_next, eps_rows=2, x_out=None, xin_next=None, xin_rows=2):
+    """``multistep_cfg_step_`` for limited-interval guidance (``ss_multistep_step``): eps is [eps_rows, n] — [uncond; cond], or
+    the conditional prediction alone (``eps_rows`` 1: e = ec, ``guidance`` unused) — and ``xin_next`` [xin_rows, n] receives one
+    copy of the next step's scaled input (the next step is unguided) or two."""
+    _req(state, "state"); _req(eps, "eps")
+    if eps_rows not in (1, 2) or xin_rows not in (1, 2):
+        raise _lib.SSError("multistep_step: eps_rows %r / xin_rows %r must be 1 or 2" % (eps_rows, xin_rows))
+    n = state.numel() // 2
+    if state.dtype != torch.float32 or state.numel() != 2 * n or eps.numel() != eps_rows * n or n == 0:
+        raise _lib.SSError("multistep_step: state must be fp32 [2, n] for eps [%d, n]" % eps_rows)
+    for t, name, cnt in ((x_out, "x_out", n), (xin_next, "xin_next", xin_rows * n)):
+        if t is not None:
+            _req(t, name)
+            if t.dtype != eps.dtype or t.numel() != cnt or t.device != eps.device:
+                raise _lib.SSError("multistep_step: %s must hold %d %s elements on %s" % (name, cnt, eps.dtype, eps.device))
+    check(lib().ss_multistep_step(p(state), p(eps), p(x_out), p(xin_next), n, eps_rows, xin_rows, float(guidance), float(sigma),
+                                  float(a), float(b), float(c), float(inv_next), dt(eps), stream()), "ss_multistep_step")
+    return state
+
+
+def euler_step_(x, eps, sigma, sigma_next):
+    """Unguided Euler step in place: x += eps * (sigma_next - sigma), eps the conditional prediction (``ss_euler_step``)."""
+    _req(x, "x"); _req(eps, "eps")
+    if eps.numel() != x.numel() or eps.dtype != x.dtype or eps.device != x.device:
+        raise _lib.SSError("euler_step: eps must hold %d %s elements on %s" % (x.numel(), x.dtype, x.device))
+    check(lib().ss_euler_step(p(x), p(eps), x.numel(), float(sigma), float(sigma_next), dt(x), stream()), "ss_euler_step")
+    return x
+
+
+def euler_scale(x, sigma, rows=2, out=None):
+    """scale_model_input into ``rows`` (1 | 2) copies: [rows, *x.shape] = x / sqrt(sigma^2 + 1) (``ss_euler_scale``); ``out``:
+    a tensor of rows * x.numel() elements to write into (a captured forward's input buffer)."""
+    _req(x, "x")
+    if rows not in (1, 2):
+        raise _lib.SSError("euler_scale: rows %r must be 1 or 2" % (rows,))
+    if out is None:
+        out = torch.empty((rows,) + tuple(x.shape), dtype=x.dtype, device=x.device)
+    else:
+        _req(out, "out")
+        if out.numel() != rows * x.numel() or out.dtype != x.dtype or out.device != x.device:
+            raise _lib.SSError("euler_scale: out must hold %d %s elements on %s" % (rows * x.numel(), x.dtype, x.device))
+    check(lib().ss_euler_scale(p(x), p(out), x.numel(), rows, float(sigma), dt(x), stream()), "ss_euler_scale")
+    return out
+
+
 def image_to_u8(x, pixels):
     _req(x)
     out = torch.empty(pixels, 3, dtype=torch.uint8, device=x.device)

@@ -227,9 +227,10 @@ class StoryRingBackend(SlotRingBackend):
     mirrored on every rank.  ``bm`` is the bench module (its Story class / mllm_part / advance_context are the
     single-GPU schedule's pieces, reused unchanged)."""
 
-    def __init__(self, bm, eng, rin, rout, vit, adapter, spg, device, dtype, diffusion_steps, seed0=4242):
+    def __init__(self, bm, eng, rin, rout, vit, adapter, spg, device, dtype, diffusion_steps, seed0=4242, guidance_interval=None):
         self.bm, self.eng, self.rin, self.rout, self.vit, self.adapter = bm, eng, rin, rout, vit, adapter
         self.spg, self.device, self.dtype, self.steps = spg, device, dtype, diffusion_steps
+        self.guidance_interval = guidance_interval      # (sigma_lo, sigma_hi) passed on to adapter.generate; None: not passed
         self.story_no = seed0
         self.sts = None
         self.render_stream = torch.cuda.Stream(device=device) if adapter is not None else None
@@ -318,7 +319,8 @@ class StoryRingBackend(SlotRingBackend):
         with self.lock, torch.cuda.stream(self.render_stream):
             if ev is not None:
                 self.render_stream.wait_event(ev)
-            self.adapter.generate(image_embeds=feat.contiguous(), num_inference_steps=self.steps, output_type="pt")
+            kw = {} if self.guidance_interval is None else {"guidance_interval": self.guidance_interval}
+            self.adapter.generate(image_embeds=feat.contiguous(), num_inference_steps=self.steps, output_type="pt", **kw)
         self.render_stream.synchronize()
 
 

@@ -212,6 +212,20 @@ def make_scheduler(args, path=None):
     return DPMSolverMultistepScheduler.from_base(euler, use_karras_sigmas=name == "dpmpp2m-karras")
 
 
+def add_guidance_interval_argument(ap):
+    """``--guidance-interval LO HI`` (shared with vis_george_sink.py)"""
+    ap.add_argument("--guidance-interval", type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                    help="classifier-free guidance only on the denoising steps with LO < sigma <= HI (the sampler's sigmas; HI "
+                         "accepts inf), e.g. 0.25 6.0; the other steps run the UNet on the conditional half of the batch (end "
+                         "quality on real weights unverified; default: every step is guided)")
+
+
+def guidance_kwargs(args):
+    """``--guidance-interval``: the keyword of ``adapter.generate`` (nothing when the option is absent)"""
+    gi = getattr(args, "guidance_interval", None)
+    return {} if gi is None else {"guidance_interval": (float(gi[0]), float(gi[1]))}
+
+
 def add_speculate_argument(ap):
     """``--speculate K`` (shared with vis_george_sink.py)"""
     ap.add_argument("--speculate", type=int, default=0, metavar="K",
@@ -356,7 +370,7 @@ def run_story(args, j, question, image, tokenizer, transform, vit, agent, adapte
         if not out['has_img_output']:
             break
         images = adapter.generate(image_embeds=out['img_gen_feat'], num_inference_steps=args.diffusion_steps,
-                                  height=size, width=size, input_image_size=transform.size)
+                                  height=size, width=size, input_image_size=transform.size, **guidance_kwargs(args))
         images[0].save(os.path.join(save_folder, 'ori_{:02d}.jpg'.format(step)))                 # :217-218
         add_subtitle(images[0], text).save(os.path.join(save_folder, '{:02d}.jpg'.format(step)))   # :212-222
         ctx.advance(out)                                                                    # :224, :231, :235-239
@@ -396,6 +410,7 @@ def main():
     add_logprobs_argument(ap)
     add_rules_arguments(ap)
     add_scheduler_argument(ap)
+    add_guidance_interval_argument(ap)
     args = ap.parse_args()
     device = "cuda:0"
     dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float16

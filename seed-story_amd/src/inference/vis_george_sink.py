@@ -21,7 +21,8 @@ import torch
 
 from seedstory.story import StoryContext
 from src.inference.gen_george import (BOI_TOKEN, EOI_TOKEN, IMG_TOKEN, add_beams_arguments, add_best_of_argument, add_logprobs_argument,
-                                      add_scheduler_argument, add_speculate_argument, speculate_kwargs,
+                                      add_guidance_interval_argument, add_scheduler_argument, add_speculate_argument, guidance_kwargs,
+                                      speculate_kwargs,
                                       add_rules_arguments, apply_beams, apply_best_of, beams_kwargs, build, logprobs_kwargs, report_beams,
                                       report_candidates, report_caption_logprobs, rules_kwargs, sample_kwargs)
 
@@ -70,7 +71,8 @@ def run_story(args, j, start_text, captions, image, tokenizer, transform, vit, a
         if not out['has_img_output']:
             break
         images = adapter.generate(image_embeds=out['img_gen_feat'], num_inference_steps=args.diffusion_steps,
-                                  height=args.image_size, width=args.image_size, input_image_size=transform.size)
+                                  height=args.image_size, width=args.image_size, input_image_size=transform.size,
+                                  **guidance_kwargs(args))
         images[0].save(os.path.join(save_folder, 'ori_{:02d}.jpg'.format(step)))
         if step >= len(captions):
             break
@@ -117,6 +119,7 @@ def main():
     add_beams_arguments(ap)
     add_speculate_argument(ap)
     add_scheduler_argument(ap)
+    add_guidance_interval_argument(ap)
     ap.add_argument("--temperature", type=float, default=0.7, help="with --best-of")
     ap.add_argument("--top-k", type=int, default=0, help="with --best-of; 0 = off")
     ap.add_argument("--top-p", type=float, default=0.5, help="with --best-of")

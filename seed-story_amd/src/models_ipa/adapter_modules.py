@@ -105,6 +105,9 @@ class SDXLAdapter(nn.Module):
 
     def generate(self, image_pil=None, image_tensor=None, image_embeds=None, seed=42, height=1024, width=1024,
                  guidance_scale=7.5, num_inference_steps=30, input_image_size=448, **kwargs):
+        """``**kwargs`` go to the pipeline call: ``latents``, ``output_type``, and ``guidance_interval=(sigma_lo, sigma_hi)`` —
+        classifier-free guidance only on the steps whose sigma lies in (sigma_lo, sigma_hi], the others run the UNet on the
+        conditional rows alone (``seedstory.diffusion.guidance_mask``; default None: every step is guided)."""
         pos, neg, pooled_pos, pooled_neg = self.get_image_embeds(image_pil=image_pil, image_tensor=image_tensor,
                                                                  image_embeds=image_embeds, return_negative=True,
                                                                  image_size=input_image_size)
