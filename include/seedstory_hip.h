@@ -1014,6 +1014,30 @@ int ss_multistep_cfg_step(float* state, const void* eps, void* x_out, void* xin_
  * SS_EINVAL before anything is launched or written: as ss_multistep_cfg_step, and eps_rows or xin_rows outside {1, 2}. */
 int ss_multistep_step(float* state, const void* eps, void* x_out, void* xin_next, int64_t n, int eps_rows, int xin_rows,
                       float guidance, float sigma, float a, float b, float c, float inv_next, int dtype, void* stream);
+/* Gaussian noise of the stochastic samplers (Euler ancestral, DPM++ 2M SDE; definition: tests/sde_ref.py).
+ * z for image seed S (64 bit), step i and flat element j of that image's latent depends on nothing else:
+ *   (w0, w1, w2, w3) = Philox4x32-10(counter (j >> 2, i, 1, 0), key (S & 0xFFFFFFFF, S >> 32));  u(w) = (w >> 8) 2^-24;
+ *   r(w) = sqrt(-2 ln(u(w) + 2^-24));  element j takes lane j & 3 of
+ *   [r(w0) cos(2 pi u(w1)), r(w0) sin(2 pi u(w1)), r(w2) cos(2 pi u(w3)), r(w2) sin(2 pi u(w3))]      (fp32; |z| <= 5.77)
+ * Counter word 2 = 1 keeps the stream apart from ss_sample_logits' (draw, slot, 0, 0).  Images with equal seeds get equal
+ * noise; the value does not depend on the batch.
+ *   out [batch, n_img] in `dtype` receives rnd(z(seeds_dev[b], step, j));  seeds_dev: uint64 [batch] in DEVICE memory.
+ * Any n_img >= 1: one store per quad when n_img % 4 == 0 and `out` is 16-byte aligned, single elements otherwise.
+ * SS_EINVAL before anything is launched or written: NULL out or seeds, batch <= 0, n_img <= 0 (or > 2^34), step < 0, an
+ * unknown dtype. */
+int ss_randn_philox(void* out, const uint64_t* seeds_dev, int64_t batch, int64_t n_img, int step, int dtype, void* stream);
+/* ss_multistep_step with a noise term: x' = ((a * x + b * d) [+ c * d_prev]) + s * z — one fp32 product and one fp32 sum after
+ * ss_multistep_step's chain, everything else (forms, state, outputs, c == 0 rule) as there.  z is ss_randn_philox's value
+ * (the same device function: bit-equal) for element i % n_img of image i / n_img, seed seeds_dev[i / n_img], step `step`.
+ * Euler ancestral: (a, b, c, s) = (sd/s_i, 1 - sd/s_i, 0, s_up); DPM++ 2M SDE: DESIGN §6.0l; the last step of both (0, 1, 0, 0).
+ * 16-byte packets when every base is 16-byte aligned and n_img is a multiple of the packet (a packet then lies in one
+ * image), single elements for everything otherwise.  s == 0: z is not generated, seeds_dev may be NULL, and every output is
+ * bit-equal to ss_multistep_step (its kernels are launched).
+ * SS_EINVAL before anything is launched or written: as ss_multistep_step, and n_img <= 0 (or > 2^34), n % n_img != 0,
+ * step < 0, a non-finite s, s != 0 with NULL seeds_dev. */
+int ss_multistep_noise_step(float* state, const void* eps, void* x_out, void* xin_next, int64_t n, int eps_rows, int xin_rows,
+                            float guidance, float sigma, float a, float b, float c, float s, float inv_next,
+                            const uint64_t* seeds_dev, int64_t n_img, int step, int dtype, void* stream);
 /* Unguided Euler step: x += rnd(eps * (sigma_next - sigma)), eps [n] the conditional prediction (ss_euler_cfg_step
  * without its guidance arithmetic, same rounding point).  SS_EINVAL: n <= 0, NULL x or eps, unknown dtype. */
 int ss_euler_step(void* x, const void* eps, int64_t n, float sigma, float sigma_next, int dtype, void* stream);

@@ -4,6 +4,7 @@
 // Activations are NHWC ([B, H*W, C] row-major) so every convolution is an implicit GEMM over
 // channels (ss_gemm.hip) and the transformer blocks need no permutes.
 #include "ss_common.h"
+#include "ss_sample.h"      // Philox4x32-10
 
 #include <cmath>
 
@@ -475,18 +476,69 @@ __global__ __launch_bounds__(256) void multistep_cfg_step_kernel(float* __restri
 // (no arithmetic, g unused).  XR == 1: the next step is unguided and takes one copy of rnd_T(x' inv_next).  Rows that a form
 // does not use are never addressed: eps and xin_next may be one row long.  Packets as above: second rows (state row 1 always,
 // eps / xin_next row 1 when the form has one) are 16-byte accesses only when row1_vec.
-template <typename T, int ER, int XR>
+//
+// Gaussian noise of the stochastic samplers (Euler ancestral, DPM++ 2M SDE; definition: tests/sde_ref.py).  The
+// four normals of quad q = j >> 2 of an image's latent (flat element j) at step `step` for the image's 64-bit seed:
+//   (w0, w1, w2, w3) = Philox4x32-10(counter (q, step, 1, 0), key (seed lo, seed hi))     word 2 = 1: apart from the token sampler
+//   u(w) = (w >> 8) 2^-24;  r(w) = sqrt(-2 ln(u(w) + 2^-24))      the log's argument is exact in fp32 and lies in (0, 1]
+//   z = [r(w0) cos(2 pi u(w1)), r(w0) sin(2 pi u(w1)), r(w2) cos(2 pi u(w3)), r(w2) sin(2 pi u(w3))]
+// cos / sin of 2 pi u are taken as cospi / sinpi of 2 u (exact argument: no rounded 2 pi).  fp32, one rounding per operation
+// (tests/test_sde_gpu.py derives its bound from this list): log, * -2 (exact), sqrt, sincospi, product.
+// ss_randn_philox and the NOISE step below both call this function, so their values agree bit for bit.
+__device__ __forceinline__ void philox_normal4(uint32_t seed_lo, uint32_t seed_hi, uint32_t step, uint32_t q, float* z) {
+    constexpr float k2m24 = 5.9604644775390625e-8f;
+    uint32_t w[4];
+    philox4x32_10(q, step, 1u, 0u, seed_lo, seed_hi, w);
+#pragma unroll
+    for (int k = 0; k < 4; k += 2) {
+        const float u0 = (float)(w[k] >> 8) * k2m24, u1 = (float)(w[k + 1] >> 8) * k2m24;
+        const float r = sqrtf(-2.0f * logf(u0 + k2m24));
+        float sn, cs;
+        sincospif(2.0f * u1, &sn, &cs);
+        z[k] = r * cs;
+        z[k + 1] = r * sn;
+    }
+}
+// NOISE (one trailing StepNoise argument; the plain step's instantiations have none and keep the code they always had):
+// x' = ((a x + b d) [+ c d_prev]) + s z, z that of element i % n_img of image i / n_img (seeds[i / n_img]): one fp32 product
+// and one fp32 sum after the chain above.  The launcher takes packets only when n_img % V == 0 (a packet then lies in one
+// image and covers whole quads) and single elements for everything otherwise; n % n_img == 0, so packets leave no tail.
+struct StepNoise {
+    float s;
+    const uint64_t* seeds;      // [n / n_img] in device memory
+    int64_t n_img;
+    uint32_t step;
+};
+template <typename T, int ER, int XR, typename... NZ>
 __global__ __launch_bounds__(256) void multistep_step_kernel(float* __restrict__ state, const T* __restrict__ eps,
                                                              T* __restrict__ x_out, T* __restrict__ xin_next, int64_t n,
                                                              int64_t npack, int row1_vec, float g, float sigma, float a, float b,
-                                                             float c, float inv_next) {
+                                                             float c, float inv_next, NZ... nz) {
+    constexpr bool NOISE = sizeof...(NZ) == 1;
+    static_assert(sizeof...(NZ) <= 1, "at most one StepNoise");
     constexpr int V = Tr<T>::kVec;
     const bool prev = c != 0.0f;
     const bool v1 = row1_vec != 0;
     const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x, stride = (int64_t)gridDim.x * blockDim.x;
+    float s = 0.f;
+    const uint64_t* seeds = nullptr;
+    int64_t n_img = 1;
+    uint32_t step = 0;
+    if constexpr (NOISE) {
+        const StepNoise& nza = (nz, ...);
+        s = nza.s; seeds = nza.seeds; n_img = nza.n_img; step = nza.step;
+    }
     for (int64_t p = tid; p < npack; p += stride) {
         const int64_t i = p * V;
         float x[V], dp[V], e0[V], ec[V], xs[V];      // e0: row 0 of eps (uncond when ER == 2, cond when ER == 1)
+        float z[V];
+        if constexpr (NOISE) {
+            const int64_t img = i / n_img, j = i - img * n_img;
+            const uint64_t sd = seeds[img];
+#pragma unroll
+            for (int k = 0; k < V; k += 4)
+                philox_normal4((uint32_t)sd, (uint32_t)(sd >> 32), step, (uint32_t)(j >> 2) + k / 4, z + k);
+        }
         ld_f32<V>(state + i, true, x);
         unpack<T>(ld16(eps + i), e0);
         if (ER == 2) {
@@ -502,6 +554,7 @@ __global__ __launch_bounds__(256) void multistep_step_kernel(float* __restrict__
         for (int j = 0; j < V; ++j) {
             if (ER == 2) multistep_one(x[j], dp[j], e0[j], ec[j], prev, g, sigma, a, b, c);
             else multistep_apply(x[j], dp[j], e0[j], prev, sigma, a, b, c);
+            if constexpr (NOISE) x[j] += s * z[j];
             xs[j] = x[j] * inv_next;
         }
         st_f32<V>(state + i, true, x);
@@ -524,6 +577,14 @@ __global__ __launch_bounds__(256) void multistep_step_kernel(float* __restrict__
         float x = state[i], dp = prev ? state[n + i] : 0.f;
         if (ER == 2) multistep_one(x, dp, Tr<T>::ld(eps + i), Tr<T>::ld(eps + n + i), prev, g, sigma, a, b, c);
         else multistep_apply(x, dp, Tr<T>::ld(eps + i), prev, sigma, a, b, c);
+        if constexpr (NOISE) {
+            const int64_t img = i / n_img, j = i - img * n_img;
+            const uint64_t sd = seeds[img];
+            float zq[4];
+            philox_normal4((uint32_t)sd, (uint32_t)(sd >> 32), step, (uint32_t)(j >> 2), zq);
+            const int l = (int)(j & 3);
+            x += s * (l == 0 ? zq[0] : l == 1 ? zq[1] : l == 2 ? zq[2] : zq[3]);
+        }
         state[i] = x;
         state[n + i] = dp;
         if (x_out) Tr<T>::st(x_out + i, x);
@@ -531,6 +592,32 @@ __global__ __launch_bounds__(256) void multistep_step_kernel(float* __restrict__
             const float v = x * inv_next;
             Tr<T>::st(xin_next + i, v);
             if (XR == 2) Tr<T>::st(xin_next + n + i, v);
+        }
+    }
+}
+// out[b, j] = rnd_T(z(seeds[b], step, j)): one thread per quad; `vec`: a quad is one store (n_img % 4 == 0, aligned base)
+template <typename T>
+__global__ __launch_bounds__(256) void randn_philox_kernel(T* __restrict__ out, const uint64_t* __restrict__ seeds,
+                                                           int64_t batch, int64_t n_img, int64_t nq, uint32_t step, int vec) {
+    const int64_t total = batch * nq;
+    for (int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; p < total; p += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t img = p / nq, q = p - img * nq;
+        const uint64_t sd = seeds[img];
+        float z[4];
+        philox_normal4((uint32_t)sd, (uint32_t)(sd >> 32), step, (uint32_t)q, z);
+        T* o = out + img * n_img + q * 4;
+        if (vec) {
+            if constexpr (sizeof(T) == 4) {
+                st16(o, pack<float>(z));
+            } else {
+                float f[8] = {z[0], z[1], z[2], z[3], 0.f, 0.f, 0.f, 0.f};
+                const uint4 u = pack<T>(f);
+                *reinterpret_cast<uint2*>(o) = make_uint2(u.x, u.y);
+            }
+        } else {
+#pragma unroll
+            for (int l = 0; l < 4; ++l)
+                if (q * 4 + l < n_img) Tr<T>::st(o + l, z[l]);
         }
     }
 }
@@ -676,6 +763,38 @@ int multistep_step_launch(float* state, const void* eps, void* x_out, void* xin_
     return SS_OK;
 }
 template <typename T>
+int multistep_noise_step_launch(float* state, const void* eps, void* x_out, void* xin_next, int64_t n, int eps_rows,
+                                int xin_rows, float g, float sigma, float a, float b, float c, float s, float inv_next,
+                                const uint64_t* seeds, int64_t n_img, int step, hipStream_t st) {
+    if (s == 0.0f)      // no noise term: the plain step's own kernels, bit for bit (seeds is not read)
+        return multistep_step_launch<T>(state, eps, x_out, xin_next, n, eps_rows, xin_rows, g, sigma, a, b, c, inv_next, st);
+    constexpr int V = Tr<T>::kVec;
+    const uintptr_t bases = (uintptr_t)state | (uintptr_t)eps | (uintptr_t)x_out | (uintptr_t)xin_next;   // NULL: no bits
+    const int64_t npack = ((bases & 15) == 0 && n_img % V == 0) ? n / V : 0;      // n % n_img == 0: all packets or none
+    const int row1_vec = npack > 0;
+    const dim3 grid(egrid(npack > 0 ? npack : n));
+    const StepNoise nz{s, seeds, n_img, (uint32_t)step};
+#define SS_MS_FORM(ER, XR)                                                                                              \
+    hipLaunchKernelGGL((multistep_step_kernel<T, ER, XR, StepNoise>), grid, dim3(256), 0, st, state, (const T*)eps, (T*)x_out, \
+                       (T*)xin_next, n, npack, row1_vec, g, sigma, a, b, c, inv_next, nz)
+    if (eps_rows == 2 && xin_rows == 2) SS_MS_FORM(2, 2);
+    else if (eps_rows == 2) SS_MS_FORM(2, 1);
+    else if (xin_rows == 2) SS_MS_FORM(1, 2);
+    else SS_MS_FORM(1, 1);
+#undef SS_MS_FORM
+    SS_LAUNCH_CHECK("multistep_noise_step");
+    return SS_OK;
+}
+template <typename T>
+int randn_philox_launch(void* out, const uint64_t* seeds, int64_t batch, int64_t n_img, int step, hipStream_t st) {
+    const int64_t nq = (n_img + 3) / 4;
+    const int vec = n_img % 4 == 0 && ((uintptr_t)out & 15) == 0;
+    hipLaunchKernelGGL(randn_philox_kernel<T>, dim3(egrid(batch * nq)), dim3(256), 0, st, (T*)out, seeds, batch, n_img, nq,
+                       (uint32_t)step, vec);
+    SS_LAUNCH_CHECK("randn_philox");
+    return SS_OK;
+}
+template <typename T>
 int euler_step_launch(void* x, const void* eps, int64_t n, float sigma, float sigma_next, hipStream_t s) {
     hipLaunchKernelGGL(euler_step_kernel<T>, dim3(egrid(n)), dim3(256), 0, s, (T*)x, (const T*)eps, n, sigma_next - sigma);
     SS_LAUNCH_CHECK("euler_step");
@@ -765,6 +884,36 @@ int ss_multistep_step(float* state, const void* eps, void* x_out, void* xin_next
                "multistep_step: unknown dtype %d or misaligned state", dtype);
     return SS_DISPATCH(dtype, multistep_step_launch, state, eps, x_out, xin_next, n, eps_rows, xin_rows, guidance, sigma, a, b,
                        c, inv_next, (hipStream_t)stream);
+}
+int ss_multistep_noise_step(float* state, const void* eps, void* x_out, void* xin_next, int64_t n, int eps_rows, int xin_rows,
+                            float guidance, float sigma, float a, float b, float c, float s, float inv_next,
+                            const uint64_t* seeds_dev, int64_t n_img, int step, int dtype, void* stream) {
+    SS_REQUIRE(n > 0, "multistep_noise_step: n = %lld", (long long)n);
+    SS_REQUIRE(state != nullptr && eps != nullptr, "multistep_noise_step: NULL state or eps");
+    SS_REQUIRE((eps_rows == 1 || eps_rows == 2) && (xin_rows == 1 || xin_rows == 2),
+               "multistep_noise_step: eps_rows %d / xin_rows %d (1 or 2)", eps_rows, xin_rows);
+    SS_REQUIRE(n_img > 0 && n_img <= ((int64_t)1 << 34) && n % n_img == 0,
+               "multistep_noise_step: n_img = %lld must be in [1, 2^34] and divide n = %lld", (long long)n_img, (long long)n);
+    SS_REQUIRE(step >= 0, "multistep_noise_step: step = %d", step);
+    SS_REQUIRE(std::isfinite(guidance) && std::isfinite(sigma) && std::isfinite(a) && std::isfinite(b) && std::isfinite(c) &&
+                   std::isfinite(s) && std::isfinite(inv_next),
+               "multistep_noise_step: non-finite coefficient (guidance %g sigma %g a %g b %g c %g s %g inv_next %g)",
+               (double)guidance, (double)sigma, (double)a, (double)b, (double)c, (double)s, (double)inv_next);
+    SS_REQUIRE(s == 0.0f || (seeds_dev != nullptr && (uintptr_t)seeds_dev % sizeof(uint64_t) == 0),
+               "multistep_noise_step: s = %g needs seeds (NULL or misaligned)", (double)s);
+    SS_REQUIRE((uintptr_t)state % sizeof(float) == 0 && (dtype == SS_F32 || dtype == SS_BF16 || dtype == SS_F16),
+               "multistep_noise_step: unknown dtype %d or misaligned state", dtype);
+    return SS_DISPATCH(dtype, multistep_noise_step_launch, state, eps, x_out, xin_next, n, eps_rows, xin_rows, guidance, sigma, a,
+                       b, c, s, inv_next, seeds_dev, n_img, step, (hipStream_t)stream);
+}
+int ss_randn_philox(void* out, const uint64_t* seeds_dev, int64_t batch, int64_t n_img, int step, int dtype, void* stream) {
+    SS_REQUIRE(out != nullptr && seeds_dev != nullptr && (uintptr_t)seeds_dev % sizeof(uint64_t) == 0,
+               "randn_philox: NULL out or seeds (or misaligned seeds)");
+    SS_REQUIRE(batch > 0 && n_img > 0 && n_img <= ((int64_t)1 << 34), "randn_philox: batch = %lld, n_img = %lld (n_img in [1, 2^34])",
+               (long long)batch, (long long)n_img);
+    SS_REQUIRE(step >= 0, "randn_philox: step = %d", step);
+    SS_REQUIRE(dtype == SS_F32 || dtype == SS_BF16 || dtype == SS_F16, "randn_philox: unknown dtype %d", dtype);
+    return SS_DISPATCH(dtype, randn_philox_launch, out, seeds_dev, batch, n_img, step, (hipStream_t)stream);
 }
 int ss_euler_step(void* x, const void* eps, int64_t n, float sigma, float sigma_next, int dtype, void* stream) {
     SS_REQUIRE(n > 0 && x != nullptr && eps != nullptr, "euler_step: n = %lld or NULL x / eps", (long long)n);

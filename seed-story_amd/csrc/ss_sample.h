@@ -124,6 +124,18 @@ __device__ __forceinline__ uint32_t philox4x32_10_word0(uint32_t c0, uint32_t c1
     }
     return c0;
 }
+// The same generator with a full counter (c0, c1, c2, c3), all four output words (the diffusion noise: ss_diffusion.hip)
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
+                                              uint32_t out[4]) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
 __device__ __forceinline__ float philox_uniform(uint32_t seed_lo, uint32_t seed_hi, uint32_t draw, uint32_t lane) {
     return (float)(philox4x32_10_word0(draw, lane, seed_lo, seed_hi) >> 8) * 5.9604644775390625e-8f;   // 2^-24: [0, 1)
 }

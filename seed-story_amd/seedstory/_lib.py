@@ -216,6 +216,9 @@ PROTOTYPES = {
     "ss_euler_cfg_step": (C.c_int, [vp, vp, i64, f32, f32, f32, C.c_int, vp]),
     "ss_multistep_cfg_step": (C.c_int, [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32, C.c_int, vp]),
     "ss_multistep_step": (C.c_int, [vp, vp, vp, vp, i64, C.c_int, C.c_int, f32, f32, f32, f32, f32, f32, C.c_int, vp]),
+    "ss_randn_philox": (C.c_int, [vp, vp, i64, i64, C.c_int, C.c_int, vp]),
+    "ss_multistep_noise_step": (C.c_int, [vp, vp, vp, vp, i64, C.c_int, C.c_int, f32, f32, f32, f32, f32, f32, f32, vp, i64, C.c_int,
+                                          C.c_int, vp]),
     "ss_euler_step": (C.c_int, [vp, vp, i64, f32, f32, C.c_int, vp]),
     "ss_euler_scale": (C.c_int, [vp, vp, i64, C.c_int, f32, C.c_int, vp]),
     "ss_resample_ksize": (C.c_int, [i64, i64, C.c_int]),

@@ -821,7 +821,7 @@ class DPMSolverMultistepScheduler:
         """The sampler over the betas and spacing of an existing scheduler object (Euler, or this class)."""
         import copy
         m = cls(use_karras_sigmas=use_karras_sigmas, solver_order=solver_order)
-        m._base = copy.copy(scheduler._base if isinstance(scheduler, cls) else scheduler)
+        m._base = copy.copy(getattr(scheduler, "_base", scheduler))      # Euler itself, or the base of a class built over one
         return m
 
     @staticmethod
@@ -862,6 +862,157 @@ class DPMSolverMultistepScheduler:
                 coef[i] = (sn / si, E * (1.0 + 1.0 / (2.0 * r)), -E / (2.0 * r))
             h_prev = h
         self.coefficients = coef
+
+
+class EulerAncestralDiscreteScheduler:
+    """Euler ancestral ("Euler a"): diffusers' EulerAncestralDiscreteScheduler, k-diffusion's ``sample_euler_ancestral`` with
+    eta = 1 and s_noise = 1 (definition: tests/sde_ref.py).  A STOCHASTIC sampler: every step but the last adds
+    sigma_up z with fresh standard normals z, which the pipeline draws on the device from ``noise_seed`` (Philox, per image,
+    per step: ``ss_multistep_noise_step``).  diffusers draws that noise from torch's generator, so images do not match it bit
+    for bit even where the mathematics does; parity against diffusers is UNPINNED (it is not installed here).
+
+    Timesteps, sigmas and ``init_noise_sigma`` are EulerDiscreteScheduler's (an instance of it is the base; its config keys
+    are this class's).  ``coefficients`` [n, 4]: step i is x <- a x + b d + c d_prev + s z with d = x - sigma_i eps and
+    (a, b, c, s) = (sigma_down / sigma_i, 1 - sigma_down / sigma_i, 0, sigma_up), the last step (0, 1, 0, 0)."""
+
+    def __init__(self, **kw):
+        self._base = EulerDiscreteScheduler(**kw)
+        self.timesteps = self.sigmas = self.coefficients = self.init_noise_sigma = None
+
+    @classmethod
+    def from_pretrained(cls, path, subfolder=None, **kw):
+        folder = os.path.join(path, subfolder) if subfolder else path
+        with open(os.path.join(folder, "scheduler_config.json")) as f:
+            jc = json.load(f)
+        cfg = {k: v for k, v in jc.items() if not k.startswith("_")}
+        cfg.update(kw)
+        return cls(**cfg)
+
+    @classmethod
+    def from_base(cls, scheduler):
+        """The sampler over the betas and spacing of an existing scheduler object (Euler, or any class built over one)."""
+        import copy
+        m = cls()
+        m._base = copy.copy(getattr(scheduler, "_base", scheduler))
+        return m
+
+    def set_timesteps(self, n):
+        self._base.set_timesteps(n)
+        self.sigmas = self._base.sigmas.astype(np.float64)
+        self.timesteps = self._base.timesteps
+        self.init_noise_sigma = self._base.init_noise_sigma
+        coef = np.zeros((n, 4), dtype=np.float64)
+        for i in range(n):
+            si, sn = float(self.sigmas[i]), float(self.sigmas[i + 1])
+            if sn == 0.0:
+                coef[i] = (0.0, 1.0, 0.0, 0.0)
+                continue
+            up = min(sn, math.sqrt(sn * sn * (si * si - sn * sn) / (si * si)))
+            down = math.sqrt(sn * sn - up * up)
+            coef[i] = (down / si, 1.0 - down / si, 0.0, up)
+        self.coefficients = coef
+
+
+class DPMSolverMultistepSDEScheduler:
+    """DPM-Solver++ 2M SDE ("DPM++ 2M SDE", with ``use_karras_sigmas`` "DPM++ 2M SDE Karras"): diffusers'
+    DPMSolverMultistepScheduler at algorithm_type "sde-dpmsolver++", solver_type "midpoint", solver_order 1 | 2; k-diffusion's
+    ``sample_dpmpp_2m_sde`` with the midpoint solver and s_noise = 1 (definition: tests/sde_ref.py).  STOCHASTIC
+    like EulerAncestralDiscreteScheduler, and UNPINNED against diffusers in the same way.  ``eta`` scales the noise; 0 is
+    DPMSolverMultistepScheduler's table with s = 0.
+
+    Base, timesteps, sigmas and ``init_noise_sigma`` as DPMSolverMultistepScheduler.  ``coefficients`` [n, 4], in double, with
+    h = ln sigma_i - ln sigma_n, E = 1 - exp(-(1 + eta) h), a = (sigma_n / sigma_i) exp(-eta h), s = sigma_n sqrt(1 - exp(-2 eta h)):
+    first step or order 1 (a, E, 0, s); else, r = h_prev / h, (a, E (1 + 1 / (2 r)), -E / (2 r), s); last step (0, 1, 0, 0)."""
+
+    def __init__(self, use_karras_sigmas=False, solver_order=2, eta=1.0, algorithm_type="sde-dpmsolver++", solver_type="midpoint",
+                 lower_order_final=True, final_sigmas_type="zero", **kw):
+        D = DPMSolverMultistepScheduler
+        for key, value, allowed in (("algorithm_type", algorithm_type, ("sde-dpmsolver++",)), ("solver_order", solver_order, (1, 2)),
+                                    ("solver_type", solver_type, ("midpoint",)), ("final_sigmas_type", final_sigmas_type, ("zero",)),
+                                    ("prediction_type", kw.get("prediction_type", "epsilon"), ("epsilon",)),
+                                    ("beta_schedule", kw.get("beta_schedule", "scaled_linear"), ("scaled_linear",)),
+                                    ("timestep_spacing", kw.get("timestep_spacing", "leading"), ("leading", "linspace", "trailing"))):
+            if value not in allowed or isinstance(value, bool):
+                raise ValueError("DPMSolverMultistepSDEScheduler: %s=%r is not supported (supported: %s)"
+                                 % (key, value, ", ".join(repr(a) for a in allowed)))
+        if isinstance(eta, bool) or not isinstance(eta, (int, float)) or not math.isfinite(eta) or eta < 0.0:
+            raise ValueError("DPMSolverMultistepSDEScheduler: eta=%r must be a finite number >= 0" % (eta,))
+        base = {}
+        for key, value in kw.items():
+            if key in D._BASE_KEYS:
+                base[key] = value
+            elif key in D._OFF:
+                if value != D._OFF[key]:
+                    raise ValueError("DPMSolverMultistepSDEScheduler: %s=%r is not supported (only %r)" % (key, value, D._OFF[key]))
+            elif key not in D._UNUSED:
+                raise ValueError("DPMSolverMultistepSDEScheduler: unknown config key %r" % key)
+        self.solver_order, self.use_karras_sigmas, self.eta = int(solver_order), bool(use_karras_sigmas), float(eta)
+        self._base = EulerDiscreteScheduler(**base)
+        self.timesteps = self.sigmas = self.coefficients = self.init_noise_sigma = None
+
+    @classmethod
+    def from_pretrained(cls, path, subfolder=None, **kw):
+        folder = os.path.join(path, subfolder) if subfolder else path
+        with open(os.path.join(folder, "scheduler_config.json")) as f:
+            jc = json.load(f)
+        cfg = {k: v for k, v in jc.items() if not k.startswith("_")}
+        cfg.update(kw)
+        return cls(**cfg)
+
+    @classmethod
+    def from_base(cls, scheduler, use_karras_sigmas=False, solver_order=2, eta=1.0):
+        """The sampler over the betas and spacing of an existing scheduler object (Euler, or any class built over one)."""
+        import copy
+        m = cls(use_karras_sigmas=use_karras_sigmas, solver_order=solver_order, eta=eta)
+        m._base = copy.copy(getattr(scheduler, "_base", scheduler))
+        return m
+
+    def set_timesteps(self, n):
+        # the deterministic class's own sigmas and timesteps (its table is not used)
+        det = DPMSolverMultistepScheduler(use_karras_sigmas=self.use_karras_sigmas)
+        det._base = self._base
+        det.set_timesteps(n)
+        self.sigmas, self.timesteps, self.init_noise_sigma = det.sigmas, det.timesteps, det.init_noise_sigma
+        eta = self.eta
+        coef = np.zeros((n, 4), dtype=np.float64)
+        h_prev = None
+        for i in range(n):
+            si, sn = float(self.sigmas[i]), float(self.sigmas[i + 1])
+            if sn == 0.0:
+                coef[i] = (0.0, 1.0, 0.0, 0.0)
+                continue
+            h = math.log(si) - math.log(sn)
+            E = -math.expm1(-(1.0 + eta) * h)
+            a = (sn / si) * math.exp(-eta * h)
+            s = sn * math.sqrt(-math.expm1(-2.0 * eta * h))
+            if i == 0 or self.solver_order == 1:
+                coef[i] = (a, E, 0.0, s)
+            else:
+                r = h_prev / h
+                coef[i] = (a, E * (1.0 + 1.0 / (2.0 * r)), -E / (2.0 * r), s)
+            h_prev = h
+        self.coefficients = coef
+
+
+# samplers whose step is x <- a x + b d + c d_prev [+ s z] on the fp32 state (ss_multistep_*); the stochastic ones carry s
+_STOCHASTIC = (EulerAncestralDiscreteScheduler, DPMSolverMultistepSDEScheduler)
+_MULTISTEP = (DPMSolverMultistepScheduler,) + _STOCHASTIC
+
+
+def noise_seed_list(noise_seed, generator, batch):
+    """The per-image 64-bit noise seeds of a pipeline call: ``noise_seed`` is an int (every image), a sequence of ``batch``
+    ints, or None — then ``generator.initial_seed()`` when a generator was given, else 0.  ValueError: another length."""
+    if noise_seed is None:
+        noise_seed = generator.initial_seed() if generator is not None else 0
+    if isinstance(noise_seed, (int, np.integer)):
+        return [int(noise_seed)] * batch
+    try:
+        seeds = [int(v) for v in noise_seed]
+    except (TypeError, ValueError):
+        raise ValueError("noise_seed must be None, an int or a sequence of %d ints, not %r" % (batch, noise_seed))
+    if len(seeds) != batch:
+        raise ValueError("noise_seed holds %d seeds for %d images" % (len(seeds), batch))
+    return seeds
 
 
 def guidance_mask(sigmas, interval):
@@ -954,15 +1105,21 @@ class StableDiffusionXLPipeline:
     @torch.no_grad()
     def __call__(self, prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds,
                  guidance_scale=7.5, num_inference_steps=30, generator=None, height=1024, width=1024, latents=None,
-                 output_type="pil", guidance_interval=None, **kw):
+                 output_type="pil", guidance_interval=None, noise_seed=None, **kw):
         """``guidance_interval`` = (sigma_lo, sigma_hi), default ``self.guidance_interval``: classifier-free guidance only on the
         steps with sigma_lo < sigma <= sigma_hi (``guidance_mask``); the other steps run the UNet on the B conditional rows and
-        take that prediction.  None: every step is guided, on the code path that knows nothing of the option."""
+        take that prediction.  None: every step is guided, on the code path that knows nothing of the option.
+
+        ``noise_seed`` (an int, or a sequence of B ints; default: ``generator.initial_seed()``, else 0): the per-image seeds of the
+        noise a STOCHASTIC scheduler (EulerAncestralDiscreteScheduler, DPMSolverMultistepSDEScheduler) adds at every step, drawn
+        on the device inside the step's launch; image b of a batch equals its own batch-1 call with ``noise_seed[b]``.  Any other
+        scheduler launches exactly what it launches without the keyword and ignores the value."""
         dev, dt = prompt_embeds.device, prompt_embeds.dtype
         lh, lw = height // 8, width // 8
         B = prompt_embeds.shape[0]           # images rendered together (UNet batch 2B: [B uncond; B cond])
         interval = self.guidance_interval if guidance_interval is None else guidance_interval
         guidance_mask((), interval)          # a bad interval is refused before anything is launched
+        seeds = noise_seed_list(noise_seed, generator, B)      # and so is a noise_seed of another length
         self.unet._ctx_key = None            # new conditioning: recompute the cached cross-attention K/V
         sampler = self._sampler()
         sampler.set_timesteps(num_inference_steps)
@@ -971,12 +1128,12 @@ class StableDiffusionXLPipeline:
         if not all(mask):
             x = self._denoise_interval(sampler, mask, prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds,
                                        negative_pooled_prompt_embeds, guidance_scale, num_inference_steps, generator, height,
-                                       width, latents)
+                                       width, latents, seeds)
             return self._finish(x, output_type)
-        if isinstance(sampler, DPMSolverMultistepScheduler):
+        if isinstance(sampler, _MULTISTEP):
             x = self._denoise_multistep(sampler, prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds,
                                         negative_pooled_prompt_embeds, guidance_scale, num_inference_steps, generator, height,
-                                        width, latents)
+                                        width, latents, seeds)
             return self._finish(x, output_type)
         self.scheduler.set_timesteps(num_inference_steps)
         sig, ts = self.scheduler.sigmas, self.scheduler.timesteps
@@ -1025,11 +1182,13 @@ class StableDiffusionXLPipeline:
         return obj
 
     def _denoise_multistep(self, sched, prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds,
-                           negative_pooled_prompt_embeds, guidance_scale, num_inference_steps, generator, height, width, latents):
+                           negative_pooled_prompt_embeds, guidance_scale, num_inference_steps, generator, height, width, latents,
+                           noise_seeds=None):
         """The denoising loop of DPMSolverMultistepScheduler: ONE point-wise launch per step (``ss_multistep_cfg_step``: CFG +
         solver update of the fp32 state + the next step's scaled, duplicated UNet input) where the Euler loop has two and a
         copy; the kernel writes that input straight into the buffer the next forward reads (the captured graph's ``x``).  Step 0
-        runs eagerly, steps >= 1 replay the captured forward, as in the Euler loop."""
+        runs eagerly, steps >= 1 replay the captured forward, as in the Euler loop.  A stochastic scheduler takes the same loop
+        with ``ss_multistep_noise_step`` as its one launch (step index i, the images' ``noise_seeds``)."""
         dev, dt = prompt_embeds.device, prompt_embeds.dtype
         lh, lw = height // 8, width // 8
         B = prompt_embeds.shape[0]
@@ -1046,6 +1205,7 @@ class StableDiffusionXLPipeline:
             state = bufs[(n, str(dev))] = torch.empty(2, n, dtype=torch.float32, device=dev)
         state[0].copy_(x.view(-1))
         x_out = torch.empty_like(x)
+        seeds_dev = self._seed_buffer(noise_seeds, B, dev) if isinstance(sched, _STOCHASTIC) else None
         time_ids = torch.tensor([[height, width, 0, 0, height, width]] * (2 * B), dtype=torch.float32)
         ctx = self._stable("ctx", torch.cat([negative_prompt_embeds, prompt_embeds], dim=0))
         pooled = self._stable("pooled", torch.cat([negative_pooled_prompt_embeds, pooled_prompt_embeds], dim=0))
@@ -1066,13 +1226,31 @@ class StableDiffusionXLPipeline:
                 eps = graph["eps"]
             last = i + 1 == num_inference_steps
             nxt = None if last else (graph["x"] if graph is not None else xin)
+            inv_next = 1.0 / math.sqrt(float(sig[i + 1]) ** 2 + 1.0)
+            if seeds_dev is not None:
+                a, b, c, s = (float(v) for v in coef[i])
+                ops.multistep_noise_step_(state, eps.contiguous(), guidance_scale, float(sig[i]), a, b, c, s, inv_next, seeds_dev, i,
+                                          x_out=x_out if last else None, xin_next=nxt)
+                continue
             a, b, c = (float(v) for v in coef[i])
             ops.multistep_cfg_step_(state, eps.contiguous(), guidance_scale, float(sig[i]), a, b, c,
-                                    1.0 / math.sqrt(float(sig[i + 1]) ** 2 + 1.0), x_out=x_out if last else None, xin_next=nxt)
+                                    inv_next, x_out=x_out if last else None, xin_next=nxt)
         return x_out
 
+    def _seed_buffer(self, noise_seeds, B, dev):
+        """The images' noise seeds in a device buffer that keeps its address from render to render (int64 [B])."""
+        bufs = self.__dict__.setdefault("_seed_bufs", {})
+        new = ops.noise_seeds(noise_seeds if noise_seeds is not None else [0] * B, dev)
+        cur = bufs.get((B, str(dev)))
+        if cur is None:
+            cur = bufs[(B, str(dev))] = new
+        else:
+            cur.copy_(new)
+        return cur
+
     def _denoise_interval(self, sched, mask, prompt_embeds, negative_prompt_embeds, pooled_prompt_embeds,
-                          negative_pooled_prompt_embeds, guidance_scale, num_inference_steps, generator, height, width, latents):
+                          negative_pooled_prompt_embeds, guidance_scale, num_inference_steps, generator, height, width, latents,
+                          noise_seeds=None):
         """The denoising loop when ``mask`` has unguided steps, for both samplers.  The UNet has two forms over the SAME stable
         conditioning buffers: guided, batch 2B on [uncond; cond], and unguided, batch B on views of the conditional half
         (rows B: of ctx and pooled, the last B rows of time_ids; cross-attention K/V: the trailing rows of the buffers computed
@@ -1081,11 +1259,13 @@ class StableDiffusionXLPipeline:
         graph is captured — or found — right after, later occurrences replay it.  Every step's update writes the next input,
         in one copy or two, straight into the buffer the next step's form reads: its graph's ``x``, or a plain tensor while
         that form has not run yet.  DPM++: one launch per step (``ss_multistep_step``), d_prev is the previous step's d,
-        guided or not.  Euler: ``ss_euler_cfg_step`` | ``ss_euler_step``, then ``ss_euler_scale``."""
+        guided or not (a stochastic scheduler: ``ss_multistep_noise_step``, the same forms).  Euler: ``ss_euler_cfg_step`` |
+        ``ss_euler_step``, then ``ss_euler_scale``."""
         dev, dt = prompt_embeds.device, prompt_embeds.dtype
         lh, lw = height // 8, width // 8
         B = prompt_embeds.shape[0]
-        multistep = isinstance(sched, DPMSolverMultistepScheduler)
+        multistep = isinstance(sched, _MULTISTEP)
+        seeds_dev = self._seed_buffer(noise_seeds, prompt_embeds.shape[0], dev) if isinstance(sched, _STOCHASTIC) else None
         sig, ts = sched.sigmas, sched.timesteps                # set_timesteps ran in __call__
         if latents is None:
             latents = torch.randn((B, 4, lh, lw), generator=generator, device=dev, dtype=dt)
@@ -1134,7 +1314,13 @@ class StableDiffusionXLPipeline:
                 eps = graph[g]["eps"]
             last = i + 1 == num_inference_steps
             gn = None if last else mask[i + 1]
-            if multistep:
+            if seeds_dev is not None:
+                a, b, c, s = (float(v) for v in sched.coefficients[i])
+                xin = None if last else target(gn)
+                ops.multistep_noise_step_(state, eps.contiguous(), guidance_scale, float(sig[i]), a, b, c, s,
+                                          1.0 / math.sqrt(float(sig[i + 1]) ** 2 + 1.0), seeds_dev, i, eps_rows=rows,
+                                          x_out=x_out if last else None, xin_next=xin, xin_rows=1 if last else forms[gn][0])
+            elif multistep:
                 a, b, c = (float(v) for v in sched.coefficients[i])
                 xin = None if last else target(gn)
                 ops.multistep_step_(state, eps.contiguous(), guidance_scale, float(sig[i]), a, b, c,

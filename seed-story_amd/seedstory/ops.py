@@ -868,6 +868,68 @@ def multistep_step_(state, eps, guidance, sigma, a, b, c, inv_next, eps_rows=2, 
     return state
 
 
+def noise_seeds(seeds, device):
+    """64-bit noise seeds (an int or a sequence of ints, any sign; taken mod 2^64) -> int64 [B] on ``device`` holding their
+    bits: what ``randn_philox`` and ``multistep_noise_step_`` read as uint64."""
+    vals = [int(seeds)] if isinstance(seeds, int) else [int(v) for v in seeds]
+    vals = [v % (1 << 64) for v in vals]
+    return torch.tensor([v - (1 << 64) if v >= (1 << 63) else v for v in vals], dtype=torch.int64).to(device)
+
+
+def _req_seeds(seeds, who):
+    _req(seeds, "seeds")
+    if seeds.dtype != torch.int64 or seeds.dim() != 1 or seeds.numel() == 0:
+        raise _lib.SSError("%s: seeds must be int64 [batch] (the bits of the uint64 seeds; see noise_seeds)" % who)
+    return seeds
+
+
+def randn_philox(seeds, n_img, step, dtype, out=None):
+    """[batch, n_img] standard normals, row b from ``seeds[b]`` (int64 [batch] device tensor, see ``noise_seeds``) and ``step``
+    alone — the noise of the stochastic samplers (``ss_randn_philox``); a row does not depend on the batch it is drawn in."""
+    _req_seeds(seeds, "randn_philox")
+    B, n_img, step = seeds.numel(), int(n_img), int(step)
+    if n_img <= 0 or step < 0:
+        raise _lib.SSError("randn_philox: n_img %d must be > 0 and step %d >= 0" % (n_img, step))
+    if out is None:
+        out = torch.empty(B, n_img, dtype=dtype, device=seeds.device)
+    else:
+        _req(out, "out")
+        if out.numel() != B * n_img or out.dtype != dtype or out.device != seeds.device:
+            raise _lib.SSError("randn_philox: out must hold %d %s elements on %s" % (B * n_img, dtype, seeds.device))
+    check(lib().ss_randn_philox(p(out), p(seeds), B, n_img, step, dt(dtype), stream()), "ss_randn_philox")
+    return out
+
+
+def multistep_noise_step_(state, eps, guidance, sigma, a, b, c, s, inv_next, seeds, step, eps_rows=2, x_out=None, xin_next=None,
+                          xin_rows=2):
+    """``multistep_step_`` with a noise term (``ss_multistep_noise_step``): x' = a x + b d + c d_prev + s z, z the standard
+    normals of ``randn_philox(seeds, n / len(seeds), step)``, generated inside the same launch.  ``seeds``: int64 [B] on the
+    device (``noise_seeds``), the state holds B images of n / B elements; ``seeds`` may be None when s == 0."""
+    _req(state, "state"); _req(eps, "eps")
+    if eps_rows not in (1, 2) or xin_rows not in (1, 2):
+        raise _lib.SSError("multistep_noise_step: eps_rows %r / xin_rows %r must be 1 or 2" % (eps_rows, xin_rows))
+    n = state.numel() // 2
+    if state.dtype != torch.float32 or state.numel() != 2 * n or eps.numel() != eps_rows * n or n == 0:
+        raise _lib.SSError("multistep_noise_step: state must be fp32 [2, n] for eps [%d, n]" % eps_rows)
+    if seeds is None:
+        if float(s) != 0.0:
+            raise _lib.SSError("multistep_noise_step: s = %r needs seeds" % (s,))
+        B = 1
+    else:
+        B = _req_seeds(seeds, "multistep_noise_step").numel()
+        if n % B or seeds.device != eps.device:
+            raise _lib.SSError("multistep_noise_step: %d seeds on %s for a state of %d elements on %s" % (B, seeds.device, n, eps.device))
+    for t, name, cnt in ((x_out, "x_out", n), (xin_next, "xin_next", xin_rows * n)):
+        if t is not None:
+            _req(t, name)
+            if t.dtype != eps.dtype or t.numel() != cnt or t.device != eps.device:
+                raise _lib.SSError("multistep_noise_step: %s must hold %d %s elements on %s" % (name, cnt, eps.dtype, eps.device))
+    check(lib().ss_multistep_noise_step(p(state), p(eps), p(x_out), p(xin_next), n, eps_rows, xin_rows, float(guidance),
+                                        float(sigma), float(a), float(b), float(c), float(s), float(inv_next), p(seeds), n // B,
+                                        int(step), dt(eps), stream()), "ss_multistep_noise_step")
+    return state
+
+
 def euler_step_(x, eps, sigma, sigma_next):
     """Unguided Euler step in place: x += eps * (sigma_next - sigma), eps the conditional prediction (``ss_euler_step``)."""
     _req(x, "x"); _req(eps, "eps")

@@ -189,19 +189,22 @@ def add_beams_arguments(ap):
     ap.add_argument("--length-penalty", type=float, default=1.0, help="with --beams: a hypothesis scores sum / length ** P")
 
 
-SCHEDULERS = ("euler", "dpmpp2m", "dpmpp2m-karras")
+SCHEDULERS = ("euler", "dpmpp2m", "dpmpp2m-karras", "euler-a", "dpmpp2m-sde", "dpmpp2m-sde-karras")
 
 
 def add_scheduler_argument(ap):
     """``--scheduler`` (shared with vis_george_sink.py)"""
     ap.add_argument("--scheduler", default="euler", choices=SCHEDULERS,
                     help="SDXL sampler: euler (the reference's), dpmpp2m = DPM-Solver++ 2M, dpmpp2m-karras = the same on Karras "
-                         "sigmas (second order: 15 - 20 --diffusion-steps instead of 30; end quality on real weights unverified)")
+                         "sigmas (second order: 15 - 20 --diffusion-steps instead of 30), euler-a = Euler ancestral, dpmpp2m-sde / "
+                         "dpmpp2m-sde-karras = DPM++ 2M SDE (stochastic: noise drawn on the device from the image's seed); end "
+                         "quality on real weights unverified")
 
 
 def make_scheduler(args, path=None):
     """The scheduler object ``--scheduler`` names, from the checkpoint's scheduler_config.json when ``path`` is given."""
-    from seedstory.diffusion import DPMSolverMultistepScheduler, EulerDiscreteScheduler
+    from seedstory.diffusion import (DPMSolverMultistepScheduler, DPMSolverMultistepSDEScheduler, EulerAncestralDiscreteScheduler,
+                                     EulerDiscreteScheduler)
     name = getattr(args, "scheduler", "euler") or "euler"
     if name not in SCHEDULERS:
         raise SystemExit("--scheduler must be one of %s" % ", ".join(SCHEDULERS))
@@ -209,6 +212,10 @@ def make_scheduler(args, path=None):
     if name == "euler":
         return euler
     # over the checkpoint's own betas and spacing (its Euler config carries keys the multistep class has no use for)
+    if name == "euler-a":
+        return EulerAncestralDiscreteScheduler.from_base(euler)
+    if name.startswith("dpmpp2m-sde"):
+        return DPMSolverMultistepSDEScheduler.from_base(euler, use_karras_sigmas=name == "dpmpp2m-sde-karras")
     return DPMSolverMultistepScheduler.from_base(euler, use_karras_sigmas=name == "dpmpp2m-karras")
 
 

@@ -107,11 +107,24 @@ class SDXLAdapter(nn.Module):
                  guidance_scale=7.5, num_inference_steps=30, input_image_size=448, **kwargs):
         """``**kwargs`` go to the pipeline call: ``latents``, ``output_type``, and ``guidance_interval=(sigma_lo, sigma_hi)`` —
         classifier-free guidance only on the steps whose sigma lies in (sigma_lo, sigma_hi], the others run the UNet on the
-        conditional rows alone (``seedstory.diffusion.guidance_mask``; default None: every step is guided)."""
+        conditional rows alone (``seedstory.diffusion.guidance_mask``; default None: every step is guided).  ``seed`` may be a
+        sequence of B ints, one per image (see below); with a stochastic scheduler the seed is also the image's noise seed."""
         pos, neg, pooled_pos, pooled_neg = self.get_image_embeds(image_pil=image_pil, image_tensor=image_tensor,
                                                                  image_embeds=image_embeds, return_negative=True,
                                                                  image_size=input_image_size)
-        generator = torch.Generator(self.device).manual_seed(seed) if seed is not None else None
+        if seed is not None and not isinstance(seed, int):
+            # one seed per image: image b starts from the latents a batch-1 call with seed[b] draws, and a stochastic scheduler
+            # takes seed[b] as its noise seed (an int, below, is the noise seed of every image: generator.initial_seed())
+            seeds = [int(v) for v in seed]
+            if len(seeds) != pos.shape[0]:
+                raise ValueError("seed holds %d seeds for %d images" % (len(seeds), pos.shape[0]))
+            kwargs.setdefault("noise_seed", seeds)
+            if "latents" not in kwargs:
+                kwargs["latents"] = torch.cat([torch.randn((1, 4, height // 8, width // 8), device=pos.device, dtype=pos.dtype,
+                                                           generator=torch.Generator(self.device).manual_seed(v)) for v in seeds])
+            generator = None
+        else:
+            generator = torch.Generator(self.device).manual_seed(seed) if seed is not None else None
         if pos.shape[0] > 1 and "latents" not in kwargs:
             # several stories rendered together: every image starts from the noise the reference draws for a
             # single call with this seed (:455), so each equals its own batch-1 generate()
