@@ -260,6 +260,35 @@ int ss_attn_decode_kv8(const void* q, const void* k_codes, const void* v_codes, 
                        void* out, void* workspace, const int32_t* kv_len_dev, int64_t n_heads, int64_t hd, int64_t cache_cap,
                        int dtype, void* stream);
 
+/* The attention of ONE decode token as the engine launches it, for nb <= 8 sequences at once: RoPE of q and of the new k, the
+ * append of the new K / V row, split-KV attention over the old keys and the new one, the split merge.  Sequence b reads
+ *   qkv + b * 3 * n_heads * hd          its pre-RoPE q | k | v row;
+ *   state[b * state_stride + w]         int32 words (device): w = kv_len_word -> L, the keys already cached (0 <= L <= cache_cap);
+ *                                       w = pos_word -> P, the RoPE position of the new token (its own word: not L);
+ *                                       w = done_word -> non-zero: the sequence is finished (done_word < 0: no such flag);
+ *   kcache / vcache + b * cache_stride  its planes [n_heads, cache_cap, hd] (cache_stride in elements),
+ * and writes out + b * n_heads * hd.  It rotates q and k at row P of cos / sin [max_pos, hd] (the bits ss_rope_kv_append
+ * produces), stores the rotated k and v at row L of every head when L < cache_cap (L == cache_cap: nothing is stored, the new
+ * key is attended all the same), and attends keys [0, L]: rows [0, L) from the cache, the new one from registers.  Rows > L are
+ * never read.  A finished sequence is skipped altogether: nothing of its planes or its out row is written.  The state is only read.
+ * The split count is that of the engine: 16 / nb rounded to 4 / 8 / 16 (knob attn_decode_nsplit).
+ * workspace: nb * ss_attn_decode_workspace_bytes(n_heads, hd).
+ * ss_attn_decode_kv8_step: the same over the fp8 shadow.  Old keys are read from k_codes / v_codes / k_scale / v_scale
+ * (sequence b: b * cache_stride codes and b * cache_stride / hd scales further on — the shadow is laid out like the planes, one
+ * scale per row), the new key is attended UNQUANTISED from registers; the new row goes to the 16-bit planes as above and, quantised as
+ * ss_kv_quantize_fp8 defines, to the shadow (codes and both scales of row L, every head).  bf16 / fp16 only.
+ * SS_EINVAL before anything is launched: a NULL pointer; qkv, a plane, a code plane or a RoPE table that is not 16-byte aligned
+ * (scales: 4); nb outside [1, 8]; a head dim the kernel does not take (hd * element size a multiple of 16, hd / vector width a
+ * power of two <= 64; the shadow: the rule of ss_attn_decode_kv8); cache_stride below n_heads * cache_cap * hd or not a multiple
+ * of hd; a negative kv_len_word / pos_word. */
+int ss_attn_decode_step(const void* qkv, void* kcache, void* vcache, const void* cos, const void* sin, void* out, void* workspace,
+                        const int32_t* state, int64_t kv_len_word, int64_t pos_word, int64_t done_word, int64_t state_stride,
+                        int64_t nb, int64_t n_heads, int64_t hd, int64_t cache_cap, int64_t cache_stride, int dtype, void* stream);
+int ss_attn_decode_kv8_step(const void* qkv, void* kcache, void* vcache, void* k_codes, void* v_codes, float* k_scale,
+                            float* v_scale, const void* cos, const void* sin, void* out, void* workspace, const int32_t* state,
+                            int64_t kv_len_word, int64_t pos_word, int64_t done_word, int64_t state_stride, int64_t nb,
+                            int64_t n_heads, int64_t hd, int64_t cache_cap, int64_t cache_stride, int dtype, void* stream);
+
 /* Attention MAP of one head, as the reference returns it under `output_attentions`
  * (modeling_llama_xformer.py:246-276, 299-301): PRE-softmax scores with the mask added, every rounding in the model dtype:
  *   s = rnd_T(rnd_T(q . k) / sqrt(head_dim)), q / k post-RoPE.

@@ -1626,6 +1626,26 @@ static AttnArgs attn_args(const void* q, const void* k, const void* v, void* out
     return a;
 }
 
+// the argument checks ss_attn_decode_step and ss_attn_decode_kv8_step share (the head_dim rule is each launch's own)
+int decode_step_check(const char* who, const void* qkv, const void* kcache, const void* vcache, const void* cos, const void* sin,
+                      const void* out, const void* workspace, const int32_t* state, int64_t kv_len_word, int64_t pos_word,
+                      int64_t state_stride, int64_t nb, int64_t n_heads, int64_t hd, int64_t cache_cap, int64_t cache_stride) {
+    SS_REQUIRE(qkv && kcache && vcache && cos && sin && out && workspace && state, "%s: NULL argument", who);
+    SS_REQUIRE((((size_t)qkv | (size_t)kcache | (size_t)vcache | (size_t)cos | (size_t)sin) & 15) == 0,
+               "%s: qkv, the cache planes and the RoPE tables must be 16-byte aligned", who);
+    SS_REQUIRE(nb >= 1 && nb <= 8, "%s: %lld sequences outside [1, 8]", who, (long long)nb);
+    SS_REQUIRE(n_heads >= 1 && hd >= 1 && cache_cap >= 1 && n_heads * cache_cap * hd < (1ll << 31),
+               "%s: bad shape (n_heads=%lld hd=%lld cache_cap=%lld)", who, (long long)n_heads, (long long)hd, (long long)cache_cap);
+    SS_REQUIRE(kv_len_word >= 0 && pos_word >= 0 && state_stride >= 0 && state_stride < (1ll << 31),
+               "%s: state words %lld / %lld, stride %lld", who, (long long)kv_len_word, (long long)pos_word, (long long)state_stride);
+    // whole rows between consecutive sequences: every row start stays 16-byte aligned, and the scale planes of the fp8 shadow
+    // (one fp32 per row) lie exactly cache_stride / hd apart
+    SS_REQUIRE(cache_stride >= n_heads * cache_cap * hd && cache_stride % hd == 0,
+               "%s: cache_stride %lld is not a multiple of hd at least n_heads * cache_cap * hd = %lld", who, (long long)cache_stride,
+               (long long)(n_heads * cache_cap * hd));
+    return SS_OK;
+}
+
 }  // namespace ss
 
 using namespace ss;
@@ -1672,6 +1692,17 @@ int ss_attn_decode(const void* q, const void* kcache, const void* vcache, void* 
                    void* stream) {
     return attn_decode_dev(q, kcache, vcache, out, workspace, kv_len_dev, nullptr, n_heads, hd, cache_cap, dtype,
                            (hipStream_t)stream);
+}
+
+int ss_attn_decode_step(const void* qkv, void* kcache, void* vcache, const void* cos, const void* sin, void* out, void* workspace,
+                        const int32_t* state, int64_t kv_len_word, int64_t pos_word, int64_t done_word, int64_t state_stride,
+                        int64_t nb, int64_t n_heads, int64_t hd, int64_t cache_cap, int64_t cache_stride, int dtype, void* stream) {
+    if (int rc = decode_step_check("attn_decode_step", qkv, kcache, vcache, cos, sin, out, workspace, state, kv_len_word,
+                                    pos_word, state_stride, nb, n_heads, hd, cache_cap, cache_stride))
+        return rc;
+    return attn_decode_fused_dev(qkv, kcache, vcache, cos, sin, out, workspace, state + kv_len_word, state + pos_word,
+                                 done_word < 0 ? nullptr : state + done_word, n_heads, hd, cache_cap, (int)nb, (int)state_stride,
+                                 cache_stride, dtype, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -18,6 +18,9 @@
 namespace ss {
 
 int decode_nsplit(int nb);      // ss_attn.hip
+int decode_step_check(const char* who, const void* qkv, const void* kcache, const void* vcache, const void* cos, const void* sin,
+                      const void* out, const void* workspace, const int32_t* state, int64_t kv_len_word, int64_t pos_word,
+                      int64_t state_stride, int64_t nb, int64_t n_heads, int64_t hd, int64_t cache_cap, int64_t cache_stride);
 int attn_combine_dev(const float* part, void* out, const int32_t* done_flag, int64_t n_heads, int64_t hd, int nb, int nsplit,
                      int state_stride, int64_t part_stride, int64_t out_stride, int dtype, hipStream_t s);
 
@@ -398,6 +401,22 @@ int ss_attn_decode_kv8(const void* q, const void* k_codes, const void* v_codes, 
     SS_REQUIRE(n_heads >= 1 && cache_cap >= 1, "attn_decode_kv8: bad shape");
     return attn_decode_kv8_dev(q, k_codes, v_codes, k_scale, v_scale, out, workspace, kv_len_dev, nullptr, n_heads, hd, cache_cap, dtype,
                                (hipStream_t)stream);
+}
+
+int ss_attn_decode_kv8_step(const void* qkv, void* kcache, void* vcache, void* k_codes, void* v_codes, float* k_scale, float* v_scale,
+                            const void* cos, const void* sin, void* out, void* workspace, const int32_t* state, int64_t kv_len_word,
+                            int64_t pos_word, int64_t done_word, int64_t state_stride, int64_t nb, int64_t n_heads, int64_t hd,
+                            int64_t cache_cap, int64_t cache_stride, int dtype, void* stream) {
+    if (int rc = kv8_check(hd, dtype, "attn_decode_kv8_step")) return rc;
+    if (int rc = decode_step_check("attn_decode_kv8_step", qkv, kcache, vcache, cos, sin, out, workspace, state, kv_len_word, pos_word,
+                                   state_stride, nb, n_heads, hd, cache_cap, cache_stride))
+        return rc;
+    SS_REQUIRE(k_codes && v_codes && k_scale && v_scale, "attn_decode_kv8_step: NULL shadow plane");
+    SS_REQUIRE((((size_t)k_codes | (size_t)v_codes) & 15) == 0 && (((size_t)k_scale | (size_t)v_scale) & 3) == 0,
+               "attn_decode_kv8_step: the code planes must be 16-byte aligned (scales: 4)");
+    return attn_decode_kv8_fused_dev(qkv, kcache, vcache, k_codes, v_codes, k_scale, v_scale, cos, sin, out, workspace,
+                                     state + kv_len_word, state + pos_word, done_word < 0 ? nullptr : state + done_word, n_heads, hd,
+                                     cache_cap, (int)nb, (int)state_stride, cache_stride, dtype, (hipStream_t)stream);
 }
 
 }  // extern "C"

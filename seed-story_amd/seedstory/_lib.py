@@ -136,6 +136,8 @@ PROTOTYPES = {
     "ss_attn_decode": (C.c_int, [vp, vp, vp, vp, vp, vp, i64, i64, i64, C.c_int, vp]),
     "ss_kv_quantize_fp8": (C.c_int, [vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, C.c_int, vp]),
     "ss_attn_decode_kv8": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, C.c_int, vp]),
+    "ss_attn_decode_step": (C.c_int, [vp] * 8 + [i64] * 9 + [C.c_int, vp]),
+    "ss_attn_decode_kv8_step": (C.c_int, [vp] * 12 + [i64] * 9 + [C.c_int, vp]),
     "ss_attn_scores": (C.c_int, [vp, i64, vp, i64, vp, i64, i64, i64, i64, C.c_int, C.c_int, vp]),
     "ss_gemm": (C.c_int, [vp, vp, vp, i64, i64, i64, i64, i64, i64, vp, vp, i64, C.c_int, C.c_int, vp]),
     "ss_gemm_tune_workspace_bytes": (sz, [i64, i64, i64, C.c_int]),

@@ -201,6 +201,63 @@ def attn_decode_spec(qkv, kcache, vcache, cos, sin, kv_len_dev, pos_dev, n_activ
     return out
 
 
+def _decode_step_args(name, qkv, kcache, vcache, cos, sin, state, n_heads, cache_cap, cache_stride, words, shadow=()):
+    """shared by attn_decode_step / attn_decode_kv8_step: the checks that keep every sequence inside the caller's buffers
+    (the argument rules themselves are the C entry point's) -> (nb, hd, cache_stride, state_stride)"""
+    for t, n in ((qkv, "qkv"), (kcache, "kcache"), (vcache, "vcache"), (cos, "cos"), (sin, "sin"), (state, "state")) + tuple(shadow):
+        _req(t, n)
+    if qkv.dim() != 2 or qkv.shape[1] % (3 * n_heads) or state.dtype != torch.int32 or state.dim() != 2 or state.shape[0] != qkv.shape[0]:
+        raise _lib.SSError("%s: qkv [nb, 3 * n_heads * hd] and an int32 state [nb, words] expected, got %s and %s %s"
+                           % (name, tuple(qkv.shape), state.dtype, tuple(state.shape)))
+    if max(words) >= state.shape[1]:
+        raise _lib.SSError("%s: state word %d of %d" % (name, max(words), state.shape[1]))
+    nb, hd = qkv.shape[0], qkv.shape[1] // (3 * n_heads)
+    plane = n_heads * cache_cap * hd
+    cache_stride = plane if cache_stride is None else int(cache_stride)
+    need = max(nb - 1, 0) * max(cache_stride, 0) + plane
+    for t, n, have in ((kcache, "kcache", kcache.numel()), (vcache, "vcache", vcache.numel())) + \
+            tuple((t, n, t.numel() * (hd if t.dtype == torch.float32 else 1)) for t, n in shadow):
+        if have < need:
+            raise _lib.SSError("%s: %s holds %d elements, %d sequences %d apart need %d" % (name, n, have, nb, cache_stride, need))
+    return nb, hd, cache_stride, state.shape[1]
+
+
+def attn_decode_step(qkv, kcache, vcache, cos, sin, state, n_heads, cache_cap, cache_stride=None, kv_len_word=0, pos_word=1,
+                     done_word=-1, out=None):
+    """The attention of one decode token as the engine launches it (``ss_attn_decode_step``): ``qkv`` [nb, 3*E] pre-RoPE rows of
+    nb <= 8 sequences; ``kcache`` / ``vcache`` any contiguous tensors that hold sequence b's planes [n_heads, cache_cap, hd] at
+    element ``b * cache_stride`` (default: back to back); ``state`` int32 [nb, words] on the device with the cached key count,
+    the RoPE position and (``done_word`` >= 0) the finished flag of sequence b in row b.  Rotates q / k, stores the new K / V
+    row at row kv_len of every live sequence's planes (in place) and returns the attention over keys [0, kv_len] as ``out``
+    [nb, E]; rows of finished sequences are left as they are."""
+    nb, hd, cache_stride, words = _decode_step_args("attn_decode_step", qkv, kcache, vcache, cos, sin, state, n_heads, cache_cap,
+                                                    cache_stride, (kv_len_word, pos_word, done_word))
+    ws = torch.empty(max(nb, 1) * lib().ss_attn_decode_workspace_bytes(n_heads, max(hd, 1)), dtype=torch.uint8, device=qkv.device)
+    out = _out(out, (nb, n_heads * hd), qkv, "attn_decode_step")
+    check(lib().ss_attn_decode_step(p(qkv), p(kcache), p(vcache), p(cos), p(sin), p(out), p(ws), p(state), int(kv_len_word),
+                                    int(pos_word), int(done_word), words, nb, n_heads, hd, cache_cap, cache_stride, dt(qkv), stream()),
+          "ss_attn_decode_step")
+    return out
+
+
+def attn_decode_kv8_step(qkv, kcache, vcache, k_codes, v_codes, k_scale, v_scale, cos, sin, state, n_heads, cache_cap,
+                         cache_stride=None, kv_len_word=0, pos_word=1, done_word=-1, out=None):
+    """``attn_decode_step`` over the e4m3 shadow (``ss_attn_decode_kv8_step``): old keys come from ``k_codes`` / ``v_codes``
+    (uint8, laid out like the planes) and ``k_scale`` / ``v_scale`` (fp32, one per row: sequence b at ``b * cache_stride / hd``),
+    the new key is attended unquantised; the new row is stored into the 16-bit planes and, quantised, into the shadow."""
+    shadow = ((k_codes, "k_codes"), (v_codes, "v_codes"), (k_scale, "k_scale"), (v_scale, "v_scale"))
+    nb, hd, cache_stride, words = _decode_step_args("attn_decode_kv8_step", qkv, kcache, vcache, cos, sin, state, n_heads, cache_cap,
+                                                    cache_stride, (kv_len_word, pos_word, done_word), shadow)
+    if k_codes.dtype != torch.uint8 or v_codes.dtype != torch.uint8 or k_scale.dtype != torch.float32 or v_scale.dtype != torch.float32:
+        raise _lib.SSError("attn_decode_kv8_step: uint8 code planes and fp32 scale planes expected")
+    ws = torch.empty(max(nb, 1) * lib().ss_attn_decode_workspace_bytes(n_heads, max(hd, 1)), dtype=torch.uint8, device=qkv.device)
+    out = _out(out, (nb, n_heads * hd), qkv, "attn_decode_kv8_step")
+    check(lib().ss_attn_decode_kv8_step(p(qkv), p(kcache), p(vcache), p(k_codes), p(v_codes), p(k_scale), p(v_scale), p(cos), p(sin),
+                                        p(out), p(ws), p(state), int(kv_len_word), int(pos_word), int(done_word), words, nb, n_heads,
+                                        hd, cache_cap, cache_stride, dt(qkv), stream()), "ss_attn_decode_kv8_step")
+    return out
+
+
 def spec_draft(history, max_ngram=2, num_tokens=3, stop_ids=()):
     """The prompt-lookup draft (``ss_spec_draft``): transformers' ``PromptLookupCandidateGenerator.get_candidates`` on the int32
     device tensor ``history`` — n-gram sizes from ``min(max_ngram, len - 1)`` down to 1, the leftmost match with a non-empty

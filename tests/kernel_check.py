@@ -1331,3 +1331,240 @@ def producer_inputs(M, N, K, dtype, seed):
     a = torch.randn(M, K, generator=g).to(dtype)
     w = (torch.randn(N, K, generator=g) / K ** 0.5).to(dtype)
     return a, w, (torch.randn(N, generator=g) * 0.3 + 9.0).to(dtype), torch.randn(M, N, generator=g).to(dtype)
+
+
+# ---- the decode step as the engine launches it (tests/test_decode_step_gpu.py; simulated in tests/test_kernel_check_cpu.py) ---
+# ss_attn_decode_step / ss_attn_decode_kv8_step: attn_decode_kernel / attn_decode_kv8_kernel in their fused, batched mode.
+DECODE_STEP_CAP = 640
+DECODE_STEP_GAP_ROWS = 16               # poisoned rows between consecutive sequences' planes: cache_stride = (H cap + 16) hd
+DECODE_STEP_WORDS = 8                   # int32 state words per sequence; kv_len, pos, done at words 0, 1, 3 (ss_llama.hip's ST_*)
+ST_KV_LEN, ST_POS, ST_DONE = 0, 1, 3
+DECODE_STEP_POS_AHEAD = 3               # pos = kv_len + 3: the RoPE position is its own word
+DECODE_STEP_DONE_KV_LEN = 37            # kv_len of a finished sequence: a row it appended all the same would land on poison
+DECODE_STEP_FAMILY = {False: "attn_decode step", True: "attn_decode_kv8 step"}
+
+
+def decode_step_nsplit(nb, knob=0):
+    """decode_nsplit of ss_attn.hip: the splits of a launch over nb sequences under knob attn_decode_nsplit"""
+    n = knob if knob > 0 else 16 // max(nb, 1)
+    return 4 if n <= 4 else 8 if n <= 8 else 16 if n <= 16 else 32
+
+
+def decode_step_n_olds(ns, cap=DECODE_STEP_CAP):
+    """cached keys before the step: ns - 1, ns, ns + 1 give empty splits and one key per split (the new key makes n_old + 1);
+    511, 512, 600 at ns = 4 put the new key into a later 4-keys-per-thread sub-chunk of its split for every NKG * 4 in
+    {32, 64, 128}; cap - 1 writes the last row; cap writes nothing and still attends the new key"""
+    return sorted({0, 1, ns - 2, ns - 1, ns, ns + 1, 63, 64, 500, 511, 512, 600, cap - 1, cap})
+
+
+def _decode_step_cases():
+    """(nb, knob, ns, n_old per sequence, done per sequence): every n_old of decode_step_n_olds(ns) at nb = 1 under knob 0 (16
+    splits), 4 and 32, and again on a live sequence of every nb > 1 (default knob: 8, 8, 4, 4 splits at 2, 3, 4, 8 sequences).
+    A batch holds nb - 1 live sequences with unequal n_old and one finished one, whose place moves from batch to batch."""
+    cases = []
+    for knob in (0, 4, 32):
+        ns = decode_step_nsplit(1, knob)
+        cases += [(1, knob, ns, (n,), (False,)) for n in decode_step_n_olds(ns)]
+    for nb in (2, 3, 4, 8):
+        ns = decode_step_nsplit(nb)
+        vals, live = decode_step_n_olds(ns), nb - 1
+        for i in range(0, len(vals), live):
+            chunk = vals[i:i + live]
+            chunk += [v for v in vals if v not in chunk][:live - len(chunk)]
+            d = (i // live) % nb
+            cases.append((nb, 0, ns, tuple(chunk[:d] + [DECODE_STEP_DONE_KV_LEN] + chunk[d:]), tuple(b == d for b in range(nb))))
+    return cases
+
+
+DECODE_STEP_CASES = _decode_step_cases()
+
+
+def decode_step_selector_cases(cap=DECODE_STEP_CAP):
+    """the exact probes: n_old 0, ns - 1, ns, 511, cap - 1 at one sequence, and two batches (8 and 4 splits)"""
+    cases = [(1, 0, 16, (n,), (False,)) for n in (0, 15, 16, 511, cap - 1)]
+    cases.append((3, 0, 8, (7, DECODE_STEP_DONE_KV_LEN, 8), (False, True, False)))
+    cases.append((4, 0, 4, (3, 4, 511, cap - 1), (False,) * 4))
+    return cases
+
+
+def bits(t):
+    """the integer view under which tensors are compared bit for bit"""
+    t = t.contiguous()
+    return t if t.dtype == torch.uint8 else t.view(torch.int16 if t.element_size() == 2 else torch.int32)
+
+
+def decode_step_pack(qkv, kc, vc, kv_lens, pos, done, dtype, shadow=False, gap_rows=DECODE_STEP_GAP_ROWS):
+    """The buffers of one launch, on the CPU, arranged so that a wrong stride or word index lands on garbage: kc / vc
+    [nb, H, cap, hd] (rows >= kv_len are poisoned here) flat with gap_rows poisoned rows after every sequence; the state
+    [nb, 8] with kv_len, pos, done at words 0, 1, 3 and large garbage elsewhere; shadow: code planes of the same layout (0x7f
+    from row kv_len on and in the gaps) and scale planes, one fp32 per row (NaN likewise), rows < kv_len from kv8_ref."""
+    import types
+    nb, H, cap, hd = kc.shape
+    plane = H * cap * hd
+    stride = plane + gap_rows * hd
+    kc, vc = kc.clone(), vc.clone()
+    flats = []
+    for pl in (kc, vc):
+        for b in range(nb):
+            poison_(pl[b][:, kv_lens[b]:])
+        f = poison_(torch.empty(nb, stride, dtype=dtype))
+        f[:, :plane] = pl.reshape(nb, plane)
+        flats.append(f.reshape(-1))
+    state = (0x40000000 + 0x00010101 * (1 + torch.arange(nb * DECODE_STEP_WORDS))).to(torch.int32).view(nb, DECODE_STEP_WORDS)
+    for b in range(nb):
+        state[b, ST_KV_LEN], state[b, ST_POS], state[b, ST_DONE] = kv_lens[b], pos[b], int(done[b])
+    inp = types.SimpleNamespace(qkv=qkv, kc=kc, vc=vc, kflat=flats[0], vflat=flats[1], state=state, kv_lens=tuple(kv_lens), pos=tuple(pos),
+                                done=tuple(done), dtype=dtype, nb=nb, H=H, cap=cap, hd=hd, plane=plane, cache_stride=stride,
+                                shadow=shadow)
+    if shadow:
+        import kv8_ref
+        codes = [torch.full((nb, stride), 0x7f, dtype=torch.uint8) for _ in range(2)]
+        scales = [torch.full((nb, stride // hd), float("nan")) for _ in range(2)]
+        for i, pl in enumerate((kc, vc)):
+            for b in range(nb):
+                n = kv_lens[b]
+                c, s, _ = kv8_ref.quantize(pl[b][:, :n])
+                codes[i][b, :plane].view(H, cap, hd)[:, :n] = c
+                scales[i][b, :H * cap].view(H, cap)[:, :n] = s
+        inp.kq, inp.vq, inp.ks, inp.vs = [t.reshape(-1) for t in codes + scales]
+    return inp
+
+
+def decode_step_inputs(case, hd, dtype, seed=0, shadow=False, H=DECODE_HEADS, cap=DECODE_STEP_CAP):
+    """fresh N(0, 1) operands of one case of DECODE_STEP_CASES -> decode_step_pack"""
+    nb, _, _, n_olds, done = case
+    g = torch.Generator().manual_seed(21000 + 131 * hd + 17 * sum(n_olds) + nb + seed)
+    qkv = torch.randn(nb, 3 * H * hd, generator=g).to(dtype)
+    kc = torch.randn(nb, H, cap, hd, generator=g).to(dtype)
+    vc = torch.randn(nb, H, cap, hd, generator=g).to(dtype)
+    return decode_step_pack(qkv, kc, vc, n_olds, [n + DECODE_STEP_POS_AHEAD for n in n_olds], done, dtype, shadow)
+
+
+def decode_step_expect(qkv, kc, vc, cos, sin, kv_lens, pos, done, dtype, shadow=False):
+    """What one decode step must leave behind, per sequence b (a list of namespaces):
+      q, k_new, v_new [H, hd]   the rotated q, the new rotated K row and the V row (rope_exact: bit-exact);
+      wrote                      not done[b] and kv_len[b] < cap: the row is stored at kv_len[b] — k_after / v_after [H, cap, hd] are
+                                 the planes after the step (that row and nothing else);
+      ref, tol [H, 1, hd]        attention_bound over keys [0, kv_len[b]], the new key included (None for a finished sequence).
+    shadow: the old keys are the de-quantised shadow (kv8_ref of rows < kv_len, exact in the model dtype), the new key is the
+    unquantised rotated row; kq_new, vq_new [H, hd] uint8 and ks_new, vs_new [H] are kv8_ref.quantize of the new rows.
+    No constant of its own: attention_bound is derived for fp32 accumulation over operands that are exact in T."""
+    import types
+    nb, H, cap, hd = kc.shape
+    rows = qkv.view(nb, 3, H, hd)
+    p = torch.tensor(list(pos))
+    q_rot, k_rot = rope_exact(rows[:, 0], cos, sin, p), rope_exact(rows[:, 1], cos, sin, p)
+    if shadow:
+        import kv8_ref
+    out = []
+    for b in range(nb):
+        n = int(kv_lens[b])
+        e = types.SimpleNamespace(q=q_rot[b], k_new=k_rot[b], v_new=rows[b, 2].clone(), wrote=(not done[b]) and n < cap, ref=None, tol=None,
+                                  k_after=kc[b].clone(), v_after=vc[b].clone())
+        if e.wrote:
+            e.k_after[:, n], e.v_after[:, n] = e.k_new, e.v_new
+        if shadow:
+            e.kq_new, e.ks_new, _ = kv8_ref.quantize(e.k_new)
+            e.vq_new, e.vs_new, _ = kv8_ref.quantize(e.v_new)
+        if not done[b]:
+            k_old, v_old = kc[b][:, :n], vc[b][:, :n]
+            if shadow:
+                k_old, v_old = kv8_ref.quantize(k_old)[2], kv8_ref.quantize(v_old)[2]
+            e.ref, e.tol = attention_bound(e.q[:, None], torch.cat([k_old, e.k_new[:, None]], 1), torch.cat([v_old, e.v_new[:, None]], 1),
+                                           1.0 / hd ** 0.5, None, dtype)
+        out.append(e)
+    return out
+
+
+def decode_step_failures(inp, exp, got, what):
+    """The assertions of the decode-step tests over what a launch (or the simulated kernel) left behind.  got: namespace with out
+    [nb, E], written [nb, E] bool (the element no longer holds the output buffer's sentinel), kflat, vflat, state and, for the
+    shadow, kq, vq, ks, vs — all on the CPU.  -> [(label, message)], empty when everything holds:
+      bound             every output element of a live sequence inside attention_bound (recorded under the family)
+      out rows          a live sequence's output row is written completely, a finished one's not at all
+      append            row kv_len of every head of both planes bit-equal to the mirror (sequences that store)
+      untouched         every other element of both flat buffers, gaps included, bit-identical to before
+      state             the state array bit-identical
+      shadow append     codes and both scales of the new row bit-equal to kv8_ref of the rotated row
+      shadow untouched  every other code and scale bit-identical"""
+    H, cap, hd, nb = inp.H, inp.cap, inp.hd, inp.nb
+    fails = []
+    fam = DECODE_STEP_FAMILY[inp.shadow]
+    for b in range(nb):
+        wb = "%s seq %d (n_old %d)" % (what, b, inp.kv_lens[b])
+        if inp.done[b]:
+            if bool(got.written[b].any()):
+                fails.append(("out rows", wb + ": the output row of a finished sequence was written"))
+            continue
+        if not bool(got.written[b].all()):
+            fails.append(("out rows", wb + ": %d output elements never written" % int((~got.written[b]).sum())))
+        try:
+            check(got.out[b].view(H, 1, hd), exp[b].ref, exp[b].tol, wb, family=fam, dtype=inp.dtype)
+        except AssertionError as err:
+            fails.append(("bound", str(err)))
+    planes = [("k", inp.kflat, got.kflat, "k_new", "append", "untouched"), ("v", inp.vflat, got.vflat, "v_new", "append", "untouched")]
+    if inp.shadow:
+        planes += [("k codes", inp.kq, got.kq, "kq_new", "shadow append", "shadow untouched"),
+                   ("v codes", inp.vq, got.vq, "vq_new", "shadow append", "shadow untouched"),
+                   ("k scales", inp.ks, got.ks, "ks_new", "shadow append", "shadow untouched"),
+                   ("v scales", inp.vs, got.vs, "vs_new", "shadow append", "shadow untouched")]
+    for name, before, after, attr, l_app, l_unt in planes:
+        width = 1 if "scales" in name else hd
+        stride = inp.cache_stride // hd * width
+        a, b0 = bits(after).view(nb, stride), bits(before).view(nb, stride)
+        appended = torch.zeros(nb, stride, dtype=torch.bool)
+        for b in range(nb):
+            if not exp[b].wrote:
+                continue
+            n = inp.kv_lens[b]
+            sl = a[b, :H * cap * width].view(H, cap, width)[:, n]
+            appended[b, :H * cap * width].view(H, cap, width)[:, n] = True
+            want = bits(getattr(exp[b], attr)).view(H, width)
+            if not torch.equal(sl, want):
+                fails.append((l_app, "%s seq %d: row %d of the %s plane differs from the mirror in %d elements"
+                              % (what, b, n, name, int((sl != want).sum()))))
+        changed = ((a != b0) & ~appended).nonzero()
+        if changed.numel():
+            s, i = int(changed[0, 0]), int(changed[0, 1])
+            fails.append((l_unt, "%s: %d elements of the %s buffer written outside the new rows, first in sequence %d's stride at "
+                          "element %d (head %d, row %d; beyond %d: the gap)" % (what, changed.shape[0], name, s, i, i // (cap * width),
+                                                                               i // width % cap, H * cap * width)))
+    if not torch.equal(got.state, inp.state):
+        fails.append(("state", what + ": the state array changed"))
+    return fails
+
+
+def decode_step_selector_inputs(case, hd, dtype, second=False, shadow=False, H=DECODE_HEADS, cap=DECODE_STEP_CAP):
+    """Exact probe of the step (identity RoPE tables keep the vectors exact): old keys and the new key form attention_selector's
+    family at kscale = 16, so the LAST key — the new one — takes all the weight and the output is the new V row, bit for bit.
+    second: the new K row is zero (score 0), so the largest score sits on key n_old - 1 and the output is v[n_old - 1]: the
+    new key does not mask the old ones (needs n_old >= 2: key 0 scores 0 as well).
+    shadow: kv8_selector's family with a third digit, key j = 256 a + 16 b + c (a <= 2; b, c <= 15) -> entries 16 a, 16 b, 16 c
+    (four significand bits: exact in e4m3 under any power-of-two row scale), q = 128 (256 e0 + 16 e1 + e2): scores
+    2048 j / sqrt(hd) again; the old V rows go through kv8_ref first, the new V row does not (it is attended unquantised).
+    -> (inp, expected [nb, H * hd] — rows of finished sequences unspecified)"""
+    nb, _, _, n_olds, done = case
+    E = H * hd
+    qkv = torch.zeros(nb, 3, H, hd, dtype=dtype)
+    kc, vc = torch.zeros(nb, H, cap, hd, dtype=dtype), torch.zeros(nb, H, cap, hd, dtype=dtype)
+    want = torch.zeros(nb, H, hd, dtype=dtype)
+    for b, n in enumerate(n_olds):
+        assert not second or n >= 2 or done[b]
+        if shadow:
+            import kv8_ref
+            g = torch.Generator().manual_seed(4100 + 7 * n + b)
+            j = torch.arange(n + 1)
+            q = torch.zeros(H, 1, hd)
+            q[..., 0], q[..., 1], q[..., 2] = 128.0 * 256.0, 128.0 * 16.0, 128.0
+            k = torch.zeros(H, n + 1, hd)
+            k[..., 0], k[..., 1], k[..., 2] = (j // 256).float() * 16.0, (j // 16 % 16).float() * 16.0, (j % 16).float() * 16.0
+            q, k, v = q.to(dtype), k.to(dtype), torch.randn(H, n + 1, hd, generator=g).to(dtype)
+            assert torch.equal(kv8_ref.quantize(k)[2], k)
+            v[:, :n] = kv8_ref.quantize(v[:, :n])[2]
+        else:
+            q, k, v = attention_selector(1, n + 1, hd, dtype, seed=n + b, H=H, kscale=16.0)
+        kc[b, :, :n], vc[b, :, :n] = k[:, :n], v[:, :n]
+        qkv[b, 0], qkv[b, 1], qkv[b, 2] = q[:, 0], (torch.zeros_like(k[:, n]) if second else k[:, n]), v[:, n]
+        want[b] = v[:, n - 1] if second else v[:, n]
+    inp = decode_step_pack(qkv.reshape(nb, 3 * E), kc, vc, n_olds, [0] * nb, done, dtype, shadow)
+    return inp, want.reshape(nb, E)

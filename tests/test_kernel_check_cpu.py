@@ -1,8 +1,8 @@
 """The checker (tests/kernel_check.py) is tested before it judges a kernel: a correct kernel SIMULATED on the CPU (fp32 math,
 chunked and reversed summation, the kernels' rounding points; attention: a tile-64 online softmax with P rounded to T) must
-produce zero violations on every case tests/test_kernel_edges_gpu.py, tests/test_pointwise_edges_gpu.py and
-tests/test_gemm_variants_edges_gpu.py run (the grid-stride shapes of the second reduced to a small shape of the same family),
-and every seeded mutant must be flagged."""
+produce zero violations on every case tests/test_kernel_edges_gpu.py, tests/test_pointwise_edges_gpu.py,
+tests/test_gemm_variants_edges_gpu.py and tests/test_decode_step_gpu.py run (the grid-stride shapes of the second reduced to a
+small shape of the same family), and every seeded mutant must be flagged."""
 import math
 
 import pytest
@@ -1186,3 +1186,209 @@ def test_mutants_splitk(dtype):
             if k1 > k0:
                 assert not torch.equal(sim_splitk(ca, cw, dtype, S, drop=i), exp)
                 assert not torch.equal(sim_splitk(ca, cw, dtype, S, twice=i), exp)
+
+
+# ---- the decode step (tests/test_decode_step_gpu.py): the simulated kernel on every case, and the mutants ----------------------
+import types
+
+import kv8_ref
+
+STEP_MUTANTS = {
+    # mutant -> the assertions of KC.decode_step_failures / the selector probes that must flag it
+    "skip new key": {"bound", "selector"},              # the new key is never attended
+    "new key twice": {"bound"},                         # attended by two key groups (a split boundary owned twice)
+    "row + 1": {"append", "untouched"},                 # the new row stored at n_old + 1
+    "done appends": {"untouched"},                      # a finished sequence stores its row all the same
+    "previous kv_len": {"bound", "append", "untouched"},        # sequence b reads sequence b - 1's kv_len word
+    "pos from kv_len": {"bound", "append"},             # the RoPE position taken from the kv_len word
+    "stride without gap": {"bound", "append", "untouched"},     # cache_stride = H cap hd: later sequences miss their planes
+    "kv8 quantised new key": {"bound", "selector"},     # shadow: the new key attended from its codes
+    "kv8 scale row - 1": {"shadow append", "shadow untouched"},  # shadow: the new row's scales written one row early
+}
+
+
+def sim_decode_step(inp, cos, sin, ns, mutant=None):
+    """attn_decode_kernel / attn_decode_kv8_kernel in their fused, batched mode, restated in fp32 torch over the flat buffers of
+    KC.decode_step_pack: per sequence the state words, RoPE of q and the new k, the append, then per split the chunk
+    [sp * chunk, (sp + 1) * chunk) of the n_old + 1 keys walked by NKG key groups (keys kg, kg + NKG, ... with a private online
+    softmax each; the 16-bit kernel meets the new key in that order, the shadow kernel after its loop, unquantised, scales 1),
+    the merge of the groups into the split's record and the merge of the records.  -> the `got` of KC.decode_step_failures."""
+    dtype, H, cap, hd, nb, shadow = inp.dtype, inp.H, inp.cap, inp.hd, inp.nb, inp.shadow
+    V = 16 if shadow else (4 if dtype == torch.float32 else 8)
+    NKG = 256 // (hd // V)
+    E = H * hd
+    scale = torch.tensor(1.0 / math.sqrt(hd), dtype=torch.float32)
+    stride = inp.plane if mutant == "stride without gap" else inp.cache_stride
+    got = types.SimpleNamespace(out=torch.zeros(nb, E, dtype=dtype), written=torch.zeros(nb, E, dtype=torch.bool), kflat=inp.kflat.clone(),
+                                vflat=inp.vflat.clone(), state=inp.state.clone())
+    if shadow:
+        got.kq, got.vq, got.ks, got.vs = inp.kq.clone(), inp.vq.clone(), inp.ks.clone(), inp.vs.clone()
+    rows = inp.qkv.view(nb, 3, H, hd)
+    f8 = lambda c: c.view(torch.float8_e4m3fn).float()
+    for b in range(nb):
+        st = inp.state[b]
+        n_old = int(inp.state[b - 1 if mutant == "previous kv_len" and b else b][KC.ST_KV_LEN])
+        pos = int(st[KC.ST_KV_LEN if mutant == "pos from kv_len" else KC.ST_POS])
+        if st[KC.ST_DONE] and mutant != "done appends":
+            continue
+        p1 = torch.tensor([pos])
+        q = KC.rope_exact(rows[b:b + 1, 0], cos, sin, p1)[0].float()
+        k_new = KC.rope_exact(rows[b:b + 1, 1], cos, sin, p1)[0]
+        v_new = rows[b, 2]
+        base = b * stride
+        if n_old < cap:
+            row = n_old + (1 if mutant == "row + 1" else 0)
+            for h in range(H):
+                o = base + (h * cap + row) * hd
+                got.kflat[o:o + hd], got.vflat[o:o + hd] = k_new[h], v_new[h]
+                if shadow:
+                    got.kq[o:o + hd], ksc, _ = kv8_ref.quantize(k_new[h])
+                    got.vq[o:o + hd], vsc, _ = kv8_ref.quantize(v_new[h])
+                    so = o // hd - (1 if mutant == "kv8 scale row - 1" and n_old else 0)
+                    got.ks[so], got.vs[so] = ksc, vsc
+        if st[KC.ST_DONE]:
+            continue
+        # the old keys as the kernel reads them, the new one from registers
+        if shadow:
+            sbase = base // hd
+            k_old = f8(inp.kq[base:base + inp.plane].view(H, cap, hd)[:, :n_old])
+            v_old = f8(inp.vq[base:base + inp.plane].view(H, cap, hd)[:, :n_old])
+            ksc = torch.cat([inp.ks[sbase:sbase + H * cap].view(H, cap)[:, :n_old], torch.ones(H, 1)], 1)
+            vsc = torch.cat([inp.vs[sbase:sbase + H * cap].view(H, cap)[:, :n_old], torch.ones(H, 1)], 1)
+            kn, vn = k_new, v_new
+            if mutant == "kv8 quantised new key":
+                kn, vn = kv8_ref.quantize(k_new)[2], kv8_ref.quantize(v_new)[2]
+        else:
+            k_old = inp.kflat[base:base + inp.plane].view(H, cap, hd)[:, :n_old].float()
+            v_old = inp.vflat[base:base + inp.plane].view(H, cap, hd)[:, :n_old].float()
+            ksc = vsc = torch.ones(H, n_old + 1)
+            kn, vn = k_new, v_new
+        K = torch.cat([k_old, kn.float()[:, None]], 1)
+        Vv = torch.cat([v_old, vn.float()[:, None]], 1)
+        kv_len = n_old + 1
+        chunk = -(-kv_len // ns)
+        in_loop = not shadow and mutant != "skip new key"
+        after = {"skip new key": 0, "new key twice": 2 if shadow else 1}.get(mutant, 1 if shadow else 0)
+        ms, ls, os_ = [], [], []
+        for sp in range(ns):
+            k_lo = sp * chunk
+            k_hi = min(kv_len, k_lo + chunk)
+            m = torch.full((H, NKG), -1e30)
+            l = torch.zeros(H, NKG)
+            acc = torch.zeros(H, NKG, hd)
+
+            def step(idx, valid, m, l, acc):
+                s = (K[:, idx] * q[:, None]).sum(-1) * ksc[:, idx] * scale
+                mn = torch.where(valid, torch.maximum(m, s), m)
+                al = torch.exp(m - mn)
+                pw = torch.where(valid, torch.exp(s - mn), torch.zeros_like(s))
+                return mn, l * al + pw, acc * al[..., None] + (pw * vsc[:, idx])[..., None] * Vv[:, idx]
+
+            for t0 in range(k_lo, k_hi, NKG):
+                idx = t0 + torch.arange(NKG)
+                valid = (idx < k_hi) & ((idx != n_old) | in_loop)
+                m, l, acc = step(idx.clamp(max=kv_len - 1), valid[None].expand(H, NKG), m, l, acc)
+            if k_lo <= n_old < k_hi:
+                own = torch.zeros(H, NKG, dtype=torch.bool)
+                own[:, (n_old - k_lo) % NKG] = True
+                for _ in range(after):
+                    m, l, acc = step(torch.full((NKG,), n_old), own, m, l, acc)
+            mm = m.amax(-1)
+            w = torch.where(l > 0, torch.exp(m - mm[:, None]), torch.zeros_like(l))
+            ms.append(mm), ls.append((w * l).sum(-1)), os_.append((w[..., None] * acc).sum(1))
+        ms, ls, os_ = torch.stack(ms), torch.stack(ls), torch.stack(os_)        # [ns, H], [ns, H], [ns, H, hd]
+        w = torch.where(ls > 0, torch.exp(ms - ms.amax(0)), torch.zeros_like(ls))
+        got.out[b] = ((w[..., None] * os_).sum(0) / (w * ls).sum(0)[:, None]).to(dtype).reshape(E)
+        got.written[b] = True
+    return got
+
+
+def step_expect(inp, cos, sin):
+    return KC.decode_step_expect(inp.qkv, inp.kc, inp.vc, cos, sin, inp.kv_lens, inp.pos, inp.done, inp.dtype, inp.shadow)
+
+
+STEP_PARAMS = [(hd, dtype, False) for hd in (64, 128) for dtype in ALL] + [(hd, dtype, True) for hd in (64, 128) for dtype in DTYPES16]
+step_ids = lambda p: "%s%d-%s" % ("kv8-" if p[2] else "", p[0], KC.NAME[p[1]])
+
+
+def test_decode_step_cases_cover_what_they_claim():
+    cap = KC.DECODE_STEP_CAP
+    assert [KC.decode_step_nsplit(nb) for nb in (1, 2, 3, 4, 8)] == [16, 8, 8, 4, 4]
+    assert (KC.decode_step_nsplit(1, 4), KC.decode_step_nsplit(1, 32)) == (4, 32)
+    seen = {}
+    for nb, knob, ns, n_olds, done in KC.DECODE_STEP_CASES:
+        assert ns == KC.decode_step_nsplit(nb, knob) and len(n_olds) == len(done) == nb and len(set(n_olds)) == nb
+        assert sum(done) == (1 if nb >= 2 else 0) and all(0 <= n <= cap for n in n_olds)
+        seen.setdefault((nb, knob), set()).update(n for n, d in zip(n_olds, done) if not d)
+    assert set(seen) == {(1, 0), (1, 4), (1, 32), (2, 0), (3, 0), (4, 0), (8, 0)}
+    for (nb, knob), vals in seen.items():       # every n_old at one sequence, and on a live sequence of every batch size
+        assert vals >= set(KC.decode_step_n_olds(KC.decode_step_nsplit(nb, knob))), (nb, knob)
+    # the new key in a later 4-keys-per-thread sub-chunk of its split (ns = 4), for every NKG * 4 the kernels run with
+    # (the owner is the last split: offsets 127, 125 and 147 into it; the shadow kernel at hd 64 walks 256 keys per sub-chunk,
+    # more than a split holds at this cap)
+    offs = [n - 3 * (-(-(n + 1) // 4)) for n in (511, 512, 600)]
+    assert min(offs) >= 64 and max(offs) >= 128
+
+
+@pytest.mark.parametrize("param", STEP_PARAMS, ids=step_ids)
+def test_simulated_decode_step_stays_inside_the_bound(param):
+    hd, dtype, shadow = param
+    cos, sin = KC.rope_tables(hd, KC.DECODE_STEP_CAP + 16, dtype)
+    for case in KC.DECODE_STEP_CASES:
+        what = "sim decode step hd %d %s nb %d ns %d n_old %s" % (hd, KC.NAME[dtype], case[0], case[2], case[3])
+        inp = KC.decode_step_inputs(case, hd, dtype, shadow=shadow)
+        fails = KC.decode_step_failures(inp, step_expect(inp, cos, sin), sim_decode_step(inp, cos, sin, case[2]), what)
+        assert not fails, "\n".join(m for _, m in fails)
+
+
+@pytest.mark.parametrize("param", STEP_PARAMS, ids=step_ids)
+def test_simulated_decode_step_selector(param):
+    hd, dtype, shadow = param
+    cos, sin = torch.ones(KC.DECODE_STEP_CAP + 16, hd).to(dtype), torch.zeros(KC.DECODE_STEP_CAP + 16, hd).to(dtype)
+    for case in KC.decode_step_selector_cases():
+        for second in (False, True):
+            if second and min(n for n, d in zip(case[3], case[4]) if not d) < 2:
+                continue
+            inp, want = KC.decode_step_selector_inputs(case, hd, dtype, second, shadow)
+            got = sim_decode_step(inp, cos, sin, case[2])
+            live = [b for b in range(case[0]) if not case[4][b]]
+            assert torch.equal(KC.bits(got.out[live]), KC.bits(want[live])), (case, second)
+
+
+def step_mutant_labels(mutant, hd, dtype, shadow):
+    """the labels that flag `mutant` over a few cases: one sequence at n_old 0, 1, ns - 1, cap - 1, cap, the first batch of
+    every nb > 1, and the selector probes"""
+    cos, sin = KC.rope_tables(hd, KC.DECODE_STEP_CAP + 16, dtype)
+    picked, seen_nb = [], set()
+    for case in KC.DECODE_STEP_CASES:
+        nb, knob, ns, n_olds, _ = case
+        if (nb == 1 and knob == 0 and n_olds[0] in (0, 1, ns - 1, KC.DECODE_STEP_CAP - 1, KC.DECODE_STEP_CAP)) or (nb > 1 and nb not in seen_nb):
+            picked.append(case)
+            seen_nb.add(nb)
+    labels = set()
+    for case in picked:
+        inp = KC.decode_step_inputs(case, hd, dtype, shadow=shadow)
+        labels |= {l for l, _ in KC.decode_step_failures(inp, step_expect(inp, cos, sin), sim_decode_step(inp, cos, sin, case[2], mutant), "mutant")}
+    one, zero = torch.ones(KC.DECODE_STEP_CAP + 16, hd).to(dtype), torch.zeros(KC.DECODE_STEP_CAP + 16, hd).to(dtype)
+    for case in KC.decode_step_selector_cases():
+        inp, want = KC.decode_step_selector_inputs(case, hd, dtype, False, shadow)
+        got = sim_decode_step(inp, one, zero, case[2], mutant)
+        live = [b for b in range(case[0]) if not case[4][b]]
+        if not torch.equal(KC.bits(got.out[live]), KC.bits(want[live])):
+            labels.add("selector")
+    return labels
+
+
+@pytest.mark.parametrize("mutant", sorted(STEP_MUTANTS))
+def test_mutants_decode_step(mutant):
+    """every mutant is flagged by the assertions STEP_MUTANTS names for it (bf16 and fp32 planes; the shadow in bf16)"""
+    worst = dict(KC.WORST)
+    try:
+        for hd, dtype, shadow in ((64, torch.bfloat16, False), (128, torch.float32, False), (64, torch.bfloat16, True), (128, torch.float16, True)):
+            if mutant.startswith("kv8") and not shadow:
+                continue
+            labels = step_mutant_labels(mutant, hd, dtype, shadow)
+            assert labels >= STEP_MUTANTS[mutant], "%s hd %d %s shadow %d: flagged by %s only" % (mutant, hd, KC.NAME[dtype], shadow, sorted(labels))
+    finally:
+        KC.WORST.clear()
+        KC.WORST.update(worst)          # a mutant's ratios are not a kernel's
